@@ -5,13 +5,16 @@ One *step* = one value-and-gradient evaluation of ``hierarchical_likelihood`` (l
 and every diagnostic site) for one hyper-parameter point, end to end from a host ``theta`` to host
 results, with the catalog already resident in HBM -- what one NUTS leapfrog costs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c5|b50k|def50k] [--full] [--detail PATH]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c5|b50k|def50k] [--full] [--detail PATH] [--dump-outputs DIR]
 
 The LAST line of stdout is ONE compact, strict JSON object (<= 4 KB, `compact_line`): the contract's keys, `roofline`,
 `cpu_baseline`, a short entry per further configuration under `configs` and, for N > 1, a short `multi_gpu` block.  Everything
-else this script measures goes to the side file (`--detail`, default ./bench_detail.json), never to stdout.  The default run
-holds the core legs only (timed K steps, latency distribution, kernel durations, blocking K = 16 batches, bounded CPU
-baseline); `--full` adds the secondary legs (sets in flight, the other batched kernels, chains, the library's NUTS, ...).
+else this script measures goes to the side file (`--detail`, default ./bench_detail.json), never to stdout.  A plain run
+sets up the headline configuration, warms up, times the K steps and prints the line (`roofline`, `cpu_baseline` and
+`batched` null, no `configs`).  `--full` adds every other leg: latency distribution, kernel durations, blocking K = 16
+batches, bounded CPU baseline, the further configurations, and the secondary legs (sets in flight, the other batched
+kernels, chains, the library's NUTS, ...).  `--dump-outputs DIR` writes what the last timed step returned (log_likelihood,
+grad) as DIR/<name>.npy; the inputs depend on the arguments only.
 
 N = 1: a single engine.  N > 1: one rank per GPU (events and injections sharded across ranks, each rank scans
 its shard, ONE exchange of the ~1 KiB partial records -- an ncclAllGather (RCCL over xGMI) inside the engine, with the
@@ -21,7 +24,7 @@ ranks -- a fresh `python -m torch.distributed.run` child, before this process ha
 the child's JSON line; under torch.distributed.run it is a rank.  Prints ONE JSON line on rank 0.
 
 The headline block (`value`, `ms_per_step`, `roofline`, `cpu_baseline`) is BASELINE config 2, the configuration
-the metric is quoted on; `configs` carries the same measurements for the B-spline configs 3 and 5.
+the metric is quoted on; with `--full`, `configs` carries the same measurements for the B-spline configs 3 and 5.
 """
 import argparse
 import glob
@@ -369,7 +372,7 @@ def compact_line(detail, detail_path=None):
     cfg = detail.get("config") or {}
     line["config"] = {k: cfg.get(k) for k in ("workload", "n_events", "n_pe", "n_inj", "n_theta", "parallelism")}
     line["median_ms_per_step"] = detail.get("median_ms_per_step")
-    line["roofline"] = _roofline_entry(detail)
+    line["roofline"] = _roofline_entry(detail) if detail.get("roofline") else None  # null when no kernel was timed (a run without --full)
     line["cpu_baseline"] = _cpu_entry(detail)
     line["batched"] = _batched_entry(detail)
     cfgs = {}
@@ -412,6 +415,14 @@ def dump_line(line):
         text = json.dumps(line, allow_nan=False, separators=(",", ":"))
     assert "\n" not in text and len(text.encode()) <= LINE_LIMIT
     return text
+
+
+def dump_outputs(directory, outputs):
+    """`--dump-outputs DIR`: every array of `outputs` (what the last timed step returned) as DIR/<name>.npy, float64.  The
+    inputs are fixed by the arguments (seeded catalog, seeded hyper-points), so two builds can be compared file by file."""
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 class Run:
@@ -502,10 +513,11 @@ class Run:
 
 def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, with_cpu=True, k_batch=16, chains=4, nuts_chains=0, prefer_rccl=False, full=False,
             cpu_budget_s=6.0):
-    """One configuration: W warm-up + exactly K timed steps (barrier + synchronise on both sides, max over ranks), then
-    the latency distribution of >= 1000 further evaluations, kernel durations of >= 20 timed launches, blocking K-point batches
-    and the bounded CPU baseline; with `full` also the secondary throughput figures.  Returns the DETAIL dict of this
-    configuration (rank 0; `compact_line` picks the record's fields from it) or None."""
+    """One configuration: W warm-up + exactly K timed steps (barrier + synchronise on both sides, max over ranks).  Without
+    `full` that is all (plus what the last timed step returned, under `outputs`).  With `full`, then the latency distribution
+    of >= 1000 further evaluations, kernel durations of >= 20 timed launches, blocking K-point batches, the bounded CPU baseline
+    and the secondary throughput figures.  Returns the DETAIL dict of this configuration (rank 0; `compact_line` picks the
+    record's fields from it) or None."""
     from gwinferno_amd.compositions import COMPOSITIONS, draw_params
     from gwinferno_amd.engine import pin_thread_to_device
     from gwinferno_amd.synthetic import make_config_catalog
@@ -518,7 +530,7 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
     comp = COMPOSITIONS[comp_name](pe, inj)
     # the driving thread next to its GPU (numactl-style host placement), before anything pinned is allocated
     pinned = pin_thread_to_device(dev) if os.environ.get("GWI_BENCH_PIN", "1") != "0" and torch.cuda.is_available() else False
-    if headline and torch.cuda.is_available():  # HIP start-up, code-object load and the first queue are not catalog setup: pay them on a throw-away engine
+    if full and headline and torch.cuda.is_available():  # HIP start-up, code-object load and the first queue are not catalog setup: pay them on a throw-away engine
         COMPOSITIONS[comp_name](pe, inj).engine(device=dev, rank=rank, world=world).close()
     t_setup = time.perf_counter()
     eng = comp.engine(device=dev, rank=rank, world=world)
@@ -579,10 +591,10 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
         def step(i):
             return vg(thetas[i % len(thetas)])
 
-    # N > 1: before timing, rank 0 checks the sharded evaluation against an unsharded engine over the whole catalog on
-    # its own GPU (same theta)
+    # N > 1 with `full`: before timing, rank 0 checks the sharded evaluation against an unsharded engine over the whole catalog
+    # on its own GPU (same theta)
     sharded_check = None
-    if dist is not None:
+    if dist is not None and full:
         ll_sh, g_sh = step(0)
         g_sh = np.array(g_sh)
         if rank == 0:
@@ -598,7 +610,7 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
 
     in_library = sharded is None and os.environ.get("GWI_BENCH_PYTHON_LOOP") != "1"
     seq = np.stack([thetas[i % len(thetas)] for i in range(max(steps, warmup, 64))])
-    clocks_before = read_clocks(dev) if rank == 0 else None
+    clocks_before = read_clocks(dev) if rank == 0 and full else None
 
     # ---- clocks up: >= spin_s seconds of evaluations whatever --steps / --warmup say (a 20-step run lasts 0.4 ms, during
     # which the GPU would still be at its idle clocks).  Rank 0 decides the count so that all ranks issue the same number.
@@ -629,10 +641,10 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
         timed = eng.configure_sequence(seq[:steps], total, min_neff_cut=False)  # buffers and marshalling outside the timed region
         run.fence()
         t0 = time.perf_counter()
-        ll_seq, _ = timed()  # ---- the timed region: exactly K steps, one library call ----
+        ll_seq, grad_seq = timed()  # ---- the timed region: exactly K steps, one library call ----
         run.fence()
         elapsed = time.perf_counter() - t0
-        last_ll = float(ll_seq[-1])
+        last_ll, last_grad = float(ll_seq[-1]), np.array(grad_seq[-1], dtype=np.float64)
     else:
         for i in range(warmup):
             step(i)
@@ -642,8 +654,40 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
             res = step(i)
         run.fence()
         elapsed = time.perf_counter() - t0
-        last_ll = float(res[0])
+        last_ll, last_grad = float(res[0]), np.array(res[1], dtype=np.float64)
     elapsed = run.max_over_ranks(elapsed)
+    # what a caller of the timed path received from its last step (bench.py --dump-outputs)
+    outputs = {"log_likelihood": np.array([last_ll], dtype=np.float64), "grad": last_grad}
+    config_block = {
+        "workload": desc,
+        "composition": comp_name,
+        "n_events": int(n_ev),
+        "n_pe": int(n_pe),
+        "n_inj": int(n_inj),
+        "n_theta": int(eng.n_theta),
+        "flags": "min_neff_cut=False (tests/inference_test.py:185)",
+        "parallelism": f"events+injections sharded over {world} rank(s), one exchange of partial records per eval" if dist is not None else "single GPU",
+    }
+    if dist is not None:
+        key = "shm" if exchange.startswith("host shared-memory") else ("rccl_allgather" if exchange.startswith("ncclAllGather") else "torch_all_gather")
+        rccl_ranks = world if (key == "rccl_allgather" or (key == "torch_all_gather" and run.backend == "nccl")) else 0
+        multi_gpu_block = {"ranks": world, "rccl_ranks": rccl_ranks, "headline_exchange_key": key, "rendezvous_backend": run.backend, "exchange": exchange,
+                           "devices_shared_between_ranks": run.shared_devices}
+
+    if not full:
+        # a plain run: the headline figure and nothing else
+        out = None
+        if rank == 0:
+            out = {"value": steps / elapsed, "unit": "evals/s", "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
+                   "warm_spin": {"seconds_requested": spin_s, "evaluations": n_spin},
+                   "step_loop": "gwi_eval_sequence: K blocking evaluations in a C loop inside the library" if in_library else "Python loop over the configured closure",
+                   "config": config_block, "last_log_likelihood": last_ll, "scan_chain": {"name": eng.scan_kernel_name(), **eng.jit_info()}, "outputs": outputs}
+            if dist is not None:
+                out["multi_gpu"] = multi_gpu_block
+        if dist is not None:
+            dist.barrier()
+        eng.close()
+        return out
 
     # ---- latency distribution: >= 1000 evaluations timed one by one inside the library (median, p5/p95)
     n_lat = max(1000, steps)
@@ -677,17 +721,15 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
                                 "median_ms_per_step": float(np.median(lat) * 1e3)})
 
     # ---- the same loop driven from Python through the allocation-free closure (what a NumPy sampler pays per step)
-    python_driven = None
-    if full:
-        n_py = min(max(steps, 200), 2000)
-        for i in range(min(50, n_py)):
-            step(i)
-        run.fence()
-        t0p = time.perf_counter()
-        for i in range(n_py):
-            step(i)
-        run.fence()
-        python_driven = n_py / run.max_over_ranks(time.perf_counter() - t0p)
+    n_py = min(max(steps, 200), 2000)
+    for i in range(min(50, n_py)):
+        step(i)
+    run.fence()
+    t0p = time.perf_counter()
+    for i in range(n_py):
+        step(i)
+    run.fence()
+    python_driven = n_py / run.max_over_ranks(time.perf_counter() - t0p)
 
     # ---- N > 1, secondary figures: (a) one independent chain per GPU over the WHOLE catalog (numpyro
     # chain_method="parallel"): no exchange, per-GPU work fixed (weak scaling); (b) the same sharded evaluation with the
@@ -720,7 +762,7 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
             eng_shm.close()
 
     replicas = None
-    if dist is not None and full:
+    if dist is not None:
         rep = COMPOSITIONS[comp_name](pe, inj)
         eng_rep = rep.engine(device=dev)
         n_rep = max(200, steps // 2)
@@ -750,16 +792,7 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
             "warm_spin": {"seconds_requested": spin_s, "evaluations": n_spin},
             "step_loop": "gwi_eval_sequence: K blocking evaluations in a C loop inside the library" if in_library else "Python loop over the configured closure",
             "python_driven_evals_per_s": python_driven,
-            "config": {
-                "workload": desc,
-                "composition": comp_name,
-                "n_events": int(n_ev),
-                "n_pe": int(n_pe),
-                "n_inj": int(n_inj),
-                "n_theta": int(eng.n_theta),
-                "flags": "min_neff_cut=False (tests/inference_test.py:185)",
-                "parallelism": f"events+injections sharded over {world} rank(s), one exchange of partial records per eval" if dist is not None else "single GPU",
-            },
+            "config": config_block,
             "roofline": {
                 "bound": "hbm",
                 "kernel": "scan_kernel",
@@ -793,8 +826,9 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
             # which scan kernel ran: an ahead-of-time chain by name, a chain compiled at gwi_create by hipRTC ("jit:..."; the time
             # that cost this process, 0 when the disk cache supplied the code object) or the generic kernel
             "scan_chain": {"name": eng.scan_kernel_name(), **eng.jit_info()},
+            "outputs": outputs,
         }
-        if dist is None and headline and full:
+        if dist is None and headline:
             # What the NumPyro seam adds on the host (likelihood._host_callback: the function jax.pure_callback calls once per leapfrog):
             # theta array in -> engine -> packed (summary, per-event sites, gradient) arrays out, without JAX's own dispatch and
             # device synchronisation around the callback, which no image here can measure.
@@ -825,11 +859,7 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
             except Exception as exc:
                 out["numpyro_seam"] = {"error": repr(exc)}
         if dist is not None:
-            key = "shm" if exchange.startswith("host shared-memory") else ("rccl_allgather" if exchange.startswith("ncclAllGather") else "torch_all_gather")
-            rccl_ranks = world if (key == "rccl_allgather" or (key == "torch_all_gather" and run.backend == "nccl")) else 0
-            out["multi_gpu"] = {"ranks": world, "rccl_ranks": rccl_ranks, "headline_exchange_key": key, "rendezvous_backend": run.backend, "exchange": exchange,
-                                "devices_shared_between_ranks": run.shared_devices, "per_rank": per_rank, "sharded_vs_single_gpu": sharded_check,
-                                "independent_chains": replicas}
+            out["multi_gpu"] = dict(multi_gpu_block, per_rank=per_rank, sharded_vs_single_gpu=sharded_check, independent_chains=replicas)
             if shm_side is not None:
                 out["multi_gpu"]["shm_side"] = shm_side
         else:
@@ -878,16 +908,15 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
                                           "useful_note": "frac_of_78.6 counts issued matrix-core flops; a quarter of them (4 of 16 rows per column) carry taps",
                                           "source": (pmc_table("batched_k16") or {}).get("source"),
                                           "what": "the design-matrix contraction sum_s w_s B_p(x_s) for 16 hyper-parameter points per wavefront (gwi_mfma.h); A = 16 bases x 4 samples with 4 non-zero taps per column"}
-            # several sets in flight (full: from T host threads and from one; default run: the one-thread form for the headline only)
-            if full or headline:
-                try:
-                    out["batched"]["sets_in_flight"] = sets_in_flight(eng, comp_name, pe, inj, total, tb, K, steps, dev, threaded=full)
-                except Exception as exc:  # a secondary figure: never the reason a line is missing
-                    out["batched"]["sets_in_flight"] = {"error": repr(exc)}
+            # several sets in flight, from T host threads and from one
+            try:
+                out["batched"]["sets_in_flight"] = sets_in_flight(eng, comp_name, pe, inj, total, tb, K, steps, dev, threaded=True)
+            except Exception as exc:  # a secondary figure: never the reason a line is missing
+                out["batched"]["sets_in_flight"] = {"error": repr(exc)}
             # the other batched kernels on the same batch, where the model has them (spline models): the 4-tap kernel (one
             # grid row per point, LDS atomics) and the LDS-row variant of the 16-points-per-wavefront kernel
             alts = {}
-            for alt_name, env_kv in ((("taps", {"GWI_BATCH_MFMA": "0"}), ("mfma", {"GWI_BATCH_MFMA": "1"}), ("rows", {"GWI_BATCH_ROWS": "1"})) if full else ()):
+            for alt_name, env_kv in ((("taps", {"GWI_BATCH_MFMA": "0"}), ("mfma", {"GWI_BATCH_MFMA": "1"}), ("rows", {"GWI_BATCH_ROWS": "1"}))):
                 saved = {k_: os.environ.get(k_) for k_ in env_kv}
                 os.environ.update(env_kv)
                 try:
@@ -912,9 +941,9 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
                 out["batched"]["other_paths"] = alts
                 out["batched"]["paths"] = ("taps: one grid row per point, 4-tap gradient into LDS rows (scan_kernel BATCH); mfma: 16 points per wavefront, gradient as "
                                            "v_mfma_f64_16x16x4 tiles (gwi_mfma.h); rows: the same kernel with the gradient in conflict-free LDS rows")
-        if dist is None and headline and chains > 1 and full:
+        if dist is None and headline and chains > 1:
             out.update(multi_chain(eng, comp, comp_name, pe, inj, total, thetas, chains, steps, dev))
-        elif dist is None and nuts_chains > 1 and full:
+        elif dist is None and nuts_chains > 1:
             # configs 3 / 5: the sampler figure under the reference's priors, on engines of its own
             comps = [comp] + [COMPOSITIONS[comp_name](pe, inj) for _ in range(nuts_chains - 1)]
             engs = [eng] + [c.engine(device=dev) for c in comps[1:]]
@@ -927,7 +956,7 @@ def measure(run, cfg, steps, warmup, timing_every, spin_s=0.6, headline=False, w
             for e in engs[1:]:
                 e.close()
         if with_cpu and world == 1:  # reported at N = 1 only (rank 0), as the contract asks
-            out["cpu_baseline"] = cpu_baseline(comp, comp_name, pe, inj, pool, thetas, total, budget_s=cpu_budget_s, numpy_reference=full and cfg != "c5")
+            out["cpu_baseline"] = cpu_baseline(comp, comp_name, pe, inj, pool, thetas, total, budget_s=cpu_budget_s, numpy_reference=cfg != "c5")
     if dist is not None:
         dist.barrier()
     eng.close()
@@ -1151,7 +1180,7 @@ def native_nuts(engines, comp_name, comp, total, thetas, n_warmup=300, n_samples
     n_lf_sampling = float(np.sum(2.0 ** depth - 1.0))
     t_sampling = dt * min(1.0, n_lf_sampling / max(n_lf, 1))
     if not convergence_fields:
-        # config 5: 300 warm-up iterations (the wall time of the default run is bounded through the iteration count) are fewer than the
+        # config 5: 300 warm-up iterations (the wall time of the --full run is bounded through the iteration count) are fewer than the
         # reference's 1 000 (pipeline/utils.py:29-39), and after them the chains' mean log posteriors still lie thousands apart on this
         # catalog: effective sample sizes and R-hat of such draws are evidence of nothing and are not reported.  The throughput is.
         return {"chains": C, "host_threads": C, "warmup_iterations": n_warmup, "sampling_iterations": n_samples, "max_tree_depth": 10, "evals": n_lf, "evals_per_s": n_lf / dt,
@@ -1335,15 +1364,21 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS), help="headline configuration (default: BASELINE config 2, the one the metric is quoted on)")
-    ap.add_argument("--also", default=None, help="comma-separated further configs reported under `configs` (default with headline c2: c3,c5,b50k,def50k at N = 1, c3,c5 at N > 1; 'none' disables)")
-    ap.add_argument("--full", action="store_true", help="also run the secondary legs (sets in flight, the other batched kernels, chains, the library's NUTS, host-side setup, NumPy reference formulation); they go to the detail file")
+    ap.add_argument("--also", default=None, help="comma-separated further configs reported under `configs` (default with --full and headline c2: c3,c5,b50k,def50k at N = 1, "
+                                                  "c3,c5 at N > 1; otherwise none; 'none' disables)")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps, run every other leg: latency distribution, kernel durations and roofline, blocking K-point "
+                                                         "batches, CPU baseline, the further configs, sets in flight, the other batched kernels, chains, the library's NUTS, "
+                                                         "host-side setup, NumPy reference formulation; they go to the detail file")
     ap.add_argument("--detail", default="bench_detail.json", help="side file for everything that is not in the compact line ('' disables)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--k-batch", type=int, default=16, help="also time batched evaluation (K hyper-points per launch); 0 disables")
-    ap.add_argument("--chains", type=int, default=4, help="also time this many independent chains interleaved on one GPU (begin/end); <= 1 disables")
-    ap.add_argument("--timing-every", type=int, default=10, help="kernel begin/end timing on every n-th step of the kernel-timing block")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step of the headline returned (log_likelihood, grad) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline")
+    ap.add_argument("--k-batch", type=int, default=16, help="(--full) also time batched evaluation (K hyper-points per launch); 0 disables")
+    ap.add_argument("--chains", type=int, default=4, help="(--full) also time this many independent chains interleaved on one GPU (begin/end); <= 1 disables")
+    ap.add_argument("--timing-every", type=int, default=10, help="(--full) kernel begin/end timing on every n-th step of the kernel-timing block")
     ap.add_argument("--spin", type=float, default=0.6, help="seconds of untimed evaluations before the timed region (GPU clocks up)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ and os.environ.get("GWI_FORCE_SHARDED") != "1":
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -1383,18 +1418,24 @@ def main():
                     rccl_leg["rccl_debug_tail"] = f"rank {fails[0]['rank']}: {fails[0]['tail']}"[-300:]
     also = args.also
     if also is None:
-        also = ("c3,c5,b50k,def50k" if args.gpus == 1 else "c3,c5") if args.config == "c2" else "none"
+        also = ("c3,c5,b50k,def50k" if args.gpus == 1 else "c3,c5") if args.config == "c2" and args.full else "none"
     extra_cfgs = [c for c in also.split(",") if c and c != "none" and c != args.config]
 
     head = measure(run, args.config, args.steps, args.warmup, args.timing_every, spin_s=args.spin, headline=True, with_cpu=not args.no_cpu_baseline, k_batch=args.k_batch,
                    chains=args.chains, prefer_rccl=prefer_rccl, full=args.full, cpu_budget_s=6.0)
+    if run.rank == 0:
+        outputs = head.pop("outputs")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
     blocks = {}
     for cfg in extra_cfgs:
         # the other BASELINE configurations with the same procedure (their own warm-up, K and latency blocks: sized so that
-        # the default run stays within minutes)
+        # the --full run stays within minutes)
         k = {"c5": 300, "c3": 600}.get(cfg, 600)
         blocks[cfg] = measure(run, cfg, k, 50, args.timing_every, spin_s=min(args.spin, 0.3), headline=False, with_cpu=not args.no_cpu_baseline, k_batch=args.k_batch, chains=0,
                               nuts_chains=args.chains, prefer_rccl=prefer_rccl, full=args.full, cpu_budget_s=2.0)
+        if blocks[cfg] is not None:
+            blocks[cfg].pop("outputs")
 
     if run.rank == 0:
         out = {

@@ -78,3 +78,26 @@ def test_an_oversized_line_sheds_secondary_blocks_not_the_contract():
     for key in CONTRACT:
         assert key in line and line[key] is not None or key == "vs_baseline"
     assert isinstance(line["configs"], str) and "dropped" in line["configs"]
+
+
+def test_plain_run_line_and_output_dump(tmp_path):
+    """A run without --full: the detail holds the timed steps only; the line still carries the contract's keys with their
+    meaning (value = steps / elapsed, ms_per_step = elapsed / steps) and says null for the legs that did not run.
+    `dump_outputs` writes the last timed step's arrays as float64 .npy files."""
+    import numpy as np
+
+    full = canned(CANNED[0])
+    detail = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+                                   "config")}
+    detail["scan_chain"] = {"name": "plpeak+plq+plz"}
+    line = json.loads(bench.dump_line(bench.compact_line(detail, None)), parse_constant=refuse_constants)
+    for key in CONTRACT:
+        assert key in line, key
+    assert line["value"] == pytest.approx(full["value"], rel=1e-5) and line["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["unit"] == "evals/s"
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["batched"] is None and "configs" not in line
+    outputs = {"log_likelihood": np.array([-160.08]), "grad": np.linspace(-1.0, 1.0, 6)}
+    bench.dump_outputs(str(tmp_path / "out"), outputs)
+    for name, arr in outputs.items():
+        got = np.load(tmp_path / "out" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, arr)

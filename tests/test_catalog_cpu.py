@@ -89,20 +89,39 @@ def test_read_pe_netcdf3_roundtrip(tmp_path):
         assert np.array_equal(pedict[p], np.stack([events[n][i, :8].astype(np.float64) for n in names]))
 
 
-_REF_PE = "/root/reference/tests/data/xarray_GWTC3_BBH_69evs_downsampled_1000samps_nospin.h5"
+def test_reader_on_the_reference_pe_file(tmp_path):
+    """A file in the layout of the reference's own GWTC-3 PE tensor (xarray's NetCDF-3 64-bit-offset output: 69 events x 9
+    params x 1000 samples, `_FillValue` on every event variable, `_Encoding` on the char `param` coordinate), whose first 64
+    samples per event are those of tests/golden/gwtc3_first64.nc and whose other 936 are seeded draws: the product reader's
+    first 64 samples equal the PE arrays stored in the committed GWTC-3 golden case (which the generator read independently),
+    and without `n_samples` it returns all 1000."""
+    from scipy.io import netcdf_file
 
+    from golden_util import GOLDEN_DIR, GoldenCase
 
-@pytest.mark.skipif(not os.path.exists(_REF_PE), reason="reference tree only exists in the build container")
-def test_reader_on_the_reference_pe_file():
-    """The reference's own GWTC-3 PE tensor, read by the product reader, equals the PE arrays stored in the
-    committed GWTC-3 golden case (which the generator read independently)."""
-    from golden_util import GoldenCase
-
-    pe, events = cat.read_pe_netcdf3(_REF_PE, n_samples=64)
+    path = str(tmp_path / "gwtc3_1000samps.h5")
+    rest = np.random.default_rng(69).uniform(0.0, 1.0, size=(9, 936)).astype(">f4")
+    with netcdf_file(os.path.join(GOLDEN_DIR, "gwtc3_first64.nc"), "r", mmap=False) as src, netcdf_file(path, "w", version=2) as f:
+        f.createDimension("param", 9)
+        f.createDimension("sample", 1000)
+        f.createDimension("string10", 10)
+        f.createVariable("sample", ">i4", ("sample",))[:] = np.arange(1000)
+        for name, v in src.variables.items():
+            if name not in ("param", "sample"):
+                ev = f.createVariable(name, ">f4", ("param", "sample"))
+                ev._FillValue = np.float32(np.nan)
+                ev[:] = np.concatenate([v.data, rest], axis=1)
+        p = f.createVariable("param", "S1", ("param", "string10"))
+        p._Encoding = "utf-8"
+        p[:] = src.variables["param"].data
+    pe, events = cat.read_pe_netcdf3(path, n_samples=64)
     case = GoldenCase("gwtc3_pl_test")
     assert len(events) == 69
     for k, v in case.pe.items():
         assert np.array_equal(pe[k], v), k
+    whole, _ = cat.read_pe_netcdf3(path)
+    for i, k in enumerate(whole):
+        assert whole[k].shape == (69, 1000) and np.array_equal(whole[k][:, :64], pe[k]) and np.array_equal(whole[k][:, 64:], np.broadcast_to(rest[i].astype(np.float64), (69, 936)))
 
 
 def _hdf5_or_skip():

@@ -197,7 +197,7 @@ def test_bench_multi_gpu_headline_is_the_rccl_exchange(tmp_path):
         env.pop(k, None)
     detail_file = str(tmp_path / "detail.json")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "200", "--warmup", "20", "--also", "none", "--no-cpu-baseline", "--k-batch", "0", "--chains", "0",
-           "--spin", "0.1", "--detail", detail_file]
+           "--spin", "0.1", "--detail", detail_file, "--full"]
     child = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     try:
         out, err = child.communicate(timeout=600)
@@ -239,7 +239,7 @@ def test_bench_in_the_drivers_launch_form_with_two_ranks_on_this_box(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "200", "--warmup", "20"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "200", "--warmup", "20", "--full"]
     child = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=str(tmp_path), start_new_session=True)
     try:
         out, err = child.communicate(timeout=900)

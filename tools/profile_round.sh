@@ -9,7 +9,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 CONFIGS=${@:-c2 c3 c5 b50k def50k}
 cd /tmp && export TMPDIR=/tmp
-B="--no-cpu-baseline --k-batch 0 --chains 0 --also none --spin 0.2 --detail /dev/null"
+B="--full --no-cpu-baseline --k-batch 0 --chains 0 --also none --spin 0.2 --detail /dev/null"
 for c in $CONFIGS; do
   out=$R/gpurun_out/prof/$c
   mkdir -p $out
@@ -19,7 +19,7 @@ for c in $CONFIGS; do
   rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_LDS --output-format csv -d $out/sq_a -- python3 $R/bench.py --config $c --steps 60 --warmup 10 $B --timing-every 0 > /dev/null 2>&1
   rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD --output-format csv -d $out/sq_b -- python3 $R/bench.py --config $c --steps 60 --warmup 10 $B --timing-every 0 > /dev/null 2>&1
   rocprofv3 --pmc SQ_LDS_ADDR_CONFLICT SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $out/lds -- python3 $R/bench.py --config $c --steps 60 --warmup 10 $B --timing-every 0 > /dev/null 2>&1
-  python3 $R/bench.py --config $c --steps 2000 --warmup 200 --also none --detail $out/bench_detail.json > $out/bench.json 2> /dev/null
+  python3 $R/bench.py --config $c --steps 2000 --warmup 200 --full --also none --detail $out/bench_detail.json > $out/bench.json 2> /dev/null
 done
 for c in c3 c5 b50k def50k; do
   for path in taps mfma rows; do
