@@ -255,9 +255,16 @@ EXPORTED_SYMBOLS = [
     "gwi_scan_kernel_name",
     "gwi_jit_compile",
     "gwi_jit_info",
+    "gwi_eval_batch_sharded",
+    "gwi_eval_batch_sharded_begin",
+    "gwi_eval_batch_sharded_end",
+    "gwi_eval_batch_partial",
+    "gwi_combine_batch",
+    "gwi_shm_exchange_batch",
 ]
 # ... and include/gwi_sampler.h
-EXPORTED_SYMBOLS += ["gwi_nuts_run", "gwi_nuts_engine", "gwi_nuts_run_lockstep", "gwi_nuts_engine_lockstep", "gwi_nuts_lockstep_stats", "gwi_nuts_run_queue", "gwi_nuts_engine_queue"]
+EXPORTED_SYMBOLS += ["gwi_nuts_run", "gwi_nuts_engine", "gwi_nuts_run_lockstep", "gwi_nuts_engine_lockstep", "gwi_nuts_lockstep_stats", "gwi_nuts_run_queue", "gwi_nuts_engine_queue",
+                     "gwi_nuts_engine_queue_sharded"]
 
 _lib = None
 
@@ -335,6 +342,19 @@ def load_library():
     lib.gwi_shm_comm_unlink.argtypes = [C.c_char_p]
     lib.gwi_shm_exchange.restype = C.c_int32
     lib.gwi_shm_exchange.argtypes = [vp, _DP, _DP]
+    if hasattr(lib, "gwi_eval_batch_sharded"):  # sharded batches: K points per exchange (absent from older builds)
+        lib.gwi_eval_batch_sharded.restype = C.c_int32
+        lib.gwi_eval_batch_sharded.argtypes = [vp, _DP, C.c_int32, C.POINTER(GwiOptions), C.POINTER(GwiSummary), _DP, _DP, _DP, _DP, _DP]
+        lib.gwi_eval_batch_sharded_begin.restype = C.c_int32
+        lib.gwi_eval_batch_sharded_begin.argtypes = [vp, _DP, C.c_int32, C.POINTER(GwiOptions), C.c_int32, C.c_int32]
+        lib.gwi_eval_batch_sharded_end.restype = C.c_int32
+        lib.gwi_eval_batch_sharded_end.argtypes = [vp, C.POINTER(GwiSummary), _DP, _DP, _DP, _DP, _DP]
+        lib.gwi_eval_batch_partial.restype = C.c_int32
+        lib.gwi_eval_batch_partial.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _DP, _DP]
+        lib.gwi_combine_batch.restype = C.c_int32
+        lib.gwi_combine_batch.argtypes = [vp, _DP, C.c_int32, _DP, C.c_int32, C.POINTER(GwiOptions), C.POINTER(GwiSummary), _DP, _DP]
+        lib.gwi_shm_exchange_batch.restype = C.c_int32
+        lib.gwi_shm_exchange_batch.argtypes = [vp, _DP, C.c_int32, _DP]
     lib.gwi_eval_latencies.restype = C.c_int32
     lib.gwi_eval_latencies.argtypes = [vp, _DP, C.c_int32, C.POINTER(GwiOptions), _DP]
     lib.gwi_batch_path.restype = C.c_char_p
@@ -400,6 +420,9 @@ def load_library():
         lib.gwi_nuts_engine_queue.restype = C.c_int32
         lib.gwi_nuts_engine_queue.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GwiOptions), C.POINTER(GwiParamPrior), C.POINTER(GwiSmoothingPenalty),
                                               C.c_int32, _DP, C.POINTER(GwiNutsOptions), _DP, _DP, _IP, C.POINTER(GwiNutsResult)]
+    if hasattr(lib, "gwi_nuts_engine_queue_sharded"):
+        lib.gwi_nuts_engine_queue_sharded.restype = C.c_int32
+        lib.gwi_nuts_engine_queue_sharded.argtypes = lib.gwi_nuts_engine_queue.argtypes
     if lib.gwi_abi_version() != GWI_ABI_VERSION:
         raise NativeEngineError(f"ABI mismatch: library {lib.gwi_abi_version()} vs binding {GWI_ABI_VERSION}")
     _lib = lib

@@ -2698,6 +2698,30 @@ __global__ __launch_bounds__(kBlock) void publish_kernel(const double* gathered,
   publish_stamp(host, seq, threadIdx.x);
 }
 
+// ---- after the all-gather of a BATCH (gwi_eval_batch_sharded, in-engine RCCL): gathered[world][K][len] -> host[K][world][len],
+//      so that the records of point k lie contiguously in the layout assemble() reads.  One workgroup per point, each with its
+//      own completion stamp in slot 0 of its block, written last.  A negative event count (record[7]: a rank's scan asked for
+//      the two-pass repeat) in any rank's record of any point stores `seq` into the one word redo_host before the stamp. ----
+__global__ __launch_bounds__(kBlock) void publish_batch_kernel(const double* gathered, double* host, unsigned long long* redo_host, int world, int K, int len,
+                                                               unsigned long long seq) {
+  __shared__ int s_redo;
+  const int k = blockIdx.x, tid = threadIdx.x, n = world * len;
+  if (tid == 0) s_redo = 0;
+  __syncthreads();
+  double* dst = host + (size_t)k * n;
+  bool redo = false;
+  for (int i = tid; i < n; i += kBlock) {
+    const int r = i / len, j = i - r * len;
+    const double v = gathered[((size_t)r * K + k) * len + j];
+    redo = redo || (j == 7 && v < 0.0);
+    if (i != 0) store_sys(dst + i, v);
+  }
+  if (redo) s_redo = 1;  // (every writer stores the same value)
+  __syncthreads();
+  if (tid == 0 && s_redo) __hip_atomic_store(redo_host, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  publish_stamp(dst, seq, tid);
+}
+
 // ---- measured HBM bandwidth (gwi_hbm_bandwidth): a read-only sweep and a STREAM triad, 16-byte accesses, grid-stride ----
 __global__ __launch_bounds__(kBlock) void bw_read_kernel(const double2* __restrict__ a, long long n2, double* out, int n_blocks /* = gridDim.x, passed explicitly: no implicit kernel arguments in this code object */) {
   // four independent 16-byte NON-TEMPORAL loads in flight per lane, 32 workgroups per CU: the best of the variants in

@@ -5,6 +5,7 @@
 #include "gwi_aql.h"
 #include "gwi_ingest.h"
 #include "gwi_jit.h"
+#include "gwi_sampler_queue.h"
 
 #include <hip/hip_ext.h>
 
@@ -462,8 +463,9 @@ struct gwi_engine {
   // in-engine RCCL communicator (optional)
   void* nccl_comm = nullptr;
   int comm_rank = 0, comm_world = 1;
-  double *d_send = nullptr, *d_recv = nullptr;
-  double *h_gather = nullptr, *h_gather_dev = nullptr;
+  double *d_send = nullptr, *d_recv = nullptr;  // [max_batch][len] / [world][max_batch][len]
+  double *h_gather = nullptr, *h_gather_dev = nullptr;  // pinned: [max_batch][world][len] (publish_batch_kernel), then one word:
+  unsigned long long *h_gather_redo = nullptr, *h_gather_redo_dev = nullptr;  // ... a gathered record asked for the repeat (= seq)
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // start/stop pairs: scan, combine, final
   float last_ms[3] = {0, 0, 0};
   bool timed_final = false;
@@ -471,6 +473,7 @@ struct gwi_engine {
   bool pending = false;          // gwi_eval_begin issued, gwi_eval_end not yet called
   bool pending_sq = false;
   bool pending_batch = false;          // ... the pending evaluation is a batch (gwi_eval_batch_begin)
+  bool pending_sharded = false;        // ... a sharded batch (gwi_eval_batch_sharded_begin)
   int pending_k = 0;
   std::vector<double> pending_thetas;
   gwi_options pending_opt{};
@@ -811,10 +814,10 @@ gwi_status launch_scan(gwi_handle h, bool logw, int K = 1, bool batch = false) {
   return GWI_OK;
 }
 
-gwi_status wait_for_stamp(gwi_handle h, double* host_buf, int K = 1);
+gwi_status wait_for_stamp(gwi_handle h, double* host_buf, int K = 1, size_t stride = 0);
 void merge_final_records(gwi_handle h, int K);
 gwi_status wait_for_rows(gwi_handle h, int K = 1);
-gwi_status wait_for_norms(gwi_handle h, double* record, int K = 1);
+gwi_status wait_for_norms(gwi_handle h, double* record, int K = 1, size_t stride = 0);
 
 // launches scan -> combine -> final; `record_dev` is where final_kernel publishes (pinned host record
 // or, for the sharded path, the device send buffer); `wait` polls the pinned completion stamp.
@@ -1152,8 +1155,9 @@ gwi_status aql_wait_slow(gwi_handle h, Ready ready, const char* what) {
   }
 }
 
-// the normaliser launch publishes Z_j + a stamp per normaliser; copy them into rank 0's record slots
-gwi_status wait_for_norms(gwi_handle h, double* record, int K) {
+// the normaliser launch publishes Z_j + a stamp per normaliser; copy them into rank 0's record slots (point k's at
+// record + k * stride; stride 0: one record per point)
+gwi_status wait_for_norms(gwi_handle h, double* record, int K, size_t stride) {
   const int n = h->spec.n_norms;
   if (n == 0) return GWI_OK;
   const int total = n * K;
@@ -1176,9 +1180,9 @@ gwi_status wait_for_norms(gwi_handle h, double* record, int K) {
       if (h->h_norm_stamp[j] != h->seq) return fail(h, GWI_ERR_HIP, "normaliser stamp mismatch after stream synchronise");
   }
   std::atomic_thread_fence(std::memory_order_acquire);
-  const int len = record_len(h);
+  const size_t step = stride ? stride : (size_t)record_len(h);
   for (int k = 0; k < K; ++k)
-    for (int j = 0; j < n; ++j) record[(size_t)k * len + kRecNormOff + j] = h->h_norm[k * n + j];
+    for (int j = 0; j < n; ++j) record[(size_t)k * step + kRecNormOff + j] = h->h_norm[k * n + j];
   return GWI_OK;
 }
 
@@ -1227,11 +1231,12 @@ void merge_final_records(gwi_handle h, int K) {
   }
 }
 
-gwi_status wait_for_stamp(gwi_handle h, double* host_buf, int K) {
+gwi_status wait_for_stamp(gwi_handle h, double* host_buf, int K, size_t stride) {
   // Completion: final_kernel stores the sequence stamp into pinned host memory LAST (system-scope
   // release after __threadfence_system), so the host can poll it instead of paying a stream
   // synchronise; after ~2 ms of polling fall back to the blocking call (and surface any error).
-  const size_t len = (size_t)record_len(h);
+  // Stamp k sits at host_buf + k * stride (stride 0: one record per stamp).
+  const size_t len = stride ? stride : (size_t)record_len(h);
   auto stamp_of = [&](int k) { return *reinterpret_cast<volatile unsigned long long*>(host_buf + (size_t)k * len); };
   bool done = false;
   if (!h->timing && h->spin_wait) {
@@ -2693,7 +2698,7 @@ gwi_status gwi_eval_batch_begin(gwi_handle h, const double* thetas, int32_t k_ba
 
 gwi_status gwi_eval_batch_end(gwi_handle h, gwi_summary* summaries, double* grads, double* log_bfs, double* log_neffs, double* variances, double* norms) {
   if (!h) return GWI_ERR_INVALID;
-  if (!h->pending || !h->pending_batch) return fail(h, GWI_ERR_INVALID, "gwi_eval_batch_end without gwi_eval_batch_begin");
+  if (!h->pending || !h->pending_batch || h->pending_sharded) return fail(h, GWI_ERR_INVALID, "gwi_eval_batch_end without gwi_eval_batch_begin");
   h->pending = false;
   h->pending_batch = false;
   GWI_HIP(hipSetDevice(h->device));
@@ -2758,20 +2763,78 @@ gwi_status gwi_comm_init(gwi_handle h, const char* rccl_path, const void* id128,
   h->comm_rank = rank;
   h->comm_world = world;
   const size_t len = (size_t)record_len(h);
-  GWI_HIP(hipMalloc(&h->d_send, sizeof(double) * len));
-  GWI_HIP(hipMalloc(&h->d_recv, sizeof(double) * len * world));
-  GWI_HIP(hipHostMalloc((void**)&h->h_gather, sizeof(double) * len * world, hipHostMallocMapped));
+  // room for a batch of max_batch points (gwi_eval_batch_sharded): K records per rank in ONE all-gather
+  const size_t KB = (size_t)h->max_batch, gather_doubles = len * world * KB;
+  GWI_HIP(hipMalloc(&h->d_send, sizeof(double) * len * KB));
+  GWI_HIP(hipMalloc(&h->d_recv, sizeof(double) * gather_doubles));
+  GWI_HIP(hipHostMalloc((void**)&h->h_gather, sizeof(double) * (gather_doubles + 1), hipHostMallocMapped));
   GWI_HIP(hipHostGetDevicePointer((void**)&h->h_gather_dev, h->h_gather, 0));
-  std::memset(h->h_gather, 0, sizeof(double) * len * world);
+  std::memset(h->h_gather, 0, sizeof(double) * (gather_doubles + 1));
+  h->h_gather_redo = reinterpret_cast<unsigned long long*>(h->h_gather + gather_doubles);
+  h->h_gather_redo_dev = reinterpret_cast<unsigned long long*>(h->h_gather_dev + gather_doubles);
   return GWI_OK;
 }
 
 
 // ---- single-node record exchange through POSIX shared memory ------------------------------------------------------
-// Segment: [2 parities][world ranks] slots of { u64 stamp; double record[len] }, each padded to a multiple of 128 B.
-// Exchange s (s = 1, 2, ...): write the record into slot [s & 1][rank], release-store the stamp s, then acquire-poll
-// the stamps of all ranks.  Two parities suffice: a rank can only reach exchange s + 2 after every rank has published
-// s + 1, i.e. after every rank has finished READING exchange s.
+// Segment: [2 parities][world ranks] slots of { u64 stamp; i32 K; i32 status; double records[K][len] }, each padded to a
+// multiple of 128 B.  A slot has room for kShmMaxRecords records -- the hard cap on GWI_MAX_BATCH -- whatever the rank's own
+// max_batch, so every rank computes the same segment size.  Exchange s (s = 1, 2, ...): write K, the status and the records
+// into slot [s & 1][rank], release-store the stamp s, then acquire-poll the stamps of all ranks.  Two parities suffice: a rank
+// can only reach exchange s + 2 after every rank has published s + 1, i.e. after every rank has finished READING exchange s.
+// A rank whose local half failed still publishes its stamp, with its (non-zero) status and no records; a rank that finds a
+// failed status, or a K other than its own, returns -- once every rank has published the exchange -- with an error that names
+// that rank.
+constexpr int kShmMaxRecords = 64;
+struct ShmHeader {
+  unsigned long long stamp;
+  int32_t k, status;
+};
+static_assert(sizeof(ShmHeader) == 16, "records follow the header 16-byte aligned");
+
+static size_t shm_slot_size(size_t len) { return ((sizeof(ShmHeader) + sizeof(double) * len * kShmMaxRecords + 127) / 128) * 128; }
+
+// publish this rank's K records (status != 0: its failure, no records), wait for every rank's, copy them to gathered[world][K][len].
+// Every rank, a failing one included, waits until every rank has published the exchange (none can then still be reading its slot
+// when it reaches the exchange after next); a failing rank returns GWI_OK: the failure it reports is its own.
+static gwi_status shm_exchange_k(gwi_handle h, const double* records, int K, int32_t status, double* gathered) {
+  const size_t len = (size_t)record_len(h);
+  const unsigned long long s = ++h->shm_seq;
+  char* const bank = h->shm_base + (size_t)(s & 1) * h->shm_slot_bytes * (size_t)h->shm_world;
+  char* mine = bank + (size_t)h->shm_rank * h->shm_slot_bytes;
+  ShmHeader* head = reinterpret_cast<ShmHeader*>(mine);
+  head->k = K;
+  head->status = status;
+  if (status == 0) std::memcpy(mine + sizeof(ShmHeader), records, sizeof(double) * len * (size_t)K);
+  __atomic_store_n(&head->stamp, s, __ATOMIC_RELEASE);
+  // every rank waits for EVERY rank's stamp, whatever it finds on the way: only then can no rank still be reading this bank when
+  // another reaches exchange s + 2 and rewrites it.  The first failure or mismatch found is reported after the loop.
+  const auto t0 = std::chrono::steady_clock::now();
+  gwi_status bad = GWI_OK;
+  std::string why;
+  for (int r = 0; r < h->shm_world; ++r) {
+    const char* theirs = bank + (size_t)r * h->shm_slot_bytes;
+    const ShmHeader* th = reinterpret_cast<const ShmHeader*>(theirs);
+    for (unsigned long long spin = 1; __atomic_load_n(&th->stamp, __ATOMIC_ACQUIRE) != s; ++spin) {
+      __builtin_ia32_pause();
+      if ((spin & 0xfffff) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0)
+        return fail(h, GWI_ERR_TIMEOUT, "shared-memory exchange: rank " + std::to_string(r) + " did not publish exchange " + std::to_string(s) + " within 60 s");
+    }
+    if (status != 0 || bad != GWI_OK) continue;
+    if (th->status != 0) {
+      bad = th->status;
+      why = "shared-memory exchange " + std::to_string(s) + ": rank " + std::to_string(r) + " failed its local evaluation (status " + std::to_string(th->status) + ")";
+    } else if (th->k != K) {
+      bad = GWI_ERR_INVALID;
+      why = "shared-memory exchange " + std::to_string(s) + ": rank " + std::to_string(r) + " published " + std::to_string(th->k) + " records, rank " +
+            std::to_string(h->shm_rank) + " " + std::to_string(K) + " (every rank must issue the same batches)";
+    } else {
+      std::memcpy(gathered + (size_t)r * K * len, theirs + sizeof(ShmHeader), sizeof(double) * len * (size_t)K);
+    }
+  }
+  return bad == GWI_OK ? GWI_OK : fail(h, bad, why);
+}
+
 gwi_status gwi_shm_comm_unlink(const char* name) {
   if (!name || !*name) return GWI_ERR_INVALID;
   return shm_unlink(name) == 0 ? GWI_OK : GWI_ERR_INVALID;
@@ -2781,16 +2844,23 @@ gwi_status gwi_shm_comm_init(gwi_handle h, const char* name, int32_t rank, int32
   if (!h || !name || !*name || world < 1 || rank < 0 || rank >= world) return GWI_ERR_INVALID;
   if (h->shm_base) return fail(h, GWI_ERR_INVALID, "gwi_shm_comm_init: already attached");
   const size_t len = (size_t)record_len(h);
-  const size_t slot = ((sizeof(unsigned long long) + sizeof(double) * len + 127) / 128) * 128;
+  const size_t slot = shm_slot_size(len);
   const size_t bytes = slot * 2 * (size_t)world;
   const int fd = shm_open(name, O_CREAT | O_RDWR, 0600);
   if (fd < 0) return fail(h, GWI_ERR_INVALID, std::string("shm_open(") + name + "): " + std::strerror(errno));
   struct stat sb;
-  // every rank sizes the (zero-filled) segment to the same length; whoever comes later finds it sized already
-  if (fstat(fd, &sb) != 0 || ((size_t)sb.st_size != bytes && ftruncate(fd, (off_t)bytes) != 0)) {
+  // every rank computes the same length (the slots do not depend on max_batch) and sizes the zero-filled segment to it; whoever
+  // comes later finds it sized already.  A segment of another length belongs to ranks that disagree about the model or the world
+  // size: refused, not resized under a rank that may have mapped it.
+  if (fstat(fd, &sb) != 0 || (sb.st_size == 0 && ftruncate(fd, (off_t)bytes) != 0)) {
     const std::string why = std::strerror(errno);
     close(fd);
     return fail(h, GWI_ERR_INVALID, std::string("sizing shared-memory segment ") + name + ": " + why);
+  }
+  if (fstat(fd, &sb) != 0 || (size_t)sb.st_size != bytes) {
+    close(fd);
+    return fail(h, GWI_ERR_INVALID, std::string("shared-memory segment ") + name + " has " + std::to_string((long long)sb.st_size) + " bytes, rank " +
+                                        std::to_string(rank) + " expects " + std::to_string(bytes) + " (same model and world size on every rank?)");
   }
   void* base = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
   close(fd);
@@ -2810,24 +2880,14 @@ gwi_status gwi_shm_comm_init(gwi_handle h, const char* name, int32_t rank, int32
 gwi_status gwi_shm_exchange(gwi_handle h, const double* record, double* gathered) {
   if (!h || !record || !gathered) return GWI_ERR_INVALID;
   if (!h->shm_base) return fail(h, GWI_ERR_INVALID, "gwi_shm_comm_init has not been called");
-  const size_t len = (size_t)record_len(h);
-  const unsigned long long s = ++h->shm_seq;
-  char* const bank = h->shm_base + (size_t)(s & 1) * h->shm_slot_bytes * (size_t)h->shm_world;
-  char* mine = bank + (size_t)h->shm_rank * h->shm_slot_bytes;
-  std::memcpy(mine + sizeof(unsigned long long), record, sizeof(double) * len);
-  __atomic_store_n(reinterpret_cast<unsigned long long*>(mine), s, __ATOMIC_RELEASE);
-  const auto t0 = std::chrono::steady_clock::now();
-  for (int r = 0; r < h->shm_world; ++r) {
-    const char* theirs = bank + (size_t)r * h->shm_slot_bytes;
-    const unsigned long long* stamp = reinterpret_cast<const unsigned long long*>(theirs);
-    for (unsigned long long spin = 1; __atomic_load_n(stamp, __ATOMIC_ACQUIRE) != s; ++spin) {
-      __builtin_ia32_pause();
-      if ((spin & 0xfffff) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 60.0)
-        return fail(h, GWI_ERR_TIMEOUT, "shared-memory exchange: rank " + std::to_string(r) + " did not publish exchange " + std::to_string(s) + " within 60 s");
-    }
-    std::memcpy(gathered + (size_t)r * len, theirs + sizeof(unsigned long long), sizeof(double) * len);
-  }
-  return GWI_OK;
+  return shm_exchange_k(h, record, 1, 0, gathered);
+}
+
+gwi_status gwi_shm_exchange_batch(gwi_handle h, const double* records, int32_t k, double* gathered) {
+  if (!h || k < 1 || (records && !gathered)) return GWI_ERR_INVALID;
+  if (k > kShmMaxRecords) return fail(h, GWI_ERR_INVALID, "gwi_shm_exchange_batch: k exceeds 64 records");
+  if (!h->shm_base) return fail(h, GWI_ERR_INVALID, "gwi_shm_comm_init has not been called");
+  return shm_exchange_k(h, records, k, records ? 0 : GWI_ERR_HIP, gathered);
 }
 
 gwi_status gwi_eval_sharded(gwi_handle h, const double* theta, const gwi_options* opt, gwi_summary* summary, double* grad, double* log_bfs,
@@ -2899,6 +2959,267 @@ gwi_status gwi_eval_sharded(gwi_handle h, const double* theta, const gwi_options
   if (log_neffs) std::memcpy(log_neffs, h->h_ev + n, sizeof(double) * n);
   if (variances) std::memcpy(variances, h->h_ev + 2 * n, sizeof(double) * n);
   return GWI_OK;
+}
+
+// ---- K points per exchange: the sharded counterpart of gwi_eval_batch -----------------------------------------------
+// the sample-independent constants of K points (what gwi_prepare_combine computes for one)
+static void host_constants(gwi_handle h, const double* thetas, int K, double* consts) {
+  std::vector<double> th(h->spec.n_theta);
+  std::vector<double> der((size_t)kMaxDerived * (h->spec.n_terms > 0 ? h->spec.n_terms : 1));
+  for (int k = 0; k < K; ++k)
+    prelude(h, thetas + (size_t)k * h->spec.n_theta, th.data(), reinterpret_cast<double (*)[kMaxDerived]>(der.data()), &consts[k]);
+}
+
+// point k's result from records[k][n_ranks][len] (the ranks' records of point k in rank order, as gwi_combine reads them)
+static void assemble_points(gwi_handle h, const double* records, const double* records_sq, int n_ranks, int K, const gwi_options* opt, const double* consts,
+                            gwi_summary* summaries, double* grads, double* norms) {
+  const size_t blk = (size_t)n_ranks * record_len(h);
+  const int n_theta = h->spec.n_theta, n_norms = h->spec.n_norms;
+  for (int k = 0; k < K; ++k) {
+    gwi_summary s;
+    assemble(h, records + k * blk, n_ranks, opt, &s, grads ? grads + (size_t)k * n_theta : nullptr, norms ? norms + (size_t)k * n_norms : nullptr, consts[k],
+             records_sq ? records_sq + k * blk : nullptr);
+    if (summaries) summaries[k] = s;
+  }
+}
+
+// [n_ranks][K][len] -> [K][n_ranks][len]
+static void points_major(const double* in, int n_ranks, int K, size_t len, std::vector<double>& out) {
+  out.resize((size_t)n_ranks * K * len);
+  for (int r = 0; r < n_ranks; ++r)
+    for (int k = 0; k < K; ++k) std::memcpy(out.data() + ((size_t)k * n_ranks + r) * len, in + ((size_t)r * K + k) * len, sizeof(double) * len);
+}
+
+// this rank's per-event sites of point k with the global constant of the assembled summary
+static void local_sites(gwi_handle h, int K, const gwi_summary* summaries, double* log_bfs, double* log_neffs, double* variances) {
+  const size_t n = (size_t)h->n_ev;
+  for (int k = 0; k < K; ++k) {
+    const double* ev = h->h_ev + (size_t)k * 3 * n;
+    const double shift = summaries[k].log_norm_const - std::log((double)h->n_pe);
+    if (log_bfs)
+      for (size_t i = 0; i < n; ++i) log_bfs[k * n + i] = ev[i] + shift;
+    if (log_neffs) std::memcpy(log_neffs + k * n, ev + n, sizeof(double) * n);
+    if (variances) std::memcpy(variances + k * n, ev + 2 * n, sizeof(double) * n);
+  }
+}
+
+gwi_status gwi_eval_batch_partial(gwi_handle h, const double* thetas, int32_t k, double* records, double* log_bfs, double* log_neffs, double* variances) {
+  if (!h || !thetas || !h->variant || k < 1) return GWI_ERR_INVALID;
+  if (k > h->max_batch) return fail(h, GWI_ERR_INVALID, "k exceeds the engine's max_batch (GWI_MAX_BATCH, default 16)");
+  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
+  gwi_status st = busy_guard(h, "gwi_eval_batch_partial");
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipSetDevice(h->device));
+  h->batch_events = log_bfs || log_neffs || variances;
+  st = run_pipeline(h, thetas, nullptr, /*wait=*/true, k, /*batch=*/true);
+  if (st != GWI_OK) return st;
+  if (records) std::memcpy(records, h->h_record, sizeof(double) * record_len(h) * (size_t)k);
+  const size_t n = (size_t)h->n_ev;
+  // per-event sites without the global constant (added by the caller after gwi_combine_batch)
+  for (int p = 0; p < k; ++p) {
+    const double* ev = h->h_ev + (size_t)p * 3 * n;
+    if (log_bfs) std::memcpy(log_bfs + p * n, ev, sizeof(double) * n);
+    if (log_neffs) std::memcpy(log_neffs + p * n, ev + n, sizeof(double) * n);
+    if (variances) std::memcpy(variances + p * n, ev + 2 * n, sizeof(double) * n);
+  }
+  return GWI_OK;
+}
+
+gwi_status gwi_combine_batch(gwi_handle h, const double* thetas, int32_t k, const double* records, int32_t n_ranks, const gwi_options* opt, gwi_summary* summaries,
+                             double* grads, double* norms) {
+  if (!h || !thetas || !records || k < 1 || n_ranks < 1 || !opt) return GWI_ERR_INVALID;
+  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
+    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
+  if (opt->marginalize_selection && grads)
+    return fail(h, GWI_ERR_UNSUPPORTED, "gradient with marginalize_selection=True needs the squared-weight records, which the caller-exchanged path (gwi_eval_batch_partial / gwi_combine_batch) does not carry: use gwi_eval_batch_sharded");
+  std::vector<double> consts(k), by_point;
+  host_constants(h, thetas, k, consts.data());
+  points_major(records, n_ranks, k, (size_t)record_len(h), by_point);
+  assemble_points(h, by_point.data(), nullptr, n_ranks, k, opt, consts.data(), summaries, grads, norms);
+  return GWI_OK;
+}
+
+// In-engine RCCL: scan -> combine -> final ([K][len] into the device send buffer) -> ONE all-gather of K * len doubles ->
+// publish_batch_kernel ([K][world][len] in pinned host memory, a stamp per point, the repeat marks folded into one word)
+static gwi_status rccl_batch_issue(gwi_handle h, const double* thetas, int K, bool square) {
+  const size_t len = (size_t)record_len(h);
+  gwi_status st = run_pipeline(h, thetas, h->d_send, /*wait=*/false, K, /*batch=*/true, square);
+  if (st != GWI_OK) return st;
+  const int rc = g_nccl.AllGather(h->d_send, h->d_recv, len * (size_t)K, kNcclDouble, h->nccl_comm, h->stream);
+  if (rc != 0) return fail(h, GWI_ERR_HIP, std::string("ncclAllGather: ") + (g_nccl.GetErrorString ? g_nccl.GetErrorString(rc) : "error"));
+  hipLaunchKernelGGL(publish_batch_kernel, dim3((unsigned)K), dim3(kBlock), 0, h->stream, h->d_recv, h->h_gather_dev, h->h_gather_redo_dev, h->comm_world, K, (int)len, h->seq);
+  GWI_HIP(hipGetLastError());
+  return GWI_OK;
+}
+static gwi_status rccl_batch_wait(gwi_handle h, int K) {
+  const size_t stride = (size_t)record_len(h) * (size_t)h->comm_world;
+  const gwi_status st = wait_for_stamp(h, h->h_gather, K, stride);
+  if (st != GWI_OK) return st;
+  return wait_for_norms(h, h->h_gather, K, stride);  // every rank integrates the same grids: rank 0's slots of each point
+}
+static bool rccl_batch_redo(const gwi_engine* h) { return *reinterpret_cast<volatile unsigned long long*>(h->h_gather_redo) == h->seq; }
+// after a collected batch: a rank whose scan asked for the two-pass repeat marked its record, every rank sees the mark in the
+// gathered records and all repeat the whole batch together (the single-point path's protocol)
+static gwi_status rccl_batch_repeat(gwi_handle h, const double* thetas, int K, bool square) {
+  if (!rccl_batch_redo(h)) return GWI_OK;
+  ++h->redo_count;
+  gwi_status st = rccl_batch_issue(h, thetas, K, square);
+  if (st == GWI_OK) st = rccl_batch_wait(h, K);
+  if (st != GWI_OK || !rccl_batch_redo(h) || !h->variant->has(jit::kSafe)) return st;
+  h->kargs.two_pass = 1;
+  st = rccl_batch_issue(h, thetas, K, square);
+  if (st == GWI_OK) st = rccl_batch_wait(h, K);
+  h->kargs.two_pass = 0;
+  return st;
+}
+
+// Shared memory: this rank's K records through the regular batched path (repeated locally, before publishing, when a scan asks
+// for it); a local failure is published too, so that the other ranks return at once.  Leaves [K][world][len] in sq / h->shm_gather.
+static gwi_status shm_batch_exchange(gwi_handle h, int K, gwi_status local, std::vector<double>& by_point) {
+  if (local != GWI_OK) {
+    const std::string why = h->err;
+    (void)shm_exchange_k(h, nullptr, K, local, nullptr);
+    h->err = why;
+    return local;
+  }
+  const size_t len = (size_t)record_len(h);
+  std::vector<double>& gathered = h->shm_gather;
+  gathered.resize(len * (size_t)h->shm_world * K);
+  const gwi_status st = shm_exchange_k(h, h->h_record, K, 0, gathered.data());
+  if (st != GWI_OK) return st;
+  points_major(gathered.data(), h->shm_world, K, len, by_point);
+  return GWI_OK;
+}
+
+// Over shared memory, a rank whose half of a batch fails before it has taken part in that batch's exchange publishes the failure
+// (the other ranks then return at once instead of after the exchange's time-out); `seq0` = the handle's exchange count when the
+// entry point was called.  Failures of the exchange itself, and the local failures shm_batch_exchange publishes, have advanced it.
+static gwi_status publish_unexchanged_failure(gwi_handle h, gwi_status st, unsigned long long seq0, int K) {
+  if (st == GWI_OK || !h->shm_base || h->shm_seq != seq0) return st;
+  const std::string why = h->err;
+  (void)shm_exchange_k(h, nullptr, K < 1 ? 1 : (K > kShmMaxRecords ? kShmMaxRecords : K), st, nullptr);
+  h->err = why;
+  return st;
+}
+
+static gwi_status sharded_begin_impl(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, int32_t want_grad, int32_t want_events) {
+  if (!thetas || !opt || !h->variant || k_batch < 1) return GWI_ERR_INVALID;
+  if (!h->nccl_comm && !h->shm_base) return fail(h, GWI_ERR_INVALID, "neither gwi_shm_comm_init nor gwi_comm_init has been called");
+  if (k_batch > h->max_batch) return fail(h, GWI_ERR_INVALID, "k_batch exceeds the engine's max_batch (GWI_MAX_BATCH, default 16)");
+  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
+    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
+  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
+  gwi_status st = busy_guard(h, "gwi_eval_batch_sharded_begin");
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipSetDevice(h->device));
+  h->pending_opt = *opt;
+  h->pending_sq = opt->marginalize_selection && want_grad;
+  h->pending_k = k_batch;
+  h->pending_thetas.assign(thetas, thetas + (size_t)k_batch * h->spec.n_theta);
+  h->batch_events = want_events != 0;
+  // the same batched kernel as gwi_eval_batch would run (a matrix-core kernel still to be compiled is compiled now)
+  if (h->mfma_jit_pending && k_batch >= h->mfma_min_batch) h->batch_autotune = try_jit_mfma(h) && h->autotune_wanted;
+  if (h->batch_autotune && h->mfma && k_batch >= h->mfma_min_batch) {
+    st = calibrate_batch_path(h, thetas, k_batch);
+    if (st != GWI_OK) return st;
+  }
+  if (h->pending_sq) {  // a first exchange, blocking, carries the K squared-weight records
+    if (h->shm_base) {
+      st = shm_batch_exchange(h, k_batch, run_pipeline(h, thetas, nullptr, true, k_batch, true, /*square=*/true), h->sq_records);
+    } else {
+      st = rccl_batch_issue(h, thetas, k_batch, true);
+      if (st == GWI_OK) st = rccl_batch_wait(h, k_batch);
+      if (st == GWI_OK) st = rccl_batch_repeat(h, thetas, k_batch, true);
+      if (st == GWI_OK) h->sq_records.assign(h->h_gather, h->h_gather + (size_t)record_len(h) * h->comm_world * k_batch);
+    }
+    if (st != GWI_OK) return st;
+  }
+  if (h->shm_base) {
+    st = run_pipeline(h, thetas, nullptr, /*wait=*/false, k_batch, true);
+    if (st != GWI_OK) {
+      std::vector<double> none;
+      return shm_batch_exchange(h, k_batch, st, none);  // publishes the failure: the other ranks return at once
+    }
+  } else {
+    st = rccl_batch_issue(h, thetas, k_batch, false);
+    if (st != GWI_OK) return st;
+  }
+  h->pending = true;
+  h->pending_batch = true;
+  h->pending_sharded = true;
+  return GWI_OK;
+}
+
+static gwi_status sharded_end_impl(gwi_handle h, gwi_summary* summaries, double* grads, double* log_bfs, double* log_neffs, double* variances, double* norms) {
+  h->pending = false;
+  h->pending_batch = false;
+  h->pending_sharded = false;
+  GWI_HIP(hipSetDevice(h->device));
+  const int K = h->pending_k;
+  const double* thetas = h->pending_thetas.data();
+  const bool need_sq = h->pending_sq && grads;
+  gwi_status st;
+  std::vector<double> by_point;
+  const double* recs;
+  int n_ranks;
+  if (h->shm_base) {
+    if (h->last_host_rows) {
+      st = wait_for_rows(h, K);
+    } else {
+      st = wait_for_stamp(h, h->h_fin, K * h->final_groups);
+      if (st == GWI_OK) merge_final_records(h, K);
+      if (st == GWI_OK) st = wait_for_norms(h, h->h_record, K);
+    }
+    if (st == GWI_OK && redo_requested(h)) st = repeat_after_redo(h, thetas, nullptr, K, true, false);  // before publishing
+    st = shm_batch_exchange(h, K, st, by_point);
+    if (st != GWI_OK) return st;
+    recs = by_point.data();
+    n_ranks = h->shm_world;
+  } else {
+    st = rccl_batch_wait(h, K);
+    if (st == GWI_OK) st = rccl_batch_repeat(h, thetas, K, false);
+    if (st != GWI_OK) return st;
+    recs = h->h_gather;
+    n_ranks = h->comm_world;
+  }
+  std::vector<double> consts(h->host_consts.begin(), h->host_consts.begin() + K);
+  std::vector<gwi_summary> s(K);
+  assemble_points(h, recs, need_sq ? h->sq_records.data() : nullptr, n_ranks, K, &h->pending_opt, consts.data(), s.data(), grads, norms);
+  if (summaries) std::memcpy(summaries, s.data(), sizeof(gwi_summary) * K);
+  local_sites(h, K, s.data(), log_bfs, log_neffs, variances);
+  return GWI_OK;
+}
+
+gwi_status gwi_eval_batch_sharded_begin(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, int32_t want_grad, int32_t want_events) {
+  if (!h) return GWI_ERR_INVALID;
+  // (a handle with a batch in flight owes that batch's exchange to gwi_eval_batch_sharded_end: nothing is published for the misuse)
+  if (h->pending) return busy_guard(h, "gwi_eval_batch_sharded_begin");
+  const unsigned long long seq0 = h->shm_seq;
+  return publish_unexchanged_failure(h, sharded_begin_impl(h, thetas, k_batch, opt, want_grad, want_events), seq0, k_batch);
+}
+
+gwi_status gwi_eval_batch_sharded_end(gwi_handle h, gwi_summary* summaries, double* grads, double* log_bfs, double* log_neffs, double* variances, double* norms) {
+  if (!h) return GWI_ERR_INVALID;
+  if (!h->pending || !h->pending_sharded) return fail(h, GWI_ERR_INVALID, "gwi_eval_batch_sharded_end without gwi_eval_batch_sharded_begin");
+  const unsigned long long seq0 = h->shm_seq;
+  return publish_unexchanged_failure(h, sharded_end_impl(h, summaries, grads, log_bfs, log_neffs, variances, norms), seq0, h->pending_k);
+}
+
+gwi_status gwi_eval_batch_sharded(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, gwi_summary* summaries, double* grads,
+                                  double* log_bfs, double* log_neffs, double* variances, double* norms) {
+  const gwi_status st = gwi_eval_batch_sharded_begin(h, thetas, k_batch, opt, grads != nullptr, (log_bfs || log_neffs || variances) ? 1 : 0);
+  if (st != GWI_OK) return st;
+  return gwi_eval_batch_sharded_end(h, summaries, grads, log_bfs, log_neffs, variances, norms);
+}
+
+gwi_status gwi_nuts_engine_queue_sharded(const gwi_handle* handles, int32_t n_groups, int32_t slots_per_group, int32_t n_chains, int32_t n_theta, const gwi_options* lopt,
+                                         const gwi_param_prior* priors, const gwi_smoothing_penalty* penalties, int32_t n_penalties, const double* u0,
+                                         const gwi_nuts_options* opt, double* samples, double* log_prob, int32_t* tree_depth, gwi_nuts_result* results) {
+  if (!handles || n_groups < 1) return GWI_ERR_INVALID;
+  for (int g = 0; g < n_groups; ++g)
+    if (!handles[g] || (!handles[g]->nccl_comm && !handles[g]->shm_base)) return handles[g] ? fail(handles[g], GWI_ERR_INVALID, "gwi_nuts_engine_queue_sharded: a handle without an exchange (gwi_shm_comm_init / gwi_comm_init)") : GWI_ERR_INVALID;
+  return gwi_detail::nuts_engine_queue_with(&gwi_eval_batch_sharded_begin, &gwi_eval_batch_sharded_end, handles, n_groups, slots_per_group, n_chains, n_theta, lopt, priors,
+                                            penalties, n_penalties, u0, opt, samples, log_prob, tree_depth, results);
 }
 
 gwi_status gwi_selftime(gwi_handle h, const double* theta, const gwi_options* opt, int32_t n_iter, double* seconds_per_eval) {

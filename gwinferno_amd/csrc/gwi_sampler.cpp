@@ -20,6 +20,7 @@
 //                     and is resumed with the batch's result.  One host thread, G groups of chains (an engine each) in
 //                     flight: group g's launches run while the others' chains do their host arithmetic.
 #include "gwi_sampler.h"
+#include "gwi_sampler_queue.h"
 
 #include <ucontext.h>
 
@@ -419,7 +420,7 @@ struct Fiber {
   int chain = 0, group = 0;
   ucontext_t ctx{};
   std::unique_ptr<char[]> stack;
-  bool done = false, waiting = false;
+  bool started = false, done = false, waiting = false;
   int rc = 0;
   const double* req_x = nullptr;  // the point this chain wants evaluated (dim doubles, owned by the chain)
   double* out_lp = nullptr;
@@ -463,6 +464,7 @@ struct Lockstep {
     swapcontext(&sched, &f.ctx);
   }
   void start(Fiber& f) {
+    f.started = true;
     f.stack.reset(new char[kStack]);
     getcontext(&f.ctx);
     f.ctx.uc_stack.ss_sp = f.stack.get();
@@ -581,9 +583,9 @@ struct Lockstep {
     if (print_stats && n_batches > 0)
       std::fprintf(stderr, "[gwi lockstep] %lld batches, %.2f points each; per batch: collect %.1f us, chains %.1f us, issue %.1f us; wall %.3f s\n", n_batches,
                    (double)n_points / n_batches, 1e6 * t_end / n_batches, 1e6 * t_host / n_batches, 1e6 * t_issue / n_batches, since(t_all));
-    if (failed)  // let every chain that is still asleep unwind (its target now returns 1 without switching)
-      for (Fiber& f : fibers)
-        while (!f.done) resume(f);
+    if (failed)  // let every chain that is still asleep unwind (its target now returns 1 without switching); queued chains
+      for (Fiber& f : fibers)  // that never started have no context to switch to
+        while (f.started && !f.done) resume(f);
     return failed ? 1 : 0;
   }
 };
@@ -605,11 +607,13 @@ struct CallbackBackend : LockstepBackend {  // an arbitrary batched target: eval
 struct EngineBackend : LockstepBackend {  // group g = engine handles[g]; the points are constrained hyper-parameters
   const gwi_handle* handles;
   gwi_options lopt;
+  gwi_detail::BatchBeginFn begin_fn = nullptr;  // gwi_eval_batch_begin / _end, or their sharded counterparts
+  gwi_detail::BatchEndFn end_fn = nullptr;
   std::vector<gwi_summary> summaries;
-  int begin(int g, int k, const int32_t*, const double* thetas) override { return gwi_eval_batch_begin(handles[g], thetas, k, &lopt, 1, 0) != GWI_OK; }
+  int begin(int g, int k, const int32_t*, const double* thetas) override { return begin_fn(handles[g], thetas, k, &lopt, 1, 0) != GWI_OK; }
   int end(int g, int k, double* lls, double* grads) override {
     summaries.resize(k);
-    if (gwi_eval_batch_end(handles[g], summaries.data(), grads, nullptr, nullptr, nullptr, nullptr) != GWI_OK) return 1;
+    if (end_fn(handles[g], summaries.data(), grads, nullptr, nullptr, nullptr, nullptr) != GWI_OK) return 1;
     for (int j = 0; j < k; ++j) lls[j] = summaries[j].log_likelihood;
     return 0;
   }
@@ -731,6 +735,18 @@ gwi_status gwi_nuts_engine_lockstep(const gwi_handle* handles, int32_t n_groups,
 gwi_status gwi_nuts_engine_queue(const gwi_handle* handles, int32_t n_groups, int32_t slots_per_group, int32_t n_chains, int32_t n_theta, const gwi_options* lopt,
                                  const gwi_param_prior* priors, const gwi_smoothing_penalty* pens, int32_t n_pens, const double* u0, const gwi_nuts_options* opt, double* samples,
                                  double* logp, int32_t* tree_depth, gwi_nuts_result* results) {
+  return gwi_detail::nuts_engine_queue_with(&gwi_eval_batch_begin, &gwi_eval_batch_end, handles, n_groups, slots_per_group, n_chains, n_theta, lopt, priors, pens, n_pens, u0,
+                                            opt, samples, logp, tree_depth, results);
+}
+
+}  // extern "C"
+
+// the body of gwi_nuts_engine_queue on a given pair of batch halves (gwi_nuts_engine_queue_sharded, gwi_engine.hip, passes the
+// sharded ones: this file references no other engine entry point)
+gwi_status gwi_detail::nuts_engine_queue_with(BatchBeginFn begin_fn, BatchEndFn end_fn, const gwi_handle* handles, int32_t n_groups, int32_t slots_per_group,
+                                              int32_t n_chains, int32_t n_theta, const gwi_options* lopt, const gwi_param_prior* priors, const gwi_smoothing_penalty* pens,
+                                              int32_t n_pens, const double* u0, const gwi_nuts_options* opt, double* samples, double* logp, int32_t* tree_depth,
+                                              gwi_nuts_result* results) {
   const int chains_per_group = slots_per_group;
   if (!handles || n_groups < 1 || slots_per_group < 1 || n_chains < 1 || n_theta < 1 || !lopt || !priors || !u0 || !opt || !samples) return GWI_ERR_INVALID;
   for (int k = 0; k < n_pens; ++k)
@@ -778,6 +794,8 @@ gwi_status gwi_nuts_engine_queue(const gwi_handle* handles, int32_t n_groups, in
   EngineBackend be;
   be.handles = handles;
   be.lopt = *lopt;
+  be.begin_fn = begin_fn;
+  be.end_fn = end_fn;
   const int failed = ls.run(be, n_groups, queued ? slots_per_group : 0);
   if (failed) return GWI_ERR_HIP;
   for (int c = 0; c < n_chains; ++c) {
@@ -786,5 +804,3 @@ gwi_status gwi_nuts_engine_queue(const gwi_handle* handles, int32_t n_groups, in
   }
   return GWI_OK;
 }
-
-}  // extern "C"

@@ -111,3 +111,37 @@ class ShardedLikelihood:
         # local per-event sites (this rank's events), global constant applied
         shift = res.summary.log_norm_const - np.log(self.engine.n_pe)
         return EvalResult(log_likelihood=res.log_likelihood, grad=res.grad, summary=res.summary, log_bfs=lb + shift, log_neffs=ln, variances=lv, norms=res.norms)
+
+    def gather_batch_records(self, records):
+        """All-gather K partial records per rank in ONE collective of K * len doubles -> (world, K, len) float64 array (same on all
+        ranks)."""
+        t = self.torch
+        records = np.ascontiguousarray(records, dtype=np.float64)
+        K, n = records.shape
+        bufs = getattr(self, "_batch_bufs", {})
+        if K not in bufs:
+            host = t.zeros(K * n, dtype=t.float64)
+            bufs[K] = (t.zeros(K * n, dtype=t.float64, device=self.device), t.zeros(self.world * K * n, dtype=t.float64, device=self.device),
+                       host.pin_memory() if self.device.type == "cuda" else host)
+            self._batch_bufs = bufs
+        send, recv, host = bufs[K]
+        host.copy_(t.from_numpy(records.reshape(-1)))
+        send.copy_(host, non_blocking=True)
+        self.dist.all_gather_into_tensor(recv, send, group=self.group)
+        return recv.cpu().numpy().reshape(self.world, K, n)
+
+    def evaluate_batch(self, thetas, marginalize_selection=False, min_neff_cut=True, max_variance_cut=False, want_grad=True):
+        """K points ``thetas[K, n_theta]`` per exchange: this rank's K partial records from one batched set of launches
+        (``eval_batch_partial``), one all-gather, and the same K results on every rank (``combine_batch``).  Returns a list of K
+        :class:`EvalResult` whose per-event arrays are this rank's events."""
+        thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        rec, lb, ln, lv = self.engine.eval_batch_partial(thetas)
+        records = self.gather_batch_records(rec)
+        results = self.engine.combine_batch(thetas, records, self.total_inj, nobs=self.engine.n_ev_global, marginalize_selection=marginalize_selection,
+                                            min_neff_cut=min_neff_cut, max_variance_cut=max_variance_cut, want_grad=want_grad)
+        out = []
+        for k, res in enumerate(results):
+            shift = res.summary.log_norm_const - np.log(self.engine.n_pe)
+            out.append(EvalResult(log_likelihood=res.log_likelihood, grad=res.grad, summary=res.summary, log_bfs=lb[k] + shift, log_neffs=ln[k], variances=lv[k],
+                                  norms=res.norms))
+        return out

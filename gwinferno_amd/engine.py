@@ -456,6 +456,8 @@ class NativePopulationLikelihood:
         self._keep = None  # the engine copied everything it needs
         self.bytes_per_sample = 8 * spec.n_cols
         self.partial_len = int(self.lib.gwi_partial_len(self.handle))
+        # points per batched launch: what gwi_create read from GWI_MAX_BATCH (default 16, clamped to [1, 64])
+        self.max_batch = min(64, max(1, int(os.environ.get("GWI_MAX_BATCH", "16") or 16)))
 
     # ---------------------------------------------------------------------------------------------
     def _check(self, st):
@@ -515,6 +517,15 @@ class NativePopulationLikelihood:
     def evaluate_batch(self, thetas, total_inj, nobs=None, marginalize_selection=False, min_neff_cut=True, max_variance_cut=False, want_grad=True):
         """K hyper-parameter points in one set of launches (vectorised chains).  ``thetas``: (K, n_theta).
         Returns a list of K :class:`EvalResult`."""
+        return self._evaluate_batch_with(self.lib.gwi_eval_batch, thetas, total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut, want_grad)
+
+    def evaluate_batch_sharded(self, thetas, total_inj, nobs=None, marginalize_selection=False, min_neff_cut=True, max_variance_cut=False, want_grad=True):
+        """:meth:`evaluate_batch` for an engine built with ``rank=/world=`` after :meth:`shm_comm_init` or :meth:`comm_init`
+        (``gwi_eval_batch_sharded``): this rank's shard for all K points, ONE exchange of K records per rank, the same K global
+        results on every rank.  Per-event arrays are this rank's events."""
+        return self._evaluate_batch_with(self.lib.gwi_eval_batch_sharded, thetas, total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut, want_grad)
+
+    def _evaluate_batch_with(self, fn, thetas, total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut, want_grad):
         thetas = N.f64(thetas)
         if thetas.ndim != 2 or thetas.shape[1] != self.n_theta:
             raise ValueError(f"thetas must have shape (K, {self.n_theta})")
@@ -525,7 +536,7 @@ class NativePopulationLikelihood:
         lb, ln, lv = np.zeros((K, self.n_ev)), np.zeros((K, self.n_ev)), np.zeros((K, self.n_ev))
         n_norms = len(self.bound.norms)
         norms = np.zeros((K, max(n_norms, 1)))
-        self._check(self.lib.gwi_eval_batch(self.handle, N.as_dp(thetas), K, C.byref(opt), summ, N.as_dp(grads), N.as_dp(lb), N.as_dp(ln), N.as_dp(lv), N.as_dp(norms)))
+        self._check(fn(self.handle, N.as_dp(thetas), K, C.byref(opt), summ, N.as_dp(grads), N.as_dp(lb), N.as_dp(ln), N.as_dp(lv), N.as_dp(norms)))
         return [EvalResult(log_likelihood=summ[k].log_likelihood, grad=grads[k] if want_grad else None, summary=summ[k], log_bfs=lb[k], log_neffs=ln[k], variances=lv[k],
                            norms=norms[k, :n_norms]) for k in range(K)]
 
@@ -630,13 +641,20 @@ class NativePopulationLikelihood:
         """The batched counterpart of :meth:`configure` for vectorised chains: returns
         ``values_and_grads(thetas[K, n_theta]) -> (log_likelihood[K], grad[K, n_theta])`` writing into
         buffers allocated once (valid until the next call)."""
+        return self._configure_batch_with(self.lib.gwi_eval_batch, k_batch, total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut)
+
+    def configure_batch_sharded(self, k_batch, total_inj, nobs=None, marginalize_selection=False, min_neff_cut=True, max_variance_cut=False):
+        """:meth:`configure_batch` on a sharded engine (``gwi_eval_batch_sharded``): every rank calls the closure with the same
+        points and gets the same global values and gradients."""
+        return self._configure_batch_with(self.lib.gwi_eval_batch_sharded, k_batch, total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut)
+
+    def _configure_batch_with(self, fn, k_batch, total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut):
         K = int(k_batch)
         opt = self._options(total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut)
         summ = (N.GwiSummary * K)()
         thetas_buf, grads = np.zeros((K, self.n_theta)), np.zeros((K, self.n_theta))
         values = np.zeros(K)
         args = (self.handle, N.as_dp(thetas_buf), K, C.byref(opt), summ, N.as_dp(grads), None, None, None, None)
-        fn = self.lib.gwi_eval_batch
         # log_likelihood is the first double of each gwi_summary: view them without a Python loop
         summ_view = np.frombuffer(summ, dtype=np.float64).reshape(K, -1)[:, 0]
 
@@ -656,23 +674,32 @@ class NativePopulationLikelihood:
         issues the launches of the K points and returns, ``end() -> (log_likelihood[K], grad[K, n_theta])`` waits for them (buffers
         allocated once, valid until the next ``end``).  Two or three engines driven alternately from ONE thread keep as many sets in
         flight: the scans of the others run while a set is in its combine / final launches and on the host."""
+        return self._configure_batch_async_with(self.lib.gwi_eval_batch_begin, self.lib.gwi_eval_batch_end, k_batch, total_inj, nobs, marginalize_selection, min_neff_cut,
+                                                max_variance_cut)
+
+    def configure_batch_sharded_async(self, k_batch, total_inj, nobs=None, marginalize_selection=False, min_neff_cut=True, max_variance_cut=False):
+        """:meth:`configure_batch_async` on a sharded engine (``gwi_eval_batch_sharded_begin`` / ``_end``): ``begin`` issues this
+        rank's launches, ``end`` waits for them, exchanges the K records and assembles."""
+        return self._configure_batch_async_with(self.lib.gwi_eval_batch_sharded_begin, self.lib.gwi_eval_batch_sharded_end, k_batch, total_inj, nobs, marginalize_selection,
+                                                min_neff_cut, max_variance_cut)
+
+    def _configure_batch_async_with(self, fn_begin, fn_end, k_batch, total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut):
         K = int(k_batch)
         opt = self._options(total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut)
         summ = (N.GwiSummary * K)()
         thetas_buf, grads, values = np.zeros((K, self.n_theta)), np.zeros((K, self.n_theta)), np.zeros(K)
         begin_args = (self.handle, N.as_dp(thetas_buf), K, C.byref(opt), 1, 0)
         end_args = (self.handle, summ, N.as_dp(grads), None, None, None, None)
-        lib = self.lib
         summ_view = np.frombuffer(summ, dtype=np.float64).reshape(K, -1)[:, 0]
 
         def begin(thetas):
             thetas_buf[:] = thetas
-            st = lib.gwi_eval_batch_begin(*begin_args)
+            st = fn_begin(*begin_args)
             if st != 0:
                 self._check(st)
 
         def end():
-            st = lib.gwi_eval_batch_end(*end_args)
+            st = fn_end(*end_args)
             if st != 0:
                 self._check(st)
             values[:] = summ_view
@@ -754,6 +781,19 @@ class NativePopulationLikelihood:
         self._check(self.lib.gwi_shm_exchange(self.handle, N.as_dp(rec), N.as_dp(out)))
         return out
 
+    def shm_exchange_batch(self, records, k=None):
+        """Publish this rank's ``(k, partial_len)`` records, return all ranks' ``(world, k, partial_len)``
+        (``gwi_shm_exchange_batch``; host-only handles included).  ``records=None`` publishes a failure of this rank instead
+        (``k`` then gives the batch size): the other ranks' calls raise, naming this rank; this one returns ``None``."""
+        if records is None:
+            self._check(self.lib.gwi_shm_exchange_batch(self.handle, None, int(k), None))
+            return None
+        rec = N.f64(records).reshape(-1, self.partial_len)
+        K = rec.shape[0]
+        out = np.zeros((self.world, K, self.partial_len))
+        self._check(self.lib.gwi_shm_exchange_batch(self.handle, N.as_dp(rec), K, N.as_dp(out)))
+        return out
+
     def evaluate_latencies(self, thetas, total_inj, nobs=None, marginalize_selection=False, min_neff_cut=True, max_variance_cut=False):
         """Wall-clock seconds of each of ``len(thetas)`` sequential blocking evaluations, measured inside the library
         (``gwi_eval_latencies``)."""
@@ -793,6 +833,31 @@ class NativePopulationLikelihood:
         lb, ln, lv = np.zeros(self.n_ev), np.zeros(self.n_ev), np.zeros(self.n_ev)
         self._check(self.lib.gwi_eval_partial(self.handle, N.as_dp(theta), N.as_dp(rec), N.as_dp(lb), N.as_dp(ln), N.as_dp(lv)))
         return rec, lb, ln, lv
+
+    def eval_batch_partial(self, thetas):
+        """This rank's K partial records ``(K, partial_len)`` (+ local per-event arrays ``(K, n_ev)`` without the global constant)
+        from one batched set of launches (``gwi_eval_batch_partial``)."""
+        thetas = N.f64(np.atleast_2d(thetas))
+        K = thetas.shape[0]
+        rec = np.zeros((K, self.partial_len))
+        lb, ln, lv = np.zeros((K, self.n_ev)), np.zeros((K, self.n_ev)), np.zeros((K, self.n_ev))
+        self._check(self.lib.gwi_eval_batch_partial(self.handle, N.as_dp(thetas), K, N.as_dp(rec), N.as_dp(lb), N.as_dp(ln), N.as_dp(lv)))
+        return rec, lb, ln, lv
+
+    def combine_batch(self, thetas, records, total_inj, nobs=None, marginalize_selection=False, min_neff_cut=True, max_variance_cut=False, want_grad=True):
+        """Assemble the K points ``thetas`` from every rank's records ``(n_ranks, K, partial_len)`` (``gwi_combine_batch``: the
+        host constants come from ``thetas``; host-only handles too).  Returns a list of K :class:`EvalResult`."""
+        thetas = N.f64(np.atleast_2d(thetas))
+        K = thetas.shape[0]
+        records = N.f64(records).reshape(-1, K, self.partial_len)
+        opt = self._options(total_inj, nobs, marginalize_selection, min_neff_cut, max_variance_cut)
+        summ = (N.GwiSummary * K)()
+        grads = np.zeros((K, self.n_theta)) if want_grad else None
+        n_norms = len(self.bound.norms)
+        norms = np.zeros((K, max(n_norms, 1)))
+        self._check(self.lib.gwi_combine_batch(self.handle, N.as_dp(thetas), K, N.as_dp(records), records.shape[0], C.byref(opt), summ, N.as_dp(grads), N.as_dp(norms)))
+        return [EvalResult(log_likelihood=summ[k].log_likelihood, grad=grads[k] if want_grad else None, summary=summ[k], log_bfs=None, log_neffs=None, variances=None,
+                           norms=norms[k, :n_norms]) for k in range(K)]
 
     def prepare_combine(self, theta):
         """Host-only handles: set the hyper-parameter point whose constants ``combine`` folds in."""

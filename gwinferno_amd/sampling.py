@@ -626,7 +626,7 @@ def _engine_sampler_args(engines, n_theta, prior, bijector, theta0s, total_inj, 
 
 
 def nuts_engine_lockstep(engines, chains_per_engine, total_inj, prior, bijector, theta0s, n_warmup=200, n_samples=200, max_tree_depth=10, target_accept=0.8, seed=0,
-                         **likelihood_flags):
+                         sharded=False, **likelihood_flags):
     """Lock-step NUTS inside the library (``gwi_nuts_engine_lockstep``): ``len(engines) * chains_per_engine`` chains, the chains of
     group ``g`` on ``engines[g]``, every leapfrog step of a group ONE batched launch (``gwi_eval_batch``'s kernels) -- numpyro's
     ``chain_method="vectorized"`` (examples/utils.py:63-85).  One host thread; with two or three engines the groups' launches
@@ -634,7 +634,11 @@ def nuts_engine_lockstep(engines, chains_per_engine, total_inj, prior, bijector,
     starting point of chain ``c``, chain ``c`` in group ``c // chains_per_engine``).  MORE starting points than
     ``len(engines) * chains_per_engine`` make a queue (``gwi_nuts_engine_queue``): every engine runs ``chains_per_engine`` chains
     at a time and a chain that ends hands its slot to the next one waiting, so the batches stay full; chain ``c`` draws what it
-    would draw alone with seed ``seed + 1000 c`` wherever it runs."""
+    would draw alone with seed ``seed + 1000 c`` wherever it runs.
+
+    ``sharded=True``: the engines are this rank's shards, each with an exchange attached (``shm_comm_init`` / ``comm_init``; one
+    segment or communicator per engine), and every batch is a ``gwi_eval_batch_sharded`` (``gwi_nuts_engine_queue_sharded``).
+    Every rank calls this with identical arguments and gets identical draws."""
     import ctypes as C
 
     from . import _native as N
@@ -645,6 +649,12 @@ def nuts_engine_lockstep(engines, chains_per_engine, total_inj, prior, bijector,
     K = int(chains_per_engine)
     if n_chains < len(engines) * K:
         raise ValueError("theta0s must hold at least len(engines) * chains_per_engine starting points")
+    for e in engines:
+        limit = getattr(e, "max_batch", None)
+        if limit is not None and K > limit:
+            raise ValueError(f"chains_per_engine = {K} exceeds the engine's max_batch of {limit} points (GWI_MAX_BATCH)")
+        if sharded and not getattr(e, "_comm", False):
+            raise ValueError("sharded=True needs an exchange on every engine (shm_comm_init or comm_init)")
     lib = engines[0].lib
     pri, pens, u0, lopt = _engine_sampler_args(engines, n_theta, prior, bijector, theta0s, total_inj, likelihood_flags)
     handles = (C.c_void_p * len(engines))(*[e.handle for e in engines])
@@ -653,8 +663,9 @@ def nuts_engine_lockstep(engines, chains_per_engine, total_inj, prior, bijector,
     depth = np.empty((n_chains, n_samples), dtype=np.int32)
     res = (N.GwiNutsResult * n_chains)()
     opt = _nuts_options(n_warmup, n_samples, max_tree_depth, target_accept, seed)
-    st = lib.gwi_nuts_engine_queue(handles, len(engines), K, n_chains, n_theta, C.byref(lopt), pri, pens, len(prior.penalties), N.as_dp(u0), C.byref(opt), N.as_dp(samples),
-                                   N.as_dp(logp), depth.ctypes.data_as(C.POINTER(C.c_int32)), res)
+    fn = lib.gwi_nuts_engine_queue_sharded if sharded else lib.gwi_nuts_engine_queue
+    st = fn(handles, len(engines), K, n_chains, n_theta, C.byref(lopt), pri, pens, len(prior.penalties), N.as_dp(u0), C.byref(opt), N.as_dp(samples), N.as_dp(logp),
+            depth.ctypes.data_as(C.POINTER(C.c_int32)), res)
     if st == -1:
         raise ValueError("gwi_nuts_engine_lockstep: a chain's starting point has zero likelihood (a cut, or outside the model's support) or a non-finite gradient")
     if st != 0:

@@ -380,6 +380,33 @@ gwi_status gwi_shm_comm_unlink(const char* name);
 /* publish `record` (gwi_partial_len() doubles) as this rank's, wait for every rank's, copy them to gathered[world][len] */
 gwi_status gwi_shm_exchange(gwi_handle h, const double* record, double* gathered);
 
+/* Sharded BATCHES: K hyper-parameter points per exchange (one process per GPU, or ranks sharing one GPU).  The counterpart of
+ * gwi_eval_batch / _begin / _end -- same arguments, same semantics, k_batch <= max_batch -- valid after gwi_shm_comm_init or
+ * gwi_comm_init: every rank scans its shard for all K points, ONE exchange carries K records per rank (the shared-memory
+ * segment; or one ncclAllGather of K records on the engine's stream, copied to host memory point-major by one workgroup per
+ * point), and every rank assembles the same K results from the ranks' records of each point in rank order, with gwi_combine's
+ * arithmetic.  summaries[k], grads[k][n_theta] and norms[k][n_norms] are the global results, identical on every rank;
+ * log_bfs / log_neffs / variances [k][n_ev] are this rank's events with the global constant applied.  A two-pass repeat is
+ * made by the rank that asks for it before it publishes (shared memory) or by every rank together (RCCL); with
+ * marginalize_selection and a gradient, a first exchange carries the K squared-weight records.  Over shared memory a rank whose
+ * half of a batch fails (any error of _begin or _end before its exchange) publishes that, and a rank whose K differs is reported
+ * as GWI_ERR_INVALID: every rank then returns, without waiting out the exchange's time-out, with an error that names the rank
+ * (over RCCL a failed rank leaves the others in the collective).  Every rank must issue the same sequence of batches. */
+gwi_status gwi_eval_batch_sharded(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, gwi_summary* summaries,
+                                  double* grads, double* log_bfs, double* log_neffs, double* variances, double* norms);
+gwi_status gwi_eval_batch_sharded_begin(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, int32_t want_grad, int32_t want_events);
+gwi_status gwi_eval_batch_sharded_end(gwi_handle h, gwi_summary* summaries, double* grads, double* log_bfs, double* log_neffs, double* variances, double* norms);
+/* ... for callers that exchange the records themselves: gwi_eval_batch_partial is the batched gwi_eval_partial (records[k][len],
+ * per-event sites [k][n_ev] without the global constant); gwi_combine_batch assembles records[n_ranks][k][len] for the points
+ * thetas[k][n_theta] (it computes their host constants itself; host-only handles too) -- for k = 1 exactly what gwi_combine gives.
+ * gwi_shm_exchange_batch publishes records[k][len] (k <= 64) and returns every rank's in gathered[world][k][len]; records NULL
+ * publishes a failure of this rank instead (the others return with an error naming it; this call returns GWI_OK once every
+ * rank has published). */
+gwi_status gwi_eval_batch_partial(gwi_handle h, const double* thetas, int32_t k, double* records, double* log_bfs, double* log_neffs, double* variances);
+gwi_status gwi_combine_batch(gwi_handle h, const double* thetas, int32_t k, const double* records, int32_t n_ranks, const gwi_options* opt,
+                             gwi_summary* summaries, double* grads, double* norms);
+gwi_status gwi_shm_exchange_batch(gwi_handle h, const double* records, int32_t k, double* gathered);
+
 /* Diagnostic: the launch geometry gwi_create chose -- out = {PE tile size, injection tile size, tiles per event, injection
  * tiles, scan workgroups per hyper-parameter point, injection groups of the combine launch} (samples / counts). */
 gwi_status gwi_launch_geometry(gwi_handle h, int32_t out[6]);

@@ -86,7 +86,7 @@ gwi_status gwi_nuts_run_lockstep(gwi_batch_target_fn fn, void* user, int32_t dim
  * kernels (several points per workgroup for parametric chains, the matrix-core kernel for spline models).  One host thread:
  * while group g's launches run, the chains of the other groups do their host arithmetic and issue theirs, so two or three
  * groups keep the GPU busy.  Target, arguments and outputs as gwi_nuts_engine (u0[n_chains][n_theta], chain c in group
- * c / chains_per_group).  Handles without a communicator. */
+ * c / chains_per_group).  Handles without a communicator (gwi_nuts_engine_queue_sharded: with one). */
 gwi_status gwi_nuts_engine_lockstep(const gwi_handle* handles, int32_t n_groups, int32_t chains_per_group, int32_t n_theta, const gwi_options* lopt,
                                     const gwi_param_prior* priors, const gwi_smoothing_penalty* penalties, int32_t n_penalties, const double* u0, const gwi_nuts_options* opt,
                                     double* samples, double* log_prob, int32_t* tree_depth, gwi_nuts_result* results);
@@ -102,6 +102,12 @@ gwi_status gwi_nuts_engine_lockstep(const gwi_handle* handles, int32_t n_groups,
 gwi_status gwi_nuts_engine_queue(const gwi_handle* handles, int32_t n_groups, int32_t slots_per_group, int32_t n_chains, int32_t n_theta, const gwi_options* lopt,
                                  const gwi_param_prior* priors, const gwi_smoothing_penalty* penalties, int32_t n_penalties, const double* u0, const gwi_nuts_options* opt,
                                  double* samples, double* log_prob, int32_t* tree_depth, gwi_nuts_result* results);
+/* The same queue on SHARDED engines (every handle after gwi_shm_comm_init or gwi_comm_init; each group's handle has its own
+ * segment or communicator): every batch is a gwi_eval_batch_sharded_begin / _end.  Every rank calls this with identical
+ * arguments; the groups are collected in a fixed order, so the ranks issue identical exchanges and get identical draws. */
+gwi_status gwi_nuts_engine_queue_sharded(const gwi_handle* handles, int32_t n_groups, int32_t slots_per_group, int32_t n_chains, int32_t n_theta, const gwi_options* lopt,
+                                         const gwi_param_prior* priors, const gwi_smoothing_penalty* penalties, int32_t n_penalties, const double* u0,
+                                         const gwi_nuts_options* opt, double* samples, double* log_prob, int32_t* tree_depth, gwi_nuts_result* results);
 gwi_status gwi_nuts_run_queue(gwi_batch_target_fn fn, void* user, int32_t dim, int32_t n_chains, int32_t slots, const double* x0, const gwi_nuts_options* opt, double* samples,
                               double* log_prob, int32_t* tree_depth, gwi_nuts_result* results);
 
