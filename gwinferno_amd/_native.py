@@ -30,6 +30,10 @@ TERM_SMOOTH = 11
 TERM_PLPEAK_SMOOTH = 12
 TERM_POWERLAW_BOUNDS = 13
 TERM_EXP_SPLINE_LERP = 14
+# narrow spline coordinates (float32 in HBM): kinds 7 / 9 otherwise, ranked as them in the canonical term order
+TERM_EXP_SPLINE_F32 = 15
+TERM_LINEAR_SPLINE_F32 = 16
+NARROW_KIND = {TERM_EXP_SPLINE: TERM_EXP_SPLINE_F32, TERM_LINEAR_SPLINE: TERM_LINEAR_SPLINE_F32}
 
 SPLINE_OUTSIDE_ZERO_EXPONENT = 1
 RATIO_LOGM_FROM_SPLINE = 8
@@ -216,6 +220,7 @@ EXPORTED_SYMBOLS = [
     "gwi_create_ingest",
     "gwi_ingest_columns",
     "gwi_read_column",
+    "gwi_resident_bytes",
     "gwi_eval",
     "gwi_eval_begin",
     "gwi_eval_end",
@@ -305,6 +310,9 @@ def load_library():
         lib.gwi_ingest_columns.argtypes = [C.POINTER(GwiIngestProgram), C.c_int64, C.c_int32, C.POINTER(_DP), C.c_int32]
         lib.gwi_read_column.restype = C.c_int32
         lib.gwi_read_column.argtypes = [vp, C.c_int32, C.c_int32, _DP]
+    if hasattr(lib, "gwi_resident_bytes"):
+        lib.gwi_resident_bytes.restype = C.c_int32
+        lib.gwi_resident_bytes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.gwi_eval.restype = C.c_int32
     lib.gwi_eval.argtypes = [vp, _DP, C.POINTER(GwiOptions), C.POINTER(GwiSummary), _DP, _DP, _DP, _DP, _DP]
     lib.gwi_eval_begin.restype = C.c_int32

@@ -34,11 +34,12 @@ class Composition:
         """Any parameter point (used only to establish the model structure)."""
         return {k: (np.zeros(s) if s else 1.0) for k, s in self.PARAMS.items()}
 
-    def engine(self, device=-1, rank=0, world=1, device_setup=None):
+    def engine(self, device=-1, rank=0, world=1, device_setup=None, narrow_columns=False):
+        """``narrow_columns``: float32 spline coordinates in HBM (NativePopulationLikelihood; False, "auto" or True)."""
         if self._engine is None:
             p = self.placeholder()
             self._engine = NativePopulationLikelihood(self.weights(p, True), self.weights(p, False), self.hypervolume(p), device=device, rank=rank, world=world,
-                                                      device_setup=device_setup)
+                                                      device_setup=device_setup, narrow_columns=narrow_columns)
         return self._engine
 
     def _theta_map(self):

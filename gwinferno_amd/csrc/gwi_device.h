@@ -499,6 +499,13 @@ struct SIdx {
 };
 typedef const char __attribute__((address_space(1))) * gbytes_t;
 __device__ __forceinline__ double gload(const double* p, SIdx i) { return *(gptr_t)((gbytes_t)(p + i.origin) + i.boff); }
+// ... the same sample of a NARROW (float32) column, widened: the pointer still travels as const double* (preloaded head
+// arguments, KArgs::pe_tcols), `origin` and the injection offset count float elements (gwi_engine.hip: alloc_pair_f32), and the
+// lane's byte offset halves
+typedef const float __attribute__((address_space(1))) * gfptr_t;
+__device__ __forceinline__ double gload_f32(const double* p, SIdx i) {
+  return (double)*(gfptr_t)((gbytes_t)(reinterpret_cast<const float*>(p) + i.origin) + (i.boff >> 1));
+}
 
 // ---- evaluation context --------------------------------------------------------------------
 struct Ctx {
@@ -923,7 +930,12 @@ struct Term<GWI_TERM_EXP_SPLINE> {
   };
   struct Acc {};
   __device__ static double eval(const TermD& t, const double*, const Ctx& c, const In& in, State& s, double&) {
-    const double u = in.x0;  // knot coordinate (see spline_locate_knot)
+    return eval_from(t, c, s, [&](bool) { return in.x0; });  // the column holds the knot coordinate (see spline_locate_knot)
+  }
+  // u = to_u(clamp): the sample's knot coordinate, asked for inside each arm of the flag's branch below, so that a term that forms
+  // it from x (the narrow kind, Term<GWI_TERM_EXP_SPLINE_F32>) clamps in one arm and not in the other instead of selecting
+  template <class ToU>
+  __device__ static double eval_from(const TermD& t, const Ctx& c, State& s, ToU&& to_u) {
     int k;
     double tt, v;
     // BSpline / LogXBSpline bases are 0 outside the closed domain (interpolation.py:175); LogY bases exclude the sample
@@ -933,13 +945,14 @@ struct Term<GWI_TERM_EXP_SPLINE> {
     // the clamps nor the two compares and three selects of the domain check
     if (t.flags & GWI_SPLINE_OUTSIDE_ZERO_EXPONENT) {
       asm volatile("");
+      const double u = to_u(false);
       spline_locate_term(u, t, k, tt);
       v = spline_value(c, t.th0 + k, tt);
       const bool outside = spline_outside(u, t);
       k = outside ? -1 : k;
       v = outside ? 0.0 : v;
     } else {
-      spline_locate_knot(u, k, tt);
+      spline_locate_knot(to_u(true), k, tt);
       v = spline_value(c, t.th0 + k, tt);
     }
     s.t = tt;
@@ -996,6 +1009,33 @@ struct Term<GWI_TERM_LINEAR_SPLINE> {
   __device__ static void rescale(Acc&, double) {}
   static constexpr int kNumAcc = 0;
   __device__ static void collect(const TermD&, const Acc&, double*, int*) {}
+};
+
+// Narrow spline kinds (include/gwi_engine.h: GWI_TERM_EXP_SPLINE_F32 / GWI_TERM_LINEAR_SPLINE_F32): the column holds the raw
+// coordinate x in float32.  The load widens it (exact); the knot coordinate is then formed here with the arithmetic of
+// spline_knot_kernel (gwi_ingest.h) -- contraction off, the same 1/dx (p2), the same clamp into [0, nextafter(n_int, 0)] for
+// exponentiated splines without the zero-outside flag -- so u, and everything after it, equals the wide kinds' to the bit.
+__device__ __forceinline__ double knot_of_x(double x, const TermD& t, bool clamp) {
+#pragma clang fp contract(off)
+  double u = (x - t.p0) * t.p2;
+  if (clamp) u = fmin(fmax(u, 0.0), __longlong_as_double(__double_as_longlong(t.p3) - 1));  // nextafter(n_int, 0): p3 >= 1
+  return u;
+}
+template <>
+struct Term<GWI_TERM_EXP_SPLINE_F32> : Term<GWI_TERM_EXP_SPLINE> {
+  using Wide = Term<GWI_TERM_EXP_SPLINE>;
+  __device__ static void load(const double* const* tc, SIdx idx, In& in) { in.x0 = gload_f32(tc[0], idx); }
+  __device__ static In knot(const TermD& t, const In& in) { return In{knot_of_x(in.x0, t, !(t.flags & GWI_SPLINE_OUTSIDE_ZERO_EXPONENT))}; }
+  __device__ static double eval(const TermD& t, const double*, const Ctx& c, const In& in, State& s, double&) {
+    return Wide::eval_from(t, c, s, [&](bool clamp) { return knot_of_x(in.x0, t, clamp); });
+  }
+};
+template <>
+struct Term<GWI_TERM_LINEAR_SPLINE_F32> : Term<GWI_TERM_LINEAR_SPLINE> {
+  using Wide = Term<GWI_TERM_LINEAR_SPLINE>;
+  __device__ static void load(const double* const* tc, SIdx idx, In& in) { in.x0 = gload_f32(tc[0], idx); }
+  __device__ static In knot(const TermD& t, const In& in) { return In{knot_of_x(in.x0, t, false)}; }
+  __device__ static double eval(const TermD& t, const double* d, const Ctx& c, const In& in, State& s, double& lin) { return Wide::eval(t, d, c, knot(t, in), s, lin); }
 };
 
 // (1-xi)/4 + xi Cn^2 exp(-((ct1-1)^2 + (ct2-1)^2)/(2 sig^2))  (parametric.py:97-102)
@@ -1375,7 +1415,8 @@ constexpr int kGenericChain = 0;
 #define GWI_FOR_EACH_KIND(X)                                                                                             \
   X(GWI_TERM_POWERLAW) X(GWI_TERM_PLPEAK) X(GWI_TERM_POWERLAW_RATIO) X(GWI_TERM_BETA) X(GWI_TERM_TILT_MIXTURE)           \
   X(GWI_TERM_POWERLAW_REDSHIFT) X(GWI_TERM_EXP_SPLINE) X(GWI_TERM_TRUNCNORM) X(GWI_TERM_LINEAR_SPLINE) X(GWI_TERM_TILT_JOINT) \
-  X(GWI_TERM_SMOOTH) X(GWI_TERM_PLPEAK_SMOOTH) X(GWI_TERM_POWERLAW_BOUNDS) X(GWI_TERM_EXP_SPLINE_LERP)
+  X(GWI_TERM_SMOOTH) X(GWI_TERM_PLPEAK_SMOOTH) X(GWI_TERM_POWERLAW_BOUNDS) X(GWI_TERM_EXP_SPLINE_LERP) X(GWI_TERM_EXP_SPLINE_F32)        \
+  X(GWI_TERM_LINEAR_SPLINE_F32)
 template <int K>
 __device__ __forceinline__ double generic_value(const TermD& t, const double* d, const Ctx& c, const double* const* tc, SIdx idx, double& lin) {
   typename Term<K>::In in;

@@ -113,6 +113,7 @@ constexpr ScanFn pbatch_scan() {
 #define K_PS GWI_TERM_PLPEAK_SMOOTH
 #define K_PB GWI_TERM_POWERLAW_BOUNDS
 #define K_SL GWI_TERM_EXP_SPLINE_LERP
+#define K_SPN GWI_TERM_EXP_SPLINE_F32
 
 // U = samples per lane per trip (2 for the register-light parametric models, 1 or 2 for spline models)
 #define GWI_VARIANT_U(NAME, U, ...) \
@@ -149,6 +150,11 @@ const Variant kVariants[] = {
     // (one sample per lane: 160 VGPRs -> 3 waves/SIMD; measured 83 vs 93 us per scan on config 5)
     GWI_VARIANT_U("plz+spline7", 1, K_PZ, K_SP, K_SP, K_SP, K_SP, K_SP, K_SP, K_SP),
     GWI_VARIANT_U("plz+spline7/u2", 2, K_PZ, K_SP, K_SP, K_SP, K_SP, K_SP, K_SP, K_SP),
+    // the same two with float32 spline coordinates (narrow columns, GWI_TERM_EXP_SPLINE_F32): config 3/4's spin magnitudes and
+    // tilts, config 5's mass ratio, magnitudes and tilts (and the one-sample-per-lane sibling config 3's small catalogs take)
+    GWI_VARIANT("plq+plz+spline+splinef4", K_PQ, K_PZ, K_SP, K_SPN, K_SPN, K_SPN, K_SPN),
+    GWI_VARIANT_U("plq+plz+spline+splinef4/u1", 1, K_PQ, K_PZ, K_SP, K_SPN, K_SPN, K_SPN, K_SPN),
+    GWI_VARIANT_U("plz+spline+splinef5+spline", 1, K_PZ, K_SP, K_SPN, K_SPN, K_SPN, K_SPN, K_SPN, K_SP),
     // PLPeakPrimaryBSplineRatio (separable.py:368-443) x PL z
     GWI_VARIANT("plpeak+plz+spline", K_PP, K_PZ, K_SP),
     // plpeak_primary_ratio_pdf (parametric.py:39-46) x B-spline spin magnitudes and tilts (IID or independent:
@@ -245,6 +251,9 @@ MfmaVariant kMfmaVariants[] = {
     GWI_MFMA("plq+plz+spline3 (32,16,16)", 1, K_PQ, K_PZ, T2(K_SP), T1(K_SP), T1(K_SP)),
     // BASELINE config 5: PL z x {m1 (30), q (14), a1, a2, ct1, ct2 (12 each), z (12)}
     GWI_MFMA("plz+spline7 (32,16,16,16,16,16,16)", 1, K_PZ, T2(K_SP), T1(K_SP), T1(K_SP), T1(K_SP), T1(K_SP), T1(K_SP), T1(K_SP)),
+    // ... both with float32 spline coordinates (narrow columns): the batched path of a narrow model is its wide twin's
+    GWI_MFMA("plq+plz+spline+splinef4 (32,16,16,16,16)", 1, K_PQ, K_PZ, T2(K_SP), T1(K_SPN), T1(K_SPN), T1(K_SPN), T1(K_SPN)),
+    GWI_MFMA("plz+spline+splinef5+spline (32,16,16,16,16,16,16)", 1, K_PZ, T2(K_SP), T1(K_SPN), T1(K_SPN), T1(K_SPN), T1(K_SPN), T1(K_SPN), T1(K_SP)),
     // the reference's default spline counts (pipeline/utils.py:29-33): m1 50, q 30, spins 16, z 20
     GWI_MFMA("plz+spline7 (64,32,16,16,16,16,32)", 1, K_PZ, T4(K_SP), T2(K_SP), T1(K_SP), T1(K_SP), T1(K_SP), T1(K_SP), T2(K_SP)),
     // linear (chi_eff / chi_p) splines
@@ -507,9 +516,14 @@ struct gwi_engine {
   ScanBlock sblock;          // what a scan launch takes: preloaded head + argument block
   KArgs& kargs = sblock.k;
   long long inj_off = 0;     // element offset of the injections inside every column allocation (inj_offset)
+  std::vector<char> col_f32;  // per entry of d_cols_pe: a narrow (float32) allocation
 };
 
 namespace {
+
+// narrow spline kinds: the coordinate column is float32 in HBM (include/gwi_engine.h: GWI_TERM_EXP_SPLINE_F32)
+inline bool is_narrow_kind(int k) { return k == GWI_TERM_EXP_SPLINE_F32 || k == GWI_TERM_LINEAR_SPLINE_F32; }
+int term_cols(int kind);
 
 #define GWI_HIP(call)                                                                               \
   do {                                                                                              \
@@ -562,6 +576,8 @@ gwi_status validate_spec(gwi_handle h, const gwi_spec* s) {
         [[fallthrough]];
       case GWI_TERM_LINEAR_SPLINE:
       case GWI_TERM_EXP_SPLINE:
+      case GWI_TERM_LINEAR_SPLINE_F32:
+      case GWI_TERM_EXP_SPLINE_F32:
         n_th = 0;
         if (tm.n_basis < 4 || !theta_ok(tm.coef_off) || !theta_ok(tm.coef_off + tm.n_basis - 1)) return fail(h, GWI_ERR_INVALID, "spline coefficient range invalid");
         if (!(tm.p[1] > tm.p[0])) return fail(h, GWI_ERR_INVALID, "spline domain invalid");
@@ -573,6 +589,21 @@ gwi_status validate_spec(gwi_handle h, const gwi_spec* s) {
     for (int k = 0; k < n_th; ++k)
       if (!theta_ok(tm.theta[k])) return fail(h, GWI_ERR_INVALID, "term theta index out of range");
     if (tm.norm >= s->n_norms) return fail(h, GWI_ERR_INVALID, "term norm index out of range");
+  }
+  // a narrow column (float32 in HBM) is read by narrow spline terms only: kappa, any other kind, a wide spline term and a
+  // GWI_RATIO_LOGM_FROM_SPLINE reference would all read it as float64
+  for (int t = 0; t < s->n_terms; ++t) {
+    if (!is_narrow_kind(s->terms[t].kind)) continue;
+    const int c = s->terms[t].cols[0];
+    if (c == s->kappa_col) return fail(h, GWI_ERR_INVALID, "term " + std::to_string(t) + " (narrow spline): its column is kappa");
+    for (int t2 = 0; t2 < s->n_terms; ++t2) {
+      const gwi_term& o = s->terms[t2];
+      const int n_read = o.kind == GWI_TERM_POWERLAW_RATIO ? 2 : term_cols(o.kind);
+      for (int j = 0; j < n_read && j < 2; ++j)
+        if (o.cols[j] == c && !(is_narrow_kind(o.kind) && j == 0))
+          return fail(h, GWI_ERR_INVALID, "term " + std::to_string(t) + " (narrow spline, kind " + std::to_string(s->terms[t].kind) + "): its column " + std::to_string(c) +
+                                              " is also read by term " + std::to_string(t2) + " (kind " + std::to_string(o.kind) + "); a narrow column may be read by narrow spline terms only");
+    }
   }
   for (int j = 0; j < s->n_norms; ++j) {
     const gwi_norm& nm = s->norms[j];
@@ -1018,7 +1049,7 @@ bool try_jit_mfma(gwi_handle h) {
       h->mfma_jit_note = "the interpolated-grid spline term has no matrix-core form";
       return false;
     }
-    const bool spline = kind == GWI_TERM_EXP_SPLINE || kind == GWI_TERM_LINEAR_SPLINE;
+    const bool spline = kind == GWI_TERM_EXP_SPLINE || kind == GWI_TERM_LINEAR_SPLINE || is_narrow_kind(kind);
     const int tiles = spline ? (s.terms[t].n_basis + 15) / 16 : 0;
     any_spline = any_spline || spline;
     kts[t] = kind + 100 * tiles;
@@ -1554,8 +1585,23 @@ gwi_status alloc_pair(gwi_handle h, double** dpe, double** dinj) {
   GWI_HIP(hipMalloc(&d, sizeof(double) * n));
   h->d_cols_pe.push_back(d);
   h->d_cols_inj.push_back(d + h->inj_off);
+  h->col_f32.push_back(0);
   *dpe = d;
   *dinj = d + h->inj_off;
+  return GWI_OK;
+}
+// The same for a NARROW column in slot c of d_cols_pe (an allocation of float32: the injections inj_offset() FLOAT elements
+// behind, as the scan's narrow loads count them, gwi_device.h: gload_f32); the slot's previous allocation is handed back in
+// `old`, for the caller to release once nothing reads it.
+gwi_status alloc_pair_f32(gwi_handle h, int c, float** dpe, double** old) {
+  float* d = nullptr;
+  const size_t n = (size_t)h->inj_off + (size_t)(h->n_inj ? h->n_inj : 1);
+  GWI_HIP(hipMalloc(&d, sizeof(float) * n));
+  *old = h->d_cols_pe[c];
+  h->d_cols_pe[c] = reinterpret_cast<double*>(d);
+  h->d_cols_inj[c] = reinterpret_cast<double*>(d + h->inj_off);
+  h->col_f32[c] = 1;
+  *dpe = d;
   return GWI_OK;
 }
 
@@ -1810,6 +1856,9 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
   h->n_pe = n_pe;
   h->n_inj = n_inj;
   h->inj_off = inj_offset(n_ev, n_pe);
+  std::vector<int> narrow_term(spec->n_cols, -1);  // per column: the first narrow spline term reading it (validate_spec: only such terms do)
+  for (int t = spec->n_terms - 1; t >= 0; --t)
+    if (is_narrow_kind(spec->terms[t].kind)) narrow_term[spec->terms[t].cols[0]] = t;
 
   // ---- columns -> HBM (struct-of-arrays: one contiguous fp64 array per column and sample set)
   std::vector<const double*> tab_pe(spec->n_cols), tab_inj(spec->n_cols);
@@ -1827,11 +1876,61 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
     for (int c = 0; c < spec->n_cols; ++c) {
       double *dpe = nullptr, *dinj = nullptr;
       if ((st = alloc_pair(h, &dpe, &dinj)) != GWI_OK) return st;
-      if (n_ev * n_pe) GWI_HIP(hipMemcpy(dpe, pe_cols[c], sizeof(double) * (size_t)(n_ev * n_pe), hipMemcpyHostToDevice));
-      if (n_inj) GWI_HIP(hipMemcpy(dinj, inj_cols[c], sizeof(double) * (size_t)n_inj, hipMemcpyHostToDevice));
+      if (narrow_term[c] < 0) {
+        if (n_ev * n_pe) GWI_HIP(hipMemcpy(dpe, pe_cols[c], sizeof(double) * (size_t)(n_ev * n_pe), hipMemcpyHostToDevice));
+        if (n_inj) GWI_HIP(hipMemcpy(dinj, inj_cols[c], sizeof(double) * (size_t)n_inj, hipMemcpyHostToDevice));
+      }
       tab_pe[c] = dpe;
       tab_inj[c] = dinj;
     }
+  }
+
+  // ---- narrow columns (GWI_TERM_EXP_SPLINE_F32 / _LINEAR_SPLINE_F32): float32 in HBM, after checking that every value survives
+  // the round trip -- on the host for columns handed over, on the device (narrow_column_kernel) for ingested ones
+  for (int c = 0; c < spec->n_cols; ++c) {
+    const int t = narrow_term[c];
+    if (t < 0) continue;
+    const gwi_term& tm = spec->terms[t];
+    const float park = (float)(0.5 * (tm.p[0] + tm.p[1]));  // the parking place of non-finite entries: the domain's middle
+    float* d = nullptr;
+    double* old = nullptr;
+    if ((st = alloc_pair_f32(h, c, &d, &old)) != GWI_OK) return st;
+    unsigned long long bad = 0;
+    if (ingest) {
+      unsigned long long* d_bad = nullptr;
+      hipError_t e = hipMalloc(&d_bad, sizeof(unsigned long long));
+      if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), h->stream);
+      if (e == hipSuccess) e = narrow_column_run(old, d, d_bad, n_ev * n_pe, park, h->stream);
+      if (e == hipSuccess) e = narrow_column_run(old + h->inj_off, d + h->inj_off, d_bad, n_inj, park, h->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+      (void)hipFree(d_bad);
+      (void)hipFree(old);
+      GWI_HIP(e);
+    } else {
+      (void)hipFree(old);
+      std::vector<float> buf((size_t)std::max<long long>(n_ev * n_pe, n_inj));
+      auto narrow = [&](const double* x, long long n) {
+        for (long long i = 0; i < n; ++i) {
+          const double v = x[i];
+          float f = (float)v;
+          if (!std::isfinite(v))
+            f = park;
+          else if ((double)f != v)
+            ++bad;
+          buf[(size_t)i] = f;
+        }
+      };
+      narrow(pe_cols[c], n_ev * n_pe);
+      if (n_ev * n_pe) GWI_HIP(hipMemcpy(d, buf.data(), sizeof(float) * (size_t)(n_ev * n_pe), hipMemcpyHostToDevice));
+      narrow(inj_cols[c], n_inj);
+      if (n_inj) GWI_HIP(hipMemcpy(d + h->inj_off, buf.data(), sizeof(float) * (size_t)n_inj, hipMemcpyHostToDevice));
+    }
+    if (bad)
+      return fail(h, GWI_ERR_INVALID, "term " + std::to_string(t) + " (narrow spline, kind " + std::to_string(tm.kind) + "): " + std::to_string(bad) + " value" +
+                                          (bad == 1 ? "" : "s") + " of column " + std::to_string(c) + " do not survive a float32 round trip");
+    tab_pe[c] = reinterpret_cast<const double*>(d);
+    tab_inj[c] = reinterpret_cast<const double*>(d + h->inj_off);
   }
 
   // ---- spline terms read the KNOT coordinate of their column (gwi_device.h: spline_locate_knot): convert x -> u once, here.
@@ -1954,7 +2053,7 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
   // register budget allows workgroups on a CU, and are zeroed and summed once per workgroup.
   bool has_spline = false;
   for (int t = 0; t < spec->n_terms; ++t)
-    has_spline = has_spline || spec->terms[t].kind == GWI_TERM_EXP_SPLINE || spec->terms[t].kind == GWI_TERM_LINEAR_SPLINE || spec->terms[t].kind == GWI_TERM_EXP_SPLINE_LERP;
+    has_spline = has_spline || jit::is_spline_kind(spec->terms[t].kind);
   has_spline = has_spline || h->generic;  // the generic chain keeps every gradient sum in the LDS rows
   if (const char* env = std::getenv("GWI_DETERMINISTIC")) h->deterministic = std::atoi(env) != 0;
   size_t scan_lds = 0;
@@ -2291,14 +2390,15 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
     std::memset(&hd, 0, sizeof(hd));
     int slot = 0;
     bool joint = true;
-    auto put = [&](const double* pe, const double* inj) {
-      joint = joint && inj == pe + h->inj_off;
+    auto put = [&](const double* pe, const double* inj, bool f32) {
+      // (a narrow column counts its offset in float elements)
+      joint = joint && (f32 ? reinterpret_cast<const void*>(reinterpret_cast<const float*>(pe) + h->inj_off) == reinterpret_cast<const void*>(inj) : inj == pe + h->inj_off);
       if (slot < kHeadCols) hd.col[slot] = pe;
       ++slot;
     };
-    put(k.kappa_pe, k.kappa_inj);
+    put(k.kappa_pe, k.kappa_inj, false);
     for (int t = 0; t < spec->n_terms; ++t)
-      for (int j = 0; j < term_cols(spec->terms[t].kind) && j < 2; ++j) put(k.pe_tcols[t][j], k.inj_tcols[t][j]);
+      for (int j = 0; j < term_cols(spec->terms[t].kind) && j < 2; ++j) put(k.pe_tcols[t][j], k.inj_tcols[t][j], j == 0 && is_narrow_kind(spec->terms[t].kind));
     for (; slot < kHeadCols; ++slot) hd.col[slot] = k.kappa_pe;  // unused slots: any valid address
     if (!joint) return fail(h, GWI_ERR_INVALID, "internal error: a column's injection part does not sit inj_offset() behind its posterior-sample part");
     if (n_ev >= (1LL << kGeomEventBits) || n_pe >= (1LL << 32) || n_inj >= (1LL << 32) || spec->n_norms >= 16 || h->tiles_per_event >= (1 << kGeomTilesBits) ||
@@ -2323,7 +2423,7 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
     d.p3 = tm.p[3];
     d.th4 = tm.kind == GWI_TERM_PLPEAK_SMOOTH ? tm.coef_off : 0;
     if (tm.kind == GWI_TERM_EXP_SPLINE_LERP) d.th1 = tm.norm;  // the grid's spline coordinates live in that normaliser's `us`
-    if (tm.kind == GWI_TERM_EXP_SPLINE || tm.kind == GWI_TERM_LINEAR_SPLINE || tm.kind == GWI_TERM_EXP_SPLINE_LERP) {
+    if (jit::is_spline_kind(tm.kind)) {  // (the narrow kinds form their knot coordinate from p0 and this p2: gwi_device.h, knot_of_x)
       d.th0 = tm.coef_off;
       d.p2 = (double)(tm.n_basis - 3) / (tm.p[1] - tm.p[0]);  // 1/dx of the uniform knots (interpolation.py:100-101)
       d.p3 = (double)(tm.n_basis - 3);                          // the closed domain in knot coordinates: [0, p3]
@@ -2372,7 +2472,34 @@ gwi_status gwi_read_column(gwi_handle h, int32_t pe_side, int32_t col, double* o
   if (col < 0 || col >= (int)cols.size()) return fail(h, GWI_ERR_INVALID, "gwi_read_column: column out of range");
   const size_t n = pe_side ? (size_t)(h->n_ev * h->n_pe) : (size_t)h->n_inj;
   GWI_HIP(hipSetDevice(h->device));
-  if (n) GWI_HIP(hipMemcpy(out, cols[col], sizeof(double) * n, hipMemcpyDeviceToHost));
+  if (n && h->col_f32[col]) {  // a narrow column: float32 values, widened
+    std::vector<float> buf(n);
+    GWI_HIP(hipMemcpy(buf.data(), cols[col], sizeof(float) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) out[i] = (double)buf[i];
+  } else if (n) {
+    GWI_HIP(hipMemcpy(out, cols[col], sizeof(double) * n, hipMemcpyDeviceToHost));
+  }
+  return GWI_OK;
+}
+
+gwi_status gwi_resident_bytes(gwi_handle h, int64_t* pe_bytes, int64_t* inj_bytes) {
+  if (!h || h->host_only) return GWI_ERR_INVALID;
+  // every distinct column allocation a scan reads: kappa and each term's columns (a knot-coordinate copy is a column of its own)
+  std::vector<const double*> seen;
+  int64_t width = 0;  // bytes per sample
+  auto add = [&](const double* p) {
+    if (!p || std::find(seen.begin(), seen.end(), p) != seen.end()) return;
+    seen.push_back(p);
+    bool f32 = false;
+    for (size_t i = 0; i < h->d_cols_pe.size(); ++i)
+      if (h->d_cols_pe[i] == p) f32 = h->col_f32[i] != 0;
+    width += f32 ? 4 : 8;
+  };
+  add(h->kargs.kappa_pe);
+  for (int t = 0; t < h->spec.n_terms; ++t)
+    for (int j = 0; j < term_cols(h->spec.terms[t].kind) && j < 2; ++j) add(h->kargs.pe_tcols[t][j]);
+  if (pe_bytes) *pe_bytes = width * (int64_t)(h->n_ev * h->n_pe);
+  if (inj_bytes) *inj_bytes = width * (int64_t)h->n_inj;
   return GWI_OK;
 }
 

@@ -148,6 +148,39 @@ inline hipError_t spline_knot_run(const double* x, double* u, long long n, doubl
   return hipGetLastError();
 }
 
+// A narrow column (include/gwi_engine.h: GWI_TERM_EXP_SPLINE_F32) after the ingest kernel wrote it in float64: narrowed to float32
+// in place of the engine's copy, counting into `bad` the finite values a float32 round trip would change (the engine refuses
+// the column then).  Non-finite values -- excluded samples, kappa = -inf -- are parked at `park`, a float32 number.
+struct NarrowArgs {
+  const double* x;
+  float* y;
+  unsigned long long* bad;
+  long long n, stride;
+  float park;
+};
+__global__ __launch_bounds__(256) void narrow_column_kernel(const NarrowArgs a) {
+  unsigned long long bad = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += a.stride) {
+    const double v = a.x[i];
+    float f = (float)v;
+    if (!(fabs(v) < __builtin_inf())) {
+      f = a.park;
+    } else if ((double)f != v) {
+      ++bad;
+    }
+    a.y[i] = f;
+  }
+  if (bad) atomicAdd(a.bad, bad);  // only ever taken for a column the engine then refuses
+}
+inline hipError_t narrow_column_run(const double* x, float* y, unsigned long long* bad, long long n, float park, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  long long blocks = (n + 255) / 256;
+  if (blocks > 256LL * 16) blocks = 256LL * 16;
+  const NarrowArgs a{x, y, bad, n, blocks * 256, park};
+  hipLaunchKernelGGL(narrow_column_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
 // Host side: validate, upload sources / tables / ops, run, release.  `d_out[c]` are device arrays of n doubles the
 // caller owns.  Returns GWI_OK or a status with `err` filled in.
 inline gwi_status ingest_check(std::string& err, const gwi_ingest_program* p, int n_cols) {

@@ -126,7 +126,12 @@ inline Rtc& rtc() {
   return r;
 }
 
-inline bool is_spline_kind(int k) { return k == GWI_TERM_EXP_SPLINE || k == GWI_TERM_LINEAR_SPLINE || k == GWI_TERM_EXP_SPLINE_LERP; }
+inline bool is_spline_kind(int k) {
+  return k == GWI_TERM_EXP_SPLINE || k == GWI_TERM_LINEAR_SPLINE || k == GWI_TERM_EXP_SPLINE_LERP || k == GWI_TERM_EXP_SPLINE_F32 || k == GWI_TERM_LINEAR_SPLINE_F32;
+}
+// position of a kind in the canonical term order: the narrow spline kinds rank as their wide twins, so that narrowing a column
+// leaves a model's term order -- and the order its kernels sum the terms in -- as it was
+inline int kind_rank(int k) { return k == GWI_TERM_EXP_SPLINE_F32 ? GWI_TERM_EXP_SPLINE : k == GWI_TERM_LINEAR_SPLINE_F32 ? GWI_TERM_LINEAR_SPLINE : k; }
 
 // The flags of the ahead-of-time build (__graft_entry__.build): a chain compiled here is the chain hipcc would have built.
 inline const std::vector<const char*>& flags() {
@@ -360,8 +365,8 @@ inline Chain* get_chain(const int* kinds, int n, int U, const char* device_h, co
   }
   for (int t = 0; t < n; ++t) {
     const int k = mfma ? kinds[t] % 100 : kinds[t], k_prev = t > 0 ? (mfma ? kinds[t - 1] % 100 : kinds[t - 1]) : 0;
-    if (k < 1 || k > GWI_TERM_EXP_SPLINE_LERP || k < k_prev || (mfma && (kinds[t] / 100 < 0 || kinds[t] / 100 > 8))) {
-      why = "jit: term kinds are the GWI_TERM_* numbers in ascending order";
+    if (k < 1 || k > GWI_TERM_LINEAR_SPLINE_F32 || kind_rank(k) < kind_rank(k_prev) || (mfma && (kinds[t] / 100 < 0 || kinds[t] / 100 > 8))) {
+      why = "jit: term kinds are the GWI_TERM_* numbers in ascending order (kinds 15 / 16 ranked as 7 / 9)";
       return nullptr;
     }
   }

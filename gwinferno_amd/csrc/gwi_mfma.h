@@ -193,6 +193,20 @@ struct Stage<GWI_TERM_LINEAR_SPLINE> {
     return 0.0;
   }
 };
+// narrow spline kinds: the staging row is formed from the knot coordinate the term computes from its float32 column
+// (gwi_device.h: knot_of_x) -- the rest is the wide kind's
+template <>
+struct Stage<GWI_TERM_EXP_SPLINE_F32> : Stage<GWI_TERM_EXP_SPLINE> {
+  __device__ static void phase_a(const TermD& t, const typename Term<GWI_TERM_EXP_SPLINE_F32>::In& in, double* row) {
+    Stage<GWI_TERM_EXP_SPLINE>::phase_a(t, Term<GWI_TERM_EXP_SPLINE_F32>::knot(t, in), row);
+  }
+};
+template <>
+struct Stage<GWI_TERM_LINEAR_SPLINE_F32> : Stage<GWI_TERM_LINEAR_SPLINE> {
+  __device__ static void phase_a(const TermD& t, const typename Term<GWI_TERM_LINEAR_SPLINE_F32>::In& in, double* row) {
+    Stage<GWI_TERM_LINEAR_SPLINE>::phase_a(t, Term<GWI_TERM_LINEAR_SPLINE_F32>::knot(t, in), row);
+  }
+};
 
 // ---- compile-time chain.  Every entry is  kind + 100 * tiles:  tiles = 16-basis gradient tiles of a spline term
 //      (n_basis <= 16 tiles, checked by the host), 0 for the other kinds. ------------------------------------------------

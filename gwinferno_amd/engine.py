@@ -118,7 +118,86 @@ def structure_key(pe, inj):
     return tuple(parts)
 
 
-def bind(pe, inj, hypervolume=None):
+def _raw_source(expr):
+    """The catalog array A if ``expr`` is A itself or A with excluded entries parked at constants -- where(valid, A, const),
+    possibly nested: the coordinate column of a spline model in x (not log x) -- else None."""
+    if expr.op == "src":
+        return expr.k
+    if expr.op == "where" and expr.args[2].op == "const":
+        return _raw_source(expr.args[1])
+    return None
+
+
+def _float32_exact(values):
+    """Whether every finite entry of ``values`` survives a float32 round trip (non-finite entries are parked, never read)."""
+    a = np.asarray(values, dtype=np.float64).ravel()
+    a = a[np.isfinite(a)]
+    return bool(np.array_equal(a.astype(np.float32).astype(np.float64), a))
+
+
+def _narrow_refusal(bm, ti, readers):
+    """Why the coordinate column of spline term ``ti`` cannot be narrowed to float32, or None."""
+    c = bm.terms[ti]["cols"][0]
+    for t2, j in readers[c]:
+        if j != 0 or bm.terms[t2]["kind"] not in N.NARROW_KIND:
+            return f"is also read by term {t2} (kind {bm.terms[t2]['kind']})"
+    for side, exprs in (("posterior-sample", bm.pe_exprs), ("injection", bm.inj_exprs)):
+        raw = _raw_source(exprs[c])
+        if raw is None:
+            return f"is not a raw catalog array on the {side} side (a transformed coordinate, e.g. log x)"
+        if not _float32_exact(raw):
+            return f"holds {side} values that do not survive a float32 round trip"
+    return None
+
+
+def _park_float32(expr, lo):
+    """``expr`` (a raw source, :func:`_raw_source`) with every parking constant replaced by a float32 number no lower than ``lo``
+    (excluded samples -- kappa = -inf -- carry a finite in-domain value only so that the kernels' per-sample state stays finite;
+    which one never reaches a result)."""
+    if expr.op != "where":
+        return expr
+    inner = _park_float32(expr.args[1], lo)
+    park = expr.args[2].k
+    f = np.float32(park)
+    if float(f) < lo:
+        f = np.nextafter(f, np.float32(np.inf))
+    return expr if float(f) == park and inner is expr.args[1] else E.where(expr.args[0], inner, float(f))
+
+
+def plan_narrow_columns(bm, narrow_columns):
+    """Turn the spline terms whose coordinate column can live in float32 into their narrow kinds (GWI_TERM_EXP_SPLINE_F32 /
+    GWI_TERM_LINEAR_SPLINE_F32, include/gwi_engine.h), in place: ``"auto"`` every term that qualifies -- the column is the raw
+    catalog array (no transform), read by no other kind of term, and every value, posterior samples and injections, survives a
+    float32 round trip -- ``True`` every spline term or ValueError naming the first that does not qualify, ``False`` none.
+    Decided on the bound model's GLOBAL arrays, so every shard of a sharded likelihood gets the same kinds."""
+    if narrow_columns is False or narrow_columns is None:
+        return []
+    if narrow_columns is not True and narrow_columns != "auto":
+        raise ValueError(f"narrow_columns must be False, 'auto' or True, not {narrow_columns!r}")
+    readers = {}
+    for ti, t in enumerate(bm.terms):
+        n_read = 2 if t["kind"] == N.TERM_POWERLAW_RATIO else len(t["cols"])
+        for j, c in enumerate(t["cols"][:n_read]):
+            readers.setdefault(c, []).append((ti, j))
+    narrowed = []
+    for ti, t in enumerate(bm.terms):
+        if t["kind"] not in N.NARROW_KIND:
+            continue
+        why = _narrow_refusal(bm, ti, readers)
+        if why is None:
+            narrowed.append(ti)
+        elif narrow_columns is True:
+            raise ValueError(f"narrow_columns=True: the coordinate column {t['cols'][0]} of spline term {ti} {why}")
+    for ti in narrowed:
+        t = bm.terms[ti]
+        t["kind"] = N.NARROW_KIND[t["kind"]]
+        c = t["cols"][0]
+        bm.pe_exprs[c] = _park_float32(bm.pe_exprs[c], t["p"][0])
+        bm.inj_exprs[c] = _park_float32(bm.inj_exprs[c], t["p"][0])
+    return narrowed
+
+
+def bind(pe, inj, hypervolume=None, narrow_columns=False):
     if not isinstance(pe, Density) or not isinstance(inj, Density):
         raise TypeError("weights must be lazy densities produced by gwinferno_amd.models (dense arrays are what the engine replaces)")
     if pe.side not in (PE, None) or inj.side not in (INJ, None):
@@ -278,6 +357,8 @@ def bind(pe, inj, hypervolume=None):
                              owner=fp.norm_owner))
     if len(bm.norms) > N.GWI_MAX_NORMS:
         raise ValueError(f"{len(bm.norms)} normalisers exceed GWI_MAX_NORMS={N.GWI_MAX_NORMS}")
+    # float32 spline coordinates (before the parking below: it wraps every column, at 0.0 -- a float32 number)
+    bm.narrowed = plan_narrow_columns(bm, narrow_columns)
     # A non-finite column entry (log of a non-positive number, NaN in the data) can only produce a NaN / Inf
     # weight, which counts as zero (tests/inference_test.py:172): exclude the sample and park a finite value
     # in its place, so that the per-sample gradient state the kernel carries stays finite (0 x NaN = NaN).
@@ -362,13 +443,17 @@ class NativePopulationLikelihood:
     SURVEY.md section 8e); the model objects must have been built from the GLOBAL arrays.
     """
 
-    def __init__(self, pe_density, inj_density, hypervolume=None, device=-1, rank=0, world=1, device_setup=None):
+    def __init__(self, pe_density, inj_density, hypervolume=None, device=-1, rank=0, world=1, device_setup=None, narrow_columns=False):
         """``device_setup``: compute the columns (transforms, masks, dVc/dz, kappa) on the GPU from the raw catalog arrays
         (``gwi_create_ingest``; the default wherever the engine has a device) or on the host with NumPy and upload them
         (``gwi_create``; ``GWI_HOST_SETUP=1`` in the environment selects it too -- the two agree to the last bit except
-        for the <= 1 ulp of the logarithms)."""
+        for the <= 1 ulp of the logarithms).
+
+        ``narrow_columns``: keep spline coordinates that are float32 numbers in float32 in HBM (4 bytes per sample instead of 8;
+        the kernels form the knot coordinate themselves, to the same bits): ``False`` (default) none, ``"auto"`` every spline term
+        whose column qualifies, ``True`` every spline term or ValueError (:func:`plan_narrow_columns`)."""
         self.lib = N.load_library()
-        self.bound = bm = bind(pe_density, inj_density, hypervolume)
+        self.bound = bm = bind(pe_density, inj_density, hypervolume, narrow_columns=narrow_columns)
         self.n_theta = bm.n_theta
         self.n_ev_global = bm.n_ev
         self.rank, self.world = rank, world
@@ -884,6 +969,13 @@ class NativePopulationLikelihood:
         out = np.empty((self.n_ev, self.n_pe) if side == PE else (self.n_inj,))
         self._check(self.lib.gwi_read_column(self.handle, 1 if side == PE else 0, int(col), N.as_dp(out)))
         return out
+
+    def resident_bytes(self):
+        """``(pe_bytes, inj_bytes)``: bytes of catalog columns the scan kernels stream for this engine's sample sets
+        (``gwi_resident_bytes``; a narrow column counts 4 bytes per sample, every other 8)."""
+        pe, inj = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.gwi_resident_bytes(self.handle, C.byref(pe), C.byref(inj)))
+        return int(pe.value), int(inj.value)
 
     def log_weights(self, theta):
         """Per-sample log importance weights (diagnostic; parity with the arrays the reference's

@@ -115,7 +115,18 @@ enum {
    * np.interp holds the end values); coef_off/n_basis; p[0]=lo, p[1]=hi of the spline coordinate; norm = the grid
    * normaliser whose `us` table (spline coordinate per grid point) and trapezoid weights define grid and Z (required);
    * flags: GWI_SPLINE_OUTSIDE_ZERO_EXPONENT as for EXP_SPLINE (otherwise a grid point outside [lo,hi] has lpdf -inf) */
-  GWI_TERM_EXP_SPLINE_LERP = 14
+  GWI_TERM_EXP_SPLINE_LERP = 14,
+  /* EXP_SPLINE / LINEAR_SPLINE with a NARROW coordinate column: meaning, p[], flags, normaliser and gradient are those of kinds 7
+   * and 9; the engine keeps cols[0] as the raw spline coordinate x in float32 (4 bytes per sample in HBM instead of 8) and the
+   * scan forms the knot coordinate u = (x - p[0]) (n_basis - 3) / (p[1] - p[0]) itself, with the arithmetic (and clamp) of the
+   * one-off conversion the wide kinds get -- the same u to the bit.  Every value of the column, posterior samples and injections,
+   * must survive a float32 round trip (gwi_create / gwi_create_ingest fail with GWI_ERR_INVALID otherwise, naming the term and
+   * the number of offending values); non-finite entries (excluded samples: kappa = -inf) are parked at the float32 value
+   * nearest the domain's midpoint.  No other term may read the column (no other kind, no kind 7 / 9, no
+   * GWI_RATIO_LOGM_FROM_SPLINE reference); several narrow terms may.  The term order of a model is canonical with these kinds
+   * ranked as their wide twins (15 as 7, 16 as 9). */
+  GWI_TERM_EXP_SPLINE_F32 = 15,
+  GWI_TERM_LINEAR_SPLINE_F32 = 16
 };
 
 /* POWERLAW flag: bare x^alpha with no normaliser and no truncation (the (m2/m1)^beta pairing factor,
@@ -275,8 +286,15 @@ gwi_status gwi_ingest_columns(const gwi_ingest_program* prog, int64_t n, int32_t
  * Resident means what the kernels read: a column that only GWI_TERM_EXP_SPLINE / GWI_TERM_LINEAR_SPLINE terms with one set of
  * knots read holds the KNOT coordinate (x - p[0]) * (n_basis - 3) / (p[1] - p[0]) of the spline coordinate x the caller handed
  * over (clamped into [0, n_basis - 3) for exponentiated splines without GWI_SPLINE_OUTSIDE_ZERO_EXPONENT), computed once at
- * gwi_create / gwi_create_ingest; every other column is returned as it was handed over or ingested. */
+ * gwi_create / gwi_create_ingest; every other column is returned as it was handed over or ingested.  A narrow column
+ * (GWI_TERM_EXP_SPLINE_F32 / GWI_TERM_LINEAR_SPLINE_F32) holds the raw coordinate in float32: it is returned widened to float64
+ * (non-finite entries as parked). */
 gwi_status gwi_read_column(gwi_handle h, int32_t pe_side, int32_t col, double* out);
+
+/* Bytes of catalog columns the scan kernels stream, per sample set: the sum over the resident columns (kappa, every term's
+ * columns and their private knot-coordinate copies) of 8 bytes (4 for a narrow column) x n_ev * n_pe (pe_bytes) or x n_inj
+ * (inj_bytes).  Either output may be NULL. */
+gwi_status gwi_resident_bytes(gwi_handle h, int64_t* pe_bytes, int64_t* inj_bytes);
 
 /* One value-and-gradient evaluation == one execution of the user's NumPyro model body ending in
  * hierarchical_likelihood(...) (analysis.py:139-319) under jit(value_and_grad)
@@ -482,7 +500,8 @@ const char* gwi_scan_kernel_name(gwi_handle h);
  * carrying a digest of (kinds, samples per lane, kernel names, code object) and is compiled over, never loaded, when it does not
  * match (tests/test_jit_cache_cpu.py).
  *
- * gwi_jit_compile(): compile (or find in the cache) the chain of `kinds` (GWI_TERM_* numbers, ascending) with
+ * gwi_jit_compile(): compile (or find in the cache) the chain of `kinds` (GWI_TERM_* numbers, ascending -- kinds 15 / 16 ranked as
+ * 7 / 9) with
  * `samples_per_lane` (1 | 2) samples per lane -- needs no GPU (samples_per_lane = 0: the batched matrix-core kernel of a spline
  * model instead, `kinds` then being kind + 100 x 16-basis gradient tiles of each term, as gwi_batch_kernel_note names it).  path_out (nullable, path_cap bytes) receives the cache file
  * ("" when no cache directory is both writable and trusted), or the reason on failure; compile_seconds = hipRTC time spent by THIS call chain
