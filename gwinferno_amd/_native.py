@@ -229,6 +229,8 @@ EXPORTED_SYMBOLS = [
     "gwi_eval_batch_end",
     "gwi_eval_sequence",
     "gwi_log_weights",
+    "gwi_set_draw_mask",
+    "gwi_draw_indices",
     "gwi_partial_len",
     "gwi_eval_partial",
     "gwi_prepare_combine",
@@ -330,6 +332,12 @@ def load_library():
     lib.gwi_eval_sequence.argtypes = [vp, _DP, C.c_int32, C.POINTER(GwiOptions), _DP, _DP, C.c_int32, C.POINTER(C.c_float)]
     lib.gwi_log_weights.restype = C.c_int32
     lib.gwi_log_weights.argtypes = [vp, _DP, _DP, _DP]
+    if hasattr(lib, "gwi_draw_indices"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _U8P, _I32P = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+        lib.gwi_set_draw_mask.restype = C.c_int32
+        lib.gwi_set_draw_mask.argtypes = [vp, _U8P, _U8P]
+        lib.gwi_draw_indices.restype = C.c_int32
+        lib.gwi_draw_indices.argtypes = [vp, _DP, C.c_int32, _DP, C.c_int32, _DP, C.c_int32, _I32P, _I32P]
     lib.gwi_partial_len.restype = C.c_int64
     lib.gwi_partial_len.argtypes = [vp]
     lib.gwi_eval_partial.restype = C.c_int32

@@ -4,6 +4,7 @@
 #include "gwi_mfma.h"
 #include "gwi_aql.h"
 #include "gwi_ingest.h"
+#include "gwi_draw.h"
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
 
@@ -429,6 +430,12 @@ struct gwi_engine {
   double *d_partials = nullptr, *d_ev_out = nullptr, *d_ev_grad = nullptr, *d_inj_out = nullptr, *d_inj_grad = nullptr;
   std::vector<double> sq_records;  // records of the squared-weight pass (marginalize_selection gradient)
   double *d_logw_pe = nullptr, *d_logw_inj = nullptr;
+  // index draws (gwi_draw.h): the caller's masks, the tiles' (max, sum, mass, prefix) + the segments' maxima, and the uniforms /
+  // indices of one gwi_draw_indices call (grown on demand, kept)
+  unsigned char *d_draw_mask_pe = nullptr, *d_draw_mask_inj = nullptr;
+  double *d_draw_tiles = nullptr, *d_draw_u = nullptr;
+  int* d_draw_idx = nullptr;
+  size_t draw_u_cap = 0, draw_idx_cap = 0;
   // pinned, device-visible host memory
   double *h_record = nullptr, *h_record_dev = nullptr;
   // device-final mode: the final launch's G workgroups publish one partial record each here; the host merges them into h_record
@@ -1546,6 +1553,11 @@ void destroy_impl(gwi_engine* h) {
   (void)hipFree(h->d_inj_grad);
   (void)hipFree(h->d_logw_pe);
   (void)hipFree(h->d_logw_inj);
+  (void)hipFree(h->d_draw_mask_pe);
+  (void)hipFree(h->d_draw_mask_inj);
+  (void)hipFree(h->d_draw_tiles);
+  (void)hipFree(h->d_draw_u);
+  (void)hipFree(h->d_draw_idx);
   if (h->nccl_comm && g_nccl.CommDestroy) (void)g_nccl.CommDestroy(h->nccl_comm);
   (void)hipFree(h->d_send);
   (void)hipFree(h->d_recv);
@@ -3424,6 +3436,29 @@ gwi_status gwi_debug_stamps(gwi_handle h, unsigned long long* out, int64_t n_wor
 }
 #endif
 
+// The log-weight role of the engine's scan chain at theta: leaves log(p(theta|Lambda)/prior) of every sample in d_logw_pe /
+// d_logw_inj, without the sample-independent constant, which is returned in *log_const.  Blocking.
+static gwi_status fill_log_weights(gwi_handle h, const double* theta, double* log_const) {
+  const size_t n_pe_tot = (size_t)(h->n_ev * h->n_pe), n_inj = (size_t)h->n_inj;
+  if (!h->d_logw_pe) GWI_HIP(hipMalloc(&h->d_logw_pe, sizeof(double) * (n_pe_tot ? n_pe_tot : 1)));
+  if (!h->d_logw_inj) GWI_HIP(hipMalloc(&h->d_logw_inj, sizeof(double) * (n_inj ? n_inj : 1)));
+  // normaliser values come from a regular evaluation
+  gwi_status st = run_pipeline(h, theta);
+  if (st != GWI_OK) return st;
+  double c = h->host_consts[0];
+  const double* nrm = h->h_record + kRecNormOff;
+  for (int t = 0; t < h->spec.n_terms; ++t)
+    if (h->spec.terms[t].norm >= 0) c -= std::log(nrm[h->spec.terms[t].norm]);
+  *log_const = c;
+  h->kargs.logw_pe = h->d_logw_pe;
+  h->kargs.logw_inj = h->d_logw_inj;
+  set_geometry(h, false);
+  st = launch_scan(h, true);
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipStreamSynchronize(h->stream));
+  return GWI_OK;
+}
+
 gwi_status gwi_log_weights(gwi_handle h, const double* theta, double* pe_logw, double* inj_logw) {
   if (!h || !theta || !h->variant) return GWI_ERR_INVALID;
   if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
@@ -3431,21 +3466,9 @@ gwi_status gwi_log_weights(gwi_handle h, const double* theta, double* pe_logw, d
   if (st != GWI_OK) return st;
   GWI_HIP(hipSetDevice(h->device));
   const size_t n_pe_tot = (size_t)(h->n_ev * h->n_pe), n_inj = (size_t)h->n_inj;
-  if (!h->d_logw_pe) GWI_HIP(hipMalloc(&h->d_logw_pe, sizeof(double) * (n_pe_tot ? n_pe_tot : 1)));
-  if (!h->d_logw_inj) GWI_HIP(hipMalloc(&h->d_logw_inj, sizeof(double) * (n_inj ? n_inj : 1)));
-  // normaliser values come from a regular evaluation
-  st = run_pipeline(h, theta);
+  double log_const = 0.0;
+  st = fill_log_weights(h, theta, &log_const);
   if (st != GWI_OK) return st;
-  double log_const = h->host_consts[0];
-  const double* nrm = h->h_record + kRecNormOff;
-  for (int t = 0; t < h->spec.n_terms; ++t)
-    if (h->spec.terms[t].norm >= 0) log_const -= std::log(nrm[h->spec.terms[t].norm]);
-  h->kargs.logw_pe = h->d_logw_pe;
-  h->kargs.logw_inj = h->d_logw_inj;
-  set_geometry(h, false);
-  st = launch_scan(h, true);
-  if (st != GWI_OK) return st;
-  GWI_HIP(hipStreamSynchronize(h->stream));
   if (pe_logw) {
     GWI_HIP(hipMemcpy(pe_logw, h->d_logw_pe, sizeof(double) * n_pe_tot, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n_pe_tot; ++i) pe_logw[i] += log_const;
@@ -3454,6 +3477,109 @@ gwi_status gwi_log_weights(gwi_handle h, const double* theta, double* pe_logw, d
     GWI_HIP(hipMemcpy(inj_logw, h->d_logw_inj, sizeof(double) * n_inj, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n_inj; ++i) inj_logw[i] += log_const;
   }
+  return GWI_OK;
+}
+
+// one mask of a set: uploaded over the previous one, or dropped (all ones) for NULL
+static gwi_status set_one_draw_mask(gwi_handle h, const unsigned char* src, size_t n, unsigned char** dst) {
+  if (!src) {
+    (void)hipFree(*dst);
+    *dst = nullptr;
+    return GWI_OK;
+  }
+  if (!*dst) GWI_HIP(hipMalloc(dst, n ? n : 1));
+  if (n) GWI_HIP(hipMemcpy(*dst, src, n, hipMemcpyHostToDevice));
+  return GWI_OK;
+}
+
+gwi_status gwi_set_draw_mask(gwi_handle h, const unsigned char* pe_mask, const unsigned char* inj_mask) {
+  if (!h) return GWI_ERR_INVALID;
+  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_set_draw_mask: host-only handle: no device to keep a mask on");
+  gwi_status st = busy_guard(h, "gwi_set_draw_mask");
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipSetDevice(h->device));
+  st = set_one_draw_mask(h, pe_mask, (size_t)(h->n_ev * h->n_pe), &h->d_draw_mask_pe);
+  if (st != GWI_OK) return st;
+  return set_one_draw_mask(h, inj_mask, (size_t)h->n_inj, &h->d_draw_mask_inj);
+}
+
+gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const double* u_pe, int32_t n_draw_pe, const double* u_inj, int32_t n_draw_inj,
+                            int32_t* idx_pe, int32_t* idx_inj) {
+  if (!h) return GWI_ERR_INVALID;
+  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: host-only handle: no device to draw on");
+  if (!h->variant) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: the engine has no scan kernel");
+  if (!thetas || k < 1) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: thetas is null or k < 1");
+  if (n_draw_pe < 0 || n_draw_inj < 0) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: a negative number of draws");
+  if (n_draw_pe > 0 && (!u_pe || !idx_pe)) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: n_draw_pe > 0 needs u_pe and idx_pe");
+  if (n_draw_inj > 0 && (!u_inj || !idx_inj)) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: n_draw_inj > 0 needs u_inj and idx_inj");
+  if (h->comm_world > 1 || h->shm_world > 1)
+    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_draw_indices: this handle holds one shard of the catalog; injection draws need the global set");
+  gwi_status st = busy_guard(h, "gwi_draw_indices");
+  if (st != GWI_OK) return st;
+  if (n_draw_pe == 0 && n_draw_inj == 0) return GWI_OK;
+  namespace D = gwi::draw;
+  const long long batches_pe = (n_draw_pe + D::kDrawBatch - 1) / D::kDrawBatch, batches_inj = (n_draw_inj + D::kDrawBatch - 1) / D::kDrawBatch;
+  const long long tiles_per_event = D::tiles_of(h->n_pe), n_inj_tiles = D::tiles_of(h->n_inj);
+  const long long n_tiles = h->n_ev * tiles_per_event + n_inj_tiles, select_blocks = h->n_ev * batches_pe + batches_inj;
+  const size_t per_point = (size_t)h->n_ev * (size_t)n_draw_pe + (size_t)n_draw_inj, total = per_point * (size_t)k;
+  if (n_tiles > 0x7fffffffLL || select_blocks > 0x7fffffffLL || h->n_pe > 0x7fffffffLL || h->n_inj > 0x7fffffffLL || total > (size_t)1 << 40)
+    return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: more draws (or samples per segment) than one launch can index");
+  GWI_HIP(hipSetDevice(h->device));
+  if (!h->d_draw_tiles) GWI_HIP(hipMalloc(&h->d_draw_tiles, sizeof(double) * (size_t)(4 * n_tiles + h->n_ev + 1)));
+  if (h->draw_u_cap < total) {
+    (void)hipFree(h->d_draw_u);
+    h->d_draw_u = nullptr;
+    h->draw_u_cap = 0;
+    GWI_HIP(hipMalloc(&h->d_draw_u, sizeof(double) * total));
+    h->draw_u_cap = total;
+  }
+  if (h->draw_idx_cap < total) {
+    (void)hipFree(h->d_draw_idx);
+    h->d_draw_idx = nullptr;
+    h->draw_idx_cap = 0;
+    GWI_HIP(hipMalloc(&h->d_draw_idx, sizeof(int) * total));
+    h->draw_idx_cap = total;
+  }
+  // uniforms: [k][n_ev][n_draw_pe], then [k][n_draw_inj]; the indices likewise
+  const size_t pe_all = (size_t)k * (size_t)h->n_ev * (size_t)n_draw_pe, pe_point = (size_t)h->n_ev * (size_t)n_draw_pe;
+  if (pe_all) GWI_HIP(hipMemcpy(h->d_draw_u, u_pe, sizeof(double) * pe_all, hipMemcpyHostToDevice));
+  if (n_draw_inj) GWI_HIP(hipMemcpy(h->d_draw_u + pe_all, u_inj, sizeof(double) * (size_t)k * (size_t)n_draw_inj, hipMemcpyHostToDevice));
+  D::DrawArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.mask_pe = h->d_draw_mask_pe;
+  a.mask_inj = h->d_draw_mask_inj;
+  a.tile_max = h->d_draw_tiles;
+  a.tile_sum = a.tile_max + n_tiles;
+  a.tile_mass = a.tile_sum + n_tiles;
+  a.tile_prefix = a.tile_mass + n_tiles;
+  a.seg_max = a.tile_prefix + n_tiles;
+  a.n_pe = h->n_pe;
+  a.n_inj = h->n_inj;
+  a.n_ev = (int)h->n_ev;
+  a.tiles_per_event = (int)tiles_per_event;
+  a.n_inj_tiles = (int)n_inj_tiles;
+  a.n_draw_pe = n_draw_pe;
+  a.n_draw_inj = n_draw_inj;
+  a.batches_pe = (int)batches_pe;
+  const int nt = h->spec.n_theta;
+  for (int p = 0; p < k; ++p) {  // one point after another: each needs its own normalisers and its own pass over the catalog
+    st = fill_log_weights(h, thetas + (size_t)p * nt, &a.log_const);
+    if (st != GWI_OK) return st;
+    a.logw_pe = h->d_logw_pe;
+    a.logw_inj = h->d_logw_inj;
+    a.u_pe = h->d_draw_u + (size_t)p * pe_point;
+    a.u_inj = h->d_draw_u + pe_all + (size_t)p * (size_t)n_draw_inj;
+    a.idx_pe = h->d_draw_idx + (size_t)p * pe_point;
+    a.idx_inj = h->d_draw_idx + pe_all + (size_t)p * (size_t)n_draw_inj;
+    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(D::draw_select_kernel, dim3((unsigned)select_blocks), dim3(D::kDrawBlock), 0, h->stream, a);
+    GWI_HIP(hipGetLastError());
+    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
+    GWI_HIP(hipStreamSynchronize(h->stream));
+  }
+  if (pe_all) GWI_HIP(hipMemcpy(idx_pe, h->d_draw_idx, sizeof(int) * pe_all, hipMemcpyDeviceToHost));
+  if (n_draw_inj) GWI_HIP(hipMemcpy(idx_inj, h->d_draw_idx + pe_all, sizeof(int) * (size_t)k * (size_t)n_draw_inj, hipMemcpyDeviceToHost));
   return GWI_OK;
 }
 

@@ -986,6 +986,62 @@ class NativePopulationLikelihood:
         self._check(self.lib.gwi_log_weights(self.handle, N.as_dp(theta), N.as_dp(pe), N.as_dp(inj)))
         return pe, inj
 
+    def set_draw_mask(self, pe_mask=None, inj_mask=None):
+        """Which samples :meth:`draw_indices` may draw (``gwi_set_draw_mask``): ``pe_mask (n_ev, n_pe)`` and ``inj_mask
+        (n_inj,)``, non-zero = may be drawn, copied to HBM once; ``None`` = every sample.  The mass cuts of the reference's
+        posterior-predictive branch (pipeline/analysis.py:326-338) belong here: :func:`gwinferno_amd.draws.mass_cut_masks`."""
+
+        def one(m, shape, name):
+            if m is None:
+                return None
+            m = np.asarray(m)
+            if m.shape != shape:
+                raise ValueError(f"{name} has shape {m.shape}, the engine's sample set {shape}")
+            return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+        pe, inj = one(pe_mask, (self.n_ev, self.n_pe), "pe_mask"), one(inj_mask, (self.n_inj,), "inj_mask")
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self.lib.gwi_set_draw_mask(self.handle, pe.ctypes.data_as(u8) if pe is not None else None, inj.ctypes.data_as(u8) if inj is not None else None))
+
+    def draw_indices(self, thetas, u_pe=None, u_inj=None):
+        """Weighted index draws on the device (``gwi_draw_indices``; semantics: :mod:`gwinferno_amd.draws`).  ``thetas``
+        is one point ``(n_theta,)`` or ``(k, n_theta)``; ``u_pe (k, n_ev, n_draw_pe)`` and ``u_inj (k, n_draw_inj)`` are the
+        caller's uniforms in ``[0, 1)`` (the leading axis may be left out for a single point; ``None`` = no draws from that
+        set).  Returns ``(idx_pe, idx_inj)``, int32 arrays of the uniforms' shapes (``None`` where no draws were asked for):
+        indices within the event / within the injection set, -1 where a segment has no sample with weight.  Only the indices
+        travel back from the device.  Not available on an engine that holds a shard (``world > 1``)."""
+        if self.world > 1:
+            raise N.NativeEngineError("GWI_ERR_UNSUPPORTED: draw_indices: this engine holds one shard of the catalog; injection draws need the global set")
+        thetas = N.f64(thetas)
+        single = thetas.ndim == 1
+        thetas = thetas.reshape(-1, self.n_theta)
+        k = thetas.shape[0]
+
+        def uniforms(u, lead, name):
+            if u is None:
+                return None, 0
+            u = N.f64(u)
+            if single and u.ndim == len(lead) + 1:
+                u = u[None]
+            if u.ndim != len(lead) + 2 or u.shape[: len(lead) + 1] != (k, *lead):
+                raise ValueError(f"{name} has shape {u.shape}; expected ({', '.join(str(v) for v in (k, *lead))}, n_draws)")
+            return u, u.shape[-1]
+
+        u_pe, n_pe_draws = uniforms(u_pe, (self.n_ev,), "u_pe")
+        u_inj, n_inj_draws = uniforms(u_inj, (), "u_inj")
+        idx_pe = np.full(u_pe.shape, -1, dtype=np.int32) if n_pe_draws else None
+        idx_inj = np.full(u_inj.shape, -1, dtype=np.int32) if n_inj_draws else None
+        i32 = C.POINTER(C.c_int32)
+        self._check(self.lib.gwi_draw_indices(self.handle, N.as_dp(thetas), k, N.as_dp(u_pe) if n_pe_draws else None, n_pe_draws, N.as_dp(u_inj) if n_inj_draws else None,
+                                              n_inj_draws, idx_pe.ctypes.data_as(i32) if n_pe_draws else None, idx_inj.ctypes.data_as(i32) if n_inj_draws else None))
+        if u_pe is not None and idx_pe is None:
+            idx_pe = np.zeros(u_pe.shape, dtype=np.int32)
+        if u_inj is not None and idx_inj is None:
+            idx_inj = np.zeros(u_inj.shape, dtype=np.int32)
+        if single:
+            idx_pe, idx_inj = (None if idx_pe is None else idx_pe[0]), (None if idx_inj is None else idx_inj[0])
+        return idx_pe, idx_inj
+
     def selftime(self, theta, total_inj, n_iter=1000, min_neff_cut=True):
         """Mean seconds per evaluation of a C-side loop of sequential gwi_eval calls (diagnostic)."""
         opt = self._options(total_inj, None, False, min_neff_cut, False)

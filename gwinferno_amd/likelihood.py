@@ -264,7 +264,50 @@ def _evaluate_jax(eng, params, total_inj, Nobs, flags):
     return {"summary": summary, "log_bfs": per_event[0], "log_neffs": per_event[1], "variances": per_event[2], "grad": None}
 
 
+_PPC_DRAWS = ["host"]
+
+
+def set_ppc_draws(where):
+    """Where the posterior-predictive indices are drawn: ``"host"`` (default: every per-sample weight is copied back with
+    ``gwi_log_weights`` and the draw is NumPy's) or ``"device"`` (``gwi_draw_indices``: the weights stay in HBM and
+    ``2 n_obs`` integers come back).  Both use the same uniforms, so they name the same samples except where a uniform
+    falls within rounding of a boundary of the cumulative weights.  Returns the previous setting."""
+    if where not in ("host", "device"):
+        raise ValueError(f"set_ppc_draws: 'host' or 'device', not {where!r}")
+    was, _PPC_DRAWS[0] = _PPC_DRAWS[0], where
+    return was
+
+
+def ppc_uniforms(n_obs):
+    """The uniforms of :func:`_ppc_indices`: ``(2, n_obs)``, row 0 for the events' posterior samples, row 1 for the injections."""
+    return np.array([[np.random.default_rng([ev, side]).uniform() for ev in range(n_obs)] for side in (0, 1)])
+
+
+def _ppc_indices_device(eng, theta, pedata, injdata, n_obs, m1min, m2min, mmax):
+    """:func:`_ppc_indices` with the draw on the device: the mass cuts become the engine's draw mask (uploaded once per
+    engine and cut values), the uniforms are the host path's.  A segment without any weight answers -1 on the device; the
+    host path's ``searchsorted`` on an all-zero cdf ends on the last sample, so that is what -1 becomes here."""
+    from .draws import mass_cut_masks
+
+    key = (float(m1min), float(m2min), float(mmax), id(pedata), id(injdata))
+    if getattr(eng, "_ppc_mask_key", None) != key:
+        eng.set_draw_mask(*mass_cut_masks(pedata, injdata, m1min, m2min, mmax))
+        eng._ppc_mask_key, eng._ppc_mask_data = key, (pedata, injdata)  # (the data stay referenced: their ids stay theirs)
+    u = ppc_uniforms(max(n_obs, eng.n_ev))
+    idx_pe, idx_inj = eng.draw_indices(theta, u[0][: eng.n_ev, None], u[1][:n_obs])
+    out = np.stack([idx_pe[:n_obs, 0], idx_inj]).astype(np.int64)
+    out[0][out[0] < 0] = eng.n_pe - 1
+    out[1][out[1] < 0] = eng.n_inj - 1
+    return out
+
+
 def _ppc_indices(eng, theta, pedata, injdata, n_obs, m1min, m2min, mmax):
+    if _PPC_DRAWS[0] == "device":
+        return _ppc_indices_device(eng, theta, pedata, injdata, n_obs, m1min, m2min, mmax)
+    return _ppc_indices_host(eng, theta, pedata, injdata, n_obs, m1min, m2min, mmax)
+
+
+def _ppc_indices_host(eng, theta, pedata, injdata, n_obs, m1min, m2min, mmax):
     """analysis.py:321-344 on the host: per-sample weights from the engine (``gwi_log_weights``), the reference's mass
     cuts, then one index per event from the PE weights and one from the injection weights.  The reference draws with
     ``jax.random.choice`` keyed by ``PRNGKey(ev)``; here the stream is ``numpy.random.default_rng([ev, 0 | 1])`` and the

@@ -218,3 +218,48 @@ def calculate_powerlaw_spline_rate_of_z_ppds(lamb, z_cs, rate, z_model, pop_frac
     draws = [(float(lamb[i]), np.concatenate([[0.0], z_cs[i]])) for i in range(n)]
     p = _curves(zs, dens, draws, (1.0, np.zeros(it.N)))
     return rate[:, None] * pop_frac[:, None] * p, zs
+
+
+def posterior_predictive_draws(eng, thetas, n_draws, seed, pedata=None, injdata=None, param_names=None, m1min=None, m2min=None, mmax=None):
+    """Population-informed posterior samples and predicted detections for K posterior hyper-parameter draws: per draw and
+    event ``n_draws`` posterior samples drawn with probability proportional to their population weight ("reweighted"
+    single-event posteriors), and ``n_draws`` found injections from the injection weights -- the draw of the reference's
+    posterior-predictive branch (pipeline/analysis.py:321-355), made on the device (``eng.draw_indices``: only indices
+    come back).
+
+    ``thetas`` is ``(K, n_theta)`` in the engine's layout.  The uniforms come from ``numpy.random.default_rng(seed)``: the
+    result is a function of ``(thetas, n_draws, seed)``.  With all of ``m1min, m2min, mmax`` given and both data
+    dictionaries at hand the reference's mass cuts (:326-338) become the engine's draw mask (``eng.set_draw_mask``); otherwise
+    the mask the engine already holds stays.
+
+    Returns a dict: ``obs_idx (K, n_ev, n_draws)`` and ``pred_idx (K, n_draws)`` (int32; -1 where nothing has weight) and,
+    when the data dictionaries are given, ``obs[p] (K, n_ev, n_draws)``, ``obs_pooled[p] (K, n_ev * n_draws)`` and
+    ``pred[p] (K, n_draws)`` for every ``p`` of ``param_names`` (default: the keys both dictionaries share); NaN where the
+    index is -1."""
+    from .draws import mass_cut_masks
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    n_draws = int(n_draws)
+    if n_draws < 1:
+        raise ValueError("n_draws must be at least 1")
+    cuts = (m1min, m2min, mmax)
+    if pedata is not None and injdata is not None and all(c is not None for c in cuts):
+        eng.set_draw_mask(*mass_cut_masks(pedata, injdata, m1min, m2min, mmax))
+    elif any(c is not None for c in cuts) and not all(c is not None for c in cuts):
+        raise ValueError("m1min, m2min and mmax are given together or not at all")
+    rng = np.random.default_rng(seed)
+    k = thetas.shape[0]
+    u_pe, u_inj = rng.uniform(size=(k, eng.n_ev, n_draws)), rng.uniform(size=(k, n_draws))
+    obs_idx, pred_idx = eng.draw_indices(thetas, u_pe, u_inj)
+    out = {"obs_idx": obs_idx, "pred_idx": pred_idx}
+    if pedata is not None and injdata is not None:
+        names = list(param_names) if param_names is not None else [p for p in pedata if p in injdata]
+        ev = np.arange(eng.n_ev)[None, :, None]
+        out["obs"], out["obs_pooled"], out["pred"] = {}, {}, {}
+        for p in names:
+            a, b = np.asarray(pedata[p], dtype=np.float64), np.asarray(injdata[p], dtype=np.float64)
+            obs = np.where(obs_idx >= 0, a[ev, np.maximum(obs_idx, 0)], np.nan)
+            out["obs"][p] = obs
+            out["obs_pooled"][p] = obs.reshape(k, -1)
+            out["pred"][p] = np.where(pred_idx >= 0, b[np.maximum(pred_idx, 0)], np.nan)
+    return out

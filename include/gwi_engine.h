@@ -361,6 +361,30 @@ const char* gwi_batch_kernel_note(gwi_handle h);
  * 174-175).  Diagnostic / parity entry point; not used on the sampling path. */
 gwi_status gwi_log_weights(gwi_handle h, const double* theta, double* pe_logw, double* inj_logw);
 
+/* Weighted index draws on the device: what the reference's posterior-predictive branch does per hyper-parameter point
+ * (pipeline/analysis.py:321-355: per event one posterior sample drawn with probability proportional to its population weight,
+ * and found injections from the injection weights) and what reweighted single-event posteriors and predicted-detection samples
+ * are made of -- without the per-sample weights ever leaving HBM (gwinferno_amd/csrc/gwi_draw.h).
+ *
+ * A segment is one event's n_pe posterior samples, or the injection set.  For a segment with log-weights lw_j (those of
+ * gwi_log_weights), a 0/1 mask a_j and a uniform u in [0, 1):  M = max of lw_j over samples with a_j = 1 and lw_j finite;
+ * w_j = a_j ? exp(lw_j - M) : 0 (0 for a non-finite lw_j);  C_j = w_0 + ... + w_j;  the draw is the smallest j with
+ * C_j > u C_last and w_j > 0 (the last sample with positive weight when rounding runs past the end), -1 for a segment without
+ * any positive weight.  The uniforms are the caller's: there is no random number generator on the device.  The order of summation
+ * is fixed, so the indices are a pure function of the arguments (same on every call and on every handle of one model).
+ *
+ * gwi_set_draw_mask(): the masks (the mass cuts of analysis.py:326-338, which depend on the catalog only) -- pe_mask has
+ * n_ev * n_pe bytes (uint8, event-major), inj_mask n_inj; copied to HBM once; NULL = all ones (the state of a new handle).
+ * gwi_draw_indices(): for each of the k points thetas[k][n_theta], n_draw_pe draws per event (u_pe[k][n_ev][n_draw_pe] ->
+ * idx_pe of the same shape: indices within the event) and n_draw_inj draws from the injection set (u_inj[k][n_draw_inj] ->
+ * idx_inj).  Either count may be 0 (its pointers are then ignored).  k is not bound by the batch limit: the points are evaluated
+ * one after another inside the library and the indices come back in one copy -- the only device-to-host traffic.
+ * GWI_ERR_INVALID for bad counts / null pointers and for host-only handles; GWI_ERR_UNSUPPORTED on a handle that holds a shard
+ * (after gwi_comm_init / gwi_shm_comm_init): injection draws need the global set. */
+gwi_status gwi_set_draw_mask(gwi_handle h, const unsigned char* pe_mask, const unsigned char* inj_mask);
+gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const double* u_pe, int32_t n_draw_pe, const double* u_inj, int32_t n_draw_inj,
+                            int32_t* idx_pe, int32_t* idx_inj);
+
 /* Multi-GPU (one process per GPU): each rank's engine holds a contiguous block of events and a
  * slice of the injections.  gwi_eval_partial() runs the scan and leaves this rank's partial
  * record (gwi_partial_len() doubles) in `record`; the caller exchanges records (RCCL all-gather
