@@ -749,7 +749,16 @@ struct Term<GWI_TERM_POWERLAW_RATIO> {
     // m1 == mmin exactly (lr = 0): the q interval is empty, the reference's weight is NaN -> 0; keep the
     // gradient state finite so that the dead sample adds 0, not NaN
     const double inv_den = (em1 != 0.0) ? -fast_rcp(em1) : 0.0;  // 1/(1 - r^(1+beta))
+    // d/dbeta = log q + 1/b1 + r^b1 log r / (1 - r^b1): the last two cancel as b1 -> 0 (what is left of 1/b1 ~ 1e15 after the
+    // subtraction carries expm1's ~6e-15 relative error: 1e-8 of the result at |b1| = 1e-6, all of it at 1e-15).  Next to the
+    // removable singularity the same number is log q - lr/2 - (lr/2) L(b1 lr/2) with the Langevin function L(t) = coth t - 1/t
+    // = t/3 - t^3/45 + 2 t^5/945 - ... (|t| < 0.03 for |b1| < 0.01 and m1 < 400 mmin: the next term is < 1e-14); continuous
+    // with the b1 == 0 branch above.  b1 is wave-uniform (a hyper-parameter), like that branch.
     s.db = lq + d[0] + (em1 + 1.0) * lr * inv_den;
+    if (__builtin_expect(__builtin_fabs(b1) < 1.0e-2, 0)) {  // (a real, rarely taken branch: ordinary points pay no series)
+      const double hl = 0.5 * lr, t = b1 * hl, u = t * t;
+      s.db = lq - hl - hl * (t * fma(u, fma(u, 2.0 / 945.0, -1.0 / 45.0), 1.0 / 3.0));
+    }
     lin *= b1 * inv_den;
     return beta * lq;
   }

@@ -313,11 +313,34 @@ constexpr int kRecNormOff = 8;
 // ------------------------------------------------------------------------------------------------
 // log of the power-law normaliser (1+a)/(hi^(1+a) - lo^(1+a)) and its alpha-derivative
 // (distributions.py:112-116), evaluated in the log domain so large |alpha| cannot overflow.
+//
+// alpha = -1 is a REMOVABLE singularity, and the closed forms below cancel next to it: log1p(-rho) loses log A to
+// eps / |t| and 1/a1 - (..)/(1 - rho) loses d log A to eps h / t^2 (t = a1 h, h = log(hi/lo) / 2) -- 1e-5 of d log A at
+// |1 + alpha| = 1e-6, all of it at 1e-8.  For |t| < 1 the same two numbers are therefore written around the midpoint
+// c = (log hi + log lo) / 2, where nothing cancels:
+//   log A   = -a1 c - log(2 h) - log(sinh t / t)
+//   dlogA/da = -c - h L(t),   L(t) = coth t - 1/t = t/3 - t^3/45 + 2 t^5/945 - ...   (the Langevin function)
+// L by its series below |t| = 0.1 (the next term, t^15 / 4.5e7, is < 1e-22 there) and directly above (coth t - 1/t is then
+// good to 10 eps).  The exact point keeps its own branch (the reference's, and the same numbers as ever), and |t| >= 1 -- every
+// draw of the benchmark priors -- the log-domain forms.
+double langevin(double t) {
+  if (std::fabs(t) < 0.1) {
+    const double u = t * t;
+    return t * (1.0 / 3.0 + u * (-1.0 / 45.0 + u * (2.0 / 945.0 + u * (-1.0 / 4725.0 + u * (2.0 / 93555.0 + u * (-1382.0 / 638512875.0 + u * (4.0 / 18243225.0)))))));
+  }
+  return 1.0 / std::tanh(t) - 1.0 / t;
+}
 void powerlaw_lognorm(double alpha, double lo, double hi, double* logA, double* dlogA) {
   const double a1 = 1.0 + alpha, llo = std::log(lo), lhi = std::log(hi);
   if (a1 == 0.0) {
     *logA = -std::log(lhi - llo);
     *dlogA = -0.5 * (lhi + llo);
+    return;
+  }
+  const double c = 0.5 * (lhi + llo), h = 0.5 * (lhi - llo), t = a1 * h;
+  if (std::fabs(t) < 1.0) {
+    *logA = -a1 * c - std::log(2.0 * h) - std::log(std::sinh(t) / t);
+    *dlogA = -c - h * langevin(t);
     return;
   }
   if (a1 > 0) {

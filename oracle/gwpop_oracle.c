@@ -85,17 +85,32 @@ static void acc_merge(acc_t* dst, const acc_t* src, int n_theta) {
     for (int p = 0; p < n_theta; ++p) dst->h[p] += f * f * src->h[p];
 }
 
-static void pl_lognorm(double alpha, double lo, double hi, double* la, double* dla) {
-  const double a1 = 1.0 + alpha, llo = log(lo), lhi = log(hi);
+/* log A and d log A / d alpha of the power-law normaliser A = a1 / (hi^a1 - lo^a1), a1 = 1 + alpha, from the LOGARITHMS of the
+ * bounds (distributions.py:112-116).  a1 = 0 is a removable singularity next to which the reference's closed form cancels
+ * (d log A is lost entirely at |a1| = 1e-8), so it is written around the midpoint c = (lhi + llo) / 2 with h = (lhi - llo) / 2,
+ * t = a1 h:  log A = -a1 c - log(2h) - log(sinh t / t),  d log A = -c - h (coth t - 1/t)  -- smooth through t = 0; the Langevin
+ * function coth t - 1/t by its series for small |t|, sinh in the log domain for large |t|. */
+static double langevin(double t) {
+  if (fabs(t) < 0.1) {
+    const double u = t * t;
+    return t * (1.0 / 3.0 + u * (-1.0 / 45.0 + u * (2.0 / 945.0 + u * (-1.0 / 4725.0 + u * (2.0 / 93555.0 + u * (-1382.0 / 638512875.0 + u * (4.0 / 18243225.0)))))));
+  }
+  return 1.0 / tanh(t) - 1.0 / t;
+}
+
+static void pl_lognorm_log(double a1, double llo, double lhi, double* la, double* dla) {
   if (a1 == 0.0) {
     *la = -log(lhi - llo);
     *dla = -0.5 * (lhi + llo);
     return;
   }
-  const double ph = pow(hi, a1), pw = pow(lo, a1);
-  *la = log(a1 / (ph - pw)); /* distributions.py:115 */
-  *dla = 1.0 / a1 - (ph * lhi - pw * llo) / (ph - pw);
+  const double c = 0.5 * (lhi + llo), h = 0.5 * (lhi - llo), t = a1 * h, at = fabs(t);
+  const double lsh = at < 1.0 ? log(sinh(t) / t) : at + log1p(-exp(-2.0 * at)) - log(2.0 * at); /* log(sinh t / t) */
+  *la = -a1 * c - log(2.0 * h) - lsh;
+  *dla = -c - h * langevin(t);
 }
+
+static void pl_lognorm(double alpha, double lo, double hi, double* la, double* dla) { pl_lognorm_log(1.0 + alpha, log(lo), log(hi), la, dla); }
 
 static void tn_lognorm(double mu, double sg, double lo, double hi, double* lc, double* dmu, double* dsg) {
   const double r2 = sqrt(2.0), a = (lo - mu) / sg, b = (hi - mu) / sg;
@@ -169,7 +184,8 @@ static double sample_logw(const gwi_spec* sp, const double* const* cols, int64_t
         push(d, tm->theta[1], T * ((x0 - mu) / (sg * sg) + der[t][3]) / p);
         push(d, tm->theta[2], T * ((x0 - mu) * (x0 - mu) / (sg * sg * sg) + der[t][4]) / p);
         push(d, tm->theta[3], (etn - epl) / p);
-        push(d, tm->coef_off, P * (-(1.0 - S) * (1.0 / y + y / ((y - dl) * (y - dl)))) / p);
+        /* S = 0 (y = 0, y = delta, or an overflowing exponent): the power-law part and its delta-derivative vanish -- not 0 x inf */
+        push(d, tm->coef_off, P > 0.0 ? P * (-(1.0 - S) * (1.0 / y + y / ((y - dl) * (y - dl)))) / p : 0.0);
         break;
       }
       case GWI_TERM_POWERLAW_RATIO: {
@@ -177,14 +193,10 @@ static double sample_logw(const gwi_spec* sp, const double* const* cols, int64_t
          * the HOST side -- what this checker is handed -- holds that spline's coordinate x = log m1 itself (only the device
          * copy is converted to knot coordinates, gwi_engine.hip: spline_knot_kernel): the same read either way. */
         const double lr = tm->p[0] - cols[tm->cols[1]][idx], beta = th[tm->theta[0]], b1 = 1.0 + beta;
-        if (b1 == 0.0) {
-          ell += -x0 - log(-lr);
-          push(d, tm->theta[0], x0 - 0.5 * lr);
-        } else {
-          const double E = exp(b1 * lr);
-          ell += beta * x0 + log(b1 / (1.0 - E));
-          push(d, tm->theta[0], x0 + 1.0 / b1 + E * lr / (1.0 - E));
-        }
+        double la, dla; /* powerlaw_pdf(q, beta, mmin / m1, 1): bounds log r and 0; m1 == mmin (lr = 0): la = +inf (b1 == 0) or NaN (sinh t / t = 0/0), excluded below by !(ell < INFINITY) */
+        pl_lognorm_log(b1, lr, 0.0, &la, &dla);
+        ell += beta * x0 + la;
+        push(d, tm->theta[0], x0 + dla);
         break;
       }
       case GWI_TERM_BETA: {
