@@ -231,6 +231,9 @@ EXPORTED_SYMBOLS = [
     "gwi_log_weights",
     "gwi_set_draw_mask",
     "gwi_draw_indices",
+    "gwi_effective_spins",
+    "gwi_chi_p_conditional_prior",
+    "gwi_spin_prior_times",
     "gwi_partial_len",
     "gwi_eval_partial",
     "gwi_prepare_combine",
@@ -338,6 +341,14 @@ def load_library():
         lib.gwi_set_draw_mask.argtypes = [vp, _U8P, _U8P]
         lib.gwi_draw_indices.restype = C.c_int32
         lib.gwi_draw_indices.argtypes = [vp, _DP, C.c_int32, _DP, C.c_int32, _DP, C.c_int32, _I32P, _I32P]
+    if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_effective_spins.restype = C.c_int32
+        lib.gwi_effective_spins.argtypes = [C.c_int64, _DP, _DP, _DP, _DP, _DP, C.c_double, _DP, _DP, _DP, _DP, _DP, C.c_int32]
+        lib.gwi_chi_p_conditional_prior.restype = C.c_int32
+        lib.gwi_chi_p_conditional_prior.argtypes = [C.c_int64, _DP, _DP, _DP, C.c_double, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _DP, _I32P, C.c_int32]
+        lib.gwi_spin_prior_times.restype = None
+        lib.gwi_spin_prior_times.argtypes = [_DP, _DP, _I32P]
     lib.gwi_partial_len.restype = C.c_int64
     lib.gwi_partial_len.argtypes = [vp]
     lib.gwi_eval_partial.restype = C.c_int32

@@ -186,3 +186,49 @@ def pe_sampling_prior(pedict, param_names, redshift_prior="comoving"):
     if "a_1" in param_names:
         prior *= 1 / 4
     return prior
+
+
+_SPIN_COLUMNS = ("mass_ratio", "a_1", "a_2", "cos_tilt_1", "cos_tilt_2")
+
+
+def effective_spin_catalog(d, param_names, injections=False, a_max=1.0, **kw):
+    """data_collection.py:210-296 (``convert_component_spins_to_chieff``) on a ``pedict`` ``(N_ev, N_pe)`` or, with
+    ``injections=True``, an ``injdict`` ``(N_inj,)``: returns a NEW dict that also holds ``chi_eff`` (and ``chi_p`` when it is in
+    ``param_names``) and whose ``prior`` is ``prior / ((2 pi a_1^2)(2 pi a_2^2)) p(chi_eff | q)`` -- times ``p(chi_p | chi_eff, q)``
+    with ``chi_p``.  As in the reference ``a = 0`` leaves a non-finite prior (the engine masks such samples).  Both steps run on
+    the device (:mod:`gwinferno_amd.spin_priors`; ``backend="host"`` is the NumPy statement of the same arithmetic).  Keywords:
+    ``backend``, ``device``, and for the conditional prior ``ndraws``, ``seed``, ``max_attempts``, ``first_index`` -- sample ``k`` of
+    the dict (C order: PE samples event-major) is sample ``first_index + k`` of the stream, so a shard passes its offset and an
+    injection set the number of PE samples before it (:func:`effective_spin_catalogs` does)."""
+    from . import spin_priors as S
+
+    backend, device = kw.pop("backend", "device"), kw.pop("device", -1)
+    cond = {k: kw.pop(k) for k in ("ndraws", "seed", "max_attempts", "first_index", "bw_method") if k in kw}
+    if kw:
+        raise TypeError(f"unexpected keywords {sorted(kw)}")
+    q, a1, a2, ct1, ct2 = (np.asarray(d[k], dtype=np.float64) for k in _SPIN_COLUMNS)
+    prior = np.asarray(d["prior"], dtype=np.float64)
+    if q.ndim != (1 if injections else 2) or prior.shape != q.shape:
+        raise ValueError(f"expected {'(N_inj,)' if injections else '(N_ev, N_pe)'} columns, got mass_ratio {q.shape} and prior {prior.shape}")
+    with_chi_p = "chi_p" in param_names
+    res = S.effective_spins(q, a1, a2, ct1, ct2, a_max=a_max, outputs=("chi_eff", "chi_p", "p_chi_eff_iso") if with_chi_p else ("chi_eff", "p_chi_eff_iso"),
+                            backend=backend, device=device)
+    new_prior_factor = res["p_chi_eff_iso"]
+    if with_chi_p:
+        new_prior_factor = new_prior_factor * S.chi_p_prior_given_chi_eff_q(res["chi_p"], res["chi_eff"], q, a_max=a_max, backend=backend, device=device, **cond)
+    out = dict(d)
+    out["chi_eff"] = res["chi_eff"]
+    if with_chi_p:
+        out["chi_p"] = res["chi_p"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["prior"] = prior / ((2 * np.pi * a1**2) * (2 * np.pi * a2**2)) * new_prior_factor
+    return out
+
+
+def effective_spin_catalogs(pedict, injdict, param_names, a_max=1.0, **kw):
+    """Both sample sets through :func:`effective_spin_catalog` with one numbering of the conditional prior's stream: the PE samples
+    event-major from ``first_index`` (default 0), the injections after them."""
+    first = int(kw.pop("first_index", 0))
+    pe = effective_spin_catalog(pedict, param_names, injections=False, a_max=a_max, first_index=first, **kw)
+    inj = effective_spin_catalog(injdict, param_names, injections=True, a_max=a_max, first_index=first + int(np.asarray(pedict["mass_ratio"]).size), **kw)
+    return pe, inj

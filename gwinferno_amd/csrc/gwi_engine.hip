@@ -5,6 +5,7 @@
 #include "gwi_aql.h"
 #include "gwi_ingest.h"
 #include "gwi_draw.h"
+#include "gwi_spinprior.h"
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
 
@@ -3604,6 +3605,167 @@ gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const
   if (pe_all) GWI_HIP(hipMemcpy(idx_pe, h->d_draw_idx, sizeof(int) * pe_all, hipMemcpyDeviceToHost));
   if (n_draw_inj) GWI_HIP(hipMemcpy(idx_inj, h->d_draw_idx + pe_all, sizeof(int) * (size_t)k * (size_t)n_draw_inj, hipMemcpyDeviceToHost));
   return GWI_OK;
+}
+
+}  // extern "C"
+
+// ---- effective-spin catalogs (gwi_spinprior.h): stand-alone entries, no handle, like gwi_ingest_columns ------------------
+namespace {
+
+struct SpinTimes {
+  double total_ms = 0.0, max_launch_ms = 0.0;
+  int launches = 0;
+};
+thread_local SpinTimes g_spin_times;
+
+// device buffers, a stream and two events that go away with the scope
+struct SpinScratch {
+  std::vector<void*> bufs;
+  hipStream_t stream = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~SpinScratch() {
+    for (void* b : bufs) (void)hipFree(b);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  template <class T>
+  T* alloc(size_t n) {
+    void* p = nullptr;
+    if (hipMalloc(&p, sizeof(T) * (n ? n : 1)) != hipSuccess) return nullptr;
+    bufs.push_back(p);
+    return (T*)p;
+  }
+  bool open() { return hipStreamCreate(&stream) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
+};
+
+// puts the calling thread back on the device it was on when the scope ends
+struct SpinDeviceGuard {
+  int previous = -1;
+  ~SpinDeviceGuard() {
+    if (previous >= 0) (void)hipSetDevice(previous);
+  }
+};
+
+gwi_status spin_device(int32_t device, SpinDeviceGuard* guard) {
+  int n_dev = 0, current = -1;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return GWI_ERR_NO_DEVICE;
+  if (device >= n_dev) return GWI_ERR_NO_DEVICE;
+  if (device < 0) return GWI_OK;
+  if (hipGetDevice(&current) != hipSuccess) return GWI_ERR_HIP;
+  if (current == device) return GWI_OK;
+  if (hipSetDevice(device) != hipSuccess) return GWI_ERR_HIP;
+  guard->previous = current;
+  return GWI_OK;
+}
+
+#define GWI_SPIN_HIP(call)                                                                  \
+  do {                                                                                      \
+    hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess) {                                                                 \
+      std::fprintf(stderr, "%s: %s: %s\n", kWhere, #call, hipGetErrorString(e_));           \
+      return GWI_ERR_HIP;                                                                   \
+    }                                                                                       \
+  } while (0)
+
+}  // namespace
+
+extern "C" {
+
+gwi_status gwi_effective_spins(int64_t n, const double* q, const double* a1, const double* a2, const double* ct1, const double* ct2, double a_max, double* chi_eff,
+                               double* chi_p, double* p_chi_eff_iso, double* p_chi_eff_aligned, double* p_chi_p_iso, int32_t device) {
+  static const char* kWhere = "gwi_effective_spins";
+  namespace S = gwi::spinprior;
+  if (n < 0 || !(a_max > 0.0) || !(a_max < __builtin_inf())) return GWI_ERR_INVALID;
+  if (n > 0 && (!q || !a1 || !a2 || !ct1 || !ct2)) return GWI_ERR_INVALID;
+  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
+  gwi_status st = spin_device(device, &guard);
+  if (st != GWI_OK) return st;
+  g_spin_times = SpinTimes();
+  if (n == 0) return GWI_OK;
+  SpinScratch sc;
+  if (!sc.open()) return GWI_ERR_HIP;
+  const size_t bytes = sizeof(double) * (size_t)n;
+  const double* in[5] = {q, a1, a2, ct1, ct2};
+  double* out[5] = {chi_eff, chi_p, p_chi_eff_iso, p_chi_eff_aligned, p_chi_p_iso};
+  double *d_in[5], *d_out[5];
+  for (int c = 0; c < 5; ++c) {
+    d_in[c] = sc.alloc<double>((size_t)n);
+    d_out[c] = out[c] ? sc.alloc<double>((size_t)n) : nullptr;
+    if (!d_in[c] || (out[c] && !d_out[c])) return GWI_ERR_HIP;
+    GWI_SPIN_HIP(hipMemcpyAsync(d_in[c], in[c], bytes, hipMemcpyHostToDevice, sc.stream));
+  }
+  const long long blocks = std::min<long long>((n + S::kBlock - 1) / S::kBlock, 2048);
+  S::SpinArgs a{d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], a_max, (long long)n, blocks * S::kBlock};
+  GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
+  hipLaunchKernelGGL(S::effective_spins_kernel, dim3((unsigned)blocks), dim3(S::kBlock), 0, sc.stream, a);
+  GWI_SPIN_HIP(hipGetLastError());
+  GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
+  for (int c = 0; c < 5; ++c)
+    if (out[c]) GWI_SPIN_HIP(hipMemcpyAsync(out[c], d_out[c], bytes, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));
+  float ms = 0.f;
+  GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
+  g_spin_times.total_ms = g_spin_times.max_launch_ms = ms;
+  g_spin_times.launches = 1;
+  return GWI_OK;
+}
+
+gwi_status gwi_chi_p_conditional_prior(int64_t n, const double* chi_p, const double* chi_eff, const double* q, double a_max, int32_t n_draws, int32_t max_attempts,
+                                       uint64_t seed, int64_t first_index, double* p, int32_t* accepted, int32_t device) {
+  static const char* kWhere = "gwi_chi_p_conditional_prior";
+  namespace S = gwi::spinprior;
+  if (n < 0 || n_draws < 2 || max_attempts < 1 || max_attempts > (1 << 16) || first_index < 0 || !(a_max > 0.0) || !(a_max < __builtin_inf())) return GWI_ERR_INVALID;
+  if (n > 0 && (!chi_p || !chi_eff || !q || !p || !accepted)) return GWI_ERR_INVALID;
+  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
+  gwi_status st = spin_device(device, &guard);
+  if (st != GWI_OK) return st;
+  g_spin_times = SpinTimes();
+  if (n == 0) return GWI_OK;
+  SpinScratch sc;
+  if (!sc.open()) return GWI_ERR_HIP;
+  const size_t bytes = sizeof(double) * (size_t)n;
+  const double* in[3] = {chi_p, chi_eff, q};
+  double* d_in[3];
+  for (int c = 0; c < 3; ++c) {
+    d_in[c] = sc.alloc<double>((size_t)n);
+    if (!d_in[c]) return GWI_ERR_HIP;
+    GWI_SPIN_HIP(hipMemcpyAsync(d_in[c], in[c], bytes, hipMemcpyHostToDevice, sc.stream));
+  }
+  double* d_p = sc.alloc<double>((size_t)n);
+  int* d_acc = sc.alloc<int>((size_t)n);
+  if (!d_p || !d_acc) return GWI_ERR_HIP;
+  // one workgroup per sample.  A launch is sized by its WORST case, every slot using all its attempts: a slot then costs 50
+  // exponentials and, over the two passes, 2 max_attempts pairs of Philox blocks, a pair being about 4 exponentials' worth of
+  // instructions -- 50 + 8 max_attempts units.  The budget is 8192 samples of 10^4 draws at the default 64 attempts (4.6e10 units);
+  // a typical slot needs two or three attempts (some 70 units), so a typical launch is about an eighth of the worst one, and a larger
+  // max_attempts shrinks the launch in proportion, down to one sample
+  const double slot_units = 50.0 + 8.0 * (double)max_attempts;
+  const long long per_launch = std::max<long long>(1, std::min<long long>(1 << 20, (long long)(4.6e10 / (slot_units * (double)n_draws))));
+  for (long long base = 0; base < n; base += per_launch) {
+    const long long m = std::min<long long>(per_launch, n - base);
+    S::CondArgs a{d_in[0] + base, d_in[1] + base, d_in[2] + base, d_p + base, d_acc + base, a_max, (unsigned long long)seed, (long long)first_index + base, n_draws, max_attempts};
+    GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
+    hipLaunchKernelGGL(S::chi_p_conditional_kernel, dim3((unsigned)m), dim3(S::kBlock), 0, sc.stream, a);
+    GWI_SPIN_HIP(hipGetLastError());
+    GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
+    GWI_SPIN_HIP(hipEventSynchronize(sc.e1));
+    float ms = 0.f;
+    GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
+    g_spin_times.total_ms += ms;
+    g_spin_times.max_launch_ms = std::max<double>(g_spin_times.max_launch_ms, ms);
+    ++g_spin_times.launches;
+  }
+  GWI_SPIN_HIP(hipMemcpyAsync(p, d_p, bytes, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SPIN_HIP(hipMemcpyAsync(accepted, d_acc, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));
+  return GWI_OK;
+}
+
+void gwi_spin_prior_times(double* total_ms, double* max_launch_ms, int32_t* launches) {
+  if (total_ms) *total_ms = g_spin_times.total_ms;
+  if (max_launch_ms) *max_launch_ms = g_spin_times.max_launch_ms;
+  if (launches) *launches = g_spin_times.launches;
 }
 
 }  // extern "C"

@@ -385,6 +385,42 @@ gwi_status gwi_set_draw_mask(gwi_handle h, const unsigned char* pe_mask, const u
 gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const double* u_pe, int32_t n_draw_pe, const double* u_inj, int32_t n_draw_inj,
                             int32_t* idx_pe, int32_t* idx_inj);
 
+/* Effective-spin catalogs (gwinferno_amd/csrc/gwi_spinprior.h; the NumPy statement is gwinferno_amd/spin_priors.py).  Stand-alone
+ * entries like gwi_ingest_columns: no handle, host pointers in and out, their own stream and buffers on `device` (negative: the
+ * calling thread's current device).  The calling thread's current device is the same after the call as before it.
+ *
+ * gwi_effective_spins(): per sample, from the component spins (q, a_1, a_2, cos tilt_1, cos tilt_2) --
+ *   chi_eff = (a1 ct1 + q a2 ct2) / (1 + q)  and  chi_p = max(a1 sin t1, (3 + 4q) / (4 + 3q) q a2 sin t2)   (preprocess/conversions.py:8-62);
+ *   p_chi_eff_iso     = p(chi_eff | q) for uniform, isotropic spins with magnitudes below a_max (Callister, arXiv:2104.09508;
+ *                       preprocess/priors.py:79-196): the closed form at chi_eff = 0, the five open cases, 0 for |chi_eff| >= a_max, and
+ *                       for a value exactly on a case boundary the mean of the form at |chi_eff| +- 1e-6;
+ *   p_chi_eff_aligned = the same for aligned spins (priors.py:38-76);   p_chi_p_iso = p(chi_p | q) (priors.py:199-244);
+ * each evaluated at the sample's own chi_eff / chi_p.  Any output may be NULL.  A sample with a NaN, q <= 0 or |cos tilt| > 1 yields
+ * NaN in every output.  n = 0 is GWI_OK and writes nothing.
+ *
+ * gwi_chi_p_conditional_prior(): p(chi_p | chi_eff, q) by the estimator of priors.py:288-333 with a counter-based generator and
+ * bounded rejection.  Slot d of sample s (catalog index first_index + s) tries attempts t = 0, 1, ... < max_attempts; attempt t draws
+ * a1 = a_max u0, a2 = a_max u1, cos t2 = 2 u2 - 1 from Philox4x32-10 with key = seed (low word, high word) and counters
+ * (index low, index high, d, 2t) -> (u0: words 0,1; u1: words 2,3) and (.., 2t + 1) -> (u2: words 0,1), a uniform being
+ * ((hi >> 5) 2^26 + (lo >> 6)) 2^-53; it is kept when |cos t1| <= 1 for cos t1 = (chi_eff (1 + q) - q a2 cos t2) / a1.  The slot's
+ * draw is the chi_p of its first kept attempt with weight (1 + q) / a1; a slot without one carries no weight.  accepted[s] counts the
+ * filled slots; with none, p[s] = NaN.  The density is scipy.stats.gaussian_kde's weighted Gaussian KDE of the draws (Scott's factor
+ * n_eff^(-1/5), n_eff = 1 / sum w^2 of the normalised weights, variance with the 1 / (1 - sum w^2) correction) on the 50 points from
+ * 0.05 to 0.95 max_chi_p, zeros added at 0 and max_chi_p, normalised by the trapezoid rule, interpolated linearly at chi_p.  The
+ * values depend on (seed, first_index + s) only -- not on how a catalog is cut into calls -- and on nothing that varies between runs.
+ * n is cut into launches sized by the worst case, every slot using all max_attempts attempts (n_draws (50 + 8 max_attempts) units
+ * per sample against a budget of 4.6e10), so a larger max_attempts means smaller launches, not longer ones.
+ * GWI_ERR_INVALID for n_draws < 2, max_attempts < 1 or > 65536, first_index < 0 or a null pointer with n > 0.
+ *
+ * gwi_spin_prior_times(): DIAGNOSTIC ONLY, for tools/effective_spins_time.py -- not part of the catalog interface, and nothing in the
+ * package depends on it.  Device time of the calling thread's last call of either entry (HIP events around the launches): the total,
+ * the longest single launch and the number of launches. */
+gwi_status gwi_effective_spins(int64_t n, const double* q, const double* a1, const double* a2, const double* ct1, const double* ct2, double a_max, double* chi_eff,
+                               double* chi_p, double* p_chi_eff_iso, double* p_chi_eff_aligned, double* p_chi_p_iso, int32_t device);
+gwi_status gwi_chi_p_conditional_prior(int64_t n, const double* chi_p, const double* chi_eff, const double* q, double a_max, int32_t n_draws, int32_t max_attempts,
+                                       uint64_t seed, int64_t first_index, double* p, int32_t* accepted, int32_t device);
+void gwi_spin_prior_times(double* total_ms, double* max_launch_ms, int32_t* launches);
+
 /* Multi-GPU (one process per GPU): each rank's engine holds a contiguous block of events and a
  * slice of the injections.  gwi_eval_partial() runs the scan and leaves this rank's partial
  * record (gwi_partial_len() doubles) in `record`; the caller exchanges records (RCCL all-gather
