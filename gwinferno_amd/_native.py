@@ -234,6 +234,9 @@ EXPORTED_SYMBOLS = [
     "gwi_effective_spins",
     "gwi_chi_p_conditional_prior",
     "gwi_spin_prior_times",
+    "gwi_table_draws",
+    "gwi_table_draws_error",
+    "gwi_table_draws_times",
     "gwi_partial_len",
     "gwi_eval_partial",
     "gwi_prepare_combine",
@@ -349,6 +352,13 @@ def load_library():
         lib.gwi_chi_p_conditional_prior.argtypes = [C.c_int64, _DP, _DP, _DP, C.c_double, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, _DP, _I32P, C.c_int32]
         lib.gwi_spin_prior_times.restype = None
         lib.gwi_spin_prior_times.argtypes = [_DP, _DP, _I32P]
+    if hasattr(lib, "gwi_table_draws"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        lib.gwi_table_draws.restype = C.c_int32
+        lib.gwi_table_draws.argtypes = [C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP, C.c_int64, C.c_uint64, C.c_uint64, _DP, _DP, _DP, C.POINTER(C.c_uint8)]
+        lib.gwi_table_draws_error.restype = C.c_char_p
+        lib.gwi_table_draws_error.argtypes = []
+        lib.gwi_table_draws_times.restype = None
+        lib.gwi_table_draws_times.argtypes = [_DP, _DP, C.POINTER(C.c_int32)]
     lib.gwi_partial_len.restype = C.c_int64
     lib.gwi_partial_len.argtypes = [vp]
     lib.gwi_eval_partial.restype = C.c_int32

@@ -6,6 +6,7 @@
 #include "gwi_ingest.h"
 #include "gwi_draw.h"
 #include "gwi_spinprior.h"
+#include "gwi_popdraw.h"
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
 
@@ -3766,6 +3767,126 @@ void gwi_spin_prior_times(double* total_ms, double* max_launch_ms, int32_t* laun
   if (total_ms) *total_ms = g_spin_times.total_ms;
   if (max_launch_ms) *max_launch_ms = g_spin_times.max_launch_ms;
   if (launches) *launches = g_spin_times.launches;
+}
+
+}  // extern "C"
+
+// ---- population draws (gwi_popdraw.h): a stand-alone entry, no handle, like gwi_effective_spins ---------------------------
+namespace {
+
+struct PopdrawTimes {
+  double cdf_ms = 0.0, draw_ms = 0.0;
+  int launches = 0;
+};
+thread_local PopdrawTimes g_popdraw_times;
+thread_local std::string g_popdraw_error;
+
+gwi_status popdraw_refuse(const std::string& why) {
+  g_popdraw_error = why;
+  return GWI_ERR_INVALID;
+}
+
+constexpr long long kPopdrawDrawsPerLaunch = 1ll << 20;    // per table
+constexpr long long kPopdrawThreadsPerLaunch = 1ll << 26;  // over the tables of a launch
+
+}  // namespace
+
+extern "C" {
+
+gwi_status gwi_table_draws(int32_t device, int32_t n_tables, int32_t n_grid, const double* lo, const double* hi, const double* pdf, int64_t n_draws, uint64_t seed,
+                           uint64_t first_index, const double* lower, double* x, double* mass, unsigned char* accept) {
+  static const char* kWhere = "gwi_table_draws";
+  namespace P = gwi::popdraw;
+  g_popdraw_error.clear();
+  g_popdraw_times = PopdrawTimes();
+  // ---- the argument checks: on the host, before anything is uploaded
+  if (n_tables < 0 || n_draws < 0) return popdraw_refuse("negative n_tables or n_draws");
+  if (n_grid < 2) return popdraw_refuse("table 0: n_grid = " + std::to_string(n_grid) + " < 2 (a table has at least one cell)");
+  if (n_grid > P::kMaxGrid) return popdraw_refuse("table 0: n_grid = " + std::to_string(n_grid) + " > " + std::to_string(P::kMaxGrid) + " (a table is staged in LDS)");
+  if (n_tables > 0 && (!lo || !hi || !pdf)) return popdraw_refuse("null lo, hi or pdf");
+  if (n_tables > 0 && n_draws > 0 && !x) return popdraw_refuse("null x");
+  for (int32_t t = 0; t < n_tables; ++t) {
+    const double width = hi[t] - lo[t];
+    if (!(hi[t] > lo[t]) || !(width < __builtin_inf())) return popdraw_refuse("table " + std::to_string(t) + ": hi <= lo (or a bound that is not finite)");
+    const double* p = pdf + (size_t)t * (size_t)n_grid;
+    for (int32_t i = 0; i < n_grid; ++i)
+      if (!(p[i] >= 0.0) || !(p[i] < __builtin_inf())) return popdraw_refuse("table " + std::to_string(t) + ": density entry " + std::to_string(i) + " is negative or not finite");
+    const double dx = width / (double)(n_grid - 1);
+    bool live = false;
+    for (int32_t i = 0; i + 1 < n_grid && !live; ++i) live = 0.5 * (p[i] + p[i + 1]) * dx > 0.0;  // the kernel's cell mass
+    if (!live) return popdraw_refuse("table " + std::to_string(t) + ": the total mass is 0");
+  }
+  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
+  gwi_status st = spin_device(device, &guard);
+  if (st != GWI_OK) return st;
+  if (n_tables == 0 || n_draws == 0) return GWI_OK;
+  SpinScratch sc;
+  if (!sc.open()) return GWI_ERR_HIP;
+  const size_t n_cell = (size_t)n_grid - 1;
+  double* d_pdf = sc.alloc<double>((size_t)n_tables * (size_t)n_grid);
+  double* d_lo = sc.alloc<double>((size_t)n_tables);
+  double* d_hi = sc.alloc<double>((size_t)n_tables);
+  double* d_prefix = sc.alloc<double>((size_t)n_tables * n_cell);
+  int* d_last = sc.alloc<int>((size_t)n_tables);
+  if (!d_pdf || !d_lo || !d_hi || !d_prefix || !d_last) return GWI_ERR_HIP;
+  GWI_SPIN_HIP(hipMemcpyAsync(d_pdf, pdf, sizeof(double) * (size_t)n_tables * (size_t)n_grid, hipMemcpyHostToDevice, sc.stream));
+  GWI_SPIN_HIP(hipMemcpyAsync(d_lo, lo, sizeof(double) * (size_t)n_tables, hipMemcpyHostToDevice, sc.stream));
+  GWI_SPIN_HIP(hipMemcpyAsync(d_hi, hi, sizeof(double) * (size_t)n_tables, hipMemcpyHostToDevice, sc.stream));
+  float ms = 0.f;
+  {
+    P::CdfArgs a{d_pdf, d_lo, d_hi, d_prefix, d_last, n_grid};
+    GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
+    hipLaunchKernelGGL(P::table_cdf_kernel, dim3((unsigned)n_tables), dim3(P::kBlock), 0, sc.stream, a);
+    GWI_SPIN_HIP(hipGetLastError());
+    GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
+    GWI_SPIN_HIP(hipEventSynchronize(sc.e1));
+    GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
+    g_popdraw_times.cdf_ms = ms;
+  }
+  // the draws, cut into launches of at most 2^20 draws per table and 2^26 lanes: a draw depends on (seed, table, first_index + j)
+  // only, so the cut changes nothing
+  const long long dc_max = std::min<long long>(n_draws, kPopdrawDrawsPerLaunch);
+  const long long lanes_per_table = (dc_max + P::kBlock - 1) / P::kBlock * P::kBlock;
+  const long long tc_max = std::max<long long>(1, std::min<long long>(std::min<long long>(n_tables, 65535), kPopdrawThreadsPerLaunch / lanes_per_table));
+  const size_t chunk = (size_t)dc_max * (size_t)tc_max;
+  double* d_lower = lower ? sc.alloc<double>(chunk) : nullptr;
+  double* d_x = sc.alloc<double>(chunk);
+  double* d_mass = mass ? sc.alloc<double>(chunk) : nullptr;
+  unsigned char* d_acc = accept ? sc.alloc<unsigned char>(chunk) : nullptr;
+  if (!d_x || (lower && !d_lower) || (mass && !d_mass) || (accept && !d_acc)) return GWI_ERR_HIP;
+  const size_t lds_bytes = sizeof(double) * (2 * n_cell + 1);
+  const size_t host_pitch = sizeof(double) * (size_t)n_draws, dev_pitch = sizeof(double) * (size_t)dc_max;
+  for (long long t0 = 0; t0 < n_tables; t0 += tc_max) {
+    const long long tc = std::min<long long>(tc_max, n_tables - t0);
+    for (long long j0 = 0; j0 < n_draws; j0 += dc_max) {
+      const long long dc = std::min<long long>(dc_max, n_draws - j0);
+      const size_t host_at = (size_t)t0 * (size_t)n_draws + (size_t)j0;
+      if (lower)
+        GWI_SPIN_HIP(hipMemcpy2DAsync(d_lower, dev_pitch, lower + host_at, host_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyHostToDevice, sc.stream));
+      P::DrawArgs a{d_pdf, d_lo, d_hi, d_prefix, d_last, d_lower, d_x, d_mass, d_acc, (unsigned long long)seed, (unsigned long long)first_index + (unsigned long long)j0,
+                    dc,    dc_max, n_grid, (int)t0};
+      GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
+      hipLaunchKernelGGL(P::table_draw_kernel, dim3((unsigned)((dc + P::kBlock - 1) / P::kBlock), (unsigned)tc), dim3(P::kBlock), lds_bytes, sc.stream, a);
+      GWI_SPIN_HIP(hipGetLastError());
+      GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
+      GWI_SPIN_HIP(hipMemcpy2DAsync(x + host_at, host_pitch, d_x, dev_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
+      if (mass) GWI_SPIN_HIP(hipMemcpy2DAsync(mass + host_at, host_pitch, d_mass, dev_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
+      if (accept) GWI_SPIN_HIP(hipMemcpy2DAsync(accept + host_at, (size_t)n_draws, d_acc, (size_t)dc_max, (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
+      GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));  // the launch's buffers are free again
+      GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
+      g_popdraw_times.draw_ms += ms;
+      ++g_popdraw_times.launches;
+    }
+  }
+  return GWI_OK;
+}
+
+const char* gwi_table_draws_error(void) { return g_popdraw_error.c_str(); }
+
+void gwi_table_draws_times(double* cdf_ms, double* draw_ms, int32_t* launches) {
+  if (cdf_ms) *cdf_ms = g_popdraw_times.cdf_ms;
+  if (draw_ms) *draw_ms = g_popdraw_times.draw_ms;
+  if (launches) *launches = g_popdraw_times.launches;
 }
 
 }  // extern "C"

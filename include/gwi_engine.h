@@ -421,6 +421,38 @@ gwi_status gwi_chi_p_conditional_prior(int64_t n, const double* chi_p, const dou
                                        uint64_t seed, int64_t first_index, double* p, int32_t* accepted, int32_t device);
 void gwi_spin_prior_times(double* total_ms, double* max_launch_ms, int32_t* launches);
 
+/* Population draws (gwinferno_amd/csrc/gwi_popdraw.h; the NumPy statement is gwinferno_amd/population_draws.py): fair draws from
+ * tabulated 1-D densities.  Stand-alone like gwi_effective_spins: no handle, host pointers in and out, its own stream and buffers on
+ * `device` (negative: the calling thread's current device), which is the thread's current device again after the call.
+ *
+ * Table t is the unnormalised density pdf[t][0..n_grid) on the uniform grid lo[t] ... hi[t], read as piecewise linear: cell c has mass
+ * m_c = (p_c + p_{c+1}) dx / 2, dx = (hi - lo) / (n_grid - 1), and C_c is the inclusive prefix of the masses (a block scan of fixed
+ * shape: the same bits on every call).  Draw j of table t takes one Philox4x32-10 block with key = seed (low word, high word) and counter
+ * (index low, index high, t, 0x504F5044), index = first_index + j; u = words 0,1 and v = words 2,3, a uniform being
+ * ((hi >> 5) 2^26 + (lo >> 6)) 2^-53.  Without `lower` the target is u C_last; a binary search finds a cell whose prefix exceeds it and
+ * whose predecessor's does not, a cell without mass is passed over for the next one with mass, a target past the end takes the last
+ * cell with mass, and with r the target's excess over the preceding prefix, s = (p_{c+1} - p_c) / dx:
+ *   x = x_c + 2 r / (p_c + sqrt(p_c^2 + 2 s r)),  clamped into the cell.
+ * With lower[t][j] the draw comes from the density restricted to x >= lower and renormalised: C(lower) = the prefix up to lower's cell
+ * plus that cell's partial trapezoid, the target is C(lower) + u (C_last - C(lower)), mass[t][j] = 1 - C(lower) / C_last is the
+ * probability the restriction keeps and accept[t][j] = (v < mass) as one byte -- thinning the draws of another factor by `accept` samples
+ * a product under the constraint exactly, with no rejection loop.  lower <= lo is no bound (mass 1, accept 1); when no mass lies at or
+ * above lower: x = min(max(lower, lo), hi), mass 0, accept 0; a NaN bound: x = mass = NaN, accept 0.  mass and accept may be NULL, and
+ * are 1 without `lower`.  x, mass, accept and lower are [n_tables][n_draws].  The call is cut into launches of at most 2^20 draws per
+ * table; a draw depends on (tables, seed, t, first_index + j) only, not on the cut or on how a request is split over calls.
+ *
+ * Checked on the host before anything is uploaded, each GWI_ERR_INVALID with a message (gwi_table_draws_error(), of the calling
+ * thread's last call) naming the first offending table: n_grid < 2 (or > 4096: a table is staged in LDS), hi <= lo, a negative or
+ * non-finite density entry, a table whose total mass is 0.  Without a gfx950 device: GWI_ERR_NO_DEVICE -- there is no CPU fallback.
+ *
+ * gwi_table_draws_times(): DIAGNOSTIC ONLY, for tools/population_draws_time.py: device time (HIP events) of the calling thread's last
+ * call -- the prefix kernel, the draw launches together, and their number. */
+gwi_status gwi_table_draws(int32_t device, int32_t n_tables, int32_t n_grid, const double* lo, const double* hi, const double* pdf /* [n_tables][n_grid] */,
+                           int64_t n_draws, uint64_t seed, uint64_t first_index, const double* lower /* [n_tables][n_draws] or NULL */,
+                           double* x /* [n_tables][n_draws] */, double* mass /* or NULL */, unsigned char* accept /* or NULL */);
+const char* gwi_table_draws_error(void);
+void gwi_table_draws_times(double* cdf_ms, double* draw_ms, int32_t* launches);
+
 /* Multi-GPU (one process per GPU): each rank's engine holds a contiguous block of events and a
  * slice of the injections.  gwi_eval_partial() runs the scan and leaves this rank's partial
  * record (gwi_partial_len() doubles) in `record`; the caller exchanges records (RCCL all-gather
