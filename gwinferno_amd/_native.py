@@ -231,6 +231,8 @@ EXPORTED_SYMBOLS = [
     "gwi_log_weights",
     "gwi_set_draw_mask",
     "gwi_draw_indices",
+    "gwi_resample_injections",
+    "gwi_resample_times",
     "gwi_effective_spins",
     "gwi_chi_p_conditional_prior",
     "gwi_spin_prior_times",
@@ -344,6 +346,12 @@ def load_library():
         lib.gwi_set_draw_mask.argtypes = [vp, _U8P, _U8P]
         lib.gwi_draw_indices.restype = C.c_int32
         lib.gwi_draw_indices.argtypes = [vp, _DP, C.c_int32, _DP, C.c_int32, _DP, C.c_int32, _I32P, _I32P]
+    if hasattr(lib, "gwi_resample_injections"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_resample_injections.restype = C.c_int32
+        lib.gwi_resample_injections.argtypes = [vp, _DP, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _DP, _I32P, _DP]
+        lib.gwi_resample_times.restype = None
+        lib.gwi_resample_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

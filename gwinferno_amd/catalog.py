@@ -232,3 +232,64 @@ def effective_spin_catalogs(pedict, injdict, param_names, a_max=1.0, **kw):
     pe = effective_spin_catalog(pedict, param_names, injections=False, a_max=a_max, first_index=first, **kw)
     inj = effective_spin_catalog(injdict, param_names, injections=True, a_max=a_max, first_index=first + int(np.asarray(pedict["mass_ratio"]).size), **kw)
     return pe, inj
+
+
+def resample_injections(seed, engine, theta, injdict, Ndraw, backend="device", inj_mask=None):
+    """preprocess/selection.py:143-156: thin a found-injection set to the set the fiducial population ``theta`` would have produced.
+    With ``w = p(.|theta) / prior`` -- the injection log-weights of ``engine``, which was built from this set -- it draws
+    ``N = floor((sum w)^2 / sum w^2)`` injections with replacement in proportion to ``w``, gathers every key of ``injdict`` at the
+    drawn indices and rewrites ``prior`` as ``p(.|theta) / norm = exp(lw_idx) prior_idx / norm`` (formed in log space),
+    ``norm = sum w / Ndraw``, ``Ndraw`` being the ``total_generated`` of the full set.  Returns ``(injdict_new, N, Neff_new)`` with
+    ``Neff_new = norm^2 / (sum w^2 / Ndraw^2 - norm^2 / Ndraw)``; ``N`` is the ``total_generated`` of the new set, under which every
+    new weight is ``norm`` at ``theta`` and the detection efficiency is that of the full set.
+
+    ``seed`` takes the place of the reference's ``rng_key``: draw ``d`` is draw ``d`` of the seed's Philox stream
+    (:func:`gwinferno_amd.draws.resample_uniforms`).  ``backend="device"`` draws on the GPU (``Engine.resample_injections``: only
+    the indices and the drawn log-weights travel back) under the engine's injection mask (``set_draw_mask``);
+    ``backend="host"`` is the NumPy statement over ``engine.log_weights`` and ``inj_mask`` -- what the kernels are tested against, not a
+    fall-back.  The reference's array form is accepted too: ``injdict = (injdata, param_map)`` with ``injdata (n_param, n_inj)`` and
+    ``param_map`` name -> row gives ``injdata_new (n_param, N)`` back.  ``ValueError`` when no injection carries weight."""
+    from . import draws
+
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    as_array = isinstance(injdict, tuple)
+    if as_array:
+        injdata, param_map = injdict
+        injdata = np.asarray(injdata)
+        columns = {k: injdata[row] for k, row in param_map.items()}
+    else:
+        columns = {k: np.asarray(v) for k, v in injdict.items()}
+    prior = np.asarray(columns["prior"], dtype=np.float64)
+    n_inj = getattr(engine, "n_inj", prior.size)
+    if prior.shape != (n_inj,):
+        raise ValueError(f"prior has shape {prior.shape}; the engine holds {n_inj} injections")
+    if backend == "device":
+        idx, lw_sel, sums = engine.resample_injections(theta, seed)
+        log_sum_w, log_sum_w2, live = sums["log_sum_w"], sums["log_sum_w2"], sums["n_live"] > 0
+        n_new = idx.size
+    else:
+        lw = np.asarray(engine.log_weights(theta)[1], dtype=np.float64).ravel()
+        w = draws.draw_weights(lw, inj_mask)
+        live = bool(np.any(w > 0.0))
+        if live:
+            big = float(np.max(lw[w > 0.0]))
+            c, q = float(np.sum(w)), float(np.sum(w * w))
+            log_sum_w, log_sum_w2 = big + np.log(c), 2.0 * big + np.log(q)
+            n_new = int(c * c // q)
+            idx = draws.resample_indices_reference(lw, inj_mask, seed, 0, n_new)
+            lw_sel = lw[idx]
+    if not live:
+        raise ValueError("resample_injections: no injection carries weight at this theta (under this mask)")
+    log_norm = log_sum_w - np.log(Ndraw)
+    with np.errstate(divide="ignore"):
+        new_prior = np.exp(lw_sel + np.log(prior[idx]) - log_norm)
+    # s2_new / norm^2 = sum w^2 / (sum w)^2 - 1 / Ndraw: the reference's ratio without its overflow
+    neff_new = 1.0 / (np.exp(log_sum_w2 - 2.0 * log_sum_w) - 1.0 / Ndraw)
+    if as_array:
+        new = np.array(injdata[:, idx])
+        new[param_map["prior"]] = new_prior
+        return new, n_new, float(neff_new)
+    new = {k: v[idx] for k, v in columns.items()}
+    new["prior"] = new_prior
+    return new, n_new, float(neff_new)

@@ -7,6 +7,7 @@
 #include "gwi_draw.h"
 #include "gwi_spinprior.h"
 #include "gwi_popdraw.h"
+#include "gwi_resample.h"
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
 
@@ -461,6 +462,11 @@ struct gwi_engine {
   double *d_draw_tiles = nullptr, *d_draw_u = nullptr;
   int* d_draw_idx = nullptr;
   size_t draw_u_cap = 0, draw_idx_cap = 0;
+  // injection resampling (gwi_resample.h): the injection tiles' (max, sum, mass, prefix, sum w^2) + M + the stats record, the tiles'
+  // live counts, the in-tile prefix of every injection, and the indices / log-weights of one select launch (grown on demand, kept)
+  double *d_rs_tiles = nullptr, *d_rs_prefix = nullptr, *d_rs_lw = nullptr;
+  int *d_rs_live = nullptr, *d_rs_idx = nullptr;
+  size_t rs_out_cap = 0;
   // pinned, device-visible host memory
   double *h_record = nullptr, *h_record_dev = nullptr;
   // device-final mode: the final launch's G workgroups publish one partial record each here; the host merges them into h_record
@@ -1583,6 +1589,11 @@ void destroy_impl(gwi_engine* h) {
   (void)hipFree(h->d_draw_tiles);
   (void)hipFree(h->d_draw_u);
   (void)hipFree(h->d_draw_idx);
+  (void)hipFree(h->d_rs_tiles);
+  (void)hipFree(h->d_rs_prefix);
+  (void)hipFree(h->d_rs_lw);
+  (void)hipFree(h->d_rs_live);
+  (void)hipFree(h->d_rs_idx);
   if (h->nccl_comm && g_nccl.CommDestroy) (void)g_nccl.CommDestroy(h->nccl_comm);
   (void)hipFree(h->d_send);
   (void)hipFree(h->d_recv);
@@ -3606,6 +3617,150 @@ gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const
   if (pe_all) GWI_HIP(hipMemcpy(idx_pe, h->d_draw_idx, sizeof(int) * pe_all, hipMemcpyDeviceToHost));
   if (n_draw_inj) GWI_HIP(hipMemcpy(idx_inj, h->d_draw_idx + pe_all, sizeof(int) * (size_t)k * (size_t)n_draw_inj, hipMemcpyDeviceToHost));
   return GWI_OK;
+}
+
+// ---- injection resampling (gwi_resample.h) --------------------------------------------------------------------------------
+struct ResampleTimes {
+  double logw_ms = 0.0, prefix_ms = 0.0, select_ms = 0.0;
+  int launches = 0;
+};
+static thread_local ResampleTimes g_resample_times;
+
+// two events that go away with the scope
+struct ResampleEvents {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~ResampleEvents() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+constexpr long long kResampleDrawsPerLaunch = 1ll << 20;
+constexpr long long kResampleBlocksPerLaunch = 2048;  // the rest of a launch's draws by grid stride
+
+gwi_status gwi_resample_injections(gwi_handle h, const double* theta, uint64_t seed, int64_t first_index, int64_t n_request, int64_t* n_draws, double* sums, int32_t* idx,
+                                   double* logw_sel) {
+  if (!h) return GWI_ERR_INVALID;
+  g_resample_times = ResampleTimes();
+  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: host-only handle: no device to draw on");
+  if (!h->variant) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: the engine has no scan kernel");
+  if (!theta || !n_draws || !sums) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: theta, n_draws or sums is null");
+  if (n_request != 0 && (!idx || !logw_sel)) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: draws are asked for: idx and logw_sel are needed");
+  if (first_index < 0) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: first_index < 0");
+  if (h->comm_world > 1 || h->shm_world > 1)
+    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_resample_injections: this handle holds one shard of the catalog; injection draws need the global set");
+  gwi_status st = busy_guard(h, "gwi_resample_injections");
+  if (st != GWI_OK) return st;
+  namespace D = gwi::draw;
+  namespace R = gwi::resample;
+  const long long n_inj = h->n_inj, n_tiles = D::tiles_of(n_inj);
+  if (n_inj > 0x7fffffffLL) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: more injections than an int32 index can address");
+  *n_draws = 0;
+  sums[0] = sums[1] = -__builtin_inf();
+  sums[2] = sums[3] = 0.0;
+  if (n_inj == 0) return GWI_OK;
+  GWI_HIP(hipSetDevice(h->device));
+  // [max | sum | mass | prefix | sum w^2][n_tiles], M, the stats record
+  if (!h->d_rs_tiles) GWI_HIP(hipMalloc(&h->d_rs_tiles, sizeof(double) * (size_t)(5 * n_tiles + 1 + R::kStats)));
+  if (!h->d_rs_live) GWI_HIP(hipMalloc(&h->d_rs_live, sizeof(int) * (size_t)n_tiles));
+  if (!h->d_rs_prefix) GWI_HIP(hipMalloc(&h->d_rs_prefix, sizeof(double) * (size_t)n_inj));
+  ResampleEvents ev;
+  GWI_HIP(hipEventCreate(&ev.e0));
+  GWI_HIP(hipEventCreate(&ev.e1));
+  double log_const = 0.0;
+  const auto t0 = std::chrono::steady_clock::now();
+  st = fill_log_weights(h, theta, &log_const);  // (blocking)
+  if (st != GWI_OK) return st;
+  g_resample_times.logw_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  // the injection set as the only segment of gwi_draw.h's first two kernels: no events, its tiles from 0
+  D::DrawArgs da;
+  std::memset(&da, 0, sizeof(da));
+  da.logw_inj = h->d_logw_inj;
+  da.mask_inj = h->d_draw_mask_inj;
+  da.tile_max = h->d_rs_tiles;
+  da.tile_sum = da.tile_max + n_tiles;
+  da.tile_mass = da.tile_sum + n_tiles;
+  da.tile_prefix = da.tile_mass + n_tiles;
+  da.seg_max = da.tile_prefix + 2 * n_tiles;
+  da.log_const = log_const;
+  da.n_inj = n_inj;
+  da.n_inj_tiles = (int)n_tiles;
+  da.tiles_per_event = 1;  // (no event has a tile: a divisor only)
+  R::Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.lw = h->d_logw_inj;
+  a.mask = h->d_draw_mask_inj;
+  a.seg_max = da.seg_max;
+  a.tile_mass = da.tile_mass;
+  a.tile_prefix = da.tile_prefix;
+  a.sample_prefix = h->d_rs_prefix;
+  a.tile_sq = da.tile_prefix + n_tiles;
+  a.tile_live = h->d_rs_live;
+  a.stats = da.seg_max + 1;
+  a.log_const = log_const;
+  a.seed = (unsigned long long)seed;
+  a.n = n_inj;
+  a.n_tiles = (int)n_tiles;
+  float ms = 0.f;
+  GWI_HIP(hipEventRecord(ev.e0, h->stream));
+  hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, da);
+  hipLaunchKernelGGL(D::draw_merge_kernel, dim3(1), dim3(D::kDrawBlock), 0, h->stream, da);
+  hipLaunchKernelGGL(R::resample_prefix_kernel, dim3((unsigned)n_tiles), dim3(R::kBlock), 0, h->stream, a);
+  hipLaunchKernelGGL(R::resample_stats_kernel, dim3(1), dim3(R::kBlock), 0, h->stream, a);
+  GWI_HIP(hipGetLastError());
+  GWI_HIP(hipEventRecord(ev.e1, h->stream));
+  double stats[R::kStats];
+  GWI_HIP(hipMemcpyAsync(stats, a.stats, sizeof(stats), hipMemcpyDeviceToHost, h->stream));
+  GWI_HIP(hipStreamSynchronize(h->stream));
+  GWI_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  g_resample_times.prefix_ms = ms;
+  const double q = stats[R::kStatQ], c_last = stats[R::kStatCLast], big = stats[R::kStatMax];
+  if (!(c_last > 0.0) || !(q > 0.0) || stats[R::kStatLastTile] < 0.0) return GWI_OK;  // no live sample: nothing to draw
+  sums[0] = big + std::log(c_last);
+  sums[1] = 2.0 * big + std::log(q);
+  sums[2] = c_last * c_last / q;
+  sums[3] = stats[R::kStatLive];
+  const long long n = n_request < 0 ? std::min<long long>((long long)std::floor(sums[2]), n_inj) : (long long)n_request;  // (n_eff <= the live samples <= n_inj)
+  const size_t chunk = (size_t)std::min<long long>(n, kResampleDrawsPerLaunch);
+  if (h->rs_out_cap < chunk) {
+    (void)hipFree(h->d_rs_idx);
+    (void)hipFree(h->d_rs_lw);
+    h->d_rs_idx = nullptr;
+    h->d_rs_lw = nullptr;
+    h->rs_out_cap = 0;
+    GWI_HIP(hipMalloc(&h->d_rs_idx, sizeof(int) * chunk));
+    GWI_HIP(hipMalloc(&h->d_rs_lw, sizeof(double) * chunk));
+    h->rs_out_cap = chunk;
+  }
+  a.idx = h->d_rs_idx;
+  a.lw_sel = h->d_rs_lw;
+  // launches of at most 2^20 draws: a draw depends on (seed, first_index + d) only, so the cut changes nothing
+  for (long long d0 = 0; d0 < n; d0 += kResampleDrawsPerLaunch) {
+    const long long dc = std::min<long long>(kResampleDrawsPerLaunch, n - d0);
+    const long long blocks = std::min<long long>((dc + R::kBlock - 1) / R::kBlock, kResampleBlocksPerLaunch);
+    a.first_index = (unsigned long long)first_index + (unsigned long long)d0;
+    a.n_draws = dc;
+    a.n_lanes = (int)(blocks * R::kBlock);
+    GWI_HIP(hipEventRecord(ev.e0, h->stream));
+    hipLaunchKernelGGL(R::resample_select_kernel, dim3((unsigned)blocks), dim3(R::kBlock), 0, h->stream, a);
+    GWI_HIP(hipGetLastError());
+    GWI_HIP(hipEventRecord(ev.e1, h->stream));
+    GWI_HIP(hipMemcpyAsync(idx + d0, h->d_rs_idx, sizeof(int) * (size_t)dc, hipMemcpyDeviceToHost, h->stream));
+    GWI_HIP(hipMemcpyAsync(logw_sel + d0, h->d_rs_lw, sizeof(double) * (size_t)dc, hipMemcpyDeviceToHost, h->stream));
+    GWI_HIP(hipStreamSynchronize(h->stream));  // the launch's buffers are free again
+    GWI_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    g_resample_times.select_ms += ms;
+    ++g_resample_times.launches;
+  }
+  *n_draws = n;
+  return GWI_OK;
+}
+
+void gwi_resample_times(double* logw_ms, double* prefix_ms, double* select_ms, int32_t* launches) {
+  if (logw_ms) *logw_ms = g_resample_times.logw_ms;
+  if (prefix_ms) *prefix_ms = g_resample_times.prefix_ms;
+  if (select_ms) *select_ms = g_resample_times.select_ms;
+  if (launches) *launches = g_resample_times.launches;
 }
 
 }  // extern "C"

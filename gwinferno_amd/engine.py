@@ -1042,6 +1042,31 @@ class NativePopulationLikelihood:
             idx_pe, idx_inj = (None if idx_pe is None else idx_pe[0]), (None if idx_inj is None else idx_inj[0])
         return idx_pe, idx_inj
 
+    def resample_injections(self, theta, seed, n_request=None, first_index=0):
+        """Seeded draws from the injection set in proportion to ``w = p(.|theta) / prior`` on the device
+        (``gwi_resample_injections``; preprocess/selection.py:143-156; semantics:
+        :func:`gwinferno_amd.draws.resample_indices_reference`).  ``n_request=None`` makes the reference's
+        ``N = floor((sum w)^2 / sum w^2)`` draws, a number exactly that many; draw ``d`` is draw ``first_index + d`` of the seed's
+        stream, so a request may be split over calls.  The injection mask of :meth:`set_draw_mask` applies.  Returns
+        ``(idx, logw_sel, sums)``: int32 indices, the drawn samples' log-weights (``log_weights(theta)[1][idx]``) and
+        ``{"log_sum_w", "log_sum_w2", "n_eff", "n_live"}``; empty arrays when no injection has weight.  Not available on an
+        engine that holds a shard (``world > 1``)."""
+        if self.world > 1:
+            raise N.NativeEngineError("GWI_ERR_UNSUPPORTED: resample_injections: this engine holds one shard of the catalog; injection draws need the global set")
+        theta = N.f64(theta)
+        if theta.shape != (self.n_theta,):
+            raise ValueError(f"theta has shape {theta.shape}; expected ({self.n_theta},)")
+        n_request = -1 if n_request is None else int(n_request)
+        if n_request < -1:
+            raise ValueError("n_request must be None or >= 0")
+        room = self.n_inj if n_request < 0 else n_request
+        idx, lw = np.full(max(room, 1), -1, dtype=np.int32), np.full(max(room, 1), np.nan)
+        sums, made = np.zeros(4), C.c_int64(0)
+        self._check(self.lib.gwi_resample_injections(self.handle, N.as_dp(theta), int(seed) & (2**64 - 1), int(first_index), n_request, C.byref(made), N.as_dp(sums),
+                                                     idx.ctypes.data_as(C.POINTER(C.c_int32)), N.as_dp(lw)))
+        n = int(made.value)
+        return idx[:n].copy(), lw[:n].copy(), {"log_sum_w": float(sums[0]), "log_sum_w2": float(sums[1]), "n_eff": float(sums[2]), "n_live": int(sums[3])}
+
     def selftime(self, theta, total_inj, n_iter=1000, min_neff_cut=True):
         """Mean seconds per evaluation of a C-side loop of sequential gwi_eval calls (diagnostic)."""
         opt = self._options(total_inj, None, False, min_neff_cut, False)

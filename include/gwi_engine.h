@@ -385,6 +385,37 @@ gwi_status gwi_set_draw_mask(gwi_handle h, const unsigned char* pe_mask, const u
 gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const double* u_pe, int32_t n_draw_pe, const double* u_inj, int32_t n_draw_inj,
                             int32_t* idx_pe, int32_t* idx_inj);
 
+/* Resampled injection sets on the device: the reference's resample_injections (preprocess/selection.py:143-156), which thins a
+ * found-injection set to the set a fiducial population theta would have produced -- N = floor((sum w)^2 / sum w^2) injections drawn
+ * with replacement in proportion to w = p(.|theta) / prior -- for many draws from one segment, with the generator on the device
+ * (gwinferno_amd/csrc/gwi_resample.h; the NumPy statement is gwinferno_amd/draws.py: resample_indices_reference).
+ *
+ * The injection set is one segment of gwi_draw_indices: the same lw_j, the same mask (the injection mask of gwi_set_draw_mask
+ * applies), M, w_j = exp(lw_j - M) and the same tile masses and tile prefix; C_j is the inclusive prefix inside a tile of 1 024 samples
+ * on top of the preceding tile's prefix, every sum of a fixed shape (the same bits on every call and on every handle of one model).
+ * Draw d has stream index first_index + d and takes one Philox4x32-10 block with key = seed (low word, high word) and counter
+ * (index low, index high, 0, 0x52534D50); u = words 0,1, a uniform being ((hi >> 5) 2^26 + (lo >> 6)) 2^-53.  The target is u C_last;
+ * a binary search finds a tile whose prefix exceeds it and whose predecessor's does not, a tile without mass is passed over for the
+ * next one with mass, a target past the end takes the last tile with mass; inside the tile the same search runs on the in-tile prefix
+ * against the rest of the target and yields the first sample with w_j > 0 from there on, else the tile's last sample with weight.
+ * idx[d] is that sample and logw_sel[d] = lw_idx (gwi_log_weights' value, sample-independent constant included: bit for bit).
+ *
+ * n_request < 0 makes the reference's N draws, N = floor(n_eff); otherwise exactly n_request draws are made.  *n_draws is the number
+ * made.  idx and logw_sel hold n_request entries, or n_inj when n_request < 0 (N <= n_inj always); they may be NULL for n_request = 0.
+ * sums[4] = { log sum w, log sum w^2, n_eff = (sum w)^2 / sum w^2, the number of injections with w_j > 0 }, the logarithms absolute
+ * (M and the sample-independent constant included), whatever n_request.  A draw depends on (catalog, mask, theta, seed,
+ * first_index + d) only -- not on the cut into launches of 2^20 draws, nor on how a request is split over calls.  Without any live
+ * sample: GWI_OK, *n_draws = 0, sums = { -inf, -inf, 0, 0 }, nothing written to idx / logw_sel.
+ * GWI_ERR_INVALID for null pointers, a host-only handle or first_index < 0; GWI_ERR_UNSUPPORTED on a handle that holds a shard, as
+ * gwi_draw_indices.
+ *
+ * gwi_resample_times(): DIAGNOSTIC ONLY, for tools/resample_injections_time.py: of the calling thread's last call, the wall time of
+ * the (blocking) log-weight pass and the device times (HIP events) of the tile / merge / prefix / stats launches together and of the
+ * select launches together, and the number of select launches. */
+gwi_status gwi_resample_injections(gwi_handle h, const double* theta, uint64_t seed, int64_t first_index, int64_t n_request, int64_t* n_draws, double* sums /* [4] */,
+                                   int32_t* idx, double* logw_sel);
+void gwi_resample_times(double* logw_ms, double* prefix_ms, double* select_ms, int32_t* launches);
+
 /* Effective-spin catalogs (gwinferno_amd/csrc/gwi_spinprior.h; the NumPy statement is gwinferno_amd/spin_priors.py).  Stand-alone
  * entries like gwi_ingest_columns: no handle, host pointers in and out, their own stream and buffers on `device` (negative: the
  * calling thread's current device).  The calling thread's current device is the same after the call as before it.
