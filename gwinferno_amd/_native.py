@@ -239,6 +239,10 @@ EXPORTED_SYMBOLS = [
     "gwi_table_draws",
     "gwi_table_draws_error",
     "gwi_table_draws_times",
+    "gwi_mock_observe",
+    "gwi_mock_posteriors",
+    "gwi_mock_error",
+    "gwi_mock_times",
     "gwi_partial_len",
     "gwi_eval_partial",
     "gwi_prepare_combine",
@@ -367,6 +371,17 @@ def load_library():
         lib.gwi_table_draws_error.argtypes = []
         lib.gwi_table_draws_times.restype = None
         lib.gwi_table_draws_times.argtypes = [_DP, _DP, C.POINTER(C.c_int32)]
+    if hasattr(lib, "gwi_mock_observe"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _IP = C.POINTER(C.c_int32)
+        lib.gwi_mock_observe.restype = C.c_int32
+        lib.gwi_mock_observe.argtypes = [C.c_int32, C.c_int32, _IP, _DP, _DP, _DP, C.c_int32, C.c_int32, C.c_int32, _DP, C.c_int32, _DP, _DP, C.c_int64, _DP, C.c_uint64,
+                                         C.c_uint64, _DP, _DP, C.POINTER(C.c_uint8)]
+        lib.gwi_mock_posteriors.restype = C.c_int32
+        lib.gwi_mock_posteriors.argtypes = [C.c_int32, C.c_int32, _IP, _DP, _DP, _DP, C.c_int64, C.c_int64, _DP, C.c_uint64, C.c_uint64, _DP, _DP]
+        lib.gwi_mock_error.restype = C.c_char_p
+        lib.gwi_mock_error.argtypes = []
+        lib.gwi_mock_times.restype = None
+        lib.gwi_mock_times.argtypes = [_DP, _DP, C.POINTER(C.c_int32)]
     lib.gwi_partial_len.restype = C.c_int64
     lib.gwi_partial_len.argtypes = [vp]
     lib.gwi_eval_partial.restype = C.c_int32

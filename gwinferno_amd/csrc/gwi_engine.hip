@@ -6,6 +6,7 @@
 #include "gwi_ingest.h"
 #include "gwi_draw.h"
 #include "gwi_spinprior.h"
+#include "gwi_mock.h"
 #include "gwi_popdraw.h"
 #include "gwi_resample.h"
 #include "gwi_jit.h"
@@ -4042,6 +4043,205 @@ void gwi_table_draws_times(double* cdf_ms, double* draw_ms, int32_t* launches) {
   if (cdf_ms) *cdf_ms = g_popdraw_times.cdf_ms;
   if (draw_ms) *draw_ms = g_popdraw_times.draw_ms;
   if (launches) *launches = g_popdraw_times.launches;
+}
+
+}  // extern "C"
+
+// ---- mock catalogs (gwi_mock.h): stand-alone entries, no handle, like gwi_table_draws ------------------------------------
+namespace {
+
+struct MockTimes {
+  double observe_ms = 0.0, posterior_ms = 0.0;
+  int launches = 0;
+};
+thread_local MockTimes g_mock_times;
+thread_local std::string g_mock_error;
+
+gwi_status mock_refuse(const std::string& why) {
+  g_mock_error = why;
+  return GWI_ERR_INVALID;
+}
+
+constexpr long long kMockLanesPerLaunch = 1ll << 20;
+
+// the observation model, checked and put into the kernels' form; *why is set when it is refused
+bool mock_model(int32_t n_coords, const int32_t* is_log, const double* sigma, const double* lo, const double* hi, gwi::mock::Model* m, std::string* why) {
+  if (n_coords < 1 || n_coords > gwi::mock::kMaxCoords) {
+    *why = "n_coords = " + std::to_string(n_coords) + " outside 1 ... " + std::to_string(gwi::mock::kMaxCoords);
+    return false;
+  }
+  if (!is_log || !sigma || !lo || !hi) {
+    *why = "null is_log, sigma, lo or hi";
+    return false;
+  }
+  *m = gwi::mock::Model();
+  m->n_coords = n_coords;
+  m->i_m1 = m->i_q = m->i_z = -1;
+  for (int32_t c = 0; c < n_coords; ++c) {
+    const std::string who = "coordinate " + std::to_string(c) + ": ";
+    if (!(sigma[c] > 0.0) || !(sigma[c] < __builtin_inf())) {
+      *why = who + "sigma <= 0 or not finite";
+      return false;
+    }
+    if (!(hi[c] > lo[c]) || !(hi[c] - lo[c] < __builtin_inf())) {
+      *why = who + "hi <= lo (or a bound that is not finite)";
+      return false;
+    }
+    if (is_log[c] && !(lo[c] > 0.0)) {
+      *why = who + "a log coordinate needs lo > 0";
+      return false;
+    }
+    m->is_log[c] = is_log[c] ? 1 : 0;
+    m->sigma[c] = sigma[c];
+    m->lo[c] = lo[c];
+    m->hi[c] = hi[c];
+    m->t_lo[c] = is_log[c] ? std::log(lo[c]) : lo[c];
+    m->t_hi[c] = is_log[c] ? std::log(hi[c]) : hi[c];
+    m->width[c] = is_log[c] ? std::log(hi[c] / lo[c]) : hi[c] - lo[c];
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+gwi_status gwi_mock_observe(int32_t device, int32_t n_coords, const int32_t* is_log, const double* sigma, const double* lo, const double* hi, int32_t i_m1, int32_t i_q,
+                            int32_t i_z, const double* detection, int32_t n_table, const double* table_z, const double* table_dl, int64_t n, const double* x_true,
+                            uint64_t seed, uint64_t first_index, double* data, double* snr, unsigned char* found) {
+  static const char* kWhere = "gwi_mock_observe";
+  namespace K = gwi::mock;
+  g_mock_error.clear();
+  g_mock_times = MockTimes();
+  // ---- the argument checks: on the host, before anything is uploaded
+  K::Model m;
+  std::string why;
+  if (!mock_model(n_coords, is_log, sigma, lo, hi, &m, &why)) return mock_refuse(why);
+  if (n < 0) return mock_refuse("negative n");
+  const int32_t roles[3] = {i_m1, i_q, i_z};
+  for (int r = 0; r < 3; ++r)
+    if (roles[r] < 0 || roles[r] >= n_coords) return mock_refuse(std::string("role index ") + (r == 0 ? "m1" : r == 1 ? "q" : "z") + " = " + std::to_string(roles[r]) + " out of range");
+  if (i_m1 == i_q || i_m1 == i_z || i_q == i_z) return mock_refuse("the role indices m1, q, z must differ");
+  if (!detection) return mock_refuse("null detection parameters");
+  for (int k = 0; k < 4; ++k)
+    if (!(detection[k] > 0.0) || !(detection[k] < __builtin_inf())) return mock_refuse("detection parameter " + std::to_string(k) + " (rho_ref, mc_ref, dl_ref, rho_th) is not positive and finite");
+  if (!table_z || !table_dl) return mock_refuse("null DL table");
+  if (n_table < 2) return mock_refuse("the DL table has fewer than two points");
+  for (int32_t i = 0; i < n_table; ++i) {
+    if (i > 0 && !(table_z[i] > table_z[i - 1])) return mock_refuse("the DL table's redshifts are not ascending at entry " + std::to_string(i));
+    if (!(table_dl[i] >= 0.0) || !(table_dl[i] < __builtin_inf()) || (i > 0 && !(table_dl[i] > 0.0)))
+      return mock_refuse("DL table entry " + std::to_string(i) + " is not positive and finite");
+  }
+  {
+    // the largest redshift the data can show: 9 sigma above the support's end (a 53-bit uniform gives |n| < 8.3)
+    const double t_top = m.t_hi[i_z] + 9.0 * m.sigma[i_z];
+    const double z_top = m.is_log[i_z] ? std::exp(t_top) : t_top;
+    if (!(table_z[0] <= 0.0) || !(table_z[n_table - 1] >= z_top))
+      return mock_refuse("the DL table covers [" + std::to_string(table_z[0]) + ", " + std::to_string(table_z[n_table - 1]) + "], not [0, hi_z + 9 sigma_z = " + std::to_string(z_top) + "]");
+  }
+  if (n > 0 && (!x_true || !data || !snr || !found)) return mock_refuse("null x_true, data, snr or found");
+  m.i_m1 = i_m1;
+  m.i_q = i_q;
+  m.i_z = i_z;
+  m.rho_ref = detection[0];
+  m.mc_ref = detection[1];
+  m.dl_ref = detection[2];
+  m.rho_th = detection[3];
+  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
+  gwi_status st = spin_device(device, &guard);
+  if (st != GWI_OK) return st;
+  if (n == 0) return GWI_OK;
+  SpinScratch sc;
+  if (!sc.open()) return GWI_ERR_HIP;
+  const size_t cn = (size_t)n_coords * (size_t)n;
+  double* d_x = sc.alloc<double>(cn);
+  double* d_d = sc.alloc<double>(cn);
+  double* d_snr = sc.alloc<double>((size_t)n);
+  unsigned char* d_found = sc.alloc<unsigned char>((size_t)n);
+  double* d_tz = sc.alloc<double>((size_t)n_table);
+  double* d_tv = sc.alloc<double>((size_t)n_table);
+  if (!d_x || !d_d || !d_snr || !d_found || !d_tz || !d_tv) return GWI_ERR_HIP;
+  GWI_SPIN_HIP(hipMemcpyAsync(d_x, x_true, sizeof(double) * cn, hipMemcpyHostToDevice, sc.stream));
+  GWI_SPIN_HIP(hipMemcpyAsync(d_tz, table_z, sizeof(double) * (size_t)n_table, hipMemcpyHostToDevice, sc.stream));
+  GWI_SPIN_HIP(hipMemcpyAsync(d_tv, table_dl, sizeof(double) * (size_t)n_table, hipMemcpyHostToDevice, sc.stream));
+  // launches of at most 2^20 lanes: a value depends on (inputs, seed, first_index + j, coordinate) only, so the cut changes nothing
+  for (long long j0 = 0; j0 < n; j0 += kMockLanesPerLaunch) {
+    const long long nj = std::min<long long>(kMockLanesPerLaunch, n - j0);
+    K::ObserveArgs a{m, d_x, d_tz, d_tv, d_d, d_snr, d_found, (unsigned long long)seed, (unsigned long long)first_index + (unsigned long long)j0, nj, (long long)n, j0, n_table};
+    GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
+    hipLaunchKernelGGL(K::mock_observe_kernel, dim3((unsigned)((nj + K::kBlock - 1) / K::kBlock)), dim3(K::kBlock), 0, sc.stream, a);
+    GWI_SPIN_HIP(hipGetLastError());
+    GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
+    GWI_SPIN_HIP(hipEventSynchronize(sc.e1));
+    float ms = 0.f;
+    GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
+    g_mock_times.observe_ms += ms;
+    ++g_mock_times.launches;
+  }
+  GWI_SPIN_HIP(hipMemcpyAsync(data, d_d, sizeof(double) * cn, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SPIN_HIP(hipMemcpyAsync(snr, d_snr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SPIN_HIP(hipMemcpyAsync(found, d_found, (size_t)n, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));
+  return GWI_OK;
+}
+
+gwi_status gwi_mock_posteriors(int32_t device, int32_t n_coords, const int32_t* is_log, const double* sigma, const double* lo, const double* hi, int64_t n_ev, int64_t n_pe,
+                               const double* data, uint64_t seed, uint64_t first_event, double* x, double* prior) {
+  static const char* kWhere = "gwi_mock_posteriors";
+  namespace K = gwi::mock;
+  g_mock_error.clear();
+  g_mock_times = MockTimes();
+  K::Model m;
+  std::string why;
+  if (!mock_model(n_coords, is_log, sigma, lo, hi, &m, &why)) return mock_refuse(why);
+  if (n_ev < 0 || n_pe < 0) return mock_refuse("negative n_ev or n_pe");
+  if (n_pe > 0xffffffffLL) return mock_refuse("n_pe does not fit the 32-bit sample word of the counter");
+  if (n_ev > 0 && !data) return mock_refuse("null data");
+  if (n_ev > 0 && n_pe > 0 && (!x || !prior)) return mock_refuse("null x or prior");
+  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
+  gwi_status st = spin_device(device, &guard);
+  if (st != GWI_OK) return st;
+  if (n_ev == 0 || n_pe == 0) return GWI_OK;
+  SpinScratch sc;
+  if (!sc.open()) return GWI_ERR_HIP;
+  const size_t plane = (size_t)n_ev * (size_t)n_pe;
+  double* d_d = sc.alloc<double>((size_t)n_coords * (size_t)n_ev);
+  double* d_x = sc.alloc<double>((size_t)n_coords * plane);
+  double* d_prior = sc.alloc<double>(plane);
+  if (!d_d || !d_x || !d_prior) return GWI_ERR_HIP;
+  GWI_SPIN_HIP(hipMemcpyAsync(d_d, data, sizeof(double) * (size_t)n_coords * (size_t)n_ev, hipMemcpyHostToDevice, sc.stream));
+  // launches of at most 2^20 lanes (and 65535 events): a sample depends on (data, seed, first_event + e, s, coordinate) only
+  const long long sc_max = std::min<long long>(n_pe, kMockLanesPerLaunch);
+  const long long lanes_per_event = (sc_max + K::kBlock - 1) / K::kBlock * K::kBlock;
+  const long long ec_max = std::max<long long>(1, std::min<long long>(std::min<long long>(n_ev, 65535), kMockLanesPerLaunch / lanes_per_event));
+  for (long long e0 = 0; e0 < n_ev; e0 += ec_max) {
+    const long long ec = std::min<long long>(ec_max, n_ev - e0);
+    for (long long s0 = 0; s0 < n_pe; s0 += sc_max) {
+      const long long ns = std::min<long long>(sc_max, n_pe - s0);
+      K::PosteriorArgs a{m, d_d, d_x, d_prior, (unsigned long long)seed, (unsigned long long)first_event, (long long)n_ev, (long long)n_pe, e0, s0, ns};
+      GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
+      hipLaunchKernelGGL(K::mock_posterior_kernel, dim3((unsigned)((ns + K::kBlock - 1) / K::kBlock), (unsigned)ec), dim3(K::kBlock), 0, sc.stream, a);
+      GWI_SPIN_HIP(hipGetLastError());
+      GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
+      GWI_SPIN_HIP(hipEventSynchronize(sc.e1));
+      float ms = 0.f;
+      GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
+      g_mock_times.posterior_ms += ms;
+      ++g_mock_times.launches;
+    }
+  }
+  GWI_SPIN_HIP(hipMemcpyAsync(x, d_x, sizeof(double) * (size_t)n_coords * plane, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SPIN_HIP(hipMemcpyAsync(prior, d_prior, sizeof(double) * plane, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));
+  return GWI_OK;
+}
+
+const char* gwi_mock_error(void) { return g_mock_error.c_str(); }
+
+void gwi_mock_times(double* observe_ms, double* posterior_ms, int32_t* launches) {
+  if (observe_ms) *observe_ms = g_mock_times.observe_ms;
+  if (posterior_ms) *posterior_ms = g_mock_times.posterior_ms;
+  if (launches) *launches = g_mock_times.launches;
 }
 
 }  // extern "C"

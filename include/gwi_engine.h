@@ -484,6 +484,53 @@ gwi_status gwi_table_draws(int32_t device, int32_t n_tables, int32_t n_grid, con
 const char* gwi_table_draws_error(void);
 void gwi_table_draws_times(double* cdf_ms, double* draw_ms, int32_t* launches);
 
+/* Mock catalogs (gwinferno_amd/csrc/gwi_mock.h; the NumPy statement is gwinferno_amd/mock_catalog.py; the model is DESIGN.md's section
+ * "Mock catalogs"): noisy data and detection of true sources, and the posterior samples of detected events.  Stand-alone like
+ * gwi_table_draws: no handle, host pointers in and out, own stream and buffers on `device` (negative: the calling thread's current
+ * device), which is the thread's current device again after the call.
+ *
+ * A source has n_coords <= 8 coordinates; coordinate c has a transform T_c (is_log[c] != 0: log, else identity), a noise scale sigma[c]
+ * in T-space and a support [lo[c], hi[c]] in natural units.
+ *
+ * gwi_mock_observe: data[c][j] = T_c(x_true[c][j]) + sigma[c] n with n standard normal.  From the data, m1_d, q_d, z_d = T^-1 of the
+ * coordinates i_m1, i_q, i_z; Mc = m1_d (1 + z_d) q_d^(3/5) / (1 + q_d)^(1/5); snr = rho_ref (Mc / mc_ref)^(5/6) dl_ref / DL(z_d) with
+ * detection = {rho_ref, mc_ref, dl_ref, rho_th} and DL by linear interpolation (numpy.interp's form) in (table_z, table_dl);
+ * found[j] = (m1_d > 0 and q_d > 0 and z_d > 0 and snr >= rho_th) as one byte.  snr = 0 where a detector-frame quantity is not positive
+ * or z_d lies past the table's end; NaN true parameters give NaN data, NaN snr and found = 0.
+ *
+ * gwi_mock_posteriors: x[c][e][s], sample s of event e, from the normal centred on data[c][e] with scale sigma[c] truncated to
+ * [T_c(lo), T_c(hi)] -- the posterior under a prior flat in T_c(x) -- by inverse CDF from one uniform, mapped back with T^-1 and clamped
+ * into [lo, hi]; prior[e][s] = prod_c |T_c'(x_c)| / (T_c(hi_c) - T_c(lo_c)), i.e. 1 / (x ln(hi / lo)) per log coordinate.  Data that
+ * are not finite give NaN samples and a NaN prior.
+ *
+ * Generator: Philox4x32-10 with key = seed (low word, high word); a coordinate takes one uniform ((hi >> 5) 2^26 + (lo >> 6)) 2^-53, so
+ * block b serves coordinates 2 b (words 0, 1) and 2 b + 1 (words 2, 3).  Counter (index low, index high, 0, 0x4D4F4B00 + b) with
+ * index = first_index + j for the data; (index low, index high, s, 0x4D4F4B10 + b) with index = first_event + e for the samples.  Word 3
+ * is disjoint from the other entries' (0x504F5044, 0x52534D50, 2 * attempt (+ 1) < 2^17).  The normal is -sqrt2 erfcinv(2 u) for
+ * u <= 1/2 (u = 0 read as 2^-54), else +sqrt2 erfcinv(2 (1 - u)).  The truncated normal with standardised bounds a, b: a > 0 is mirrored
+ * (a, b, u) -> (-b, -a, 1 - u); b <= 0: y = -sqrt2 erfcinv(2 (Phi(a) + u (Phi(b) - Phi(a)))); else Z = 1 - Phi(a) - Q(b) and
+ * y = -sqrt2 erfcinv(2 (Phi(a) + u Z)) while that argument is <= 1, else y = +sqrt2 erfcinv(2 (Q(b) + (1 - u) Z)); Phi and Q come from
+ * erfc of a non-negative argument and erfcinv never sees an argument above 1.  A value is a pure function of (inputs, seed, stream
+ * index, sample index, coordinate): requests are cut into launches of at most 2^20 lanes, and neither the cut nor a split of a request
+ * over calls (first_index / first_event) changes a value.
+ *
+ * Checked on the host before anything is uploaded, each GWI_ERR_INVALID with a message (gwi_mock_error(), of the calling thread's last
+ * call): n_coords outside 1 ... 8, sigma <= 0 or not finite, hi <= lo, a log coordinate with lo <= 0, a role index out of range (or two
+ * equal), detection parameters that are not positive and finite, a DL table that is not ascending or does not cover
+ * [0, T^-1(T(hi_z) + 9 sigma_z)], null pointers.  Without a gfx950 device: GWI_ERR_NO_DEVICE -- there is no CPU fallback.
+ *
+ * gwi_mock_times(): DIAGNOSTIC ONLY, for tools/mock_catalog_time.py: device time (HIP events) of the calling thread's last call -- the
+ * observe launches, the posterior launches, and their number. */
+gwi_status gwi_mock_observe(int32_t device, int32_t n_coords, const int32_t* is_log, const double* sigma, const double* lo, const double* hi, int32_t i_m1, int32_t i_q,
+                            int32_t i_z, const double* detection /* [4] */, int32_t n_table, const double* table_z, const double* table_dl, int64_t n,
+                            const double* x_true /* [n_coords][n] */, uint64_t seed, uint64_t first_index, double* data /* [n_coords][n] */, double* snr /* [n] */,
+                            unsigned char* found /* [n] */);
+gwi_status gwi_mock_posteriors(int32_t device, int32_t n_coords, const int32_t* is_log, const double* sigma, const double* lo, const double* hi, int64_t n_ev, int64_t n_pe,
+                               const double* data /* [n_coords][n_ev] */, uint64_t seed, uint64_t first_event, double* x /* [n_coords][n_ev][n_pe] */,
+                               double* prior /* [n_ev][n_pe] */);
+const char* gwi_mock_error(void);
+void gwi_mock_times(double* observe_ms, double* posterior_ms, int32_t* launches);
+
 /* Multi-GPU (one process per GPU): each rank's engine holds a contiguous block of events and a
  * slice of the injections.  gwi_eval_partial() runs the scan and leaves this rank's partial
  * record (gwi_partial_len() doubles) in `record`; the caller exchanges records (RCCL all-gather
