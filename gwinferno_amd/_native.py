@@ -233,6 +233,9 @@ EXPORTED_SYMBOLS = [
     "gwi_draw_indices",
     "gwi_resample_injections",
     "gwi_resample_times",
+    "gwi_set_histogram_bins",
+    "gwi_weighted_histograms",
+    "gwi_histogram_times",
     "gwi_effective_spins",
     "gwi_chi_p_conditional_prior",
     "gwi_spin_prior_times",
@@ -356,6 +359,14 @@ def load_library():
         lib.gwi_resample_injections.argtypes = [vp, _DP, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _DP, _I32P, _DP]
         lib.gwi_resample_times.restype = None
         lib.gwi_resample_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_weighted_histograms"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _U16P, _I32P = C.POINTER(C.c_uint16), C.POINTER(C.c_int32)
+        lib.gwi_set_histogram_bins.restype = C.c_int32
+        lib.gwi_set_histogram_bins.argtypes = [vp, C.c_int32, C.c_int32, _U16P, _U16P]
+        lib.gwi_weighted_histograms.restype = C.c_int32
+        lib.gwi_weighted_histograms.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _I32P]
+        lib.gwi_histogram_times.restype = None
+        lib.gwi_histogram_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

@@ -9,6 +9,7 @@
 #include "gwi_mock.h"
 #include "gwi_popdraw.h"
 #include "gwi_resample.h"
+#include "gwi_hist.h"
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
 
@@ -468,6 +469,12 @@ struct gwi_engine {
   double *d_rs_tiles = nullptr, *d_rs_prefix = nullptr, *d_rs_lw = nullptr;
   int *d_rs_live = nullptr, *d_rs_idx = nullptr;
   size_t rs_out_cap = 0;
+  // weighted histograms (gwi_hist.h): the bin codes of gwi_set_histogram_bins, the tiles' partial histograms, the running sums
+  // [n_ev + 1][n_cols][n_bins] and the dead counts [n_ev + 1] of one gwi_weighted_histograms call (allocated with the bins, kept)
+  unsigned short *d_hist_bins_pe = nullptr, *d_hist_bins_inj = nullptr;
+  double *d_hist_partial = nullptr, *d_hist = nullptr;
+  int* d_hist_dead = nullptr;
+  int hist_cols = 0, hist_bins = 0;
   // pinned, device-visible host memory
   double *h_record = nullptr, *h_record_dev = nullptr;
   // device-final mode: the final launch's G workgroups publish one partial record each here; the host merges them into h_record
@@ -1595,6 +1602,11 @@ void destroy_impl(gwi_engine* h) {
   (void)hipFree(h->d_rs_lw);
   (void)hipFree(h->d_rs_live);
   (void)hipFree(h->d_rs_idx);
+  (void)hipFree(h->d_hist_bins_pe);
+  (void)hipFree(h->d_hist_bins_inj);
+  (void)hipFree(h->d_hist_partial);
+  (void)hipFree(h->d_hist);
+  (void)hipFree(h->d_hist_dead);
   if (h->nccl_comm && g_nccl.CommDestroy) (void)g_nccl.CommDestroy(h->nccl_comm);
   (void)hipFree(h->d_send);
   (void)hipFree(h->d_recv);
@@ -3762,6 +3774,167 @@ void gwi_resample_times(double* logw_ms, double* prefix_ms, double* select_ms, i
   if (prefix_ms) *prefix_ms = g_resample_times.prefix_ms;
   if (select_ms) *select_ms = g_resample_times.select_ms;
   if (launches) *launches = g_resample_times.launches;
+}
+
+// ---- weighted histograms (gwi_hist.h) ---------------------------------------------------------------------------------------
+struct HistogramTimes {
+  double logw_ms = 0.0, tile_ms = 0.0, merge_ms = 0.0;
+  int launches = 0;
+};
+static thread_local HistogramTimes g_histogram_times;
+
+// the bins go away: gwi_weighted_histograms refuses until they are set again
+static void drop_histogram_bins(gwi_handle h) {
+  (void)hipFree(h->d_hist_bins_pe);
+  (void)hipFree(h->d_hist_bins_inj);
+  (void)hipFree(h->d_hist_partial);
+  (void)hipFree(h->d_hist);
+  (void)hipFree(h->d_hist_dead);
+  h->d_hist_bins_pe = h->d_hist_bins_inj = nullptr;
+  h->d_hist_partial = h->d_hist = nullptr;
+  h->d_hist_dead = nullptr;
+  h->hist_cols = h->hist_bins = 0;
+}
+
+gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, const uint16_t* pe_bins, const uint16_t* inj_bins) {
+  if (!h) return GWI_ERR_INVALID;
+  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: host-only handle: no device to keep the bins on");
+  namespace D = gwi::draw;
+  namespace H = gwi::hist;
+  if (n_cols < 1 || n_cols > H::kMaxCols)
+    return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: n_cols = " + std::to_string(n_cols) + " is not in 1 ... " + std::to_string(H::kMaxCols));
+  if (n_bins < 1 || n_bins > H::kMaxBins)
+    return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: n_bins = " + std::to_string(n_bins) + " is not in 1 ... " + std::to_string(H::kMaxBins));
+  if (!pe_bins && !inj_bins) return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: pe_bins and inj_bins are both null");
+  if (h->comm_world > 1 || h->shm_world > 1)
+    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_set_histogram_bins: this handle holds one shard of the catalog; the injection histogram needs the global set");
+  gwi_status st = busy_guard(h, "gwi_set_histogram_bins");
+  if (st != GWI_OK) return st;
+  const size_t n_pe_codes = pe_bins ? (size_t)n_cols * (size_t)(h->n_ev * h->n_pe) : 0, n_inj_codes = inj_bins ? (size_t)n_cols * (size_t)h->n_inj : 0;
+  for (int set = 0; set < 2; ++set) {
+    const uint16_t* codes = set ? inj_bins : pe_bins;
+    const size_t n = set ? n_inj_codes : n_pe_codes;
+    for (size_t i = 0; i < n; ++i)
+      if (codes[i] >= n_bins && codes[i] != H::kOutside)
+        return fail(h, GWI_ERR_INVALID, std::string("gwi_set_histogram_bins: ") + (set ? "inj_bins" : "pe_bins") + " entry " + std::to_string(i) + " is " + std::to_string(codes[i]) +
+                                            ": neither a bin below n_bins = " + std::to_string(n_bins) + " nor 0xFFFF (outside every bin)");
+  }
+  const long long tiles_per_event = D::tiles_of(h->n_pe), n_inj_tiles = D::tiles_of(h->n_inj), n_tiles = h->n_ev * tiles_per_event + n_inj_tiles;
+  if (n_tiles > 0x7fffffffLL || h->n_pe > 0x7fffffffLL || h->n_inj > 0x7fffffffLL) return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: more tiles (or samples per segment) than one launch can index");
+  GWI_HIP(hipSetDevice(h->device));
+  drop_histogram_bins(h);
+  const size_t per_seg = (size_t)n_cols * (size_t)n_bins;
+  if (n_pe_codes) {
+    GWI_HIP(hipMalloc(&h->d_hist_bins_pe, sizeof(uint16_t) * n_pe_codes));
+    GWI_HIP(hipMemcpy(h->d_hist_bins_pe, pe_bins, sizeof(uint16_t) * n_pe_codes, hipMemcpyHostToDevice));
+  }
+  if (n_inj_codes) {
+    GWI_HIP(hipMalloc(&h->d_hist_bins_inj, sizeof(uint16_t) * n_inj_codes));
+    GWI_HIP(hipMemcpy(h->d_hist_bins_inj, inj_bins, sizeof(uint16_t) * n_inj_codes, hipMemcpyHostToDevice));
+  }
+  GWI_HIP(hipMalloc(&h->d_hist_partial, sizeof(double) * std::max<size_t>((size_t)n_tiles * per_seg, 1)));
+  GWI_HIP(hipMalloc(&h->d_hist, sizeof(double) * (size_t)(h->n_ev + 1) * per_seg));
+  GWI_HIP(hipMalloc(&h->d_hist_dead, sizeof(int) * (size_t)(h->n_ev + 1)));
+  if (!h->d_draw_tiles) GWI_HIP(hipMalloc(&h->d_draw_tiles, sizeof(double) * (size_t)(4 * n_tiles + h->n_ev + 1)));  // (gwi_draw_indices' own)
+  h->hist_cols = n_cols;
+  h->hist_bins = n_bins;
+  return GWI_OK;
+}
+
+gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k, double* hist_pe, double* hist_inj, int32_t* dead) {
+  if (!h) return GWI_ERR_INVALID;
+  g_histogram_times = HistogramTimes();
+  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: host-only handle: no device to sum on");
+  if (!h->variant) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: the engine has no scan kernel");
+  if (!h->hist_cols) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: no bins are set (gwi_set_histogram_bins)");
+  if (!thetas || k < 1) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: thetas is null or k < 1");
+  const bool with_pe = h->d_hist_bins_pe != nullptr, with_inj = h->d_hist_bins_inj != nullptr;
+  if (with_pe && !hist_pe) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: pe_bins are set: hist_pe is needed");
+  if (with_inj && !hist_inj) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: inj_bins are set: hist_inj is needed");
+  if (!dead) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: dead is null");
+  if (h->comm_world > 1 || h->shm_world > 1)
+    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_weighted_histograms: this handle holds one shard of the catalog; the injection histogram needs the global set");
+  gwi_status st = busy_guard(h, "gwi_weighted_histograms");
+  if (st != GWI_OK) return st;
+  namespace D = gwi::draw;
+  namespace H = gwi::hist;
+  const long long tiles_per_event = D::tiles_of(h->n_pe), n_inj_tiles = D::tiles_of(h->n_inj);
+  const long long n_pe_tiles = h->n_ev * tiles_per_event, n_tiles = n_pe_tiles + n_inj_tiles;
+  const size_t per_seg = (size_t)h->hist_cols * (size_t)h->hist_bins, n_pe_out = (size_t)h->n_ev * per_seg;
+  GWI_HIP(hipSetDevice(h->device));
+  // the caller's running sums: the points of this call are added onto them, so a request may be split over calls
+  if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(h->d_hist, hist_pe, sizeof(double) * n_pe_out, hipMemcpyHostToDevice));
+  if (with_inj) GWI_HIP(hipMemcpy(h->d_hist + n_pe_out, hist_inj, sizeof(double) * per_seg, hipMemcpyHostToDevice));
+  GWI_HIP(hipMemcpy(h->d_hist_dead, dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyHostToDevice));
+  H::Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.d.mask_pe = h->d_draw_mask_pe;
+  a.d.mask_inj = h->d_draw_mask_inj;
+  a.d.tile_max = h->d_draw_tiles;
+  a.d.tile_sum = a.d.tile_max + n_tiles;
+  a.d.tile_mass = a.d.tile_sum + n_tiles;
+  a.d.tile_prefix = a.d.tile_mass + n_tiles;
+  a.d.seg_max = a.d.tile_prefix + n_tiles;
+  a.d.n_pe = h->n_pe;
+  a.d.n_inj = h->n_inj;
+  a.d.n_ev = (int)h->n_ev;
+  a.d.tiles_per_event = (int)tiles_per_event;
+  a.d.n_inj_tiles = (int)n_inj_tiles;
+  a.bins_pe = h->d_hist_bins_pe;
+  a.bins_inj = h->d_hist_bins_inj;
+  a.partial = h->d_hist_partial;
+  a.hist = h->d_hist;
+  a.n_dead = h->d_hist_dead;
+  a.n_cols = h->hist_cols;
+  a.n_bins = h->hist_bins;
+  // a set without bins is left out of the two new launches: PE tiles and segments come first, the injection set's last
+  a.first_tile = with_pe ? 0 : (int)n_pe_tiles;
+  a.first_seg = with_pe ? 0 : (int)h->n_ev;
+  const long long hist_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? n_inj_tiles : 0), hist_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
+  struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~Events() {
+      for (hipEvent_t v : e)
+        if (v) (void)hipEventDestroy(v);
+    }
+  } ev;
+  for (hipEvent_t& v : ev.e) GWI_HIP(hipEventCreate(&v));
+  const int nt = h->spec.n_theta;
+  for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
+    const auto t0 = std::chrono::steady_clock::now();
+    st = fill_log_weights(h, thetas + (size_t)p * nt, &a.d.log_const);  // (blocking)
+    if (st != GWI_OK) return st;
+    g_histogram_times.logw_ms += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    a.d.logw_pe = h->d_logw_pe;
+    a.d.logw_inj = h->d_logw_inj;
+    GWI_HIP(hipEventRecord(ev.e[0], h->stream));
+    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a.d);
+    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.d);
+    if (hist_tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)hist_tiles), dim3(H::kBlock), 0, h->stream, a);
+    GWI_HIP(hipEventRecord(ev.e[1], h->stream));
+    if (hist_segs) hipLaunchKernelGGL(H::hist_merge_kernel, dim3((unsigned)hist_segs, (unsigned)a.n_cols), dim3(H::kBlock), 0, h->stream, a);
+    GWI_HIP(hipGetLastError());
+    GWI_HIP(hipEventRecord(ev.e[2], h->stream));
+    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
+    GWI_HIP(hipStreamSynchronize(h->stream));
+    float tile_ms = 0.f, merge_ms = 0.f;
+    GWI_HIP(hipEventElapsedTime(&tile_ms, ev.e[0], ev.e[1]));
+    GWI_HIP(hipEventElapsedTime(&merge_ms, ev.e[1], ev.e[2]));
+    g_histogram_times.tile_ms += tile_ms;
+    g_histogram_times.merge_ms += merge_ms;
+    g_histogram_times.launches += 4;
+  }
+  if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(hist_pe, h->d_hist, sizeof(double) * n_pe_out, hipMemcpyDeviceToHost));
+  if (with_inj) GWI_HIP(hipMemcpy(hist_inj, h->d_hist + n_pe_out, sizeof(double) * per_seg, hipMemcpyDeviceToHost));
+  GWI_HIP(hipMemcpy(dead, h->d_hist_dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyDeviceToHost));
+  return GWI_OK;
+}
+
+void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) {
+  if (logw_ms) *logw_ms = g_histogram_times.logw_ms;
+  if (tile_ms) *tile_ms = g_histogram_times.tile_ms;
+  if (merge_ms) *merge_ms = g_histogram_times.merge_ms;
+  if (launches) *launches = g_histogram_times.launches;
 }
 
 }  // extern "C"

@@ -9,10 +9,14 @@ sample with ``w_j = 0``; the last sample with positive weight when rounding runs
 
 ``gwi_resample_injections`` (gwinferno_amd/csrc/gwi_resample.h; the reference's ``resample_injections``,
 preprocess/selection.py:143-156) draws from the injection segment by the same rule with uniforms of its own:
-:func:`resample_uniforms` states them and :func:`resample_indices_reference` the draws."""
+:func:`resample_uniforms` states them and :func:`resample_indices_reference` the draws.
+
+``gwi_weighted_histograms`` (gwinferno_amd/csrc/gwi_hist.h) sums the same ``w_j`` into bins instead of drawing from them:
+:func:`weighted_histograms_reference` states one hyper-parameter point of it, :func:`digitize` the bin codes."""
 import numpy as np
 
 RESAMPLE_TAG = 0x52534D50  # counter word 3 of the resampling stream (gwi_resample.h: kTag)
+OUTSIDE_BIN = 0xFFFF       # bin code of a sample outside every bin (gwi_hist.h: kOutside)
 
 
 def draw_weights(logw, mask=None):
@@ -82,3 +86,59 @@ def mass_cut_masks(pedata, injdata, m1min, m2min, mmax):
             return (~((m1 < m1min) | (m1 > mmax) | (m1 * q < m2min))).astype(np.uint8)
 
     return one(pedata), one(injdata)
+
+
+def digitize(values, edges):
+    """uint16 bin codes of ``values`` for the increasing ``edges`` (``B + 1`` of them, uniform or not), ``np.histogram``'s rule:
+    bin ``b`` holds ``edges[b] <= x < edges[b + 1]``, the last bin its right edge too; :data:`OUTSIDE_BIN` for every other value
+    (NaN included)."""
+    edges = np.asarray(edges, dtype=np.float64).ravel()
+    if edges.size < 2 or not np.all(np.diff(edges) > 0):
+        raise ValueError("edges must be at least two increasing numbers")
+    if edges.size - 1 >= OUTSIDE_BIN:
+        raise ValueError("too many bins for a uint16 code")
+    x = np.asarray(values, dtype=np.float64)
+    code = np.searchsorted(edges, x, side="right") - 1
+    code = np.where(x == edges[-1], edges.size - 2, code)
+    with np.errstate(invalid="ignore"):
+        inside = (x >= edges[0]) & (x <= edges[-1])
+    return np.where(inside, code, OUTSIDE_BIN).astype(np.uint16)
+
+
+def weighted_histogram_segment(logw, mask, bins, n_bins):
+    """ONE segment at one point: ``(h (n_cols, n_bins), live)`` with ``h[c][b] = (sum of w_j over the samples with bins[c][j] == b)
+    / (sum of w_j over the segment)`` in float64 -- a sample coded :data:`OUTSIDE_BIN` is in no bin but counts in the total --
+    and zeros with ``live = False`` when no sample has weight."""
+    bins = np.asarray(bins)
+    w = draw_weights(logw, mask)
+    total = w.sum()
+    h = np.zeros((bins.shape[0], int(n_bins)))
+    if not (total > 0.0 and np.isfinite(total)):
+        return h, False
+    for c in range(bins.shape[0]):
+        code = bins[c].ravel().astype(np.int64)
+        inside = code < n_bins
+        h[c] = np.bincount(code[inside], weights=w[inside], minlength=int(n_bins)) / total
+    return h, True
+
+
+def weighted_histograms_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins, inj_bins, n_bins):
+    """One hyper-parameter point of ``gwi_weighted_histograms``: ``logw_pe (n_ev, n_pe)``, ``pe_bins (n_cols, n_ev, n_pe)``,
+    ``logw_inj (n_inj,)``, ``inj_bins (n_cols, n_inj)`` -> ``(hist_pe (n_ev, n_cols, n_bins), hist_inj (n_cols, n_bins), dead
+    (n_ev + 1,) int32)``: what the point adds to the running sums, and 1 in ``dead`` for every segment without weight (the
+    injection set last).  A set whose bins are ``None`` is left out (``None`` in its place, 0 in ``dead``)."""
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    n_ev = logw_pe.shape[0]
+    dead = np.zeros(n_ev + 1, dtype=np.int32)
+    hist_pe = hist_inj = None
+    if pe_bins is not None:
+        pe_bins = np.asarray(pe_bins)
+        pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(logw_pe.shape)
+        hist_pe = np.zeros((n_ev, pe_bins.shape[0], int(n_bins)))
+        for ev in range(n_ev):
+            hist_pe[ev], live = weighted_histogram_segment(logw_pe[ev], None if pe_mask is None else pe_mask[ev], pe_bins[:, ev], n_bins)
+            dead[ev] = 0 if live else 1
+    if inj_bins is not None:
+        hist_inj, live = weighted_histogram_segment(logw_inj, inj_mask, np.asarray(inj_bins), n_bins)
+        dead[n_ev] = 0 if live else 1
+    return hist_pe, hist_inj, dead

@@ -1067,6 +1067,77 @@ class NativePopulationLikelihood:
         n = int(made.value)
         return idx[:n].copy(), lw[:n].copy(), {"log_sum_w": float(sums[0]), "log_sum_w2": float(sums[1]), "n_eff": float(sums[2]), "n_live": int(sums[3])}
 
+    def set_histogram_bins(self, pe_bins=None, inj_bins=None, n_bins=None):
+        """The bin codes :meth:`weighted_histograms` sums into (``gwi_set_histogram_bins``): ``pe_bins (n_cols, n_ev, n_pe)`` and
+        ``inj_bins (n_cols, n_inj)``, integers in ``[0, n_bins)`` or ``0xFFFF`` for a sample outside every bin (it still counts in
+        the segment's total); ``None`` leaves that set out, not both.  ``1 <= n_cols <= 8``, ``1 <= n_bins <= 256``.  The codes
+        depend on the catalog only: they are copied to HBM once, and the workspace is allocated here.  Not available on an engine
+        that holds a shard (``world > 1``)."""
+        if self.world > 1:
+            raise N.NativeEngineError("GWI_ERR_UNSUPPORTED: set_histogram_bins: this engine holds one shard of the catalog; the injection histogram needs the global set")
+        if n_bins is None:
+            raise ValueError("n_bins is needed")
+        if pe_bins is None and inj_bins is None:
+            raise ValueError("pe_bins and inj_bins are both None")
+
+        def one(b, shape, name):
+            if b is None:
+                return None
+            b = np.asarray(b)
+            if b.ndim != len(shape) + 1 or b.shape[1:] != shape:
+                raise ValueError(f"{name} has shape {b.shape}; expected (n_cols, {', '.join(str(v) for v in shape)})")
+            if b.dtype.kind not in "iu":
+                raise ValueError(f"{name} holds {b.dtype}, not integer bin codes")
+            if b.size and (b.min() < 0 or b.max() > 0xFFFF):
+                raise ValueError(f"{name} holds codes outside 0 ... 0xFFFF")
+            return np.ascontiguousarray(b, dtype=np.uint16)
+
+        pe, inj = one(pe_bins, (self.n_ev, self.n_pe), "pe_bins"), one(inj_bins, (self.n_inj,), "inj_bins")
+        if pe is not None and inj is not None and pe.shape[0] != inj.shape[0]:
+            raise ValueError(f"pe_bins holds {pe.shape[0]} columns, inj_bins {inj.shape[0]}")
+        n_cols = (pe if pe is not None else inj).shape[0]
+        u16 = C.POINTER(C.c_uint16)
+        self._check(self.lib.gwi_set_histogram_bins(self.handle, n_cols, int(n_bins), pe.ctypes.data_as(u16) if pe is not None else None,
+                                                    inj.ctypes.data_as(u16) if inj is not None else None))
+        self._hist_shape = (n_cols, int(n_bins), pe is not None, inj is not None)
+
+    def weighted_histograms(self, thetas, out=None):
+        """Weighted histograms on the device (``gwi_weighted_histograms``; semantics:
+        :func:`gwinferno_amd.draws.weighted_histograms_reference`).  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.
+        Returns ``(hist_pe (n_ev, n_cols, n_bins), hist_inj (n_cols, n_bins), dead (n_ev + 1,) int32)``: running SUMS over the
+        points of each point's normalised histogram (``None`` for a set without bins), and per segment (the injection set last)
+        the number of points at which nothing had weight -- the mean over the live points is ``hist / (K - dead)``.  ``out``
+        is such a triple from an earlier call: the new points are added onto it in place, with the bits one call over all
+        points would give.  Only the sums travel back from the device.  Not available on an engine that holds a shard
+        (``world > 1``)."""
+        if self.world > 1:
+            raise N.NativeEngineError("GWI_ERR_UNSUPPORTED: weighted_histograms: this engine holds one shard of the catalog; the injection histogram needs the global set")
+        thetas = N.f64(thetas)
+        if thetas.ndim not in (1, 2) or thetas.shape[-1] != self.n_theta or thetas.size == 0:
+            raise ValueError(f"thetas has shape {thetas.shape}; expected ({self.n_theta},) or (k, {self.n_theta})")
+        thetas = thetas.reshape(-1, self.n_theta)
+        shape = getattr(self, "_hist_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        if shape is None:  # the library says so
+            self._check(self.lib.gwi_weighted_histograms(self.handle, N.as_dp(thetas), thetas.shape[0], None, None, None))
+            raise N.NativeEngineError("GWI_ERR_INVALID: weighted_histograms: no bins are set (set_histogram_bins)")
+        n_cols, n_bins, with_pe, with_inj = shape
+        want = ((self.n_ev, n_cols, n_bins) if with_pe else None, (n_cols, n_bins) if with_inj else None, (self.n_ev + 1,))
+        if out is None:
+            out = tuple(None if s is None else np.zeros(s, dtype=np.int32 if i == 2 else np.float64) for i, s in enumerate(want))
+        else:
+            if len(out) != 3:
+                raise ValueError("out is (hist_pe, hist_inj, dead)")
+            for o, s, name, dt in zip(out, want, ("hist_pe", "hist_inj", "dead"), (np.float64, np.float64, np.int32)):
+                if s is None:
+                    continue
+                if not isinstance(o, np.ndarray) or o.shape != s or o.dtype != dt or not o.flags.c_contiguous or not o.flags.writeable:
+                    raise ValueError(f"out: {name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape {s}")
+        hist_pe, hist_inj, dead = out
+        self._check(self.lib.gwi_weighted_histograms(self.handle, N.as_dp(thetas), thetas.shape[0], N.as_dp(hist_pe) if with_pe else None, N.as_dp(hist_inj) if with_inj else None,
+                                                     dead.ctypes.data_as(i32)))
+        return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead
+
     def selftime(self, theta, total_inj, n_iter=1000, min_neff_cut=True):
         """Mean seconds per evaluation of a C-side loop of sequential gwi_eval calls (diagnostic)."""
         opt = self._options(total_inj, None, False, min_neff_cut, False)

@@ -263,3 +263,102 @@ def posterior_predictive_draws(eng, thetas, n_draws, seed, pedata=None, injdata=
             out["obs_pooled"][p] = obs.reshape(k, -1)
             out["pred"][p] = np.where(pred_idx >= 0, b[np.maximum(pred_idx, 0)], np.nan)
     return out
+
+
+HISTOGRAM_CHUNK = 64  # points per gwi_weighted_histograms call of reweighted_event_posteriors (the sums do not depend on it)
+
+
+def reweighted_event_posteriors(eng, thetas, pe_values, edges, inj_values=None, pedata=None, injdata=None, param_names=None, m1min=None, m2min=None, mmax=None,
+                                backend="device", chunk=HISTOGRAM_CHUNK):
+    """The population-informed posterior of every event, marginalised over K posterior hyper-parameter draws, as binned densities,
+    and the predicted detected distribution from the injections: per event, quantity and bin the mean over the draws of
+    ``(sum of w_i in the bin) / (sum of w_i)`` with ``w_i = p(x_i | theta_k) / prior_i`` -- the exact sums whose Monte-Carlo
+    estimate :func:`posterior_predictive_draws` gives with one index per draw (the reference's posterior-predictive branch,
+    pipeline/analysis.py:321-355).  On the device (``eng.weighted_histograms``) the weights never leave HBM and
+    ``(n_ev + 1) * len(names) * B`` doubles come back per chunk of points.
+
+    ``thetas`` is ``(K, n_theta)`` in the engine's layout.  ``pe_values`` maps a name to the ``(n_ev, n_pe)`` array of the
+    quantity to bin (any derived quantity, e.g. ``m2 = q * m1``), ``inj_values`` the same names to ``(n_inj,)`` arrays (``None``:
+    no predicted distribution); ``edges`` maps each name to increasing bin edges, uniform or not, all with the same number of
+    bins ``B <= 256`` (``np.histogram``'s rule: the last edge is inclusive).  ``param_names`` selects and orders the names
+    (default: the keys of ``pe_values``; at most 8).  The mass cuts are :func:`posterior_predictive_draws`': with all of
+    ``m1min, m2min, mmax`` given and both data dictionaries at hand they become the engine's draw mask, otherwise the mask the
+    engine holds stays.  The values are digitised once on the host; the points go to the engine in chunks of at most
+    ``chunk <= 64``, which does not change a bit of the result.  ``backend="host"`` runs the NumPy statement
+    (:func:`gwinferno_amd.draws.weighted_histograms_reference`) on ``eng.log_weights`` under the masks given here (none without
+    the cuts): the statement the kernels are tested against, not a fall-back.
+
+    Returns a dict per name: ``events (n_ev, B)``, the mean normalised histogram divided by the bin widths (a density: ``events *
+    widths`` sums to ``1 - outside``); ``predicted (B,)``, the same for the injection set (when ``inj_values`` is given);
+    ``outside``, ``{"events": (n_ev,), "predicted": float}``, the weight fraction outside the edges; and ``n_points``, the same
+    layout, the points at which the segment had weight (NaN densities where that is 0); beside them ``"edges"`` itself."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    chunk = int(chunk)
+    if not 1 <= chunk <= HISTOGRAM_CHUNK:
+        raise ValueError(f"chunk must be in 1 ... {HISTOGRAM_CHUNK}")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    names = list(param_names) if param_names is not None else list(pe_values)
+    if not 1 <= len(names) <= 8:
+        raise ValueError("between 1 and 8 quantities can be binned in one pass")
+    n_ev, n_pe, n_inj = eng.n_ev, eng.n_pe, eng.n_inj
+    grid = {p: np.asarray(edges[p], dtype=np.float64).ravel() for p in names}
+    n_bins = grid[names[0]].size - 1
+    if any(g.size - 1 != n_bins for g in grid.values()):
+        raise ValueError("every quantity needs the same number of bins")
+    if not 1 <= n_bins <= 256:
+        raise ValueError("n_bins must be in 1 ... 256")
+    pe_bins = np.empty((len(names), n_ev, n_pe), dtype=np.uint16)
+    inj_bins = np.empty((len(names), n_inj), dtype=np.uint16) if inj_values is not None else None
+    for c, p in enumerate(names):
+        v = np.asarray(pe_values[p], dtype=np.float64)
+        if v.shape != (n_ev, n_pe):
+            raise ValueError(f"pe_values[{p!r}] has shape {v.shape}, the engine's sample set {(n_ev, n_pe)}")
+        pe_bins[c] = D.digitize(v, grid[p])
+        if inj_bins is not None:
+            v = np.asarray(inj_values[p], dtype=np.float64)
+            if v.shape != (n_inj,):
+                raise ValueError(f"inj_values[{p!r}] has shape {v.shape}, the engine's injection set {(n_inj,)}")
+            inj_bins[c] = D.digitize(v, grid[p])
+    cuts = (m1min, m2min, mmax)
+    masks = (None, None)
+    if pedata is not None and injdata is not None and all(c is not None for c in cuts):
+        masks = D.mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+        if backend == "device":
+            eng.set_draw_mask(*masks)
+    elif any(c is not None for c in cuts) and not all(c is not None for c in cuts):
+        raise ValueError("m1min, m2min and mmax are given together or not at all")
+    if backend == "device":
+        eng.set_histogram_bins(pe_bins, inj_bins, n_bins=n_bins)
+        out = None
+        for i in range(0, k, chunk):
+            out = eng.weighted_histograms(thetas[i : i + chunk], out=out)
+        hist_pe, hist_inj, dead = out
+    else:
+        hist_pe, hist_inj, dead = np.zeros((n_ev, len(names), n_bins)), (np.zeros((len(names), n_bins)) if inj_bins is not None else None), np.zeros(n_ev + 1, dtype=np.int32)
+        for th in thetas:
+            lw_pe, lw_inj = eng.log_weights(th)
+            h_pe, h_inj, d = D.weighted_histograms_reference(lw_pe, lw_inj, masks[0], masks[1], pe_bins, inj_bins, n_bins)
+            hist_pe += h_pe
+            if hist_inj is not None:
+                hist_inj += h_inj
+            dead += d
+    live = (k - dead).astype(np.float64)
+    result = {"edges": {p: grid[p] for p in names}}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for c, p in enumerate(names):
+            widths = np.diff(grid[p])
+            mean_pe = hist_pe[:, c, :] / live[:n_ev, None]
+            entry = {"events": mean_pe / widths, "outside": {"events": 1.0 - mean_pe.sum(axis=1)}, "n_points": {"events": (k - dead[:n_ev]).astype(np.int64)}}
+            if hist_inj is not None:
+                mean_inj = hist_inj[c] / live[n_ev]
+                entry["predicted"] = mean_inj / widths
+                entry["outside"]["predicted"] = float(1.0 - mean_inj.sum())
+                entry["n_points"]["predicted"] = int(k - dead[n_ev])
+            result[p] = entry
+    return result

@@ -416,6 +416,40 @@ gwi_status gwi_resample_injections(gwi_handle h, const double* theta, uint64_t s
                                    int32_t* idx, double* logw_sel);
 void gwi_resample_times(double* logw_ms, double* prefix_ms, double* select_ms, int32_t* launches);
 
+/* Weighted histograms on the device: the population-informed posterior of every event, marginalised over hyper-parameter points,
+ * and its counterpart for the selection, the predicted detected distribution from the injection set -- the deterministic
+ * counterpart of the observed-versus-predicted check of the reference's posterior-predictive branch (pipeline/analysis.py:321-355),
+ * which gwi_draw_indices estimates with one index per point (gwinferno_amd/csrc/gwi_hist.h; the NumPy statement is
+ * gwinferno_amd/draws.py: weighted_histograms_reference).
+ *
+ * Segments, lw_j, the masks, M and w_j = exp(lw_j - M) are gwi_draw_indices' (the masks of gwi_set_draw_mask apply).  With
+ * S = the sum of w_j over the whole segment, a point adds  h[c][b] = (the sum of w_j over the samples whose code in column c is b) / S
+ * onto the running sums:  H[segment][c][b] += h[c][b], the points in the order of the call.  A sample coded 0xFFFF is in no bin but
+ * counts in S, so a column's bins sum to at most 1 and the deficit is the weight share outside.  A segment whose S is 0 or not
+ * finite adds nothing; dead[segment] is incremented instead (segment n_ev is the injection set).  Every sum has a fixed shape --
+ * sample order within a tile of 1 024 samples and a bin, then tile order, then point order -- and there are no atomics: the bits of H
+ * are a pure function of the arguments.
+ *
+ * gwi_set_histogram_bins(): 1 <= n_cols <= 8 binned quantities with 1 <= n_bins <= 256 bins each; pe_bins[n_cols][n_ev][n_pe] and
+ * inj_bins[n_cols][n_inj] are the samples' bin codes (uint16; they do not depend on theta), copied to HBM once; either may be NULL
+ * (that set is then left out), not both.  A code >= n_bins other than 0xFFFF is refused.  The workspace is allocated here.  A new
+ * call replaces the bins.
+ * gwi_weighted_histograms(): hist_pe[n_ev][n_cols][n_bins] (ignored without pe_bins), hist_inj[n_cols][n_bins] (ignored without
+ * inj_bins) and dead[n_ev + 1] are IN/OUT: the caller's values are uploaded, the k points thetas[k][n_theta] are added in order, and
+ * the sums are copied back -- (n_ev + 1) n_cols n_bins doubles per call, whatever k.  A request split over calls (2 + 1, 1 + 1 + 1)
+ * therefore returns the bits of one call.  k is not bound by the batch limit.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for limits, codes, null pointers, a host-only handle and a call before the bins
+ * are set; GWI_ERR_UNSUPPORTED on a handle that holds a shard, as gwi_draw_indices.
+ *
+ * gwi_histogram_times(): DIAGNOSTIC ONLY, for tools/weighted_histograms_time.py: of the calling thread's last call, summed over its
+ * points, the wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge / histogram
+ * tile launches together and of the histogram merge launches, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, const uint16_t* pe_bins /* [n_cols][n_ev][n_pe] or NULL */,
+                                  const uint16_t* inj_bins /* [n_cols][n_inj] or NULL */);
+gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k, double* hist_pe /* in/out [n_ev][n_cols][n_bins] */,
+                                   double* hist_inj /* in/out [n_cols][n_bins] */, int32_t* dead /* in/out [n_ev + 1] */);
+void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches);
+
 /* Effective-spin catalogs (gwinferno_amd/csrc/gwi_spinprior.h; the NumPy statement is gwinferno_amd/spin_priors.py).  Stand-alone
  * entries like gwi_ingest_columns: no handle, host pointers in and out, their own stream and buffers on `device` (negative: the
  * calling thread's current device).  The calling thread's current device is the same after the call as before it.
