@@ -410,6 +410,61 @@ bool load_nccl(const char* path, std::string* err) {
   g_nccl.lib = lib;
   return true;
 }
+
+// An owned device array that only grows: reserve(n) keeps the allocation while it holds n elements and otherwise frees it and
+// allocates anew (always at least one element); reset() frees it.  It is freed on the device that is current at the time, so the
+// owner selects the array's device first.
+template <class T>
+struct DeviceBuffer {
+  T* ptr = nullptr;
+  size_t cap = 0;
+  DeviceBuffer() = default;
+  DeviceBuffer(DeviceBuffer&& o) noexcept : ptr(o.ptr), cap(o.cap) { o.ptr = nullptr, o.cap = 0; }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {  // (the previous allocation goes away with `o`)
+    std::swap(ptr, o.ptr);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DeviceBuffer() { reset(); }
+  hipError_t reserve(size_t n) {
+    n = n ? n : 1;
+    if (n <= cap) return hipSuccess;
+    reset();
+    const hipError_t e = hipMalloc(&ptr, sizeof(T) * n);
+    if (e != hipSuccess) ptr = nullptr;
+    cap = ptr ? n : 0;
+    return e;
+  }
+  void reset() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+  }
+  operator T*() const { return ptr; }
+};
+
+// Device memory of the post-processing entries of one engine.  destroy_impl assigns an empty set over it where the engine's other
+// device memory is freed; gwi_set_histogram_bins does the same with `hist`.
+struct PostprocessBuffers {
+  DeviceBuffer<double> d_logw_pe, d_logw_inj;  // the log-weight role of the scan chain (fill_log_weights)
+  // index draws (gwi_draw.h): the caller's masks, the tiles' (max, sum, mass, prefix) + the segments' maxima, and the uniforms /
+  // indices of one gwi_draw_indices call (grown on demand, kept)
+  DeviceBuffer<unsigned char> d_draw_mask_pe, d_draw_mask_inj;
+  DeviceBuffer<double> d_draw_tiles, d_draw_u;
+  DeviceBuffer<int> d_draw_idx;
+  // injection resampling (gwi_resample.h): the injection tiles' (max, sum, mass, prefix, sum w^2) + M + the stats record, the tiles'
+  // live counts, the in-tile prefix of every injection, and the indices / log-weights of one select launch (grown on demand, kept)
+  DeviceBuffer<double> d_rs_tiles, d_rs_prefix, d_rs_lw;
+  DeviceBuffer<int> d_rs_live, d_rs_idx;
+  // weighted histograms (gwi_hist.h): the bin codes of gwi_set_histogram_bins, the tiles' partial histograms, the running sums
+  // [n_ev + 1][n_cols][n_bins] and the dead counts [n_ev + 1] of one gwi_weighted_histograms call (allocated with the bins, kept)
+  struct Histogram {
+    DeviceBuffer<unsigned short> d_bins_pe, d_bins_inj;
+    DeviceBuffer<double> d_partial, d_sums;
+    DeviceBuffer<int> d_dead;
+    int cols = 0, bins = 0;
+  } hist;
+};
 }  // namespace
 
 struct gwi_engine {
@@ -457,24 +512,7 @@ struct gwi_engine {
   std::vector<double*> d_norm_arrays;
   double *d_partials = nullptr, *d_ev_out = nullptr, *d_ev_grad = nullptr, *d_inj_out = nullptr, *d_inj_grad = nullptr;
   std::vector<double> sq_records;  // records of the squared-weight pass (marginalize_selection gradient)
-  double *d_logw_pe = nullptr, *d_logw_inj = nullptr;
-  // index draws (gwi_draw.h): the caller's masks, the tiles' (max, sum, mass, prefix) + the segments' maxima, and the uniforms /
-  // indices of one gwi_draw_indices call (grown on demand, kept)
-  unsigned char *d_draw_mask_pe = nullptr, *d_draw_mask_inj = nullptr;
-  double *d_draw_tiles = nullptr, *d_draw_u = nullptr;
-  int* d_draw_idx = nullptr;
-  size_t draw_u_cap = 0, draw_idx_cap = 0;
-  // injection resampling (gwi_resample.h): the injection tiles' (max, sum, mass, prefix, sum w^2) + M + the stats record, the tiles'
-  // live counts, the in-tile prefix of every injection, and the indices / log-weights of one select launch (grown on demand, kept)
-  double *d_rs_tiles = nullptr, *d_rs_prefix = nullptr, *d_rs_lw = nullptr;
-  int *d_rs_live = nullptr, *d_rs_idx = nullptr;
-  size_t rs_out_cap = 0;
-  // weighted histograms (gwi_hist.h): the bin codes of gwi_set_histogram_bins, the tiles' partial histograms, the running sums
-  // [n_ev + 1][n_cols][n_bins] and the dead counts [n_ev + 1] of one gwi_weighted_histograms call (allocated with the bins, kept)
-  unsigned short *d_hist_bins_pe = nullptr, *d_hist_bins_inj = nullptr;
-  double *d_hist_partial = nullptr, *d_hist = nullptr;
-  int* d_hist_dead = nullptr;
-  int hist_cols = 0, hist_bins = 0;
+  PostprocessBuffers post;  // what the post-processing entries keep on the device (none of it allocated before its first use)
   // pinned, device-visible host memory
   double *h_record = nullptr, *h_record_dev = nullptr;
   // device-final mode: the final launch's G workgroups publish one partial record each here; the host merges them into h_record
@@ -1576,6 +1614,7 @@ void destroy_impl(gwi_engine* h) {
   if (h->poisoned && !aql::drain(h->aq, 2.0)) {
     // a kernel of the timed-out evaluation may still be running: leak the device buffers rather than free them under it
     aql::abandon_queue(h->aq);
+    (void)new PostprocessBuffers(std::move(h->post));  // (out of the handle's reach and never destroyed)
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return;
@@ -1590,23 +1629,7 @@ void destroy_impl(gwi_engine* h) {
   (void)hipFree(h->d_ev_grad);
   (void)hipFree(h->d_inj_out);
   (void)hipFree(h->d_inj_grad);
-  (void)hipFree(h->d_logw_pe);
-  (void)hipFree(h->d_logw_inj);
-  (void)hipFree(h->d_draw_mask_pe);
-  (void)hipFree(h->d_draw_mask_inj);
-  (void)hipFree(h->d_draw_tiles);
-  (void)hipFree(h->d_draw_u);
-  (void)hipFree(h->d_draw_idx);
-  (void)hipFree(h->d_rs_tiles);
-  (void)hipFree(h->d_rs_prefix);
-  (void)hipFree(h->d_rs_lw);
-  (void)hipFree(h->d_rs_live);
-  (void)hipFree(h->d_rs_idx);
-  (void)hipFree(h->d_hist_bins_pe);
-  (void)hipFree(h->d_hist_bins_inj);
-  (void)hipFree(h->d_hist_partial);
-  (void)hipFree(h->d_hist);
-  (void)hipFree(h->d_hist_dead);
+  h->post = PostprocessBuffers();
   if (h->nccl_comm && g_nccl.CommDestroy) (void)g_nccl.CommDestroy(h->nccl_comm);
   (void)hipFree(h->d_send);
   (void)hipFree(h->d_recv);
@@ -1672,6 +1695,144 @@ gwi_status busy_guard(gwi_handle h, const char* who) {
   if (h->poisoned) return fail(h, GWI_ERR_INVALID, std::string(who) + ": an earlier evaluation of this handle timed out or its queue failed; destroy the handle");
   if (h->pending) return fail(h, GWI_ERR_INVALID, std::string(who) + ": an evaluation begun with gwi_eval_begin has not been collected (gwi_eval_end)");
   return GWI_OK;
+}
+
+// ---- the scaffold of the post-processing entries ----------------------------------------------------------------------------------
+
+// What the handle-bound entries refuse, in their common order: a host-only handle ("no device to <no_device_to>"), the entry's own
+// arguments (bad_args() names what is wrong with them, or returns an empty string), a handle that holds a shard ("<global_set_for>
+// the global set"), a handle that is busy or poisoned.
+template <class ArgCheck>
+gwi_status post_preflight(gwi_handle h, const char* who, const char* no_device_to, const char* global_set_for, ArgCheck&& bad_args) {
+  const std::string entry = std::string(who) + ": ";
+  if (h->host_only) return fail(h, GWI_ERR_INVALID, entry + "host-only handle: no device to " + no_device_to);
+  const std::string why = bad_args();
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, entry + why);
+  if (h->comm_world > 1 || h->shm_world > 1) return fail(h, GWI_ERR_UNSUPPORTED, entry + "this handle holds one shard of the catalog; " + global_set_for + " the global set");
+  return busy_guard(h, who);
+}
+
+// puts the calling thread back on the device it was on when the scope ends.  Declared before an entry's buffers: they are freed on
+// `device`, then the thread goes back
+struct DeviceScope {
+  int previous = -1;
+  ~DeviceScope() {
+    if (previous >= 0) (void)hipSetDevice(previous);
+  }
+  gwi_status select(int32_t device) {  // (device < 0: the current one)
+    int n_dev = 0, current = -1;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return GWI_ERR_NO_DEVICE;
+    if (device >= n_dev) return GWI_ERR_NO_DEVICE;
+    if (device < 0) return GWI_OK;
+    if (hipGetDevice(&current) != hipSuccess) return GWI_ERR_HIP;
+    if (current == device) return GWI_OK;
+    if (hipSetDevice(device) != hipSuccess) return GWI_ERR_HIP;
+    previous = current;
+    return GWI_OK;
+  }
+};
+
+// a failed call of an entry without a handle: "<entry>: <call>: <hip error string>" on stderr and GWI_ERR_HIP (`sc` is the
+// entry's LaunchScratch)
+#define GWI_SCRATCH_HIP(call)                                  \
+  do {                                                         \
+    if (sc.failed((call), #call)) return GWI_ERR_HIP;          \
+  } while (0)
+
+// device buffers, a stream and events that go away with the scope
+struct LaunchScratch {
+  const char* where;  // the entry, for the line a failed call prints
+  std::vector<void*> bufs;
+  hipStream_t stream = nullptr;
+  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+  explicit LaunchScratch(const char* entry) : where(entry) {}
+  LaunchScratch(const LaunchScratch&) = delete;
+  ~LaunchScratch() {
+    for (void* b : bufs) (void)hipFree(b);
+    for (hipEvent_t v : e)
+      if (v) (void)hipEventDestroy(v);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  template <class T>
+  T* alloc(size_t n) {
+    void* p = nullptr;
+    if (hipMalloc(&p, sizeof(T) * (n ? n : 1)) != hipSuccess) return nullptr;
+    bufs.push_back(p);
+    return (T*)p;
+  }
+  hipError_t events(int n) {  // (an entry that launches on its engine's stream opens these only)
+    hipError_t err = hipSuccess;
+    for (int i = 0; i < n && err == hipSuccess; ++i) err = hipEventCreate(&e[i]);
+    return err;
+  }
+  bool open() { return hipStreamCreate(&stream) == hipSuccess && events(2) == hipSuccess; }
+  bool failed(hipError_t err, const char* call) const {
+    if (err != hipSuccess) std::fprintf(stderr, "%s: %s: %s\n", where, call, hipGetErrorString(err));
+    return err != hipSuccess;
+  }
+  // launch() between the two events on the scope's stream
+  template <class Launch>
+  gwi_status enqueue_timed(Launch&& launch) {
+    LaunchScratch& sc = *this;
+    GWI_SCRATCH_HIP(hipEventRecord(e[0], stream));
+    launch();
+    GWI_SCRATCH_HIP(hipGetLastError());
+    GWI_SCRATCH_HIP(hipEventRecord(e[1], stream));
+    return GWI_OK;
+  }
+  // ... waited for: *ms is the time between the events
+  template <class Launch>
+  gwi_status timed(Launch&& launch, float* ms) {
+    LaunchScratch& sc = *this;
+    const gwi_status st = enqueue_timed(launch);
+    if (st != GWI_OK) return st;
+    GWI_SCRATCH_HIP(hipEventSynchronize(e[1]));
+    GWI_SCRATCH_HIP(hipEventElapsedTime(ms, e[0], e[1]));
+    return GWI_OK;
+  }
+  // ... with what after() enqueues behind it (the copies of its results), and the whole stream waited for
+  template <class Launch, class After>
+  gwi_status timed(Launch&& launch, After&& after, float* ms) {
+    LaunchScratch& sc = *this;
+    gwi_status st = enqueue_timed(launch);
+    if (st == GWI_OK) st = after();
+    if (st != GWI_OK) return st;
+    GWI_SCRATCH_HIP(hipStreamSynchronize(stream));
+    GWI_SCRATCH_HIP(hipEventElapsedTime(ms, e[0], e[1]));
+    return GWI_OK;
+  }
+};
+
+// up to three times of a feature's last call on the calling thread, and its launches; every feature has an instance of its own
+struct StageTimes {
+  double ms[3] = {0.0, 0.0, 0.0};
+  int launches = 0;
+  void report(double* ms0, double* ms1, double* ms2, int32_t* n) const {
+    if (ms0) *ms0 = ms[0];
+    if (ms1) *ms1 = ms[1];
+    if (ms2) *ms2 = ms[2];
+    if (n) *n = launches;
+  }
+};
+
+// why a feature's last call on the calling thread was refused
+struct ErrorSlot {
+  std::string text;
+  gwi_status refuse(const std::string& why) {
+    text = why;
+    return GWI_ERR_INVALID;
+  }
+};
+
+// A grid of rows x items cut into launches: at most items_cap items of a row per launch (rounded up to whole workgroups they are
+// its lanes), and as many rows as 65535 (grid.y) and lane_budget lanes allow, at least one
+struct LaunchCut {
+  long long items_max, rows_max;
+};
+LaunchCut launch_cut(long long n_rows, long long n_items, long long items_cap, long long lane_budget, int block) {
+  const long long items_max = std::min<long long>(n_items, items_cap);
+  const long long lanes_per_row = (items_max + block - 1) / block * block;
+  return {items_max, std::max<long long>(1, std::min<long long>(std::min<long long>(n_rows, 65535), lane_budget / lanes_per_row))};
 }
 
 }  // namespace
@@ -2515,14 +2676,13 @@ gwi_status gwi_ingest_columns(const gwi_ingest_program* prog, int64_t n, int32_t
   if (device >= n_dev) return GWI_ERR_NO_DEVICE;
   if (device >= 0 && hipSetDevice(device) != hipSuccess) return GWI_ERR_HIP;
   std::string err;
+  LaunchScratch sc("gwi_ingest_columns");
   std::vector<double*> d(n_cols, nullptr);
-  gwi_status st = GWI_OK;
-  for (int c = 0; c < n_cols && st == GWI_OK; ++c)
-    if (hipMalloc(&d[c], sizeof(double) * (size_t)(n ? n : 1)) != hipSuccess) st = GWI_ERR_HIP;
-  if (st == GWI_OK) st = ingest_run(err, prog, n, n_cols, d.data(), nullptr);
+  for (int c = 0; c < n_cols; ++c)
+    if (!(d[c] = sc.alloc<double>((size_t)n))) return GWI_ERR_HIP;
+  gwi_status st = ingest_run(err, prog, n, n_cols, d.data(), nullptr);
   for (int c = 0; c < n_cols && st == GWI_OK; ++c)
     if (n && hipMemcpy(cols[c], d[c], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) st = GWI_ERR_HIP;
-  for (double* q : d) (void)hipFree(q);
   if (st != GWI_OK && !err.empty()) std::fprintf(stderr, "gwi_ingest_columns: %s\n", err.c_str());
   return st;
 }
@@ -2631,48 +2791,35 @@ gwi_status gwi_hbm_bandwidth(int32_t device, int64_t n_doubles, int32_t iters, d
   if (device == GWI_DEVICE_CURRENT && hipGetDevice(&device) != hipSuccess) return GWI_ERR_HIP;
   if (device < 0 || device >= n_dev || hipSetDevice(device) != hipSuccess) return GWI_ERR_INVALID;
   const long long n2 = n_doubles / 2;
-  double2 *a = nullptr, *b = nullptr, *c = nullptr;
-  double* out = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t st = nullptr;
-  gwi_status rc = GWI_ERR_HIP;
-  do {
-    if (hipMalloc(&a, sizeof(double2) * n2) != hipSuccess || hipMalloc(&b, sizeof(double2) * n2) != hipSuccess || hipMalloc(&c, sizeof(double2) * n2) != hipSuccess ||
-        hipMalloc(&out, 64 * sizeof(double)) != hipSuccess)
-      break;
-    if (hipStreamCreate(&st) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) break;
-    if (hipMemsetAsync(a, 0, sizeof(double2) * n2, st) != hipSuccess || hipMemsetAsync(b, 0, sizeof(double2) * n2, st) != hipSuccess ||
-        hipMemsetAsync(c, 0, sizeof(double2) * n2, st) != hipSuccess || hipMemsetAsync(out, 0, 64 * sizeof(double), st) != hipSuccess)
-      break;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) break;
-    const unsigned grid = (unsigned)prop.multiProcessorCount * 32u;
-    float best_r = 1e30f, best_t = 1e30f;
-    bool ok = true;
-    for (int it = 0; it < iters + 2 && ok; ++it) {  // two untimed warm-up rounds
-      float ms = 0.0f;
-      ok = ok && hipEventRecord(e0, st) == hipSuccess;
-      hipLaunchKernelGGL(bw_read_kernel, dim3(grid), dim3(kBlock), 0, st, (const double2*)b, n2, out, (int)grid);
-      ok = ok && hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-      if (it >= 2 && ms < best_r) best_r = ms;
-      ok = ok && hipEventRecord(e0, st) == hipSuccess;
-      hipLaunchKernelGGL(bw_triad_kernel, dim3(grid), dim3(kBlock), 0, st, a, (const double2*)b, (const double2*)c, 3.0, n2, (int)grid);
-      ok = ok && hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
-      if (it >= 2 && ms < best_t) best_t = ms;
-    }
-    if (!ok || hipGetLastError() != hipSuccess) break;
-    *read_gbs = 16.0 * (double)n2 / ((double)best_r * 1e-3) / 1e9;
-    *triad_gbs = 48.0 * (double)n2 / ((double)best_t * 1e-3) / 1e9;
-    rc = GWI_OK;
-  } while (false);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  (void)hipFree(a);
-  (void)hipFree(b);
-  (void)hipFree(c);
-  (void)hipFree(out);
-  return rc;
+  LaunchScratch sc("gwi_hbm_bandwidth");
+  double2 *a = sc.alloc<double2>((size_t)n2), *b = sc.alloc<double2>((size_t)n2), *c = sc.alloc<double2>((size_t)n2);
+  double* out = sc.alloc<double>(64);
+  if (!a || !b || !c || !out || !sc.open()) return GWI_ERR_HIP;
+  hipStream_t st = sc.stream;
+  hipEvent_t e0 = sc.e[0], e1 = sc.e[1];
+  if (hipMemsetAsync(a, 0, sizeof(double2) * n2, st) != hipSuccess || hipMemsetAsync(b, 0, sizeof(double2) * n2, st) != hipSuccess ||
+      hipMemsetAsync(c, 0, sizeof(double2) * n2, st) != hipSuccess || hipMemsetAsync(out, 0, 64 * sizeof(double), st) != hipSuccess)
+    return GWI_ERR_HIP;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return GWI_ERR_HIP;
+  const unsigned grid = (unsigned)prop.multiProcessorCount * 32u;
+  float best_r = 1e30f, best_t = 1e30f;
+  bool ok = true;
+  for (int it = 0; it < iters + 2 && ok; ++it) {  // two untimed warm-up rounds
+    float ms = 0.0f;
+    ok = ok && hipEventRecord(e0, st) == hipSuccess;
+    hipLaunchKernelGGL(bw_read_kernel, dim3(grid), dim3(kBlock), 0, st, (const double2*)b, n2, out, (int)grid);
+    ok = ok && hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+    if (it >= 2 && ms < best_r) best_r = ms;
+    ok = ok && hipEventRecord(e0, st) == hipSuccess;
+    hipLaunchKernelGGL(bw_triad_kernel, dim3(grid), dim3(kBlock), 0, st, a, (const double2*)b, (const double2*)c, 3.0, n2, (int)grid);
+    ok = ok && hipEventRecord(e1, st) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess;
+    if (it >= 2 && ms < best_t) best_t = ms;
+  }
+  if (!ok || hipGetLastError() != hipSuccess) return GWI_ERR_HIP;
+  *read_gbs = 16.0 * (double)n2 / ((double)best_r * 1e-3) / 1e9;
+  *triad_gbs = 48.0 * (double)n2 / ((double)best_t * 1e-3) / 1e9;
+  return GWI_OK;
 }
 
 const char* gwi_dispatch_info(gwi_handle h) {
@@ -3488,9 +3635,8 @@ gwi_status gwi_debug_stamps(gwi_handle h, unsigned long long* out, int64_t n_wor
 // The log-weight role of the engine's scan chain at theta: leaves log(p(theta|Lambda)/prior) of every sample in d_logw_pe /
 // d_logw_inj, without the sample-independent constant, which is returned in *log_const.  Blocking.
 static gwi_status fill_log_weights(gwi_handle h, const double* theta, double* log_const) {
-  const size_t n_pe_tot = (size_t)(h->n_ev * h->n_pe), n_inj = (size_t)h->n_inj;
-  if (!h->d_logw_pe) GWI_HIP(hipMalloc(&h->d_logw_pe, sizeof(double) * (n_pe_tot ? n_pe_tot : 1)));
-  if (!h->d_logw_inj) GWI_HIP(hipMalloc(&h->d_logw_inj, sizeof(double) * (n_inj ? n_inj : 1)));
+  GWI_HIP(h->post.d_logw_pe.reserve((size_t)(h->n_ev * h->n_pe)));
+  GWI_HIP(h->post.d_logw_inj.reserve((size_t)h->n_inj));
   // normaliser values come from a regular evaluation
   gwi_status st = run_pipeline(h, theta);
   if (st != GWI_OK) return st;
@@ -3499,8 +3645,8 @@ static gwi_status fill_log_weights(gwi_handle h, const double* theta, double* lo
   for (int t = 0; t < h->spec.n_terms; ++t)
     if (h->spec.terms[t].norm >= 0) c -= std::log(nrm[h->spec.terms[t].norm]);
   *log_const = c;
-  h->kargs.logw_pe = h->d_logw_pe;
-  h->kargs.logw_inj = h->d_logw_inj;
+  h->kargs.logw_pe = h->post.d_logw_pe;
+  h->kargs.logw_inj = h->post.d_logw_inj;
   set_geometry(h, false);
   st = launch_scan(h, true);
   if (st != GWI_OK) return st;
@@ -3519,94 +3665,132 @@ gwi_status gwi_log_weights(gwi_handle h, const double* theta, double* pe_logw, d
   st = fill_log_weights(h, theta, &log_const);
   if (st != GWI_OK) return st;
   if (pe_logw) {
-    GWI_HIP(hipMemcpy(pe_logw, h->d_logw_pe, sizeof(double) * n_pe_tot, hipMemcpyDeviceToHost));
+    GWI_HIP(hipMemcpy(pe_logw, h->post.d_logw_pe, sizeof(double) * n_pe_tot, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n_pe_tot; ++i) pe_logw[i] += log_const;
   }
   if (inj_logw) {
-    GWI_HIP(hipMemcpy(inj_logw, h->d_logw_inj, sizeof(double) * n_inj, hipMemcpyDeviceToHost));
+    GWI_HIP(hipMemcpy(inj_logw, h->post.d_logw_inj, sizeof(double) * n_inj, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n_inj; ++i) inj_logw[i] += log_const;
   }
   return GWI_OK;
 }
 
 // one mask of a set: uploaded over the previous one, or dropped (all ones) for NULL
-static gwi_status set_one_draw_mask(gwi_handle h, const unsigned char* src, size_t n, unsigned char** dst) {
+static gwi_status set_one_draw_mask(gwi_handle h, const unsigned char* src, size_t n, DeviceBuffer<unsigned char>* dst) {
   if (!src) {
-    (void)hipFree(*dst);
-    *dst = nullptr;
+    dst->reset();
     return GWI_OK;
   }
-  if (!*dst) GWI_HIP(hipMalloc(dst, n ? n : 1));
+  GWI_HIP(dst->reserve(n));
   if (n) GWI_HIP(hipMemcpy(*dst, src, n, hipMemcpyHostToDevice));
   return GWI_OK;
 }
 
+// (no scan kernel is needed and a shard may keep a mask: the refusals of post_preflight do not fit)
 gwi_status gwi_set_draw_mask(gwi_handle h, const unsigned char* pe_mask, const unsigned char* inj_mask) {
   if (!h) return GWI_ERR_INVALID;
   if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_set_draw_mask: host-only handle: no device to keep a mask on");
   gwi_status st = busy_guard(h, "gwi_set_draw_mask");
   if (st != GWI_OK) return st;
   GWI_HIP(hipSetDevice(h->device));
-  st = set_one_draw_mask(h, pe_mask, (size_t)(h->n_ev * h->n_pe), &h->d_draw_mask_pe);
+  st = set_one_draw_mask(h, pe_mask, (size_t)(h->n_ev * h->n_pe), &h->post.d_draw_mask_pe);
   if (st != GWI_OK) return st;
-  return set_one_draw_mask(h, inj_mask, (size_t)h->n_inj, &h->d_draw_mask_inj);
+  return set_one_draw_mask(h, inj_mask, (size_t)h->n_inj, &h->post.d_draw_mask_inj);
+}
+
+// The tile workspace of gwi_draw.h's first two kernels over the whole catalog, and the one place that knows its size and layout:
+// [max | sum | mass | prefix][n_tiles] (the PE tiles event-major, then the injection tiles), then the segments' maxima [n_ev + 1].
+// Refuses a catalog one launch cannot index ("<who>: more <what> (or samples per segment) ..."), selects the engine's device,
+// reserves the workspace and leaves *a zeroed but for the geometry, the masks and the carved pointers.
+static gwi_status draw_workspace(gwi_handle h, const char* who, const char* what, gwi::draw::DrawArgs* a, long long* n_tiles_out) {
+  namespace D = gwi::draw;
+  const long long tiles_per_event = D::tiles_of(h->n_pe), n_inj_tiles = D::tiles_of(h->n_inj), n_tiles = h->n_ev * tiles_per_event + n_inj_tiles;
+  if (n_tiles > 0x7fffffffLL || h->n_pe > 0x7fffffffLL || h->n_inj > 0x7fffffffLL)
+    return fail(h, GWI_ERR_INVALID, std::string(who) + ": more " + what + " (or samples per segment) than one launch can index");
+  GWI_HIP(hipSetDevice(h->device));
+  GWI_HIP(h->post.d_draw_tiles.reserve((size_t)(4 * n_tiles + h->n_ev + 1)));
+  std::memset(a, 0, sizeof(*a));
+  a->mask_pe = h->post.d_draw_mask_pe;
+  a->mask_inj = h->post.d_draw_mask_inj;
+  a->tile_max = h->post.d_draw_tiles;
+  a->tile_sum = a->tile_max + n_tiles;
+  a->tile_mass = a->tile_sum + n_tiles;
+  a->tile_prefix = a->tile_mass + n_tiles;
+  a->seg_max = a->tile_prefix + n_tiles;
+  a->n_pe = h->n_pe;
+  a->n_inj = h->n_inj;
+  a->n_ev = (int)h->n_ev;
+  a->tiles_per_event = (int)tiles_per_event;
+  a->n_inj_tiles = (int)n_inj_tiles;
+  *n_tiles_out = n_tiles;
+  return GWI_OK;
+}
+
+// ... and that of gwi_resample_injections, which runs the same two kernels over the injection set as the only segment (no events,
+// its tiles from 0) and keeps more per tile: [max | sum | mass | prefix | sum w^2][n_tiles], M, the stats record; beside it the
+// tiles' live counts and every injection's prefix within its tile.  n_inj is at least 1 and fits an int32 index.
+static gwi_status resample_workspace(gwi_handle h, gwi::draw::DrawArgs* da, gwi::resample::Args* a) {
+  namespace R = gwi::resample;
+  const long long n_inj = h->n_inj, n_tiles = gwi::draw::tiles_of(n_inj);
+  GWI_HIP(hipSetDevice(h->device));
+  GWI_HIP(h->post.d_rs_tiles.reserve((size_t)(5 * n_tiles + 1 + R::kStats)));
+  GWI_HIP(h->post.d_rs_live.reserve((size_t)n_tiles));
+  GWI_HIP(h->post.d_rs_prefix.reserve((size_t)n_inj));
+  std::memset(da, 0, sizeof(*da));
+  da->mask_inj = h->post.d_draw_mask_inj;
+  da->tile_max = h->post.d_rs_tiles;
+  da->tile_sum = da->tile_max + n_tiles;
+  da->tile_mass = da->tile_sum + n_tiles;
+  da->tile_prefix = da->tile_mass + n_tiles;
+  da->seg_max = da->tile_prefix + 2 * n_tiles;
+  da->n_inj = n_inj;
+  da->n_inj_tiles = (int)n_tiles;
+  da->tiles_per_event = 1;  // (no event has a tile: a divisor only)
+  std::memset(a, 0, sizeof(*a));
+  a->mask = da->mask_inj;
+  a->seg_max = da->seg_max;
+  a->tile_mass = da->tile_mass;
+  a->tile_prefix = da->tile_prefix;
+  a->sample_prefix = h->post.d_rs_prefix;
+  a->tile_sq = da->tile_prefix + n_tiles;
+  a->tile_live = h->post.d_rs_live;
+  a->stats = da->seg_max + 1;
+  a->n = n_inj;
+  a->n_tiles = (int)n_tiles;
+  return GWI_OK;
 }
 
 gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const double* u_pe, int32_t n_draw_pe, const double* u_inj, int32_t n_draw_inj,
                             int32_t* idx_pe, int32_t* idx_inj) {
   if (!h) return GWI_ERR_INVALID;
-  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: host-only handle: no device to draw on");
-  if (!h->variant) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: the engine has no scan kernel");
-  if (!thetas || k < 1) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: thetas is null or k < 1");
-  if (n_draw_pe < 0 || n_draw_inj < 0) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: a negative number of draws");
-  if (n_draw_pe > 0 && (!u_pe || !idx_pe)) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: n_draw_pe > 0 needs u_pe and idx_pe");
-  if (n_draw_inj > 0 && (!u_inj || !idx_inj)) return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: n_draw_inj > 0 needs u_inj and idx_inj");
-  if (h->comm_world > 1 || h->shm_world > 1)
-    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_draw_indices: this handle holds one shard of the catalog; injection draws need the global set");
-  gwi_status st = busy_guard(h, "gwi_draw_indices");
+  gwi_status st = post_preflight(h, "gwi_draw_indices", "draw on", "injection draws need", [&]() -> std::string {
+    if (!h->variant) return "the engine has no scan kernel";
+    if (!thetas || k < 1) return "thetas is null or k < 1";
+    if (n_draw_pe < 0 || n_draw_inj < 0) return "a negative number of draws";
+    if (n_draw_pe > 0 && (!u_pe || !idx_pe)) return "n_draw_pe > 0 needs u_pe and idx_pe";
+    if (n_draw_inj > 0 && (!u_inj || !idx_inj)) return "n_draw_inj > 0 needs u_inj and idx_inj";
+    return "";
+  });
   if (st != GWI_OK) return st;
   if (n_draw_pe == 0 && n_draw_inj == 0) return GWI_OK;
   namespace D = gwi::draw;
   const long long batches_pe = (n_draw_pe + D::kDrawBatch - 1) / D::kDrawBatch, batches_inj = (n_draw_inj + D::kDrawBatch - 1) / D::kDrawBatch;
-  const long long tiles_per_event = D::tiles_of(h->n_pe), n_inj_tiles = D::tiles_of(h->n_inj);
-  const long long n_tiles = h->n_ev * tiles_per_event + n_inj_tiles, select_blocks = h->n_ev * batches_pe + batches_inj;
+  const long long select_blocks = h->n_ev * batches_pe + batches_inj;
   const size_t per_point = (size_t)h->n_ev * (size_t)n_draw_pe + (size_t)n_draw_inj, total = per_point * (size_t)k;
-  if (n_tiles > 0x7fffffffLL || select_blocks > 0x7fffffffLL || h->n_pe > 0x7fffffffLL || h->n_inj > 0x7fffffffLL || total > (size_t)1 << 40)
+  if (select_blocks > 0x7fffffffLL || total > (size_t)1 << 40)
     return fail(h, GWI_ERR_INVALID, "gwi_draw_indices: more draws (or samples per segment) than one launch can index");
-  GWI_HIP(hipSetDevice(h->device));
-  if (!h->d_draw_tiles) GWI_HIP(hipMalloc(&h->d_draw_tiles, sizeof(double) * (size_t)(4 * n_tiles + h->n_ev + 1)));
-  if (h->draw_u_cap < total) {
-    (void)hipFree(h->d_draw_u);
-    h->d_draw_u = nullptr;
-    h->draw_u_cap = 0;
-    GWI_HIP(hipMalloc(&h->d_draw_u, sizeof(double) * total));
-    h->draw_u_cap = total;
-  }
-  if (h->draw_idx_cap < total) {
-    (void)hipFree(h->d_draw_idx);
-    h->d_draw_idx = nullptr;
-    h->draw_idx_cap = 0;
-    GWI_HIP(hipMalloc(&h->d_draw_idx, sizeof(int) * total));
-    h->draw_idx_cap = total;
-  }
+  D::DrawArgs a;
+  long long n_tiles = 0;
+  st = draw_workspace(h, "gwi_draw_indices", "draws", &a, &n_tiles);
+  if (st != GWI_OK) return st;
+  GWI_HIP(h->post.d_draw_u.reserve(total));
+  GWI_HIP(h->post.d_draw_idx.reserve(total));
+  double* const d_u = h->post.d_draw_u;
+  int* const d_idx = h->post.d_draw_idx;
   // uniforms: [k][n_ev][n_draw_pe], then [k][n_draw_inj]; the indices likewise
   const size_t pe_all = (size_t)k * (size_t)h->n_ev * (size_t)n_draw_pe, pe_point = (size_t)h->n_ev * (size_t)n_draw_pe;
-  if (pe_all) GWI_HIP(hipMemcpy(h->d_draw_u, u_pe, sizeof(double) * pe_all, hipMemcpyHostToDevice));
-  if (n_draw_inj) GWI_HIP(hipMemcpy(h->d_draw_u + pe_all, u_inj, sizeof(double) * (size_t)k * (size_t)n_draw_inj, hipMemcpyHostToDevice));
-  D::DrawArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.mask_pe = h->d_draw_mask_pe;
-  a.mask_inj = h->d_draw_mask_inj;
-  a.tile_max = h->d_draw_tiles;
-  a.tile_sum = a.tile_max + n_tiles;
-  a.tile_mass = a.tile_sum + n_tiles;
-  a.tile_prefix = a.tile_mass + n_tiles;
-  a.seg_max = a.tile_prefix + n_tiles;
-  a.n_pe = h->n_pe;
-  a.n_inj = h->n_inj;
-  a.n_ev = (int)h->n_ev;
-  a.tiles_per_event = (int)tiles_per_event;
-  a.n_inj_tiles = (int)n_inj_tiles;
+  if (pe_all) GWI_HIP(hipMemcpy(d_u, u_pe, sizeof(double) * pe_all, hipMemcpyHostToDevice));
+  if (n_draw_inj) GWI_HIP(hipMemcpy(d_u + pe_all, u_inj, sizeof(double) * (size_t)k * (size_t)n_draw_inj, hipMemcpyHostToDevice));
   a.n_draw_pe = n_draw_pe;
   a.n_draw_inj = n_draw_inj;
   a.batches_pe = (int)batches_pe;
@@ -3614,12 +3798,12 @@ gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const
   for (int p = 0; p < k; ++p) {  // one point after another: each needs its own normalisers and its own pass over the catalog
     st = fill_log_weights(h, thetas + (size_t)p * nt, &a.log_const);
     if (st != GWI_OK) return st;
-    a.logw_pe = h->d_logw_pe;
-    a.logw_inj = h->d_logw_inj;
-    a.u_pe = h->d_draw_u + (size_t)p * pe_point;
-    a.u_inj = h->d_draw_u + pe_all + (size_t)p * (size_t)n_draw_inj;
-    a.idx_pe = h->d_draw_idx + (size_t)p * pe_point;
-    a.idx_inj = h->d_draw_idx + pe_all + (size_t)p * (size_t)n_draw_inj;
+    a.logw_pe = h->post.d_logw_pe;
+    a.logw_inj = h->post.d_logw_inj;
+    a.u_pe = d_u + (size_t)p * pe_point;
+    a.u_inj = d_u + pe_all + (size_t)p * (size_t)n_draw_inj;
+    a.idx_pe = d_idx + (size_t)p * pe_point;
+    a.idx_inj = d_idx + pe_all + (size_t)p * (size_t)n_draw_inj;
     if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a);
     hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a);
     hipLaunchKernelGGL(D::draw_select_kernel, dim3((unsigned)select_blocks), dim3(D::kDrawBlock), 0, h->stream, a);
@@ -3627,26 +3811,14 @@ gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const
     // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
     GWI_HIP(hipStreamSynchronize(h->stream));
   }
-  if (pe_all) GWI_HIP(hipMemcpy(idx_pe, h->d_draw_idx, sizeof(int) * pe_all, hipMemcpyDeviceToHost));
-  if (n_draw_inj) GWI_HIP(hipMemcpy(idx_inj, h->d_draw_idx + pe_all, sizeof(int) * (size_t)k * (size_t)n_draw_inj, hipMemcpyDeviceToHost));
+  if (pe_all) GWI_HIP(hipMemcpy(idx_pe, d_idx, sizeof(int) * pe_all, hipMemcpyDeviceToHost));
+  if (n_draw_inj) GWI_HIP(hipMemcpy(idx_inj, d_idx + pe_all, sizeof(int) * (size_t)k * (size_t)n_draw_inj, hipMemcpyDeviceToHost));
   return GWI_OK;
 }
 
 // ---- injection resampling (gwi_resample.h) --------------------------------------------------------------------------------
-struct ResampleTimes {
-  double logw_ms = 0.0, prefix_ms = 0.0, select_ms = 0.0;
-  int launches = 0;
-};
-static thread_local ResampleTimes g_resample_times;
-
-// two events that go away with the scope
-struct ResampleEvents {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~ResampleEvents() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
+enum { kResampleLogw, kResamplePrefix, kResampleSelect };
+static thread_local StageTimes g_resample_times;
 
 constexpr long long kResampleDrawsPerLaunch = 1ll << 20;
 constexpr long long kResampleBlocksPerLaunch = 2048;  // the rest of a launch's draws by grid stride
@@ -3654,15 +3826,14 @@ constexpr long long kResampleBlocksPerLaunch = 2048;  // the rest of a launch's 
 gwi_status gwi_resample_injections(gwi_handle h, const double* theta, uint64_t seed, int64_t first_index, int64_t n_request, int64_t* n_draws, double* sums, int32_t* idx,
                                    double* logw_sel) {
   if (!h) return GWI_ERR_INVALID;
-  g_resample_times = ResampleTimes();
-  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: host-only handle: no device to draw on");
-  if (!h->variant) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: the engine has no scan kernel");
-  if (!theta || !n_draws || !sums) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: theta, n_draws or sums is null");
-  if (n_request != 0 && (!idx || !logw_sel)) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: draws are asked for: idx and logw_sel are needed");
-  if (first_index < 0) return fail(h, GWI_ERR_INVALID, "gwi_resample_injections: first_index < 0");
-  if (h->comm_world > 1 || h->shm_world > 1)
-    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_resample_injections: this handle holds one shard of the catalog; injection draws need the global set");
-  gwi_status st = busy_guard(h, "gwi_resample_injections");
+  g_resample_times = StageTimes();
+  gwi_status st = post_preflight(h, "gwi_resample_injections", "draw on", "injection draws need", [&]() -> std::string {
+    if (!h->variant) return "the engine has no scan kernel";
+    if (!theta || !n_draws || !sums) return "theta, n_draws or sums is null";
+    if (n_request != 0 && (!idx || !logw_sel)) return "draws are asked for: idx and logw_sel are needed";
+    if (first_index < 0) return "first_index < 0";
+    return "";
+  });
   if (st != GWI_OK) return st;
   namespace D = gwi::draw;
   namespace R = gwi::resample;
@@ -3672,61 +3843,32 @@ gwi_status gwi_resample_injections(gwi_handle h, const double* theta, uint64_t s
   sums[0] = sums[1] = -__builtin_inf();
   sums[2] = sums[3] = 0.0;
   if (n_inj == 0) return GWI_OK;
-  GWI_HIP(hipSetDevice(h->device));
-  // [max | sum | mass | prefix | sum w^2][n_tiles], M, the stats record
-  if (!h->d_rs_tiles) GWI_HIP(hipMalloc(&h->d_rs_tiles, sizeof(double) * (size_t)(5 * n_tiles + 1 + R::kStats)));
-  if (!h->d_rs_live) GWI_HIP(hipMalloc(&h->d_rs_live, sizeof(int) * (size_t)n_tiles));
-  if (!h->d_rs_prefix) GWI_HIP(hipMalloc(&h->d_rs_prefix, sizeof(double) * (size_t)n_inj));
-  ResampleEvents ev;
-  GWI_HIP(hipEventCreate(&ev.e0));
-  GWI_HIP(hipEventCreate(&ev.e1));
-  double log_const = 0.0;
-  const auto t0 = std::chrono::steady_clock::now();
-  st = fill_log_weights(h, theta, &log_const);  // (blocking)
-  if (st != GWI_OK) return st;
-  g_resample_times.logw_ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  // the injection set as the only segment of gwi_draw.h's first two kernels: no events, its tiles from 0
   D::DrawArgs da;
-  std::memset(&da, 0, sizeof(da));
-  da.logw_inj = h->d_logw_inj;
-  da.mask_inj = h->d_draw_mask_inj;
-  da.tile_max = h->d_rs_tiles;
-  da.tile_sum = da.tile_max + n_tiles;
-  da.tile_mass = da.tile_sum + n_tiles;
-  da.tile_prefix = da.tile_mass + n_tiles;
-  da.seg_max = da.tile_prefix + 2 * n_tiles;
-  da.log_const = log_const;
-  da.n_inj = n_inj;
-  da.n_inj_tiles = (int)n_tiles;
-  da.tiles_per_event = 1;  // (no event has a tile: a divisor only)
   R::Args a;
-  std::memset(&a, 0, sizeof(a));
-  a.lw = h->d_logw_inj;
-  a.mask = h->d_draw_mask_inj;
-  a.seg_max = da.seg_max;
-  a.tile_mass = da.tile_mass;
-  a.tile_prefix = da.tile_prefix;
-  a.sample_prefix = h->d_rs_prefix;
-  a.tile_sq = da.tile_prefix + n_tiles;
-  a.tile_live = h->d_rs_live;
-  a.stats = da.seg_max + 1;
-  a.log_const = log_const;
+  st = resample_workspace(h, &da, &a);
+  if (st != GWI_OK) return st;
+  LaunchScratch ev("gwi_resample_injections");
+  GWI_HIP(ev.events(2));
+  const auto t0 = std::chrono::steady_clock::now();
+  st = fill_log_weights(h, theta, &da.log_const);  // (blocking)
+  if (st != GWI_OK) return st;
+  g_resample_times.ms[kResampleLogw] = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  da.logw_inj = a.lw = h->post.d_logw_inj;
+  a.log_const = da.log_const;
   a.seed = (unsigned long long)seed;
-  a.n = n_inj;
-  a.n_tiles = (int)n_tiles;
   float ms = 0.f;
-  GWI_HIP(hipEventRecord(ev.e0, h->stream));
+  GWI_HIP(hipEventRecord(ev.e[0], h->stream));
   hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, da);
   hipLaunchKernelGGL(D::draw_merge_kernel, dim3(1), dim3(D::kDrawBlock), 0, h->stream, da);
   hipLaunchKernelGGL(R::resample_prefix_kernel, dim3((unsigned)n_tiles), dim3(R::kBlock), 0, h->stream, a);
   hipLaunchKernelGGL(R::resample_stats_kernel, dim3(1), dim3(R::kBlock), 0, h->stream, a);
   GWI_HIP(hipGetLastError());
-  GWI_HIP(hipEventRecord(ev.e1, h->stream));
+  GWI_HIP(hipEventRecord(ev.e[1], h->stream));
   double stats[R::kStats];
   GWI_HIP(hipMemcpyAsync(stats, a.stats, sizeof(stats), hipMemcpyDeviceToHost, h->stream));
   GWI_HIP(hipStreamSynchronize(h->stream));
-  GWI_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-  g_resample_times.prefix_ms = ms;
+  GWI_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  g_resample_times.ms[kResamplePrefix] = ms;
   const double q = stats[R::kStatQ], c_last = stats[R::kStatCLast], big = stats[R::kStatMax];
   if (!(c_last > 0.0) || !(q > 0.0) || stats[R::kStatLastTile] < 0.0) return GWI_OK;  // no live sample: nothing to draw
   sums[0] = big + std::log(c_last);
@@ -3735,18 +3877,10 @@ gwi_status gwi_resample_injections(gwi_handle h, const double* theta, uint64_t s
   sums[3] = stats[R::kStatLive];
   const long long n = n_request < 0 ? std::min<long long>((long long)std::floor(sums[2]), n_inj) : (long long)n_request;  // (n_eff <= the live samples <= n_inj)
   const size_t chunk = (size_t)std::min<long long>(n, kResampleDrawsPerLaunch);
-  if (h->rs_out_cap < chunk) {
-    (void)hipFree(h->d_rs_idx);
-    (void)hipFree(h->d_rs_lw);
-    h->d_rs_idx = nullptr;
-    h->d_rs_lw = nullptr;
-    h->rs_out_cap = 0;
-    GWI_HIP(hipMalloc(&h->d_rs_idx, sizeof(int) * chunk));
-    GWI_HIP(hipMalloc(&h->d_rs_lw, sizeof(double) * chunk));
-    h->rs_out_cap = chunk;
-  }
-  a.idx = h->d_rs_idx;
-  a.lw_sel = h->d_rs_lw;
+  GWI_HIP(h->post.d_rs_idx.reserve(chunk));
+  GWI_HIP(h->post.d_rs_lw.reserve(chunk));
+  a.idx = h->post.d_rs_idx;
+  a.lw_sel = h->post.d_rs_lw;
   // launches of at most 2^20 draws: a draw depends on (seed, first_index + d) only, so the cut changes nothing
   for (long long d0 = 0; d0 < n; d0 += kResampleDrawsPerLaunch) {
     const long long dc = std::min<long long>(kResampleDrawsPerLaunch, n - d0);
@@ -3754,61 +3888,36 @@ gwi_status gwi_resample_injections(gwi_handle h, const double* theta, uint64_t s
     a.first_index = (unsigned long long)first_index + (unsigned long long)d0;
     a.n_draws = dc;
     a.n_lanes = (int)(blocks * R::kBlock);
-    GWI_HIP(hipEventRecord(ev.e0, h->stream));
+    GWI_HIP(hipEventRecord(ev.e[0], h->stream));
     hipLaunchKernelGGL(R::resample_select_kernel, dim3((unsigned)blocks), dim3(R::kBlock), 0, h->stream, a);
     GWI_HIP(hipGetLastError());
-    GWI_HIP(hipEventRecord(ev.e1, h->stream));
-    GWI_HIP(hipMemcpyAsync(idx + d0, h->d_rs_idx, sizeof(int) * (size_t)dc, hipMemcpyDeviceToHost, h->stream));
-    GWI_HIP(hipMemcpyAsync(logw_sel + d0, h->d_rs_lw, sizeof(double) * (size_t)dc, hipMemcpyDeviceToHost, h->stream));
+    GWI_HIP(hipEventRecord(ev.e[1], h->stream));
+    GWI_HIP(hipMemcpyAsync(idx + d0, a.idx, sizeof(int) * (size_t)dc, hipMemcpyDeviceToHost, h->stream));
+    GWI_HIP(hipMemcpyAsync(logw_sel + d0, a.lw_sel, sizeof(double) * (size_t)dc, hipMemcpyDeviceToHost, h->stream));
     GWI_HIP(hipStreamSynchronize(h->stream));  // the launch's buffers are free again
-    GWI_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    g_resample_times.select_ms += ms;
+    GWI_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    g_resample_times.ms[kResampleSelect] += ms;
     ++g_resample_times.launches;
   }
   *n_draws = n;
   return GWI_OK;
 }
 
-void gwi_resample_times(double* logw_ms, double* prefix_ms, double* select_ms, int32_t* launches) {
-  if (logw_ms) *logw_ms = g_resample_times.logw_ms;
-  if (prefix_ms) *prefix_ms = g_resample_times.prefix_ms;
-  if (select_ms) *select_ms = g_resample_times.select_ms;
-  if (launches) *launches = g_resample_times.launches;
-}
+void gwi_resample_times(double* logw_ms, double* prefix_ms, double* select_ms, int32_t* launches) { g_resample_times.report(logw_ms, prefix_ms, select_ms, launches); }
 
 // ---- weighted histograms (gwi_hist.h) ---------------------------------------------------------------------------------------
-struct HistogramTimes {
-  double logw_ms = 0.0, tile_ms = 0.0, merge_ms = 0.0;
-  int launches = 0;
-};
-static thread_local HistogramTimes g_histogram_times;
-
-// the bins go away: gwi_weighted_histograms refuses until they are set again
-static void drop_histogram_bins(gwi_handle h) {
-  (void)hipFree(h->d_hist_bins_pe);
-  (void)hipFree(h->d_hist_bins_inj);
-  (void)hipFree(h->d_hist_partial);
-  (void)hipFree(h->d_hist);
-  (void)hipFree(h->d_hist_dead);
-  h->d_hist_bins_pe = h->d_hist_bins_inj = nullptr;
-  h->d_hist_partial = h->d_hist = nullptr;
-  h->d_hist_dead = nullptr;
-  h->hist_cols = h->hist_bins = 0;
-}
+enum { kHistLogw, kHistTile, kHistMerge };
+static thread_local StageTimes g_histogram_times;
 
 gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, const uint16_t* pe_bins, const uint16_t* inj_bins) {
   if (!h) return GWI_ERR_INVALID;
-  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: host-only handle: no device to keep the bins on");
-  namespace D = gwi::draw;
   namespace H = gwi::hist;
-  if (n_cols < 1 || n_cols > H::kMaxCols)
-    return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: n_cols = " + std::to_string(n_cols) + " is not in 1 ... " + std::to_string(H::kMaxCols));
-  if (n_bins < 1 || n_bins > H::kMaxBins)
-    return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: n_bins = " + std::to_string(n_bins) + " is not in 1 ... " + std::to_string(H::kMaxBins));
-  if (!pe_bins && !inj_bins) return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: pe_bins and inj_bins are both null");
-  if (h->comm_world > 1 || h->shm_world > 1)
-    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_set_histogram_bins: this handle holds one shard of the catalog; the injection histogram needs the global set");
-  gwi_status st = busy_guard(h, "gwi_set_histogram_bins");
+  gwi_status st = post_preflight(h, "gwi_set_histogram_bins", "keep the bins on", "the injection histogram needs", [&]() -> std::string {
+    if (n_cols < 1 || n_cols > H::kMaxCols) return "n_cols = " + std::to_string(n_cols) + " is not in 1 ... " + std::to_string(H::kMaxCols);
+    if (n_bins < 1 || n_bins > H::kMaxBins) return "n_bins = " + std::to_string(n_bins) + " is not in 1 ... " + std::to_string(H::kMaxBins);
+    if (!pe_bins && !inj_bins) return "pe_bins and inj_bins are both null";
+    return "";
+  });
   if (st != GWI_OK) return st;
   const size_t n_pe_codes = pe_bins ? (size_t)n_cols * (size_t)(h->n_ev * h->n_pe) : 0, n_inj_codes = inj_bins ? (size_t)n_cols * (size_t)h->n_inj : 0;
   for (int set = 0; set < 2; ++set) {
@@ -3819,94 +3928,79 @@ gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, 
         return fail(h, GWI_ERR_INVALID, std::string("gwi_set_histogram_bins: ") + (set ? "inj_bins" : "pe_bins") + " entry " + std::to_string(i) + " is " + std::to_string(codes[i]) +
                                             ": neither a bin below n_bins = " + std::to_string(n_bins) + " nor 0xFFFF (outside every bin)");
   }
-  const long long tiles_per_event = D::tiles_of(h->n_pe), n_inj_tiles = D::tiles_of(h->n_inj), n_tiles = h->n_ev * tiles_per_event + n_inj_tiles;
-  if (n_tiles > 0x7fffffffLL || h->n_pe > 0x7fffffffLL || h->n_inj > 0x7fffffffLL) return fail(h, GWI_ERR_INVALID, "gwi_set_histogram_bins: more tiles (or samples per segment) than one launch can index");
-  GWI_HIP(hipSetDevice(h->device));
-  drop_histogram_bins(h);
+  gwi::draw::DrawArgs geometry;
+  long long n_tiles = 0;
+  st = draw_workspace(h, "gwi_set_histogram_bins", "tiles", &geometry, &n_tiles);
+  if (st != GWI_OK) return st;
+  // the previous bins go away first: should an allocation fail, gwi_weighted_histograms refuses until they are set again
+  PostprocessBuffers::Histogram& hist = h->post.hist;
+  hist = PostprocessBuffers::Histogram();
   const size_t per_seg = (size_t)n_cols * (size_t)n_bins;
   if (n_pe_codes) {
-    GWI_HIP(hipMalloc(&h->d_hist_bins_pe, sizeof(uint16_t) * n_pe_codes));
-    GWI_HIP(hipMemcpy(h->d_hist_bins_pe, pe_bins, sizeof(uint16_t) * n_pe_codes, hipMemcpyHostToDevice));
+    GWI_HIP(hist.d_bins_pe.reserve(n_pe_codes));
+    GWI_HIP(hipMemcpy(hist.d_bins_pe, pe_bins, sizeof(uint16_t) * n_pe_codes, hipMemcpyHostToDevice));
   }
   if (n_inj_codes) {
-    GWI_HIP(hipMalloc(&h->d_hist_bins_inj, sizeof(uint16_t) * n_inj_codes));
-    GWI_HIP(hipMemcpy(h->d_hist_bins_inj, inj_bins, sizeof(uint16_t) * n_inj_codes, hipMemcpyHostToDevice));
+    GWI_HIP(hist.d_bins_inj.reserve(n_inj_codes));
+    GWI_HIP(hipMemcpy(hist.d_bins_inj, inj_bins, sizeof(uint16_t) * n_inj_codes, hipMemcpyHostToDevice));
   }
-  GWI_HIP(hipMalloc(&h->d_hist_partial, sizeof(double) * std::max<size_t>((size_t)n_tiles * per_seg, 1)));
-  GWI_HIP(hipMalloc(&h->d_hist, sizeof(double) * (size_t)(h->n_ev + 1) * per_seg));
-  GWI_HIP(hipMalloc(&h->d_hist_dead, sizeof(int) * (size_t)(h->n_ev + 1)));
-  if (!h->d_draw_tiles) GWI_HIP(hipMalloc(&h->d_draw_tiles, sizeof(double) * (size_t)(4 * n_tiles + h->n_ev + 1)));  // (gwi_draw_indices' own)
-  h->hist_cols = n_cols;
-  h->hist_bins = n_bins;
+  GWI_HIP(hist.d_partial.reserve((size_t)n_tiles * per_seg));
+  GWI_HIP(hist.d_sums.reserve((size_t)(h->n_ev + 1) * per_seg));
+  GWI_HIP(hist.d_dead.reserve((size_t)(h->n_ev + 1)));
+  hist.cols = n_cols;
+  hist.bins = n_bins;
   return GWI_OK;
 }
 
 gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k, double* hist_pe, double* hist_inj, int32_t* dead) {
   if (!h) return GWI_ERR_INVALID;
-  g_histogram_times = HistogramTimes();
-  if (h->host_only) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: host-only handle: no device to sum on");
-  if (!h->variant) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: the engine has no scan kernel");
-  if (!h->hist_cols) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: no bins are set (gwi_set_histogram_bins)");
-  if (!thetas || k < 1) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: thetas is null or k < 1");
-  const bool with_pe = h->d_hist_bins_pe != nullptr, with_inj = h->d_hist_bins_inj != nullptr;
-  if (with_pe && !hist_pe) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: pe_bins are set: hist_pe is needed");
-  if (with_inj && !hist_inj) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: inj_bins are set: hist_inj is needed");
-  if (!dead) return fail(h, GWI_ERR_INVALID, "gwi_weighted_histograms: dead is null");
-  if (h->comm_world > 1 || h->shm_world > 1)
-    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_weighted_histograms: this handle holds one shard of the catalog; the injection histogram needs the global set");
-  gwi_status st = busy_guard(h, "gwi_weighted_histograms");
+  g_histogram_times = StageTimes();
+  const PostprocessBuffers::Histogram& hist = h->post.hist;
+  const bool with_pe = hist.d_bins_pe.ptr != nullptr, with_inj = hist.d_bins_inj.ptr != nullptr;
+  gwi_status st = post_preflight(h, "gwi_weighted_histograms", "sum on", "the injection histogram needs", [&]() -> std::string {
+    if (!h->variant) return "the engine has no scan kernel";
+    if (!hist.cols) return "no bins are set (gwi_set_histogram_bins)";
+    if (!thetas || k < 1) return "thetas is null or k < 1";
+    if (with_pe && !hist_pe) return "pe_bins are set: hist_pe is needed";
+    if (with_inj && !hist_inj) return "inj_bins are set: hist_inj is needed";
+    if (!dead) return "dead is null";
+    return "";
+  });
   if (st != GWI_OK) return st;
   namespace D = gwi::draw;
   namespace H = gwi::hist;
-  const long long tiles_per_event = D::tiles_of(h->n_pe), n_inj_tiles = D::tiles_of(h->n_inj);
-  const long long n_pe_tiles = h->n_ev * tiles_per_event, n_tiles = n_pe_tiles + n_inj_tiles;
-  const size_t per_seg = (size_t)h->hist_cols * (size_t)h->hist_bins, n_pe_out = (size_t)h->n_ev * per_seg;
-  GWI_HIP(hipSetDevice(h->device));
-  // the caller's running sums: the points of this call are added onto them, so a request may be split over calls
-  if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(h->d_hist, hist_pe, sizeof(double) * n_pe_out, hipMemcpyHostToDevice));
-  if (with_inj) GWI_HIP(hipMemcpy(h->d_hist + n_pe_out, hist_inj, sizeof(double) * per_seg, hipMemcpyHostToDevice));
-  GWI_HIP(hipMemcpy(h->d_hist_dead, dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyHostToDevice));
   H::Args a;
   std::memset(&a, 0, sizeof(a));
-  a.d.mask_pe = h->d_draw_mask_pe;
-  a.d.mask_inj = h->d_draw_mask_inj;
-  a.d.tile_max = h->d_draw_tiles;
-  a.d.tile_sum = a.d.tile_max + n_tiles;
-  a.d.tile_mass = a.d.tile_sum + n_tiles;
-  a.d.tile_prefix = a.d.tile_mass + n_tiles;
-  a.d.seg_max = a.d.tile_prefix + n_tiles;
-  a.d.n_pe = h->n_pe;
-  a.d.n_inj = h->n_inj;
-  a.d.n_ev = (int)h->n_ev;
-  a.d.tiles_per_event = (int)tiles_per_event;
-  a.d.n_inj_tiles = (int)n_inj_tiles;
-  a.bins_pe = h->d_hist_bins_pe;
-  a.bins_inj = h->d_hist_bins_inj;
-  a.partial = h->d_hist_partial;
-  a.hist = h->d_hist;
-  a.n_dead = h->d_hist_dead;
-  a.n_cols = h->hist_cols;
-  a.n_bins = h->hist_bins;
+  long long n_tiles = 0;
+  st = draw_workspace(h, "gwi_weighted_histograms", "tiles", &a.d, &n_tiles);  // (as gwi_set_histogram_bins found it)
+  if (st != GWI_OK) return st;
+  const long long n_pe_tiles = h->n_ev * a.d.tiles_per_event;
+  const size_t per_seg = (size_t)hist.cols * (size_t)hist.bins, n_pe_out = (size_t)h->n_ev * per_seg;
+  // the caller's running sums: the points of this call are added onto them, so a request may be split over calls
+  if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(hist.d_sums, hist_pe, sizeof(double) * n_pe_out, hipMemcpyHostToDevice));
+  if (with_inj) GWI_HIP(hipMemcpy(hist.d_sums + n_pe_out, hist_inj, sizeof(double) * per_seg, hipMemcpyHostToDevice));
+  GWI_HIP(hipMemcpy(hist.d_dead, dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyHostToDevice));
+  a.bins_pe = hist.d_bins_pe;
+  a.bins_inj = hist.d_bins_inj;
+  a.partial = hist.d_partial;
+  a.hist = hist.d_sums;
+  a.n_dead = hist.d_dead;
+  a.n_cols = hist.cols;
+  a.n_bins = hist.bins;
   // a set without bins is left out of the two new launches: PE tiles and segments come first, the injection set's last
   a.first_tile = with_pe ? 0 : (int)n_pe_tiles;
   a.first_seg = with_pe ? 0 : (int)h->n_ev;
-  const long long hist_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? n_inj_tiles : 0), hist_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
-  struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    ~Events() {
-      for (hipEvent_t v : e)
-        if (v) (void)hipEventDestroy(v);
-    }
-  } ev;
-  for (hipEvent_t& v : ev.e) GWI_HIP(hipEventCreate(&v));
+  const long long hist_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? a.d.n_inj_tiles : 0), hist_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
+  LaunchScratch ev("gwi_weighted_histograms");
+  GWI_HIP(ev.events(3));
   const int nt = h->spec.n_theta;
   for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
     const auto t0 = std::chrono::steady_clock::now();
     st = fill_log_weights(h, thetas + (size_t)p * nt, &a.d.log_const);  // (blocking)
     if (st != GWI_OK) return st;
-    g_histogram_times.logw_ms += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    a.d.logw_pe = h->d_logw_pe;
-    a.d.logw_inj = h->d_logw_inj;
+    g_histogram_times.ms[kHistLogw] += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    a.d.logw_pe = h->post.d_logw_pe;
+    a.d.logw_inj = h->post.d_logw_inj;
     GWI_HIP(hipEventRecord(ev.e[0], h->stream));
     if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a.d);
     hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.d);
@@ -3920,100 +4014,39 @@ gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k
     float tile_ms = 0.f, merge_ms = 0.f;
     GWI_HIP(hipEventElapsedTime(&tile_ms, ev.e[0], ev.e[1]));
     GWI_HIP(hipEventElapsedTime(&merge_ms, ev.e[1], ev.e[2]));
-    g_histogram_times.tile_ms += tile_ms;
-    g_histogram_times.merge_ms += merge_ms;
+    g_histogram_times.ms[kHistTile] += tile_ms;
+    g_histogram_times.ms[kHistMerge] += merge_ms;
     g_histogram_times.launches += 4;
   }
-  if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(hist_pe, h->d_hist, sizeof(double) * n_pe_out, hipMemcpyDeviceToHost));
-  if (with_inj) GWI_HIP(hipMemcpy(hist_inj, h->d_hist + n_pe_out, sizeof(double) * per_seg, hipMemcpyDeviceToHost));
-  GWI_HIP(hipMemcpy(dead, h->d_hist_dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyDeviceToHost));
+  if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(hist_pe, hist.d_sums, sizeof(double) * n_pe_out, hipMemcpyDeviceToHost));
+  if (with_inj) GWI_HIP(hipMemcpy(hist_inj, hist.d_sums + n_pe_out, sizeof(double) * per_seg, hipMemcpyDeviceToHost));
+  GWI_HIP(hipMemcpy(dead, hist.d_dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyDeviceToHost));
   return GWI_OK;
 }
 
-void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) {
-  if (logw_ms) *logw_ms = g_histogram_times.logw_ms;
-  if (tile_ms) *tile_ms = g_histogram_times.tile_ms;
-  if (merge_ms) *merge_ms = g_histogram_times.merge_ms;
-  if (launches) *launches = g_histogram_times.launches;
-}
+void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) { g_histogram_times.report(logw_ms, tile_ms, merge_ms, launches); }
 
 }  // extern "C"
 
-// ---- effective-spin catalogs (gwi_spinprior.h): stand-alone entries, no handle, like gwi_ingest_columns ------------------
+// ---- effective-spin catalogs (gwi_spinprior.h): stand-alone entries, no handle ----------------------------------------------
 namespace {
-
-struct SpinTimes {
-  double total_ms = 0.0, max_launch_ms = 0.0;
-  int launches = 0;
-};
-thread_local SpinTimes g_spin_times;
-
-// device buffers, a stream and two events that go away with the scope
-struct SpinScratch {
-  std::vector<void*> bufs;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~SpinScratch() {
-    for (void* b : bufs) (void)hipFree(b);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  template <class T>
-  T* alloc(size_t n) {
-    void* p = nullptr;
-    if (hipMalloc(&p, sizeof(T) * (n ? n : 1)) != hipSuccess) return nullptr;
-    bufs.push_back(p);
-    return (T*)p;
-  }
-  bool open() { return hipStreamCreate(&stream) == hipSuccess && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess; }
-};
-
-// puts the calling thread back on the device it was on when the scope ends
-struct SpinDeviceGuard {
-  int previous = -1;
-  ~SpinDeviceGuard() {
-    if (previous >= 0) (void)hipSetDevice(previous);
-  }
-};
-
-gwi_status spin_device(int32_t device, SpinDeviceGuard* guard) {
-  int n_dev = 0, current = -1;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return GWI_ERR_NO_DEVICE;
-  if (device >= n_dev) return GWI_ERR_NO_DEVICE;
-  if (device < 0) return GWI_OK;
-  if (hipGetDevice(&current) != hipSuccess) return GWI_ERR_HIP;
-  if (current == device) return GWI_OK;
-  if (hipSetDevice(device) != hipSuccess) return GWI_ERR_HIP;
-  guard->previous = current;
-  return GWI_OK;
-}
-
-#define GWI_SPIN_HIP(call)                                                                  \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      std::fprintf(stderr, "%s: %s: %s\n", kWhere, #call, hipGetErrorString(e_));           \
-      return GWI_ERR_HIP;                                                                   \
-    }                                                                                       \
-  } while (0)
-
+enum { kSpinTotal, kSpinMaxLaunch };
+thread_local StageTimes g_spin_times;
 }  // namespace
 
 extern "C" {
 
 gwi_status gwi_effective_spins(int64_t n, const double* q, const double* a1, const double* a2, const double* ct1, const double* ct2, double a_max, double* chi_eff,
                                double* chi_p, double* p_chi_eff_iso, double* p_chi_eff_aligned, double* p_chi_p_iso, int32_t device) {
-  static const char* kWhere = "gwi_effective_spins";
   namespace S = gwi::spinprior;
   if (n < 0 || !(a_max > 0.0) || !(a_max < __builtin_inf())) return GWI_ERR_INVALID;
   if (n > 0 && (!q || !a1 || !a2 || !ct1 || !ct2)) return GWI_ERR_INVALID;
-  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
-  gwi_status st = spin_device(device, &guard);
+  DeviceScope scope;
+  gwi_status st = scope.select(device);
   if (st != GWI_OK) return st;
-  g_spin_times = SpinTimes();
+  g_spin_times = StageTimes();
   if (n == 0) return GWI_OK;
-  SpinScratch sc;
+  LaunchScratch sc("gwi_effective_spins");
   if (!sc.open()) return GWI_ERR_HIP;
   const size_t bytes = sizeof(double) * (size_t)n;
   const double* in[5] = {q, a1, a2, ct1, ct2};
@@ -4023,36 +4056,35 @@ gwi_status gwi_effective_spins(int64_t n, const double* q, const double* a1, con
     d_in[c] = sc.alloc<double>((size_t)n);
     d_out[c] = out[c] ? sc.alloc<double>((size_t)n) : nullptr;
     if (!d_in[c] || (out[c] && !d_out[c])) return GWI_ERR_HIP;
-    GWI_SPIN_HIP(hipMemcpyAsync(d_in[c], in[c], bytes, hipMemcpyHostToDevice, sc.stream));
+    GWI_SCRATCH_HIP(hipMemcpyAsync(d_in[c], in[c], bytes, hipMemcpyHostToDevice, sc.stream));
   }
   const long long blocks = std::min<long long>((n + S::kBlock - 1) / S::kBlock, 2048);
   S::SpinArgs a{d_in[0], d_in[1], d_in[2], d_in[3], d_in[4], d_out[0], d_out[1], d_out[2], d_out[3], d_out[4], a_max, (long long)n, blocks * S::kBlock};
-  GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
-  hipLaunchKernelGGL(S::effective_spins_kernel, dim3((unsigned)blocks), dim3(S::kBlock), 0, sc.stream, a);
-  GWI_SPIN_HIP(hipGetLastError());
-  GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
-  for (int c = 0; c < 5; ++c)
-    if (out[c]) GWI_SPIN_HIP(hipMemcpyAsync(out[c], d_out[c], bytes, hipMemcpyDeviceToHost, sc.stream));
-  GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));
   float ms = 0.f;
-  GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
-  g_spin_times.total_ms = g_spin_times.max_launch_ms = ms;
+  st = sc.timed([&] { hipLaunchKernelGGL(S::effective_spins_kernel, dim3((unsigned)blocks), dim3(S::kBlock), 0, sc.stream, a); },
+                [&] {
+                  for (int c = 0; c < 5; ++c)
+                    if (out[c]) GWI_SCRATCH_HIP(hipMemcpyAsync(out[c], d_out[c], bytes, hipMemcpyDeviceToHost, sc.stream));
+                  return GWI_OK;
+                },
+                &ms);
+  if (st != GWI_OK) return st;
+  g_spin_times.ms[kSpinTotal] = g_spin_times.ms[kSpinMaxLaunch] = ms;
   g_spin_times.launches = 1;
   return GWI_OK;
 }
 
 gwi_status gwi_chi_p_conditional_prior(int64_t n, const double* chi_p, const double* chi_eff, const double* q, double a_max, int32_t n_draws, int32_t max_attempts,
                                        uint64_t seed, int64_t first_index, double* p, int32_t* accepted, int32_t device) {
-  static const char* kWhere = "gwi_chi_p_conditional_prior";
   namespace S = gwi::spinprior;
   if (n < 0 || n_draws < 2 || max_attempts < 1 || max_attempts > (1 << 16) || first_index < 0 || !(a_max > 0.0) || !(a_max < __builtin_inf())) return GWI_ERR_INVALID;
   if (n > 0 && (!chi_p || !chi_eff || !q || !p || !accepted)) return GWI_ERR_INVALID;
-  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
-  gwi_status st = spin_device(device, &guard);
+  DeviceScope scope;
+  gwi_status st = scope.select(device);
   if (st != GWI_OK) return st;
-  g_spin_times = SpinTimes();
+  g_spin_times = StageTimes();
   if (n == 0) return GWI_OK;
-  SpinScratch sc;
+  LaunchScratch sc("gwi_chi_p_conditional_prior");
   if (!sc.open()) return GWI_ERR_HIP;
   const size_t bytes = sizeof(double) * (size_t)n;
   const double* in[3] = {chi_p, chi_eff, q};
@@ -4060,7 +4092,7 @@ gwi_status gwi_chi_p_conditional_prior(int64_t n, const double* chi_p, const dou
   for (int c = 0; c < 3; ++c) {
     d_in[c] = sc.alloc<double>((size_t)n);
     if (!d_in[c]) return GWI_ERR_HIP;
-    GWI_SPIN_HIP(hipMemcpyAsync(d_in[c], in[c], bytes, hipMemcpyHostToDevice, sc.stream));
+    GWI_SCRATCH_HIP(hipMemcpyAsync(d_in[c], in[c], bytes, hipMemcpyHostToDevice, sc.stream));
   }
   double* d_p = sc.alloc<double>((size_t)n);
   int* d_acc = sc.alloc<int>((size_t)n);
@@ -4075,45 +4107,29 @@ gwi_status gwi_chi_p_conditional_prior(int64_t n, const double* chi_p, const dou
   for (long long base = 0; base < n; base += per_launch) {
     const long long m = std::min<long long>(per_launch, n - base);
     S::CondArgs a{d_in[0] + base, d_in[1] + base, d_in[2] + base, d_p + base, d_acc + base, a_max, (unsigned long long)seed, (long long)first_index + base, n_draws, max_attempts};
-    GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
-    hipLaunchKernelGGL(S::chi_p_conditional_kernel, dim3((unsigned)m), dim3(S::kBlock), 0, sc.stream, a);
-    GWI_SPIN_HIP(hipGetLastError());
-    GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
-    GWI_SPIN_HIP(hipEventSynchronize(sc.e1));
     float ms = 0.f;
-    GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
-    g_spin_times.total_ms += ms;
-    g_spin_times.max_launch_ms = std::max<double>(g_spin_times.max_launch_ms, ms);
+    st = sc.timed([&] { hipLaunchKernelGGL(S::chi_p_conditional_kernel, dim3((unsigned)m), dim3(S::kBlock), 0, sc.stream, a); }, &ms);
+    if (st != GWI_OK) return st;
+    g_spin_times.ms[kSpinTotal] += ms;
+    g_spin_times.ms[kSpinMaxLaunch] = std::max<double>(g_spin_times.ms[kSpinMaxLaunch], ms);
     ++g_spin_times.launches;
   }
-  GWI_SPIN_HIP(hipMemcpyAsync(p, d_p, bytes, hipMemcpyDeviceToHost, sc.stream));
-  GWI_SPIN_HIP(hipMemcpyAsync(accepted, d_acc, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, sc.stream));
-  GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(p, d_p, bytes, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(accepted, d_acc, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipStreamSynchronize(sc.stream));
   return GWI_OK;
 }
 
-void gwi_spin_prior_times(double* total_ms, double* max_launch_ms, int32_t* launches) {
-  if (total_ms) *total_ms = g_spin_times.total_ms;
-  if (max_launch_ms) *max_launch_ms = g_spin_times.max_launch_ms;
-  if (launches) *launches = g_spin_times.launches;
-}
+void gwi_spin_prior_times(double* total_ms, double* max_launch_ms, int32_t* launches) { g_spin_times.report(total_ms, max_launch_ms, nullptr, launches); }
 
 }  // extern "C"
 
-// ---- population draws (gwi_popdraw.h): a stand-alone entry, no handle, like gwi_effective_spins ---------------------------
+// ---- population draws (gwi_popdraw.h): a stand-alone entry, no handle -------------------------------------------------------
 namespace {
 
-struct PopdrawTimes {
-  double cdf_ms = 0.0, draw_ms = 0.0;
-  int launches = 0;
-};
-thread_local PopdrawTimes g_popdraw_times;
-thread_local std::string g_popdraw_error;
-
-gwi_status popdraw_refuse(const std::string& why) {
-  g_popdraw_error = why;
-  return GWI_ERR_INVALID;
-}
+enum { kPopdrawCdf, kPopdrawDraw };
+thread_local StageTimes g_popdraw_times;
+thread_local ErrorSlot g_popdraw_error;
 
 constexpr long long kPopdrawDrawsPerLaunch = 1ll << 20;    // per table
 constexpr long long kPopdrawThreadsPerLaunch = 1ll << 26;  // over the tables of a launch
@@ -4124,32 +4140,32 @@ extern "C" {
 
 gwi_status gwi_table_draws(int32_t device, int32_t n_tables, int32_t n_grid, const double* lo, const double* hi, const double* pdf, int64_t n_draws, uint64_t seed,
                            uint64_t first_index, const double* lower, double* x, double* mass, unsigned char* accept) {
-  static const char* kWhere = "gwi_table_draws";
   namespace P = gwi::popdraw;
-  g_popdraw_error.clear();
-  g_popdraw_times = PopdrawTimes();
+  ErrorSlot& err = g_popdraw_error;
+  err.text.clear();
+  g_popdraw_times = StageTimes();
   // ---- the argument checks: on the host, before anything is uploaded
-  if (n_tables < 0 || n_draws < 0) return popdraw_refuse("negative n_tables or n_draws");
-  if (n_grid < 2) return popdraw_refuse("table 0: n_grid = " + std::to_string(n_grid) + " < 2 (a table has at least one cell)");
-  if (n_grid > P::kMaxGrid) return popdraw_refuse("table 0: n_grid = " + std::to_string(n_grid) + " > " + std::to_string(P::kMaxGrid) + " (a table is staged in LDS)");
-  if (n_tables > 0 && (!lo || !hi || !pdf)) return popdraw_refuse("null lo, hi or pdf");
-  if (n_tables > 0 && n_draws > 0 && !x) return popdraw_refuse("null x");
+  if (n_tables < 0 || n_draws < 0) return err.refuse("negative n_tables or n_draws");
+  if (n_grid < 2) return err.refuse("table 0: n_grid = " + std::to_string(n_grid) + " < 2 (a table has at least one cell)");
+  if (n_grid > P::kMaxGrid) return err.refuse("table 0: n_grid = " + std::to_string(n_grid) + " > " + std::to_string(P::kMaxGrid) + " (a table is staged in LDS)");
+  if (n_tables > 0 && (!lo || !hi || !pdf)) return err.refuse("null lo, hi or pdf");
+  if (n_tables > 0 && n_draws > 0 && !x) return err.refuse("null x");
   for (int32_t t = 0; t < n_tables; ++t) {
     const double width = hi[t] - lo[t];
-    if (!(hi[t] > lo[t]) || !(width < __builtin_inf())) return popdraw_refuse("table " + std::to_string(t) + ": hi <= lo (or a bound that is not finite)");
+    if (!(hi[t] > lo[t]) || !(width < __builtin_inf())) return err.refuse("table " + std::to_string(t) + ": hi <= lo (or a bound that is not finite)");
     const double* p = pdf + (size_t)t * (size_t)n_grid;
     for (int32_t i = 0; i < n_grid; ++i)
-      if (!(p[i] >= 0.0) || !(p[i] < __builtin_inf())) return popdraw_refuse("table " + std::to_string(t) + ": density entry " + std::to_string(i) + " is negative or not finite");
+      if (!(p[i] >= 0.0) || !(p[i] < __builtin_inf())) return err.refuse("table " + std::to_string(t) + ": density entry " + std::to_string(i) + " is negative or not finite");
     const double dx = width / (double)(n_grid - 1);
     bool live = false;
     for (int32_t i = 0; i + 1 < n_grid && !live; ++i) live = 0.5 * (p[i] + p[i + 1]) * dx > 0.0;  // the kernel's cell mass
-    if (!live) return popdraw_refuse("table " + std::to_string(t) + ": the total mass is 0");
+    if (!live) return err.refuse("table " + std::to_string(t) + ": the total mass is 0");
   }
-  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
-  gwi_status st = spin_device(device, &guard);
+  DeviceScope scope;
+  gwi_status st = scope.select(device);
   if (st != GWI_OK) return st;
   if (n_tables == 0 || n_draws == 0) return GWI_OK;
-  SpinScratch sc;
+  LaunchScratch sc("gwi_table_draws");
   if (!sc.open()) return GWI_ERR_HIP;
   const size_t n_cell = (size_t)n_grid - 1;
   double* d_pdf = sc.alloc<double>((size_t)n_tables * (size_t)n_grid);
@@ -4158,25 +4174,20 @@ gwi_status gwi_table_draws(int32_t device, int32_t n_tables, int32_t n_grid, con
   double* d_prefix = sc.alloc<double>((size_t)n_tables * n_cell);
   int* d_last = sc.alloc<int>((size_t)n_tables);
   if (!d_pdf || !d_lo || !d_hi || !d_prefix || !d_last) return GWI_ERR_HIP;
-  GWI_SPIN_HIP(hipMemcpyAsync(d_pdf, pdf, sizeof(double) * (size_t)n_tables * (size_t)n_grid, hipMemcpyHostToDevice, sc.stream));
-  GWI_SPIN_HIP(hipMemcpyAsync(d_lo, lo, sizeof(double) * (size_t)n_tables, hipMemcpyHostToDevice, sc.stream));
-  GWI_SPIN_HIP(hipMemcpyAsync(d_hi, hi, sizeof(double) * (size_t)n_tables, hipMemcpyHostToDevice, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_pdf, pdf, sizeof(double) * (size_t)n_tables * (size_t)n_grid, hipMemcpyHostToDevice, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_lo, lo, sizeof(double) * (size_t)n_tables, hipMemcpyHostToDevice, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_hi, hi, sizeof(double) * (size_t)n_tables, hipMemcpyHostToDevice, sc.stream));
   float ms = 0.f;
   {
     P::CdfArgs a{d_pdf, d_lo, d_hi, d_prefix, d_last, n_grid};
-    GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
-    hipLaunchKernelGGL(P::table_cdf_kernel, dim3((unsigned)n_tables), dim3(P::kBlock), 0, sc.stream, a);
-    GWI_SPIN_HIP(hipGetLastError());
-    GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
-    GWI_SPIN_HIP(hipEventSynchronize(sc.e1));
-    GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
-    g_popdraw_times.cdf_ms = ms;
+    st = sc.timed([&] { hipLaunchKernelGGL(P::table_cdf_kernel, dim3((unsigned)n_tables), dim3(P::kBlock), 0, sc.stream, a); }, &ms);
+    if (st != GWI_OK) return st;
+    g_popdraw_times.ms[kPopdrawCdf] = ms;
   }
   // the draws, cut into launches of at most 2^20 draws per table and 2^26 lanes: a draw depends on (seed, table, first_index + j)
   // only, so the cut changes nothing
-  const long long dc_max = std::min<long long>(n_draws, kPopdrawDrawsPerLaunch);
-  const long long lanes_per_table = (dc_max + P::kBlock - 1) / P::kBlock * P::kBlock;
-  const long long tc_max = std::max<long long>(1, std::min<long long>(std::min<long long>(n_tables, 65535), kPopdrawThreadsPerLaunch / lanes_per_table));
+  const LaunchCut cut = launch_cut(n_tables, n_draws, kPopdrawDrawsPerLaunch, kPopdrawThreadsPerLaunch, P::kBlock);
+  const long long dc_max = cut.items_max, tc_max = cut.rows_max;
   const size_t chunk = (size_t)dc_max * (size_t)tc_max;
   double* d_lower = lower ? sc.alloc<double>(chunk) : nullptr;
   double* d_x = sc.alloc<double>(chunk);
@@ -4191,49 +4202,37 @@ gwi_status gwi_table_draws(int32_t device, int32_t n_tables, int32_t n_grid, con
       const long long dc = std::min<long long>(dc_max, n_draws - j0);
       const size_t host_at = (size_t)t0 * (size_t)n_draws + (size_t)j0;
       if (lower)
-        GWI_SPIN_HIP(hipMemcpy2DAsync(d_lower, dev_pitch, lower + host_at, host_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyHostToDevice, sc.stream));
+        GWI_SCRATCH_HIP(hipMemcpy2DAsync(d_lower, dev_pitch, lower + host_at, host_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyHostToDevice, sc.stream));
       P::DrawArgs a{d_pdf, d_lo, d_hi, d_prefix, d_last, d_lower, d_x, d_mass, d_acc, (unsigned long long)seed, (unsigned long long)first_index + (unsigned long long)j0,
                     dc,    dc_max, n_grid, (int)t0};
-      GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
-      hipLaunchKernelGGL(P::table_draw_kernel, dim3((unsigned)((dc + P::kBlock - 1) / P::kBlock), (unsigned)tc), dim3(P::kBlock), lds_bytes, sc.stream, a);
-      GWI_SPIN_HIP(hipGetLastError());
-      GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
-      GWI_SPIN_HIP(hipMemcpy2DAsync(x + host_at, host_pitch, d_x, dev_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
-      if (mass) GWI_SPIN_HIP(hipMemcpy2DAsync(mass + host_at, host_pitch, d_mass, dev_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
-      if (accept) GWI_SPIN_HIP(hipMemcpy2DAsync(accept + host_at, (size_t)n_draws, d_acc, (size_t)dc_max, (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
-      GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));  // the launch's buffers are free again
-      GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
-      g_popdraw_times.draw_ms += ms;
+      st = sc.timed([&] { hipLaunchKernelGGL(P::table_draw_kernel, dim3((unsigned)((dc + P::kBlock - 1) / P::kBlock), (unsigned)tc), dim3(P::kBlock), lds_bytes, sc.stream, a); },
+                    [&] {  // (once the stream has been waited for, the launch's buffers are free again)
+                      GWI_SCRATCH_HIP(hipMemcpy2DAsync(x + host_at, host_pitch, d_x, dev_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
+                      if (mass) GWI_SCRATCH_HIP(hipMemcpy2DAsync(mass + host_at, host_pitch, d_mass, dev_pitch, sizeof(double) * (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
+                      if (accept) GWI_SCRATCH_HIP(hipMemcpy2DAsync(accept + host_at, (size_t)n_draws, d_acc, (size_t)dc_max, (size_t)dc, (size_t)tc, hipMemcpyDeviceToHost, sc.stream));
+                      return GWI_OK;
+                    },
+                    &ms);
+      if (st != GWI_OK) return st;
+      g_popdraw_times.ms[kPopdrawDraw] += ms;
       ++g_popdraw_times.launches;
     }
   }
   return GWI_OK;
 }
 
-const char* gwi_table_draws_error(void) { return g_popdraw_error.c_str(); }
+const char* gwi_table_draws_error(void) { return g_popdraw_error.text.c_str(); }
 
-void gwi_table_draws_times(double* cdf_ms, double* draw_ms, int32_t* launches) {
-  if (cdf_ms) *cdf_ms = g_popdraw_times.cdf_ms;
-  if (draw_ms) *draw_ms = g_popdraw_times.draw_ms;
-  if (launches) *launches = g_popdraw_times.launches;
-}
+void gwi_table_draws_times(double* cdf_ms, double* draw_ms, int32_t* launches) { g_popdraw_times.report(cdf_ms, draw_ms, nullptr, launches); }
 
 }  // extern "C"
 
-// ---- mock catalogs (gwi_mock.h): stand-alone entries, no handle, like gwi_table_draws ------------------------------------
+// ---- mock catalogs (gwi_mock.h): stand-alone entries, no handle -------------------------------------------------------------
 namespace {
 
-struct MockTimes {
-  double observe_ms = 0.0, posterior_ms = 0.0;
-  int launches = 0;
-};
-thread_local MockTimes g_mock_times;
-thread_local std::string g_mock_error;
-
-gwi_status mock_refuse(const std::string& why) {
-  g_mock_error = why;
-  return GWI_ERR_INVALID;
-}
+enum { kMockObserve, kMockPosterior };
+thread_local StageTimes g_mock_times;
+thread_local ErrorSlot g_mock_error;
 
 constexpr long long kMockLanesPerLaunch = 1ll << 20;
 
@@ -4274,7 +4273,6 @@ bool mock_model(int32_t n_coords, const int32_t* is_log, const double* sigma, co
   }
   return true;
 }
-
 }  // namespace
 
 extern "C" {
@@ -4282,37 +4280,37 @@ extern "C" {
 gwi_status gwi_mock_observe(int32_t device, int32_t n_coords, const int32_t* is_log, const double* sigma, const double* lo, const double* hi, int32_t i_m1, int32_t i_q,
                             int32_t i_z, const double* detection, int32_t n_table, const double* table_z, const double* table_dl, int64_t n, const double* x_true,
                             uint64_t seed, uint64_t first_index, double* data, double* snr, unsigned char* found) {
-  static const char* kWhere = "gwi_mock_observe";
   namespace K = gwi::mock;
-  g_mock_error.clear();
-  g_mock_times = MockTimes();
+  ErrorSlot& err = g_mock_error;
+  err.text.clear();
+  g_mock_times = StageTimes();
   // ---- the argument checks: on the host, before anything is uploaded
   K::Model m;
   std::string why;
-  if (!mock_model(n_coords, is_log, sigma, lo, hi, &m, &why)) return mock_refuse(why);
-  if (n < 0) return mock_refuse("negative n");
+  if (!mock_model(n_coords, is_log, sigma, lo, hi, &m, &why)) return err.refuse(why);
+  if (n < 0) return err.refuse("negative n");
   const int32_t roles[3] = {i_m1, i_q, i_z};
   for (int r = 0; r < 3; ++r)
-    if (roles[r] < 0 || roles[r] >= n_coords) return mock_refuse(std::string("role index ") + (r == 0 ? "m1" : r == 1 ? "q" : "z") + " = " + std::to_string(roles[r]) + " out of range");
-  if (i_m1 == i_q || i_m1 == i_z || i_q == i_z) return mock_refuse("the role indices m1, q, z must differ");
-  if (!detection) return mock_refuse("null detection parameters");
+    if (roles[r] < 0 || roles[r] >= n_coords) return err.refuse(std::string("role index ") + (r == 0 ? "m1" : r == 1 ? "q" : "z") + " = " + std::to_string(roles[r]) + " out of range");
+  if (i_m1 == i_q || i_m1 == i_z || i_q == i_z) return err.refuse("the role indices m1, q, z must differ");
+  if (!detection) return err.refuse("null detection parameters");
   for (int k = 0; k < 4; ++k)
-    if (!(detection[k] > 0.0) || !(detection[k] < __builtin_inf())) return mock_refuse("detection parameter " + std::to_string(k) + " (rho_ref, mc_ref, dl_ref, rho_th) is not positive and finite");
-  if (!table_z || !table_dl) return mock_refuse("null DL table");
-  if (n_table < 2) return mock_refuse("the DL table has fewer than two points");
+    if (!(detection[k] > 0.0) || !(detection[k] < __builtin_inf())) return err.refuse("detection parameter " + std::to_string(k) + " (rho_ref, mc_ref, dl_ref, rho_th) is not positive and finite");
+  if (!table_z || !table_dl) return err.refuse("null DL table");
+  if (n_table < 2) return err.refuse("the DL table has fewer than two points");
   for (int32_t i = 0; i < n_table; ++i) {
-    if (i > 0 && !(table_z[i] > table_z[i - 1])) return mock_refuse("the DL table's redshifts are not ascending at entry " + std::to_string(i));
+    if (i > 0 && !(table_z[i] > table_z[i - 1])) return err.refuse("the DL table's redshifts are not ascending at entry " + std::to_string(i));
     if (!(table_dl[i] >= 0.0) || !(table_dl[i] < __builtin_inf()) || (i > 0 && !(table_dl[i] > 0.0)))
-      return mock_refuse("DL table entry " + std::to_string(i) + " is not positive and finite");
+      return err.refuse("DL table entry " + std::to_string(i) + " is not positive and finite");
   }
   {
     // the largest redshift the data can show: 9 sigma above the support's end (a 53-bit uniform gives |n| < 8.3)
     const double t_top = m.t_hi[i_z] + 9.0 * m.sigma[i_z];
     const double z_top = m.is_log[i_z] ? std::exp(t_top) : t_top;
     if (!(table_z[0] <= 0.0) || !(table_z[n_table - 1] >= z_top))
-      return mock_refuse("the DL table covers [" + std::to_string(table_z[0]) + ", " + std::to_string(table_z[n_table - 1]) + "], not [0, hi_z + 9 sigma_z = " + std::to_string(z_top) + "]");
+      return err.refuse("the DL table covers [" + std::to_string(table_z[0]) + ", " + std::to_string(table_z[n_table - 1]) + "], not [0, hi_z + 9 sigma_z = " + std::to_string(z_top) + "]");
   }
-  if (n > 0 && (!x_true || !data || !snr || !found)) return mock_refuse("null x_true, data, snr or found");
+  if (n > 0 && (!x_true || !data || !snr || !found)) return err.refuse("null x_true, data, snr or found");
   m.i_m1 = i_m1;
   m.i_q = i_q;
   m.i_z = i_z;
@@ -4320,11 +4318,11 @@ gwi_status gwi_mock_observe(int32_t device, int32_t n_coords, const int32_t* is_
   m.mc_ref = detection[1];
   m.dl_ref = detection[2];
   m.rho_th = detection[3];
-  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
-  gwi_status st = spin_device(device, &guard);
+  DeviceScope scope;
+  gwi_status st = scope.select(device);
   if (st != GWI_OK) return st;
   if (n == 0) return GWI_OK;
-  SpinScratch sc;
+  LaunchScratch sc("gwi_mock_observe");
   if (!sc.open()) return GWI_ERR_HIP;
   const size_t cn = (size_t)n_coords * (size_t)n;
   double* d_x = sc.alloc<double>(cn);
@@ -4334,87 +4332,74 @@ gwi_status gwi_mock_observe(int32_t device, int32_t n_coords, const int32_t* is_
   double* d_tz = sc.alloc<double>((size_t)n_table);
   double* d_tv = sc.alloc<double>((size_t)n_table);
   if (!d_x || !d_d || !d_snr || !d_found || !d_tz || !d_tv) return GWI_ERR_HIP;
-  GWI_SPIN_HIP(hipMemcpyAsync(d_x, x_true, sizeof(double) * cn, hipMemcpyHostToDevice, sc.stream));
-  GWI_SPIN_HIP(hipMemcpyAsync(d_tz, table_z, sizeof(double) * (size_t)n_table, hipMemcpyHostToDevice, sc.stream));
-  GWI_SPIN_HIP(hipMemcpyAsync(d_tv, table_dl, sizeof(double) * (size_t)n_table, hipMemcpyHostToDevice, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_x, x_true, sizeof(double) * cn, hipMemcpyHostToDevice, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_tz, table_z, sizeof(double) * (size_t)n_table, hipMemcpyHostToDevice, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_tv, table_dl, sizeof(double) * (size_t)n_table, hipMemcpyHostToDevice, sc.stream));
   // launches of at most 2^20 lanes: a value depends on (inputs, seed, first_index + j, coordinate) only, so the cut changes nothing
   for (long long j0 = 0; j0 < n; j0 += kMockLanesPerLaunch) {
     const long long nj = std::min<long long>(kMockLanesPerLaunch, n - j0);
     K::ObserveArgs a{m, d_x, d_tz, d_tv, d_d, d_snr, d_found, (unsigned long long)seed, (unsigned long long)first_index + (unsigned long long)j0, nj, (long long)n, j0, n_table};
-    GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
-    hipLaunchKernelGGL(K::mock_observe_kernel, dim3((unsigned)((nj + K::kBlock - 1) / K::kBlock)), dim3(K::kBlock), 0, sc.stream, a);
-    GWI_SPIN_HIP(hipGetLastError());
-    GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
-    GWI_SPIN_HIP(hipEventSynchronize(sc.e1));
     float ms = 0.f;
-    GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
-    g_mock_times.observe_ms += ms;
+    st = sc.timed([&] { hipLaunchKernelGGL(K::mock_observe_kernel, dim3((unsigned)((nj + K::kBlock - 1) / K::kBlock)), dim3(K::kBlock), 0, sc.stream, a); }, &ms);
+    if (st != GWI_OK) return st;
+    g_mock_times.ms[kMockObserve] += ms;
     ++g_mock_times.launches;
   }
-  GWI_SPIN_HIP(hipMemcpyAsync(data, d_d, sizeof(double) * cn, hipMemcpyDeviceToHost, sc.stream));
-  GWI_SPIN_HIP(hipMemcpyAsync(snr, d_snr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, sc.stream));
-  GWI_SPIN_HIP(hipMemcpyAsync(found, d_found, (size_t)n, hipMemcpyDeviceToHost, sc.stream));
-  GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(data, d_d, sizeof(double) * cn, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(snr, d_snr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(found, d_found, (size_t)n, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipStreamSynchronize(sc.stream));
   return GWI_OK;
 }
 
 gwi_status gwi_mock_posteriors(int32_t device, int32_t n_coords, const int32_t* is_log, const double* sigma, const double* lo, const double* hi, int64_t n_ev, int64_t n_pe,
                                const double* data, uint64_t seed, uint64_t first_event, double* x, double* prior) {
-  static const char* kWhere = "gwi_mock_posteriors";
   namespace K = gwi::mock;
-  g_mock_error.clear();
-  g_mock_times = MockTimes();
+  ErrorSlot& err = g_mock_error;
+  err.text.clear();
+  g_mock_times = StageTimes();
   K::Model m;
   std::string why;
-  if (!mock_model(n_coords, is_log, sigma, lo, hi, &m, &why)) return mock_refuse(why);
-  if (n_ev < 0 || n_pe < 0) return mock_refuse("negative n_ev or n_pe");
-  if (n_pe > 0xffffffffLL) return mock_refuse("n_pe does not fit the 32-bit sample word of the counter");
-  if (n_ev > 0 && !data) return mock_refuse("null data");
-  if (n_ev > 0 && n_pe > 0 && (!x || !prior)) return mock_refuse("null x or prior");
-  SpinDeviceGuard guard;  // (declared before the buffers: they are freed on `device`, then the thread goes back)
-  gwi_status st = spin_device(device, &guard);
+  if (!mock_model(n_coords, is_log, sigma, lo, hi, &m, &why)) return err.refuse(why);
+  if (n_ev < 0 || n_pe < 0) return err.refuse("negative n_ev or n_pe");
+  if (n_pe > 0xffffffffLL) return err.refuse("n_pe does not fit the 32-bit sample word of the counter");
+  if (n_ev > 0 && !data) return err.refuse("null data");
+  if (n_ev > 0 && n_pe > 0 && (!x || !prior)) return err.refuse("null x or prior");
+  DeviceScope scope;
+  gwi_status st = scope.select(device);
   if (st != GWI_OK) return st;
   if (n_ev == 0 || n_pe == 0) return GWI_OK;
-  SpinScratch sc;
+  LaunchScratch sc("gwi_mock_posteriors");
   if (!sc.open()) return GWI_ERR_HIP;
   const size_t plane = (size_t)n_ev * (size_t)n_pe;
   double* d_d = sc.alloc<double>((size_t)n_coords * (size_t)n_ev);
   double* d_x = sc.alloc<double>((size_t)n_coords * plane);
   double* d_prior = sc.alloc<double>(plane);
   if (!d_d || !d_x || !d_prior) return GWI_ERR_HIP;
-  GWI_SPIN_HIP(hipMemcpyAsync(d_d, data, sizeof(double) * (size_t)n_coords * (size_t)n_ev, hipMemcpyHostToDevice, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_d, data, sizeof(double) * (size_t)n_coords * (size_t)n_ev, hipMemcpyHostToDevice, sc.stream));
   // launches of at most 2^20 lanes (and 65535 events): a sample depends on (data, seed, first_event + e, s, coordinate) only
-  const long long sc_max = std::min<long long>(n_pe, kMockLanesPerLaunch);
-  const long long lanes_per_event = (sc_max + K::kBlock - 1) / K::kBlock * K::kBlock;
-  const long long ec_max = std::max<long long>(1, std::min<long long>(std::min<long long>(n_ev, 65535), kMockLanesPerLaunch / lanes_per_event));
+  const LaunchCut cut = launch_cut(n_ev, n_pe, kMockLanesPerLaunch, kMockLanesPerLaunch, K::kBlock);
+  const long long sc_max = cut.items_max, ec_max = cut.rows_max;
   for (long long e0 = 0; e0 < n_ev; e0 += ec_max) {
     const long long ec = std::min<long long>(ec_max, n_ev - e0);
     for (long long s0 = 0; s0 < n_pe; s0 += sc_max) {
       const long long ns = std::min<long long>(sc_max, n_pe - s0);
       K::PosteriorArgs a{m, d_d, d_x, d_prior, (unsigned long long)seed, (unsigned long long)first_event, (long long)n_ev, (long long)n_pe, e0, s0, ns};
-      GWI_SPIN_HIP(hipEventRecord(sc.e0, sc.stream));
-      hipLaunchKernelGGL(K::mock_posterior_kernel, dim3((unsigned)((ns + K::kBlock - 1) / K::kBlock), (unsigned)ec), dim3(K::kBlock), 0, sc.stream, a);
-      GWI_SPIN_HIP(hipGetLastError());
-      GWI_SPIN_HIP(hipEventRecord(sc.e1, sc.stream));
-      GWI_SPIN_HIP(hipEventSynchronize(sc.e1));
       float ms = 0.f;
-      GWI_SPIN_HIP(hipEventElapsedTime(&ms, sc.e0, sc.e1));
-      g_mock_times.posterior_ms += ms;
+      st = sc.timed([&] { hipLaunchKernelGGL(K::mock_posterior_kernel, dim3((unsigned)((ns + K::kBlock - 1) / K::kBlock), (unsigned)ec), dim3(K::kBlock), 0, sc.stream, a); }, &ms);
+      if (st != GWI_OK) return st;
+      g_mock_times.ms[kMockPosterior] += ms;
       ++g_mock_times.launches;
     }
   }
-  GWI_SPIN_HIP(hipMemcpyAsync(x, d_x, sizeof(double) * (size_t)n_coords * plane, hipMemcpyDeviceToHost, sc.stream));
-  GWI_SPIN_HIP(hipMemcpyAsync(prior, d_prior, sizeof(double) * plane, hipMemcpyDeviceToHost, sc.stream));
-  GWI_SPIN_HIP(hipStreamSynchronize(sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(x, d_x, sizeof(double) * (size_t)n_coords * plane, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(prior, d_prior, sizeof(double) * plane, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipStreamSynchronize(sc.stream));
   return GWI_OK;
 }
 
-const char* gwi_mock_error(void) { return g_mock_error.c_str(); }
+const char* gwi_mock_error(void) { return g_mock_error.text.c_str(); }
 
-void gwi_mock_times(double* observe_ms, double* posterior_ms, int32_t* launches) {
-  if (observe_ms) *observe_ms = g_mock_times.observe_ms;
-  if (posterior_ms) *posterior_ms = g_mock_times.posterior_ms;
-  if (launches) *launches = g_mock_times.launches;
-}
+void gwi_mock_times(double* observe_ms, double* posterior_ms, int32_t* launches) { g_mock_times.report(observe_ms, posterior_ms, nullptr, launches); }
 
 }  // extern "C"

@@ -213,6 +213,89 @@ def test_pure_function_of_the_inputs(comp_name):
     eng2.close()
 
 
+def test_buffer_lifetime_across_entries_of_one_handle():
+    """The device buffers one handle keeps for draw_indices, weighted_histograms and resample_injections, grown, dropped and shared
+    between the entries: engine A draws (2 draws per segment at K = 1, then 64 at K = 3, which regrows the uniforms and the
+    indices), sums histograms at K = 2 with (C, B) = (1, 4) and, the bins dropped and set anew, (2, 16), resamples 8 and then 600
+    injections (which regrows the output pair) and repeats its first draw; engine B, fresh on the same catalog, starts with the
+    histograms, so that they and not the draws allocate the tile workspace, then resamples, then draws.  Every result of A equals
+    B's bit for bit, A's last draw its first, and each the NumPy statement (gwinferno_amd/draws.py) under the neighbouring tests'
+    bounds: the bracket of this file for every index; the drawn log-weights those of log_weights bit for bit and the sums within
+    1e-9 of the host's (tests/test_gpu_resample.py); every bin within hist_util.bound of the statement fed with the engine's own
+    log-weights (tests/test_gpu_hist.py) -- the bound of one point holds for the running sum of two: all terms are non-negative, so
+    the sum of two bins each within tol of its statement is within tol of the statements' sum, and the one rounding the addition
+    makes on either side (2^-53 each) is inside the 8 units of 2^-52 the bound has to spare.
+    3 events x 1 500 PE samples (two tiles, the second partial) and 2 500 injections (three tiles)."""
+    import hist_util
+    import resample_util
+    from gwinferno_amd.compositions import COMPOSITIONS
+    from gwinferno_amd.draws import digitize, resample_uniforms, weighted_histograms_reference
+    from gwinferno_amd.synthetic import make_catalog
+
+    n_ev, seed = 3, 77
+    pe, inj, total = make_catalog(n_ev, 1500, 2500, seed=61)
+    comp_a, comp_b = COMPOSITIONS["plpeak"](pe, inj), COMPOSITIONS["plpeak"](pe, inj)
+    thetas = _thetas(comp_a, "plpeak", 3, seed=5)
+    rng = np.random.default_rng(8)
+    u1, u64 = (rng.uniform(size=(n_ev, 2)), rng.uniform(size=2)), (rng.uniform(size=(3, n_ev, 64)), rng.uniform(size=(3, 64)))
+    bins = {}
+    for cols, n_bins in ((("mass_1",), 4), (("mass_1", "mass_2"), 16)):
+        edges = {c: np.linspace(*np.quantile(np.concatenate([pe[c].ravel(), inj[c]]), [0.02, 0.98]), n_bins + 1) for c in cols}
+        bins[n_bins] = (np.stack([digitize(pe[c], edges[c]) for c in cols]), np.stack([digitize(inj[c], edges[c]) for c in cols]))
+
+    def draws(eng, out):
+        out["draw 2"] = eng.draw_indices(thetas[0], *u1)
+        out["draw 64"] = eng.draw_indices(thetas, *u64)
+
+    def histograms(eng, out):
+        for n_bins in (4, 16):
+            eng.set_histogram_bins(*bins[n_bins], n_bins=n_bins)
+            out["hist", n_bins] = eng.weighted_histograms(thetas[:2])
+
+    def resamples(eng, out):
+        for n in (8, 600):
+            out["resample", n] = eng.resample_injections(thetas[0], seed, n_request=n)
+
+    eng_a, eng_b = comp_a.engine(), comp_b.engine()
+    a, b = {}, {}
+    try:
+        for step in (draws, histograms, resamples):
+            step(eng_a, a)
+        a["draw 2 again"] = eng_a.draw_indices(thetas[0], *u1)
+        for step in (histograms, resamples, draws):
+            step(eng_b, b)
+        lw_dev = [eng_a.log_weights(t) for t in thetas[:2]]  # (after every step: log_weights shares the entries' buffers)
+        lw_host = [_bound_log_weights(eng_a.bound, t) for t in thetas]
+    finally:
+        eng_a.close()
+        eng_b.close()
+    for key, got in b.items():
+        for x, y in zip(a[key], got):
+            assert x == y if isinstance(x, dict) else (x.dtype == y.dtype and np.array_equal(x, y)), key
+    assert all(np.array_equal(x, y) for x, y in zip(a["draw 2 again"], a["draw 2"]))
+    # ... and each against its statement
+    _check_point(*lw_host[0], (None, None), *u1, *a["draw 2"], "draw 2")
+    for p in range(3):
+        _check_point(*lw_host[p], (None, None), u64[0][p], u64[1][p], a["draw 64"][0][p], a["draw 64"][1][p], ("draw 64", p))
+    for lw in lw_dev:  # (hist_util.bound asks that no live weight underflows next to its segment's largest)
+        assert all(np.min(seg[np.isfinite(seg)]) - np.max(seg[np.isfinite(seg)]) > hist_util.LOG_FLOOR for seg in (*lw[0], lw[1]))
+    for n_bins in (4, 16):
+        want = [weighted_histograms_reference(*lw, None, None, *bins[n_bins], n_bins) for lw in lw_dev]
+        hist_pe, hist_inj, dead = a["hist", n_bins]
+        assert dead.dtype == np.int32 and np.array_equal(dead, want[0][2] + want[1][2])
+        for seg in range(n_ev + 1):
+            g, w = (hist_pe[seg], want[0][0][seg] + want[1][0][seg]) if seg < n_ev else (hist_inj, want[0][1] + want[1][1])
+            tol = hist_util.bound(max(hist_util.n_live(lw[0][seg] if seg < n_ev else lw[1], None) for lw in lw_dev))
+            assert g.shape == w.shape == (len(bins[n_bins][0]), n_bins) and np.all(np.abs(g - w) <= tol * w), (n_bins, seg)
+    host = resample_util.host_sums(lw_host[0][1])
+    for n in (8, 600):
+        idx, lw_sel, sums = a["resample", n]
+        assert idx.dtype == np.int32 and idx.size == n and np.array_equal(lw_sel, lw_dev[0][1][idx])
+        _check_segment(lw_host[0][1], None, resample_uniforms(seed, 0, n), idx, ("resample", n))
+        assert abs(sums["log_sum_w"] - host["log_sum_w"]) <= 1e-9 and abs(sums["log_sum_w2"] - host["log_sum_w2"]) <= 1e-9
+        assert abs(sums["n_eff"] - host["n_eff"]) <= 1e-9 * host["n_eff"] and sums["n_live"] == host["n_live"] > 0
+
+
 def _chm_model(name, case):
     """construct_hierarchical_model's dictionaries for the golden case, as tests/test_gpu_dropin_api.py feeds them."""
     from gwinferno_amd import interpolation as I
