@@ -236,6 +236,12 @@ EXPORTED_SYMBOLS = [
     "gwi_set_histogram_bins",
     "gwi_weighted_histograms",
     "gwi_histogram_times",
+    "gwi_marginal_weights_reset",
+    "gwi_marginal_weights_add",
+    "gwi_marginal_weights_read",
+    "gwi_set_quantile_columns",
+    "gwi_weighted_quantiles",
+    "gwi_quantile_times",
     "gwi_effective_spins",
     "gwi_chi_p_conditional_prior",
     "gwi_spin_prior_times",
@@ -367,6 +373,20 @@ def load_library():
         lib.gwi_weighted_histograms.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _I32P]
         lib.gwi_histogram_times.restype = None
         lib.gwi_histogram_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_weighted_quantiles"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_marginal_weights_reset.restype = C.c_int32
+        lib.gwi_marginal_weights_reset.argtypes = [vp]
+        lib.gwi_marginal_weights_add.restype = C.c_int32
+        lib.gwi_marginal_weights_add.argtypes = [vp, _DP, C.c_int32]
+        lib.gwi_marginal_weights_read.restype = C.c_int32
+        lib.gwi_marginal_weights_read.argtypes = [vp, _DP, _DP, _I32P, C.POINTER(C.c_int64)]
+        lib.gwi_set_quantile_columns.restype = C.c_int32
+        lib.gwi_set_quantile_columns.argtypes = [vp, C.c_int32, _DP, _I32P, _DP, _I32P]
+        lib.gwi_weighted_quantiles.restype = C.c_int32
+        lib.gwi_weighted_quantiles.argtypes = [vp, _DP, C.c_int32, _I32P, _I32P, _DP, _DP, _DP]
+        lib.gwi_quantile_times.restype = None
+        lib.gwi_quantile_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

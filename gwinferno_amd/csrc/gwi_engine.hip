@@ -10,6 +10,7 @@
 #include "gwi_popdraw.h"
 #include "gwi_resample.h"
 #include "gwi_hist.h"
+#include "gwi_quant.h"
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
 
@@ -464,6 +465,20 @@ struct PostprocessBuffers {
     DeviceBuffer<int> d_dead;
     int cols = 0, bins = 0;
   } hist;
+  // marginal weights and their quantiles (gwi_quant.h).  The state of the handle: one running double per sample [n_ev n_pe | n_inj],
+  // the dead counts [n_ev + 1] (allocated and zeroed on the first use of any of the entries) and the number of points added
+  struct Marginal {
+    DeviceBuffer<double> d_w;
+    DeviceBuffer<int> d_dead;
+    long long n_points = 0;
+  } marg;
+  // ... the columns of gwi_set_quantile_columns (values and orders of either set), the tiles' sums [n_tiles][n_cols][3] and their
+  // prefix [n_tiles][n_cols] (allocated with the columns, kept), and the levels / indices / (moments, mass) of one query
+  struct Quantile {
+    DeviceBuffer<double> d_x_pe, d_x_inj, d_partial, d_prefix, d_levels, d_out;
+    DeviceBuffer<int> d_order_pe, d_order_inj, d_idx;
+    int cols = 0;
+  } quant;
 };
 }  // namespace
 
@@ -4025,6 +4040,250 @@ gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k
 }
 
 void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) { g_histogram_times.report(logw_ms, tile_ms, merge_ms, launches); }
+
+// ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
+enum { kQuantLogw, kQuantAdd, kQuantQuery };
+static thread_local StageTimes g_quantile_times;
+
+// the handle's marginal weights and dead counts on the engine's device (selected by the caller): allocated and zeroed on first use
+static gwi_status marginal_state(gwi_handle h) {
+  PostprocessBuffers::Marginal& m = h->post.marg;
+  if (m.d_w.ptr && m.d_dead.ptr) return GWI_OK;
+  const size_t n_w = (size_t)(h->n_ev * h->n_pe) + (size_t)h->n_inj, n_dead = (size_t)(h->n_ev + 1);
+  m = PostprocessBuffers::Marginal();
+  GWI_HIP(m.d_w.reserve(n_w));
+  GWI_HIP(m.d_dead.reserve(n_dead));
+  GWI_HIP(hipMemsetAsync(m.d_w, 0, sizeof(double) * (n_w ? n_w : 1), h->stream));
+  GWI_HIP(hipMemsetAsync(m.d_dead, 0, sizeof(int) * n_dead, h->stream));
+  GWI_HIP(hipStreamSynchronize(h->stream));
+  return GWI_OK;
+}
+
+gwi_status gwi_marginal_weights_reset(gwi_handle h) {
+  if (!h) return GWI_ERR_INVALID;
+  gwi_status st = post_preflight(h, "gwi_marginal_weights_reset", "keep the weights on", "the injection weights need", []() -> std::string { return ""; });
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipSetDevice(h->device));
+  h->post.marg = PostprocessBuffers::Marginal();  // (zeroed anew on the next use)
+  return marginal_state(h);
+}
+
+gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t k) {
+  if (!h) return GWI_ERR_INVALID;
+  g_quantile_times = StageTimes();
+  gwi_status st = post_preflight(h, "gwi_marginal_weights_add", "sum on", "the injection weights need", [&]() -> std::string {
+    if (!h->variant) return "the engine has no scan kernel";
+    if (!thetas || k < 0) return "thetas is null or k < 0";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  namespace D = gwi::draw;
+  namespace Q = gwi::quant;
+  Q::MargArgs a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, "gwi_marginal_weights_add", "tiles", &a.d, &n_tiles);
+  if (st != GWI_OK) return st;
+  st = marginal_state(h);
+  if (st != GWI_OK) return st;
+  PostprocessBuffers::Marginal& m = h->post.marg;
+  a.w_pe = m.d_w;
+  a.w_inj = m.d_w + (size_t)(h->n_ev * h->n_pe);
+  a.dead = m.d_dead;
+  LaunchScratch ev("gwi_marginal_weights_add");
+  GWI_HIP(ev.events(2));
+  const int nt = h->spec.n_theta;
+  for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
+    const auto t0 = std::chrono::steady_clock::now();
+    st = fill_log_weights(h, thetas + (size_t)p * nt, &a.d.log_const);  // (blocking)
+    if (st != GWI_OK) return st;
+    g_quantile_times.ms[kQuantLogw] += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    a.d.logw_pe = h->post.d_logw_pe;
+    a.d.logw_inj = h->post.d_logw_inj;
+    GWI_HIP(hipEventRecord(ev.e[0], h->stream));
+    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a.d);
+    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.d);
+    if (n_tiles) hipLaunchKernelGGL(Q::marg_add_kernel, dim3((unsigned)n_tiles), dim3(Q::kBlock), 0, h->stream, a);
+    GWI_HIP(hipGetLastError());
+    GWI_HIP(hipEventRecord(ev.e[1], h->stream));
+    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
+    GWI_HIP(hipStreamSynchronize(h->stream));
+    ++m.n_points;
+    float add_ms = 0.f;
+    GWI_HIP(hipEventElapsedTime(&add_ms, ev.e[0], ev.e[1]));
+    g_quantile_times.ms[kQuantAdd] += add_ms;
+    g_quantile_times.launches += 3;
+  }
+  return GWI_OK;
+}
+
+gwi_status gwi_marginal_weights_read(gwi_handle h, double* pe_w, double* inj_w, int32_t* dead, int64_t* n_points) {
+  if (!h) return GWI_ERR_INVALID;
+  gwi_status st = post_preflight(h, "gwi_marginal_weights_read", "keep the weights on", "the injection weights need", [&]() -> std::string {
+    if (!dead || !n_points) return "dead or n_points is null";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipSetDevice(h->device));
+  st = marginal_state(h);
+  if (st != GWI_OK) return st;
+  const PostprocessBuffers::Marginal& m = h->post.marg;
+  const size_t n_pe_tot = (size_t)(h->n_ev * h->n_pe), n_inj = (size_t)h->n_inj;
+  if (pe_w && n_pe_tot) GWI_HIP(hipMemcpy(pe_w, m.d_w, sizeof(double) * n_pe_tot, hipMemcpyDeviceToHost));
+  if (inj_w && n_inj) GWI_HIP(hipMemcpy(inj_w, m.d_w + n_pe_tot, sizeof(double) * n_inj, hipMemcpyDeviceToHost));
+  GWI_HIP(hipMemcpy(dead, m.d_dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyDeviceToHost));
+  *n_points = m.n_points;
+  return GWI_OK;
+}
+
+// what is wrong with one set's columns (x and order [n_cols][n_segs][n]), or an empty string: every order a permutation of its
+// segment, every value finite, no value smaller than the one before it along the order
+static std::string bad_quantile_columns(const char* set, bool with_events, int n_cols, long long n_segs, long long n, const double* x, const int32_t* order) {
+  std::vector<unsigned char> seen((size_t)n);
+  for (int c = 0; c < n_cols; ++c)
+    for (long long s = 0; s < n_segs; ++s) {
+      const size_t at = ((size_t)c * (size_t)n_segs + (size_t)s) * (size_t)n;
+      const std::string where = std::string(set) + " column " + std::to_string(c) + (with_events ? ", event " + std::to_string(s) : std::string());
+      std::fill(seen.begin(), seen.end(), 0);
+      double before = -__builtin_inf();
+      for (long long r = 0; r < n; ++r) {
+        const long long j = order[at + (size_t)r];
+        if (j < 0 || j >= n || seen[(size_t)j]) return "order_" + where + ": rank " + std::to_string(r) + " holds " + std::to_string(j) + ": not a permutation of the segment's " + std::to_string(n) + " samples";
+        seen[(size_t)j] = 1;
+        const double v = x[at + (size_t)j];
+        if (!(std::fabs(v) < __builtin_inf())) return "x_" + where + ": sample " + std::to_string(j) + " is not finite";
+        if (v < before) return "x_" + where + ": the values decrease along the order at rank " + std::to_string(r);
+        before = v;
+      }
+    }
+  return "";
+}
+
+gwi_status gwi_set_quantile_columns(gwi_handle h, int32_t n_cols, const double* x_pe, const int32_t* order_pe, const double* x_inj, const int32_t* order_inj) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace Q = gwi::quant;
+  gwi_status st = post_preflight(h, "gwi_set_quantile_columns", "keep the columns on", "the injection quantiles need", [&]() -> std::string {
+    if (n_cols < 1 || n_cols > Q::kMaxCols) return "n_cols = " + std::to_string(n_cols) + " is not in 1 ... " + std::to_string(Q::kMaxCols);
+    if (!x_pe && !x_inj) return "x_pe and x_inj are both null";
+    if ((x_pe != nullptr) != (order_pe != nullptr)) return "x_pe and order_pe are given together";
+    if ((x_inj != nullptr) != (order_inj != nullptr)) return "x_inj and order_inj are given together";
+    if (h->n_pe > 0x7fffffffLL || h->n_inj > 0x7fffffffLL) return "more samples per segment than an int32 index can address";
+    if (x_pe) {
+      const std::string why = bad_quantile_columns("pe", true, n_cols, h->n_ev, h->n_pe, x_pe, order_pe);
+      if (!why.empty()) return why;
+    }
+    if (x_inj) return bad_quantile_columns("inj", false, n_cols, 1, h->n_inj, x_inj, order_inj);
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  gwi::draw::DrawArgs geometry;
+  long long n_tiles = 0;
+  st = draw_workspace(h, "gwi_set_quantile_columns", "tiles", &geometry, &n_tiles);
+  if (st != GWI_OK) return st;
+  // the previous columns go away first: should an allocation fail, gwi_weighted_quantiles refuses until they are set again
+  PostprocessBuffers::Quantile& quant = h->post.quant;
+  quant = PostprocessBuffers::Quantile();
+  const size_t n_pe_vals = x_pe ? (size_t)n_cols * (size_t)(h->n_ev * h->n_pe) : 0, n_inj_vals = x_inj ? (size_t)n_cols * (size_t)h->n_inj : 0;
+  if (x_pe) {
+    GWI_HIP(quant.d_x_pe.reserve(n_pe_vals));
+    GWI_HIP(quant.d_order_pe.reserve(n_pe_vals));
+    if (n_pe_vals) GWI_HIP(hipMemcpy(quant.d_x_pe, x_pe, sizeof(double) * n_pe_vals, hipMemcpyHostToDevice));
+    if (n_pe_vals) GWI_HIP(hipMemcpy(quant.d_order_pe, order_pe, sizeof(int32_t) * n_pe_vals, hipMemcpyHostToDevice));
+  }
+  if (x_inj) {
+    GWI_HIP(quant.d_x_inj.reserve(n_inj_vals));
+    GWI_HIP(quant.d_order_inj.reserve(n_inj_vals));
+    if (n_inj_vals) GWI_HIP(hipMemcpy(quant.d_x_inj, x_inj, sizeof(double) * n_inj_vals, hipMemcpyHostToDevice));
+    if (n_inj_vals) GWI_HIP(hipMemcpy(quant.d_order_inj, order_inj, sizeof(int32_t) * n_inj_vals, hipMemcpyHostToDevice));
+  }
+  GWI_HIP(quant.d_partial.reserve((size_t)n_tiles * (size_t)n_cols * Q::kSums));
+  GWI_HIP(quant.d_prefix.reserve((size_t)n_tiles * (size_t)n_cols));
+  quant.cols = n_cols;
+  return GWI_OK;
+}
+
+gwi_status gwi_weighted_quantiles(gwi_handle h, const double* levels, int32_t n_levels, int32_t* idx_pe, int32_t* idx_inj, double* moments_pe, double* moments_inj, double* mass) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace Q = gwi::quant;
+  PostprocessBuffers::Quantile& quant = h->post.quant;
+  const bool with_pe = quant.d_x_pe.ptr != nullptr, with_inj = quant.d_x_inj.ptr != nullptr;
+  gwi_status st = post_preflight(h, "gwi_weighted_quantiles", "select on", "the injection quantiles need", [&]() -> std::string {
+    if (!quant.cols) return "no columns are set (gwi_set_quantile_columns)";
+    if (n_levels < 1 || n_levels > Q::kMaxLevels) return "n_levels = " + std::to_string(n_levels) + " is not in 1 ... " + std::to_string(Q::kMaxLevels);
+    if (!levels) return "levels is null";
+    for (int q = 0; q < n_levels; ++q)
+      if (!(levels[q] >= 0.0 && levels[q] <= 1.0)) return "level " + std::to_string(q) + " is " + std::to_string(levels[q]) + ": not in [0, 1]";
+    if (with_pe && (!idx_pe || !moments_pe)) return "PE columns are set: idx_pe and moments_pe are needed";
+    if (with_inj && (!idx_inj || !moments_inj)) return "injection columns are set: idx_inj and moments_inj are needed";
+    if (!mass) return "mass is null";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  gwi::draw::DrawArgs geometry;
+  long long n_tiles = 0;
+  st = draw_workspace(h, "gwi_weighted_quantiles", "tiles", &geometry, &n_tiles);  // (as gwi_set_quantile_columns found it)
+  if (st != GWI_OK) return st;
+  st = marginal_state(h);
+  if (st != GWI_OK) return st;
+  const size_t n_segs = (size_t)(h->n_ev + 1), per_seg_idx = (size_t)quant.cols * (size_t)n_levels, per_seg_mom = (size_t)quant.cols * 2;
+  GWI_HIP(quant.d_levels.reserve((size_t)n_levels));
+  GWI_HIP(quant.d_idx.reserve(n_segs * per_seg_idx));
+  GWI_HIP(quant.d_out.reserve(n_segs * per_seg_mom + n_segs));
+  GWI_HIP(hipMemcpy(quant.d_levels, levels, sizeof(double) * (size_t)n_levels, hipMemcpyHostToDevice));
+  GWI_HIP(hipMemsetAsync(quant.d_out, 0, sizeof(double) * (n_segs * per_seg_mom + n_segs), h->stream));  // (the mass of a set that is left out)
+  Q::Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.w_pe = h->post.marg.d_w;
+  a.w_inj = h->post.marg.d_w + (size_t)(h->n_ev * h->n_pe);
+  a.x_pe = quant.d_x_pe;
+  a.x_inj = quant.d_x_inj;
+  a.order_pe = quant.d_order_pe;
+  a.order_inj = quant.d_order_inj;
+  a.partial = quant.d_partial;
+  a.prefix = quant.d_prefix;
+  a.levels = quant.d_levels;
+  a.idx = quant.d_idx;
+  a.moments = quant.d_out;
+  a.mass = quant.d_out + n_segs * per_seg_mom;
+  a.n_pe = h->n_pe;
+  a.n_inj = h->n_inj;
+  a.n_ev = (int)h->n_ev;
+  a.tiles_per_event = geometry.tiles_per_event;
+  a.n_inj_tiles = geometry.n_inj_tiles;
+  a.n_cols = quant.cols;
+  a.n_levels = n_levels;
+  // a set without columns is left out of the launches: PE tiles and segments come first, the injection set's last
+  const long long n_pe_tiles = h->n_ev * geometry.tiles_per_event;
+  a.first_tile = with_pe ? 0 : (int)n_pe_tiles;
+  a.first_seg = with_pe ? 0 : (int)h->n_ev;
+  const long long q_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? geometry.n_inj_tiles : 0), q_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
+  LaunchScratch ev("gwi_weighted_quantiles");
+  GWI_HIP(ev.events(2));
+  GWI_HIP(hipEventRecord(ev.e[0], h->stream));
+  if (q_tiles) hipLaunchKernelGGL(Q::quant_tile_kernel, dim3((unsigned)q_tiles, (unsigned)a.n_cols), dim3(Q::kBlock), 0, h->stream, a);
+  if (q_segs) hipLaunchKernelGGL(Q::quant_merge_kernel, dim3((unsigned)q_segs, (unsigned)a.n_cols), dim3(Q::kBlock), 0, h->stream, a);
+  if (q_segs) hipLaunchKernelGGL(Q::quant_select_kernel, dim3((unsigned)q_segs, (unsigned)a.n_cols), dim3(Q::kBlock), 0, h->stream, a);
+  GWI_HIP(hipGetLastError());
+  GWI_HIP(hipEventRecord(ev.e[1], h->stream));
+  GWI_HIP(hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  GWI_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+  g_quantile_times.ms[kQuantQuery] = ms;
+  g_quantile_times.launches = 3;
+  const size_t n_ev = (size_t)h->n_ev;
+  if (with_pe && n_ev) {
+    GWI_HIP(hipMemcpy(idx_pe, quant.d_idx, sizeof(int) * n_ev * per_seg_idx, hipMemcpyDeviceToHost));
+    GWI_HIP(hipMemcpy(moments_pe, quant.d_out, sizeof(double) * n_ev * per_seg_mom, hipMemcpyDeviceToHost));
+  }
+  if (with_inj) {
+    GWI_HIP(hipMemcpy(idx_inj, quant.d_idx + n_ev * per_seg_idx, sizeof(int) * per_seg_idx, hipMemcpyDeviceToHost));
+    GWI_HIP(hipMemcpy(moments_inj, quant.d_out + n_ev * per_seg_mom, sizeof(double) * per_seg_mom, hipMemcpyDeviceToHost));
+  }
+  GWI_HIP(hipMemcpy(mass, a.mass, sizeof(double) * n_segs, hipMemcpyDeviceToHost));
+  return GWI_OK;
+}
+
+void gwi_quantile_times(double* logw_ms, double* add_ms, double* query_ms, int32_t* launches) { g_quantile_times.report(logw_ms, add_ms, query_ms, launches); }
 
 }  // extern "C"
 

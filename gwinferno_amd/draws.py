@@ -12,7 +12,15 @@ preprocess/selection.py:143-156) draws from the injection segment by the same ru
 :func:`resample_uniforms` states them and :func:`resample_indices_reference` the draws.
 
 ``gwi_weighted_histograms`` (gwinferno_amd/csrc/gwi_hist.h) sums the same ``w_j`` into bins instead of drawing from them:
-:func:`weighted_histograms_reference` states one hyper-parameter point of it, :func:`digitize` the bin codes."""
+:func:`weighted_histograms_reference` states one hyper-parameter point of it, :func:`digitize` the bin codes.
+
+``gwi_marginal_weights_add`` / ``gwi_weighted_quantiles`` (gwinferno_amd/csrc/gwi_quant.h) keep the same ``w_j``, normalised and
+summed over the points, per sample -- the marginal posterior weight ``W_j`` -- and select weighted quantiles and moments under it:
+:func:`marginal_weights_reference` and :func:`weighted_quantiles_reference` state them."""
+import bisect
+import itertools
+import math
+
 import numpy as np
 
 RESAMPLE_TAG = 0x52534D50  # counter word 3 of the resampling stream (gwi_resample.h: kTag)
@@ -142,3 +150,73 @@ def weighted_histograms_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins,
         hist_inj, live = weighted_histogram_segment(logw_inj, inj_mask, np.asarray(inj_bins), n_bins)
         dead[n_ev] = 0 if live else 1
     return hist_pe, hist_inj, dead
+
+
+def marginal_weights_reference(logw_pe, logw_inj, pe_mask, inj_mask):
+    """The state ``gwi_marginal_weights_add`` leaves after the K points of ``logw_pe (K, n_ev, n_pe)`` and ``logw_inj (K, n_inj)``,
+    added in order: ``(W_pe (n_ev, n_pe), W_inj (n_inj,), dead (n_ev + 1,) int32, n_points)`` with ``W_j = sum_k w_kj / S_k``,
+    ``w`` from :func:`draw_weights` under the masks and ``S_k`` the segment's total by ``math.fsum`` (the exact sum, rounded once);
+    a segment whose total is 0 adds nothing at that point and is counted in ``dead`` (the injection set last)."""
+    logw_pe, logw_inj = np.asarray(logw_pe, dtype=np.float64), np.asarray(logw_inj, dtype=np.float64)
+    if logw_pe.ndim != 3 or logw_inj.ndim != 2 or logw_pe.shape[0] != logw_inj.shape[0]:
+        raise ValueError("logw_pe is (K, n_ev, n_pe) and logw_inj (K, n_inj)")
+    k, n_ev, n_pe = logw_pe.shape
+    pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(n_ev, n_pe)
+    w_pe, w_inj, dead = np.zeros((n_ev, n_pe)), np.zeros(logw_inj.shape[1]), np.zeros(n_ev + 1, dtype=np.int32)
+    for p in range(k):
+        for seg in range(n_ev + 1):
+            w = draw_weights(logw_pe[p, seg], None if pe_mask is None else pe_mask[seg]) if seg < n_ev else draw_weights(logw_inj[p], inj_mask)
+            total = math.fsum(w.tolist())
+            if not (total > 0.0 and np.isfinite(total)):
+                dead[seg] += 1
+                continue
+            if seg < n_ev:
+                w_pe[seg] += w / total
+            else:
+                w_inj += w / total
+    return w_pe, w_inj, dead, k
+
+
+def _exact_integers(w):
+    """The non-negative finite doubles ``w`` as Python integers in units of one common power of two: ``(ints, exponent)`` with
+    ``w_j == ints[j] * 2**exponent`` exactly."""
+    m, e = np.frexp(np.asarray(w, dtype=np.float64))
+    mant = np.ldexp(m, 53).astype(np.int64)  # (53 bits: exact)
+    e = e.astype(np.int64) - 53
+    low = int(e[mant > 0].min()) if np.any(mant > 0) else 0
+    return [int(a) << (int(b) - low) if a else 0 for a, b in zip(mant.tolist(), e.tolist())], low
+
+
+def weighted_quantiles_reference(W, order, x, levels):
+    """Quantiles and moments of ONE segment and ONE quantity under the marginal weights ``W (n,)``: ``order (n,)`` is a permutation
+    of the sample indices along which ``x (n,)`` does not decrease (``np.argsort(x, kind="stable")``), ``levels`` lie in ``[0, 1]``.
+    Rule "inverted CDF" with an EXACT prefix (integer arithmetic on the doubles' bits: the exact answer, not a second rounding):
+    the sample at the smallest rank ``r`` with ``C_r >= p C_last`` and ``W > 0`` there, ``C_r = W[order[0]] + ... + W[order[r]]``;
+    ``-1`` without weight.  ``p = 0`` is the smallest value with weight, ``p = 1`` the largest.  Returns ``(idx (Q,) int32, (m1, m2),
+    mass)`` with ``m1 = sum W x``, ``m2 = sum W x^2`` (``math.fsum`` of the rounded products) and ``mass = C_last`` rounded once."""
+    W, x = np.asarray(W, dtype=np.float64).ravel(), np.asarray(x, dtype=np.float64).ravel()
+    order = np.asarray(order).ravel().astype(np.int64)
+    levels = np.asarray(levels, dtype=np.float64).ravel()
+    if not (W.size == x.size == order.size) or not np.array_equal(np.sort(order), np.arange(W.size)):
+        raise ValueError("order must be a permutation of the segment's sample indices")
+    if np.any(~np.isfinite(W)) or np.any(W < 0.0):
+        raise ValueError("W must be finite and non-negative")
+    if np.any(~((levels >= 0.0) & (levels <= 1.0))):
+        raise ValueError("levels must lie in [0, 1]")
+    ws, xs = W[order], x[order]
+    if np.any(np.diff(xs) < 0.0):
+        raise ValueError("x decreases along the order")
+    idx = np.full(levels.size, -1, dtype=np.int32)
+    live = np.nonzero(ws > 0.0)[0]
+    if live.size == 0:
+        return idx, (0.0, 0.0), 0.0
+    ints, low = _exact_integers(ws[live])
+    cum = list(itertools.accumulate(ints))  # exact inclusive prefixes over the ranks with weight
+    c_last = cum[-1]
+    for q, p in enumerate(levels.tolist()):
+        num, den = float(p).as_integer_ratio()
+        target = -((-num * c_last) // den)  # the smallest integer >= p C_last: C_r >= p C_last exactly when C_r >= it
+        idx[q] = order[live[min(bisect.bisect_left(cum, target), live.size - 1)]]
+    m1, m2 = math.fsum((ws * xs).tolist()), math.fsum((ws * xs * xs).tolist())
+    mass = c_last / 2 ** (-low) if low < 0 else float(c_last * 2**low)  # (true division of integers rounds once)
+    return idx, (m1, m2), float(mass)

@@ -1138,6 +1138,92 @@ class NativePopulationLikelihood:
                                                      dead.ctypes.data_as(i32)))
         return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead
 
+    def _whole_catalog(self, what, need):
+        if self.world > 1:
+            raise N.NativeEngineError(f"GWI_ERR_UNSUPPORTED: {what}: this engine holds one shard of the catalog; {need} the global set")
+
+    def marginal_weights_reset(self):
+        """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""
+        self._whole_catalog("marginal_weights_reset", "the injection weights need")
+        self._check(self.lib.gwi_marginal_weights_reset(self.handle))
+
+    def marginal_weights_add(self, thetas):
+        """Adds the points ``thetas`` -- ``(n_theta,)`` or ``(k, n_theta)``, in order -- onto the marginal weights the engine keeps in
+        HBM (``gwi_marginal_weights_add``; semantics: :func:`gwinferno_amd.draws.marginal_weights_reference`): ``W_i += w_i / S`` per
+        sample under the masks of :meth:`set_draw_mask`.  Nothing travels back.  The sums stay until :meth:`marginal_weights_reset`;
+        changing the mask does not reset them.  Not available on an engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("marginal_weights_add", "the injection weights need")
+        thetas = N.f64(thetas)
+        if thetas.ndim not in (1, 2) or thetas.shape[-1] != self.n_theta:
+            raise ValueError(f"thetas has shape {thetas.shape}; expected ({self.n_theta},) or (k, {self.n_theta})")
+        thetas = thetas.reshape(-1, self.n_theta)
+        self._check(self.lib.gwi_marginal_weights_add(self.handle, N.as_dp(thetas), thetas.shape[0]))
+
+    def marginal_weights(self, weights=True):
+        """``(W_pe (n_ev, n_pe), W_inj (n_inj,), dead (n_ev + 1,) int32, n_points)``: the marginal weights read back once
+        (``gwi_marginal_weights_read``; 8 bytes per sample, whatever the number of points added), per segment (the injection set
+        last) the number of points at which nothing had weight, and the number of points added since the last reset.
+        ``weights=False`` leaves the two arrays on the device (``None`` in their places)."""
+        self._whole_catalog("marginal_weights", "the injection weights need")
+        pe, inj = (np.zeros((self.n_ev, self.n_pe)), np.zeros(self.n_inj)) if weights else (None, None)
+        dead, n = np.zeros(self.n_ev + 1, dtype=np.int32), C.c_int64(0)
+        self._check(self.lib.gwi_marginal_weights_read(self.handle, N.as_dp(pe), N.as_dp(inj), dead.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        return pe, inj, dead, int(n.value)
+
+    def set_quantile_columns(self, pe_values=None, inj_values=None):
+        """The quantities :meth:`weighted_quantiles` selects from (``gwi_set_quantile_columns``): ``pe_values (n_cols, n_ev, n_pe)``
+        and ``inj_values (n_cols, n_inj)``, finite; ``None`` leaves that set out, not both; ``1 <= n_cols <= 8``.  The sort order of
+        every segment is made here (``np.argsort(kind="stable")``: ties stay in sample order) and copied to HBM with the values,
+        once: it does not depend on theta.  Not available on an engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("set_quantile_columns", "the injection quantiles need")
+        if pe_values is None and inj_values is None:
+            raise ValueError("pe_values and inj_values are both None")
+
+        def one(v, shape, name):
+            if v is None:
+                return None, None
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.ndim != len(shape) + 1 or v.shape[1:] != shape:
+                raise ValueError(f"{name} has shape {v.shape}; expected (n_cols, {', '.join(str(s) for s in shape)})")
+            if not np.all(np.isfinite(v)):
+                raise ValueError(f"{name} holds values that are not finite")
+            return v, np.ascontiguousarray(np.argsort(v, axis=-1, kind="stable"), dtype=np.int32)
+
+        pe, order_pe = one(pe_values, (self.n_ev, self.n_pe), "pe_values")
+        inj, order_inj = one(inj_values, (self.n_inj,), "inj_values")
+        if pe is not None and inj is not None and pe.shape[0] != inj.shape[0]:
+            raise ValueError(f"pe_values holds {pe.shape[0]} columns, inj_values {inj.shape[0]}")
+        n_cols = (pe if pe is not None else inj).shape[0]
+        i32 = C.POINTER(C.c_int32)
+        self._quant_shape = None
+        self._check(self.lib.gwi_set_quantile_columns(self.handle, n_cols, N.as_dp(pe) if pe is not None else None, order_pe.ctypes.data_as(i32) if pe is not None else None,
+                                                      N.as_dp(inj) if inj is not None else None, order_inj.ctypes.data_as(i32) if inj is not None else None))
+        self._quant_shape = (n_cols, pe is not None, inj is not None)
+
+    def weighted_quantiles(self, levels):
+        """Weighted quantiles and moments under the marginal weights, on the device (``gwi_weighted_quantiles``; semantics:
+        :func:`gwinferno_amd.draws.weighted_quantiles_reference`).  ``levels`` are 1 to 32 numbers in ``[0, 1]``.  Returns ``(idx_pe
+        (n_ev, n_cols, Q), idx_inj (n_cols, Q), moments_pe (n_ev, n_cols, 2), moments_inj (n_cols, 2), mass (n_ev + 1,))``: int32
+        sample indices within the segment (-1 where nothing has weight; ``None`` for a set without columns), ``(sum W x, sum W
+        x^2)`` and per segment ``sum W`` (the injection set last), so that ``mean = m1 / mass``.  Only these travel back."""
+        self._whole_catalog("weighted_quantiles", "the injection quantiles need")
+        levels = np.ascontiguousarray(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        if levels.ndim != 1:
+            raise ValueError(f"levels has shape {levels.shape}; expected (n_levels,)")
+        shape = getattr(self, "_quant_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        mass = np.zeros(self.n_ev + 1)
+        if shape is None:  # the library says so
+            self._check(self.lib.gwi_weighted_quantiles(self.handle, N.as_dp(levels), levels.size, None, None, None, None, N.as_dp(mass)))
+            raise N.NativeEngineError("GWI_ERR_INVALID: weighted_quantiles: no columns are set (set_quantile_columns)")
+        n_cols, with_pe, with_inj = shape
+        idx_pe, mom_pe = (np.full((self.n_ev, n_cols, levels.size), -1, dtype=np.int32), np.zeros((self.n_ev, n_cols, 2))) if with_pe else (None, None)
+        idx_inj, mom_inj = (np.full((n_cols, levels.size), -1, dtype=np.int32), np.zeros((n_cols, 2))) if with_inj else (None, None)
+        self._check(self.lib.gwi_weighted_quantiles(self.handle, N.as_dp(levels), levels.size, idx_pe.ctypes.data_as(i32) if with_pe else None,
+                                                    idx_inj.ctypes.data_as(i32) if with_inj else None, N.as_dp(mom_pe) if with_pe else None, N.as_dp(mom_inj) if with_inj else None,
+                                                    N.as_dp(mass)))
+        return idx_pe, idx_inj, mom_pe, mom_inj, mass
+
     def selftime(self, theta, total_inj, n_iter=1000, min_neff_cut=True):
         """Mean seconds per evaluation of a C-side loop of sequential gwi_eval calls (diagnostic)."""
         opt = self._options(total_inj, None, False, min_neff_cut, False)

@@ -362,3 +362,109 @@ def reweighted_event_posteriors(eng, thetas, pe_values, edges, inj_values=None, 
                 entry["n_points"]["predicted"] = int(k - dead[n_ev])
             result[p] = entry
     return result
+
+
+def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), inj_values=None, pedata=None, injdata=None, param_names=None, m1min=None, m2min=None,
+                             mmax=None, backend="device", return_weights=False):
+    """Credible intervals of the population-informed posterior of every event, marginalised over K posterior hyper-parameter draws:
+    per event and quantity the weighted quantiles of ``levels`` (rule "inverted CDF": the value of a sample, never an interpolation),
+    the mean and the standard deviation under the marginal posterior weight ``W_i = sum_k w_ki / S_k`` of the event's samples,
+    ``w_i = p(x_i | theta_k) / prior_i`` -- the table population papers print for ``m1``, ``q`` and ``chi_eff`` -- and the same for the
+    predicted detected distribution from the injections.  On the device (``eng.marginal_weights_add``, ``eng.weighted_quantiles``)
+    the weights never leave HBM; only sample indices and two sums per quantity come back.
+
+    ``thetas`` is ``(K, n_theta)`` in the engine's layout.  ``pe_values`` maps a name to the ``(n_ev, n_pe)`` array of the quantity
+    (any derived quantity, e.g. ``m2 = q * m1``), ``inj_values`` the same names to ``(n_inj,)`` arrays (``None``: no predicted
+    distribution); with ``pe_values=None`` the quantities are read from ``pedata`` / ``injdata`` by ``param_names``.  ``param_names``
+    selects and orders the names (default: the keys of ``pe_values``; at most 8).  The mass cuts are
+    :func:`reweighted_event_posteriors`': with all of ``m1min, m2min, mmax`` given and both data dictionaries at hand they become
+    the engine's draw mask, otherwise the mask the engine holds stays.  The device backend resets the engine's marginal weights
+    first.  ``backend="host"`` runs the NumPy statement (:func:`gwinferno_amd.draws.marginal_weights_reference`,
+    :func:`gwinferno_amd.draws.weighted_quantiles_reference`) on ``eng.log_weights`` under the masks given here (none without the
+    cuts): the statement the kernels are tested against, not a fall-back.
+
+    Returns a dict: ``names``; ``levels``; ``quantiles (n_ev, C, Q)``, ``mean`` and ``sd (n_ev, C)``; ``dead (n_ev,)``, the points at
+    which the event had no weight; ``n_points``; with ``inj_values`` also ``quantiles_inj (C, Q)``, ``mean_inj``, ``sd_inj (C,)``
+    and ``dead_inj``; with ``return_weights=True`` also ``weights`` and ``weights_inj``, the ``W`` arrays.  A segment without weight
+    gives NaN."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or not 1 <= levels.size <= 32:
+        raise ValueError("between 1 and 32 levels can be asked for in one query")
+    if not np.all((levels >= 0.0) & (levels <= 1.0)):
+        raise ValueError("levels must lie in [0, 1]")
+    if pe_values is None:
+        if pedata is None or param_names is None:
+            raise ValueError("without pe_values, pedata and param_names name the quantities")
+        pe_values = pedata
+        if inj_values is None and injdata is not None:
+            inj_values = injdata
+    names = list(param_names) if param_names is not None else list(pe_values)
+    if not 1 <= len(names) <= 8:
+        raise ValueError("between 1 and 8 quantities can be summarised in one pass")
+    n_ev, n_pe, n_inj = eng.n_ev, eng.n_pe, eng.n_inj
+    x_pe = np.empty((len(names), n_ev, n_pe))
+    x_inj = np.empty((len(names), n_inj)) if inj_values is not None else None
+    for c, p in enumerate(names):
+        v = np.asarray(pe_values[p], dtype=np.float64)
+        if v.shape != (n_ev, n_pe):
+            raise ValueError(f"pe_values[{p!r}] has shape {v.shape}, the engine's sample set {(n_ev, n_pe)}")
+        x_pe[c] = v
+        if x_inj is not None:
+            v = np.asarray(inj_values[p], dtype=np.float64)
+            if v.shape != (n_inj,):
+                raise ValueError(f"inj_values[{p!r}] has shape {v.shape}, the engine's injection set {(n_inj,)}")
+            x_inj[c] = v
+    if not np.all(np.isfinite(x_pe)) or (x_inj is not None and not np.all(np.isfinite(x_inj))):
+        raise ValueError("the quantities must be finite")
+    cuts = (m1min, m2min, mmax)
+    masks = (None, None)
+    if pedata is not None and injdata is not None and all(c is not None for c in cuts):
+        masks = D.mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+        if backend == "device":
+            eng.set_draw_mask(*masks)
+    elif any(c is not None for c in cuts) and not all(c is not None for c in cuts):
+        raise ValueError("m1min, m2min and mmax are given together or not at all")
+    n_cols, n_q = len(names), levels.size
+    if backend == "device":
+        eng.set_quantile_columns(x_pe, x_inj)
+        eng.marginal_weights_reset()
+        eng.marginal_weights_add(thetas)
+        idx_pe, idx_inj, mom_pe, mom_inj, mass = eng.weighted_quantiles(levels)
+        w_pe, w_inj, dead, n_points = eng.marginal_weights(weights=return_weights)
+    else:
+        lw = [eng.log_weights(th) for th in thetas]
+        w_pe, w_inj, dead, n_points = D.marginal_weights_reference(np.stack([a for a, _ in lw]), np.stack([b for _, b in lw]), masks[0], masks[1])
+        idx_pe, mom_pe, mass = np.full((n_ev, n_cols, n_q), -1, dtype=np.int32), np.zeros((n_ev, n_cols, 2)), np.zeros(n_ev + 1)
+        idx_inj, mom_inj = (np.full((n_cols, n_q), -1, dtype=np.int32), np.zeros((n_cols, 2))) if x_inj is not None else (None, None)
+        for c in range(n_cols):
+            for ev in range(n_ev):
+                idx_pe[ev, c], mom_pe[ev, c], mass[ev] = D.weighted_quantiles_reference(w_pe[ev], np.argsort(x_pe[c, ev], kind="stable"), x_pe[c, ev], levels)
+            if x_inj is not None:
+                idx_inj[c], mom_inj[c], mass[n_ev] = D.weighted_quantiles_reference(w_inj, np.argsort(x_inj[c], kind="stable"), x_inj[c], levels)
+
+    def summary(idx, values, mom, m):
+        """values (..., C, n) looked up at idx (..., C, Q); the mean and sd from the two sums and the mass m (...)"""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            q = np.where(idx >= 0, np.take_along_axis(values, np.maximum(idx, 0).astype(np.int64), axis=-1), np.nan)
+            mean = mom[..., 0] / m[..., None]
+            sd = np.sqrt(np.maximum(mom[..., 1] / m[..., None] - mean * mean, 0.0))
+        nothing = ~(m > 0.0)
+        mean[nothing], sd[nothing] = np.nan, np.nan
+        return q, mean, sd
+
+    out = {"names": names, "levels": levels, "n_points": n_points, "dead": np.asarray(dead[:n_ev]).copy()}
+    out["quantiles"], out["mean"], out["sd"] = summary(idx_pe, np.moveaxis(x_pe, 0, 1), mom_pe, mass[:n_ev])
+    if x_inj is not None:
+        out["quantiles_inj"], out["mean_inj"], out["sd_inj"] = summary(idx_inj, x_inj, mom_inj, mass[n_ev : n_ev + 1].reshape(()))
+        out["dead_inj"] = int(dead[n_ev])
+    if return_weights:
+        out["weights"], out["weights_inj"] = w_pe, w_inj
+    return out

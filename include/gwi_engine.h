@@ -450,6 +450,58 @@ gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k
                                    double* hist_inj /* in/out [n_cols][n_bins] */, int32_t* dead /* in/out [n_ev + 1] */);
 void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches);
 
+/* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
+ * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is
+ * gwinferno_amd/draws.py: marginal_weights_reference, weighted_quantiles_reference).
+ *
+ * Segments, lw_i, the masks, M, w_i = exp(lw_i - M) and the segment total S are gwi_draw_indices' and gwi_weighted_histograms'.
+ * Marginal weights: W_i += w_i / S, one point after another in the order of the call -- one running double per sample in HBM,
+ * n_ev n_pe + n_inj of them.  A segment whose S is 0 or not finite adds nothing; dead[segment] is incremented instead (segment n_ev
+ * is the injection set).  n_points counts the points added.  W, dead and n_points are state of the handle: zero at creation and
+ * after gwi_marginal_weights_reset(), released with the handle; they do not depend on any quantile column (one accumulation serves
+ * any number of column sets) and changing the draw mask does NOT reset them: a mask applies to the points added while it is set.
+ *
+ * Quantile columns: 1 <= n_cols <= 8 quantities.  Quantity c supplies its values x_pe[c][n_ev][n_pe] and / or x_inj[c][n_inj] and
+ * per segment a sort order, an int32 permutation of the segment's sample indices along which the values do not decrease
+ * (order_pe[c][n_ev][n_pe], order_inj[c][n_inj]).  The library does not sort: ties are in the caller's order.  Either set may be
+ * NULL (it is then left out), not both.  Values and orders are checked on the host and copied to HBM once; a new call replaces them.
+ *
+ * Quantile of level p in [0, 1], rule "inverted CDF": with C_r the inclusive prefix of W along the order and C_last the last prefix,
+ * the sample at the smallest rank r with C_r >= p C_last and W > 0 at that rank; the last rank with weight when rounding runs past
+ * the end; -1 when the segment has no weight.  p = 0 is the smallest value with weight, p = 1 the largest.  The entry returns the
+ * sample's index within its segment.  Moments, per (segment, column), summed along the order: m1 = sum W_i x_i, m2 = sum W_i x_i^2;
+ * mass[segment] = C_last (of column 0's order), so that mean = m1 / mass and variance = m2 / mass - mean^2.
+ *
+ * Every sum has a fixed shape -- rank order inside a tile of 1 024 ranks, then tile order, then, for W, point order on one stream --
+ * and there are no atomics: the bits of W, of the indices and of the moments are a pure function of the arguments and of the order
+ * of the points.  A request split over calls (2 + 1, 1 + 1 + 1) gives the bits of one call; two handles of one model give the same.
+ *
+ * gwi_marginal_weights_add(): adds the k >= 0 points thetas[k][n_theta]; k is not bound by the batch limit.
+ * gwi_marginal_weights_read(): copies W (pe_w[n_ev][n_pe] and inj_w[n_inj]; either may be NULL), dead[n_ev + 1] and n_points back:
+ * 8 bytes per sample, whatever the number of points.
+ * gwi_weighted_quantiles(): 1 <= n_levels <= 32 levels; idx_pe[n_ev][n_cols][n_levels] and moments_pe[n_ev][n_cols][2] (ignored
+ * without PE columns), idx_inj[n_cols][n_levels] and moments_inj[n_cols][2] (ignored without injection columns), mass[n_ev + 1]
+ * (0 for a set that is left out).  With nothing accumulated every index is -1 and mass is 0.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for null pointers, k < 0, n_cols outside 1 ... 8, n_levels outside 1 ... 32, a level
+ * that is NaN or outside [0, 1], an order that is no permutation of its segment, values that are not finite or decrease along the
+ * order, a quantile call before the columns are set and a host-only handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard, as
+ * gwi_draw_indices.
+ *
+ * gwi_quantile_times(): DIAGNOSTIC ONLY, for tools/weighted_quantiles_time.py: of the calling thread's last gwi_marginal_weights_add,
+ * summed over its points, the wall time of the (blocking) log-weight passes and the device time (HIP events) of the draw tile / draw
+ * merge / marginal add launches; the device time of the calling thread's last gwi_weighted_quantiles (its three launches); and the
+ * number of kernel launches of the last of the two calls. */
+gwi_status gwi_marginal_weights_reset(gwi_handle h);
+gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t k);
+gwi_status gwi_marginal_weights_read(gwi_handle h, double* pe_w /* [n_ev][n_pe] or NULL */, double* inj_w /* [n_inj] or NULL */, int32_t* dead /* [n_ev + 1] */,
+                                     int64_t* n_points);
+gwi_status gwi_set_quantile_columns(gwi_handle h, int32_t n_cols, const double* x_pe /* [n_cols][n_ev][n_pe] or NULL */, const int32_t* order_pe /* like x_pe */,
+                                    const double* x_inj /* [n_cols][n_inj] or NULL */, const int32_t* order_inj /* like x_inj */);
+gwi_status gwi_weighted_quantiles(gwi_handle h, const double* levels, int32_t n_levels, int32_t* idx_pe /* [n_ev][n_cols][n_levels] */,
+                                  int32_t* idx_inj /* [n_cols][n_levels] */, double* moments_pe /* [n_ev][n_cols][2] */, double* moments_inj /* [n_cols][2] */,
+                                  double* mass /* [n_ev + 1] */);
+void gwi_quantile_times(double* logw_ms, double* add_ms, double* query_ms, int32_t* launches);
+
 /* Effective-spin catalogs (gwinferno_amd/csrc/gwi_spinprior.h; the NumPy statement is gwinferno_amd/spin_priors.py).  Stand-alone
  * entries like gwi_ingest_columns: no handle, host pointers in and out, their own stream and buffers on `device` (negative: the
  * calling thread's current device).  The calling thread's current device is the same after the call as before it.
