@@ -13,6 +13,7 @@
 #include "gwi_quant.h"
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
+#include "gwi_plan.h"
 
 #include <hip/hip_ext.h>
 
@@ -37,6 +38,10 @@
 #include <vector>
 
 using namespace gwi;
+
+// gwi_plan.h plans launches without the device headers: its copies of their constants are the same numbers
+static_assert(gwi_plan::kBlock == kBlock && gwi_plan::kGeomTilesBits == kGeomTilesBits && gwi_plan::kRegularRepShift == kRegularRepShift && gwi_plan::kPolyStride == kPolyStride,
+              "gwi_plan.h restates constants of gwi_device.h");
 
 // The two headers a scan chain is compiled from, embedded as text: what hipRTC gets when a model's term sequence has no
 // ahead-of-time instantiation (gwi_jit.h).  (.incbin searches the -I directories of the build; host pass only.)
@@ -536,20 +541,15 @@ struct gwi_engine {
   double *h_ev = nullptr, *h_ev_dev = nullptr;
   // host-final mode: per-group result rows + normaliser values in pinned host memory
   bool host_final = false;
-  // launch geometry of batched launches (K >= 4, device-final) where it differs from the single evaluation's: two trips
-  // per workgroup instead of one (gwi_create)
-  struct BatchGeometry {
-    bool distinct = false;
-    int chunk_pe = 0, chunk_inj = 0, tiles_per_event = 0, n_inj_tiles = 0, n_scan_blocks = 0, tiles_per_inj_group = 0, n_inj_groups = 0;
-  } bgeo;
-  bool use_bgeo = false;  // the pipeline being issued runs on bgeo
+  // launch geometry (gwi_plan.h): [0] the single evaluation's, [1] that of batched launches (K >= 4, device-final) where it
+  // differs ([1].distinct): two trips per workgroup instead of one
+  gwi_plan::Geometry geo[2] = {{256, 256, 1, 1, 0, 1, 1}, {}};
+  int geo_now = 0;  // which of the two the pipeline being issued runs on (set_geometry)
+  const gwi_plan::Geometry& cur() const { return geo[geo_now]; }
+  int rec_stride = 0;
   double *h_rows = nullptr, *h_rows_dev = nullptr;
   double *h_norm = nullptr, *h_norm_dev = nullptr;                    // pinned: Z_j
   unsigned long long *h_norm_stamp = nullptr, *h_norm_stamp_dev = nullptr;  // pinned: per-normaliser stamps
-  // launch geometry
-  int tiles_per_event = 1, chunk_pe = 256, n_inj_tiles = 1, chunk_inj = 256, rec_stride = 0, n_scan_blocks = 0;
-  int n_inj_groups = 1, tiles_per_inj_group = 1;
-
   size_t scan_lds_bytes = 0;
   int gacc_rep = 1;
   bool deterministic = false;   // GWI_DETERMINISTIC=1: replay mode of the shared gradient rows (scan_kernel)
@@ -864,10 +864,10 @@ bool pbatch_applies(const gwi_engine* h) {
 // Points per grid row of a pbatch launch of K points.  One row (every sample loaded once for all K points) is the least work,
 // but a tile x K points is a long workgroup: the rows are split until the launch has about eight workgroups per CU to balance
 // (config 2, K = 16: 788 tiles on 256 CUs -- one row leaves a quarter of the chip idle behind the CUs that drew four tiles).
-int pbatch_points(const gwi_engine* h, int K, int on_bgeo = -1) {
+int pbatch_points(const gwi_engine* h, int K, const gwi_plan::Geometry& g) {
   int pts = h->pbatch_pts;
   if (pts <= 0) {
-    const long long blocks = (on_bgeo < 0 ? h->use_bgeo : on_bgeo != 0) ? h->bgeo.n_scan_blocks : h->n_scan_blocks;
+    const long long blocks = g.n_scan_blocks;
     int rows = 1;
     while (rows < K && blocks * rows < 8LL * h->n_cus) rows *= 2;
     pts = (K + rows - 1) / rows;
@@ -878,16 +878,16 @@ int pbatch_points(const gwi_engine* h, int K, int on_bgeo = -1) {
 constexpr int kPbatchBalancedFrom = 8;  // points per launch from which the balanced mode is used
 // Balanced mode: how many workgroups a pbatch launch of K points gets.  One round of resident workgroups, or the next smaller
 // count with which every workgroup draws the same number of (tile, point) units: ceil(N / ceil(N / capacity)).
-int pbatch_workgroups(const gwi_engine* h, int K, int on_bgeo = -1) {
-  const long long blocks = (on_bgeo < 0 ? h->use_bgeo : on_bgeo != 0) ? h->bgeo.n_scan_blocks : h->n_scan_blocks;
-  const long long n_units = blocks * K, capacity = (long long)h->n_cus * h->pbatch_wgs_per_cu;
+int pbatch_workgroups(const gwi_engine* h, int K) {
+  const long long n_units = (long long)h->cur().n_scan_blocks * K, capacity = (long long)h->n_cus * h->pbatch_wgs_per_cu;
   const long long per_wg = (n_units + capacity - 1) / capacity;
   return (int)((n_units + per_wg - 1) / per_wg);
 }
 
 gwi_status launch_scan(gwi_handle h, bool logw, int K = 1, bool batch = false) {
   if (logw) h->aql_now = false;  // the log-weight variant is another kernel and always goes through the HIP stream
-  const int grid = (h->use_bgeo && !logw ? h->bgeo.n_scan_blocks : h->n_scan_blocks) + (logw ? 0 : h->spec.n_norms);  // the first n_norms workgroups integrate the normaliser grids
+  // the first n_norms workgroups integrate the normaliser grids (a log-weight launch has none and runs on the single evaluation's geometry: fill_log_weights)
+  const int grid = h->cur().n_scan_blocks + (logw ? 0 : h->spec.n_norms);
   // two-pass repeats and the replay mode run the SAFE instantiation (spline models; it takes single and batched launches)
   // ... and so does any replica count other than the 16 the regular kernels are built for (GWI_GACC_REP)
   const bool safe = !logw && h->variant->has(jit::kSafe) && (h->generic || h->kargs.two_pass || h->kargs.deterministic || h->gacc_rep != (1 << kRegularRepShift));
@@ -897,7 +897,7 @@ gwi_status launch_scan(gwi_handle h, bool logw, int K = 1, bool batch = false) {
   // (balanced mode from eight points on: below that the shared loads no longer pay for the staging -- config 2, K = 4: 18.5 us
   // against 17.4 with one grid row per point, K = 2: 12.8 against 11.3; profiles/round6/balanced_ab.txt)
   const bool balanced = h->pbatch_balanced && K >= kPbatchBalancedFrom;
-  const bool pb = batch && !safe && !logw && pbatch_applies(h) && (balanced || pbatch_points(h, K) > 1);
+  const bool pb = batch && !safe && !logw && pbatch_applies(h) && (balanced || pbatch_points(h, K, h->cur()) > 1);
   h->scan_role = logw ? jit::kLogw : (safe ? jit::kSafe : (pb ? jit::kPbatch : (batch ? jit::kBatch : jit::kScan)));
   ScanFn fn = h->variant->fn[h->scan_role];
   h->scan_is_safe = safe;
@@ -911,7 +911,7 @@ gwi_status launch_scan(gwi_handle h, bool logw, int K = 1, bool batch = false) {
       GWI_HIP(hipGetLastError());
       return GWI_OK;
     }
-    const int pts = pbatch_points(h, K);
+    const int pts = pbatch_points(h, K, h->cur());
     h->kargs.pbatch_pts = pts;
     launch_timed(h, 0, fn, dim3(grid - h->spec.n_norms + h->spec.n_norms * K, (K + pts - 1) / pts), dim3(kBlock), 0, h->sblock, used);
     GWI_HIP(hipGetLastError());
@@ -974,7 +974,8 @@ long g_phase_calls = 0;
 
 // Arguments of the combine / final launches.  Nothing in them changes from one evaluation to the next (the completion
 // stamp travels through a device word the scan writes): on the AQL path they sit in two persistent kernel-argument slots.
-TailArgs tail_args(const gwi_engine* h, double* record_dev, bool batch_geometry = false) {
+TailArgs tail_args(const gwi_engine* h, double* record_dev, int which_geo = 0) {
+  const gwi_plan::Geometry& g = h->geo[which_geo];
   TailArgs ta;
   std::memset(&ta, 0, sizeof(ta));
   ta.partials = h->d_partials;
@@ -989,13 +990,13 @@ TailArgs tail_args(const gwi_engine* h, double* record_dev, bool batch_geometry 
   ta.seq_ptr = h->d_seq;
   ta.redo_ptr = h->d_seq + 1;
   ta.n_ev = (int)h->n_ev;
-  ta.tiles_per_event = batch_geometry ? h->bgeo.tiles_per_event : h->tiles_per_event;
-  ta.n_inj_tiles = batch_geometry ? h->bgeo.n_inj_tiles : h->n_inj_tiles;
-  ta.n_inj_groups = batch_geometry ? h->bgeo.n_inj_groups : h->n_inj_groups;
-  ta.tiles_per_inj_group = batch_geometry ? h->bgeo.tiles_per_inj_group : h->tiles_per_inj_group;
+  ta.tiles_per_event = g.tiles_per_event;
+  ta.n_inj_tiles = g.n_inj_tiles;
+  ta.n_inj_groups = g.n_inj_groups;
+  ta.tiles_per_inj_group = g.tiles_per_inj_group;
   ta.n_theta = h->spec.n_theta;
   ta.rec_stride = h->rec_stride;
-  ta.n_scan_blocks = batch_geometry ? h->bgeo.n_scan_blocks : h->n_scan_blocks;
+  ta.n_scan_blocks = g.n_scan_blocks;
   ta.n_norms = h->spec.n_norms;
   ta.record_len = record_len(h);
   ta.n_pe = (double)h->n_pe;
@@ -1005,13 +1006,14 @@ TailArgs tail_args(const gwi_engine* h, double* record_dev, bool batch_geometry 
   return ta;
 }
 
-// which launch geometry the scan's argument block describes: the batched one (bgeo) or the single evaluation's
+// which launch geometry the scan's argument block describes: the batched one (geo[1]) or the single evaluation's
 void set_geometry(gwi_engine* h, bool batched) {
-  h->use_bgeo = batched;
-  h->kargs.tiles_per_event = batched ? h->bgeo.tiles_per_event : h->tiles_per_event;
-  h->kargs.chunk_pe = batched ? h->bgeo.chunk_pe : h->chunk_pe;
-  h->kargs.n_inj_tiles = batched ? h->bgeo.n_inj_tiles : h->n_inj_tiles;
-  h->kargs.chunk_inj = batched ? h->bgeo.chunk_inj : h->chunk_inj;
+  h->geo_now = batched ? 1 : 0;
+  const gwi_plan::Geometry& g = h->cur();
+  h->kargs.tiles_per_event = g.tiles_per_event;
+  h->kargs.chunk_pe = g.chunk_pe;
+  h->kargs.n_inj_tiles = g.n_inj_tiles;
+  h->kargs.chunk_inj = g.chunk_inj;
   ScanHead& hd = h->sblock.head;
   hd.geom = (unsigned)h->kargs.n_ev | ((unsigned)h->kargs.tiles_per_event << kGeomEventBits) | ((unsigned)h->kargs.n_norms << (kGeomEventBits + kGeomTilesBits));
   hd.chunks = pack_chunk(h->kargs.chunk_pe) | (pack_chunk(h->kargs.chunk_inj) << 16);
@@ -1036,11 +1038,11 @@ gwi_status run_pipeline_once(gwi_handle h, const double* theta, double* record_d
   const int n_theta = h->spec.n_theta;
   h->kargs.square = square ? 1 : 0;
   // tile references: row 0 belongs to single evaluations, rows 1..max_batch to the points of a batch on the single
-  // evaluation's tiling, rows 1 + max_batch.. to the points of a batch on the batched launches' own tiling (bgeo: other tile
+  // evaluation's tiling, rows 1 + max_batch.. to the points of a batch on the batched launches' own tiling (geo[1]: other tile
   // boundaries, so another tile's maximum).  Row k of a block keeps meaning "point k of the batch": a vectorised caller
   // should keep chain k in slot k from one call to the next (a reference left by another chain is still only a range
   // question -- a miss costs one repeat, never a wrong bit).
-  h->kargs.nref_row0 = batch ? ((K >= 4 && h->bgeo.distinct) ? 1 + h->max_batch : 1) : 0;
+  h->kargs.nref_row0 = batch ? ((K >= 4 && h->geo[1].distinct) ? 1 + h->max_batch : 1) : 0;
   // plain evaluations go through the engine's AQL queue; whatever must be ordered with other work on the HIP stream
   // (batched theta uploads, the sharded path's exchange behind record_dev) stays on the stream, and so does everything
   // after gwi_set_timing(h, 2)
@@ -1080,8 +1082,8 @@ gwi_status run_pipeline_once(gwi_handle h, const double* theta, double* record_d
   }
   const unsigned gy = batch ? (unsigned)K : 1u;
   // batched device-final launches run on their own geometry where gwi_create found one (two trips per workgroup)
-  set_geometry(h, batch && K >= 4 && h->bgeo.distinct);
-  TailArgs ta = tail_args(h, record_dev, h->use_bgeo);
+  set_geometry(h, batch && K >= 4 && h->geo[1].distinct);
+  TailArgs ta = tail_args(h, record_dev, h->geo_now);
   if (batch && K >= 4) {
     // Many points per launch: sum over groups on the DEVICE whatever the problem size.  Host-final mode publishes one row
     // per (group, point) -- K x (N_ev + injection groups) rows of two small posted PCIe writes each, which is what a
@@ -1277,7 +1279,7 @@ gwi_status aql_wait_slow(gwi_handle h, Ready ready, const char* what) {
                   ", evaluation " + std::to_string((unsigned long long)h->seq) + ", doorbell rung again: " + (rung_again ? "yes" : "no") + "; normaliser stamps";
           for (int j = 0; j < h->spec.n_norms && j < 16; ++j) state += " " + std::to_string((unsigned long long)h->h_norm_stamp[j]) + ":" + std::to_string(h->h_norm[j]);
           state += "; redo word " + std::to_string((unsigned long long)*reinterpret_cast<volatile unsigned long long*>(h->h_redo)) + "; kernel " + (h->variant ? h->variant->name : "?") +
-                   ", role " + std::to_string(h->scan_role) + ", blocks " + std::to_string(h->n_scan_blocks) + ")";
+                   ", role " + std::to_string(h->scan_role) + ", blocks " + std::to_string(h->geo[0].n_scan_blocks) + ")";
         }
         return fail(h, GWI_ERR_TIMEOUT, std::string(what) + " did not arrive from the AQL queue within 10 s" + state);
       }
@@ -1515,7 +1517,7 @@ void assemble(const gwi_engine* h, const double* records, int n_ranks, const gwi
 // Host-final mode: poll every group's stamp, then do what final_kernel does (fixed summation order)
 // into h_record so that assemble() is shared with the device-final and sharded paths.
 gwi_status wait_for_rows(gwi_handle h, int K) {
-  const int n_groups = (int)h->n_ev + h->n_inj_groups;
+  const int n_groups = (int)h->n_ev + h->geo[0].n_inj_groups;
   const int n_theta = h->spec.n_theta, n_lines = (3 + n_theta + 6) / 7, stride = 8 * n_lines;
   const size_t total_lines = (size_t)n_groups * K * n_lines;
   // every 64-byte line carries the evaluation's sequence number in its eighth slot
@@ -1586,9 +1588,9 @@ gwi_status wait_for_rows(gwi_handle h, int K) {
       for (int p = 0; p < n_theta; ++p) gpe[p] += row[3 + p];
     }
     double M = -INFINITY;
-    for (int j = 0; j < h->n_inj_groups; ++j) M = std::fmax(M, rows[(size_t)(n_ev + j) * stride]);
+    for (int j = 0; j < h->geo[0].n_inj_groups; ++j) M = std::fmax(M, rows[(size_t)(n_ev + j) * stride]);
     double S1 = 0.0, S2 = 0.0;
-    for (int j = 0; j < h->n_inj_groups; ++j) {
+    for (int j = 0; j < h->geo[0].n_inj_groups; ++j) {
       unpack(n_ev + j);
       const double mj = row[0];
       const double f = (mj == -INFINITY) ? 0.0 : std::exp(mj - M);
@@ -1928,7 +1930,7 @@ static void setup_aql(gwi_engine* h, const hipDeviceProp_t& prop) {
   if (!aql::open_queue(dev, h->aq, h->aql_note)) return;
   if (have_batch_kernel && sizeof(ThetaBlock) * (size_t)h->max_batch <= aql::kExtraBytes) {
     for (int ev = 0; ev < 2; ++ev) {
-      TailArgs tb = tail_args(h, nullptr, h->bgeo.distinct);
+      TailArgs tb = tail_args(h, nullptr, h->geo[1].distinct ? 1 : 0);
       tb.host_rows = nullptr;
       tb.publish_events = ev;
       h->aq_tail_batch[ev] = aql::stage_args(h->aq, aql::kSlots - 2 - ev, &tb, sizeof(tb));
@@ -1950,55 +1952,33 @@ static void setup_aql(gwi_engine* h, const hipDeviceProp_t& prop) {
   h->aql_note = "active";
 }
 
-// gwi_create / gwi_create_ingest: the columns either come from the host ready-made (pe_cols / inj_cols) or are computed
-// on the device from raw sources by the two setup programs (gwi_ingest.h)
-static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols, int64_t n_ev, int64_t n_pe, const double* const* inj_cols, int64_t n_inj,
-                              int32_t device, gwi_handle* out, const gwi_ingest_program* ing_pe, const gwi_ingest_program* ing_inj) {
-  if (!out) return GWI_ERR_INVALID;
-  *out = nullptr;
-  const bool ingest = ing_pe != nullptr;
-  if (!spec || n_ev < 0 || n_pe < 1 || n_inj < 0) return GWI_ERR_INVALID;
-  if (ingest ? !ing_inj : (!pe_cols || !inj_cols)) return GWI_ERR_INVALID;
-  int n_dev = 0;
-  if (device != GWI_DEVICE_HOST_ONLY && (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1)) return GWI_ERR_NO_DEVICE;
-  gwi_engine* h = new (std::nothrow) gwi_engine();
-  if (!h) return GWI_ERR_INVALID;
-  *out = h;  // returned even on failure so gwi_last_error() can explain; caller must gwi_destroy()
-  gwi_status st = validate_spec(h, spec);
-  if (st != GWI_OK) return st;
-  h->spec = *spec;
-  if (device == GWI_DEVICE_HOST_ONLY) {
-    h->host_only = true;
-    h->n_ev = n_ev;
-    h->n_pe = n_pe;
-    h->n_inj = n_inj;
-    for (int j = 0; j < spec->n_norms; ++j) h->spec.norms[j].tw = h->spec.norms[j].lb = h->spec.norms[j].l1 = h->spec.norms[j].us = nullptr;
-    std::memset(&h->kargs, 0, sizeof(h->kargs));
-    return GWI_OK;
-  }
-  if (device < 0) {
-    GWI_HIP(hipGetDevice(&h->device));
-  } else {
-    if (device >= n_dev) return fail(h, GWI_ERR_NO_DEVICE, "device index out of range");
-    h->device = device;
-  }
-  GWI_HIP(hipSetDevice(h->device));
-  hipDeviceProp_t prop;
-  GWI_HIP(hipGetDeviceProperties(&prop, h->device));
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(h, GWI_ERR_NO_DEVICE, std::string("engine is built for gfx950 only; device reports ") + prop.gcnArchName);
-  h->n_cus = prop.multiProcessorCount;
-  // ---- the scan kernel of this product of terms: an ahead-of-time chain (kVariants), else a chain compiled now for exactly
-  // this sequence (gwi_jit.h: hipRTC, cached on disk), else -- hipRTC missing, GWI_JIT=0 -- the generic kernel
-  auto env_on = [](const char* name) {
-    const char* e = std::getenv(name);
-    return e && std::atoi(e) != 0;
-  };
-  const bool force_generic = env_on("GWI_FORCE_GENERIC");  // tests / measurements: the generic kernel for a model that has a compiled chain
-  const bool force_jit = env_on("GWI_FORCE_JIT");          // ... a run-time compiled chain for a model that has an ahead-of-time one
+// ---- gwi_create / gwi_create_ingest: the columns either come from the host ready-made (pe_cols / inj_cols) or are computed
+// on the device from raw sources by the two setup programs (gwi_ingest.h).  create_impl runs the phases below in order; on
+// failure the handle stays with the caller (gwi_last_error, gwi_destroy), whatever the phases allocated so far in it.
+
+// what the phases hand to one another
+struct Creation {
+  const gwi_spec* spec;
+  const double* const* pe_cols;
+  const double* const* inj_cols;
+  const gwi_ingest_program *ing_pe, *ing_inj;
+  long long n_ev, n_pe, n_inj;
+  gwi_plan::Knobs knobs;
+  std::vector<int> narrow_term;                                       // per column: the first narrow spline term reading it (validate_spec: only such terms do)
+  std::vector<const double*> tab_pe, tab_inj;                         // per column: its array in HBM
+  std::vector<const double*> over_pe, over_inj, over_pe1, over_inj1;  // per term: the knot coordinates that stand in for its cols[0] / cols[1]
+  bool has_spline = false;                                            // the scan keeps gradient rows in LDS
+  int max_scan_blocks = 0, max_inj_groups = 0;                        // over the launch geometries in use
+};
+
+// The scan kernel of this product of terms: an ahead-of-time chain (kVariants), else a chain compiled now for exactly
+// this sequence (gwi_jit.h: hipRTC, cached on disk), else -- hipRTC missing, GWI_JIT=0 -- the generic kernel
+static void choose_scan_kernel(gwi_engine* h, const Creation& cr) {
+  const gwi_spec* spec = cr.spec;
+  const gwi_plan::Knobs& knobs = cr.knobs;
+  const bool force_generic = knobs.force_generic.on(), force_jit = knobs.force_jit.on();
   h->variant = (force_generic || force_jit) ? nullptr : find_variant(*spec);
-  bool jit_allowed = !force_generic;
-  if (const char* env = std::getenv("GWI_JIT")) jit_allowed = jit_allowed && std::atoi(env) != 0;
+  const bool jit_allowed = !force_generic && !knobs.jit.off();
   if (!h->variant && jit_allowed) {
     int kinds[GWI_MAX_TERMS], n_spline = 0;
     for (int t = 0; t < spec->n_terms; ++t) {
@@ -2006,15 +1986,11 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
       n_spline += jit::is_spline_kind(kinds[t]) ? 1 : 0;
     }
     // samples per lane: 2, or 1 from six spline terms on (the register budget of the config-5 chain) and for small catalogs
-    // of spline models (the rule below: one round of small workgroups)
+    // of spline models (gwi_plan.h, small_catalog: one round of small workgroups)
     int U = n_spline >= 6 ? 1 : 2;
-    const long long total = n_ev * n_pe + n_inj;
-    const bool geometry_knobs = std::getenv("GWI_SAMPLES_PER_BLOCK") || std::getenv("GWI_PE_CHUNK") || std::getenv("GWI_INJ_CHUNK") ||
-                                (std::getenv("GWI_SMALL_GEOMETRY") && std::atoi(std::getenv("GWI_SMALL_GEOMETRY")) == 0);
     bool small = false;
-    if (U == 2 && n_spline > 0 && !geometry_knobs && total < 2816LL * prop.multiProcessorCount && total >= 64LL * prop.multiProcessorCount) U = 1, small = true;
-    if (const char* env = std::getenv("GWI_SAMPLES_PER_LANE"))
-      if (std::atoi(env) == 1 || std::atoi(env) == 2) U = std::atoi(env), small = false;
+    if (U == 2 && n_spline > 0 && !gwi_plan::explicit_geometry(knobs) && gwi_plan::small_catalog(cr.n_ev, cr.n_pe, cr.n_inj, h->n_cus)) U = 1, small = true;
+    if (knobs.samples_per_lane.v == 1 || knobs.samples_per_lane.v == 2) U = knobs.samples_per_lane.v, small = false;
     std::string why;
     jit::Chain* jc = jit::get_chain(kinds, spec->n_terms, U, gwi_embedded_device_h, gwi_embedded_engine_h, why);
     hipModule_t mod = jc ? jit::module_on(jc, h->device, why) : nullptr;
@@ -2054,7 +2030,7 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
     h->variant = &kGenericVariant;
     h->generic = true;
     static std::atomic<bool> warned{false};
-    if (!force_generic && !warned.exchange(true) && !std::getenv("GWI_QUIET")) {
+    if (!force_generic && !warned.exchange(true) && !knobs.quiet.set) {
       std::string cmd;
       for (int t = 0; t < spec->n_terms; ++t) cmd += (t ? " " : "") + std::to_string(spec->terms[t].kind);
       std::fprintf(stderr,
@@ -2063,69 +2039,63 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
                    cmd.c_str(), h->jit_note.c_str(), cmd.c_str());
     }
   }
-  // Small catalogs of spline models (fewer than ~11 trips of 256 samples per CU: BASELINE config 3) are a chain of latencies, not
-  // a throughput problem: more and smaller workgroups of the one-sample-per-lane sibling -- four per CU, equal tiles inside an
-  // event -- measured 12.5-12.9 us for the config-3 scan against 13.4-14.3 for 443 workgroups of two samples per lane and two trips
-  // (tools/geometry_sweep.py; profiles/round3/EXPERIMENTS.md).  Explicit geometry knobs switch the rule off.
-  if (!h->variant->jit && h->variant->samples_per_lane == 2 && h->variant->has(jit::kSafe) && !h->generic && !std::getenv("GWI_SAMPLES_PER_LANE") && !std::getenv("GWI_SAMPLES_PER_BLOCK") &&
-      !std::getenv("GWI_PE_CHUNK") && !std::getenv("GWI_INJ_CHUNK") && !(std::getenv("GWI_SMALL_GEOMETRY") && std::atoi(std::getenv("GWI_SMALL_GEOMETRY")) == 0)) {
-    const Variant* sib = nullptr;
+  // small catalogs of spline models: the one-sample-per-lane sibling of an ahead-of-time chain (gwi_plan.h, small_catalog)
+  if (!h->variant->jit && h->variant->samples_per_lane == 2 && h->variant->has(jit::kSafe) && !h->generic && !knobs.samples_per_lane.set && !gwi_plan::explicit_geometry(knobs) &&
+      gwi_plan::small_catalog(cr.n_ev, cr.n_pe, cr.n_inj, h->n_cus)) {
     for (int v = 0; v < kNumVariants; ++v) {
-      const Variant& c = kVariants[v];
-      if (c.samples_per_lane != 1 || c.n != h->variant->n) continue;
+      const Variant& s = kVariants[v];
+      if (s.samples_per_lane != 1 || s.n != h->variant->n) continue;
       bool same = true;
-      for (int t = 0; t < c.n; ++t) same = same && c.kinds[t] == h->variant->kinds[t];
-      if (same) sib = &c;
-    }
-    const long long total = n_ev * n_pe + n_inj;
-    if (sib && total < 2816LL * prop.multiProcessorCount && total >= 64LL * prop.multiProcessorCount) {
-      h->variant = sib;
-      h->small_geometry = true;
+      for (int t = 0; t < s.n; ++t) same = same && s.kinds[t] == h->variant->kinds[t];
+      if (same) {
+        h->variant = &s;
+        h->small_geometry = true;
+      }
     }
   }
-  GWI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  if (const char* env = std::getenv("GWI_SPIN_WAIT")) h->spin_wait = std::atoi(env) != 0;
-  for (auto& e : h->ev) GWI_HIP(hipEventCreate(&e));
-  if (const char* env = std::getenv("GWI_MAX_BATCH")) h->max_batch = std::atoi(env);
-  if (h->max_batch < 1) h->max_batch = 1;
-  if (h->max_batch > 64) h->max_batch = 64;
-  h->n_ev = n_ev;
-  h->n_pe = n_pe;
-  h->n_inj = n_inj;
-  h->inj_off = inj_offset(n_ev, n_pe);
-  std::vector<int> narrow_term(spec->n_cols, -1);  // per column: the first narrow spline term reading it (validate_spec: only such terms do)
-  for (int t = spec->n_terms - 1; t >= 0; --t)
-    if (is_narrow_kind(spec->terms[t].kind)) narrow_term[spec->terms[t].cols[0]] = t;
+}
 
-  // ---- columns -> HBM (struct-of-arrays: one contiguous fp64 array per column and sample set)
-  std::vector<const double*> tab_pe(spec->n_cols), tab_inj(spec->n_cols);
-  if (ingest) {
+// columns -> HBM (struct-of-arrays: one contiguous fp64 array per column and sample set)
+static gwi_status upload_columns(gwi_engine* h, Creation& cr) {
+  const gwi_spec* spec = cr.spec;
+  gwi_status st;
+  cr.narrow_term.assign(spec->n_cols, -1);
+  for (int t = spec->n_terms - 1; t >= 0; --t)
+    if (is_narrow_kind(spec->terms[t].kind)) cr.narrow_term[spec->terms[t].cols[0]] = t;
+  cr.tab_pe.assign(spec->n_cols, nullptr);
+  cr.tab_inj.assign(spec->n_cols, nullptr);
+  if (cr.ing_pe) {
     // setup on the device: raw catalog columns up, one kernel per sample set writes the engine's columns (gwi_ingest.h)
     for (int c = 0; c < spec->n_cols; ++c) {
       double *dpe = nullptr, *dinj = nullptr;
       if ((st = alloc_pair(h, &dpe, &dinj)) != GWI_OK) return st;
-      tab_pe[c] = dpe;
-      tab_inj[c] = dinj;
+      cr.tab_pe[c] = dpe;
+      cr.tab_inj[c] = dinj;
     }
-    if ((st = ingest_run(h->err, ing_pe, n_ev * n_pe, spec->n_cols, h->d_cols_pe.data(), h->stream)) != GWI_OK) return st;
-    if ((st = ingest_run(h->err, ing_inj, n_inj, spec->n_cols, h->d_cols_inj.data(), h->stream)) != GWI_OK) return st;
+    if ((st = ingest_run(h->err, cr.ing_pe, h->n_ev * h->n_pe, spec->n_cols, h->d_cols_pe.data(), h->stream)) != GWI_OK) return st;
+    if ((st = ingest_run(h->err, cr.ing_inj, h->n_inj, spec->n_cols, h->d_cols_inj.data(), h->stream)) != GWI_OK) return st;
   } else {
     for (int c = 0; c < spec->n_cols; ++c) {
       double *dpe = nullptr, *dinj = nullptr;
       if ((st = alloc_pair(h, &dpe, &dinj)) != GWI_OK) return st;
-      if (narrow_term[c] < 0) {
-        if (n_ev * n_pe) GWI_HIP(hipMemcpy(dpe, pe_cols[c], sizeof(double) * (size_t)(n_ev * n_pe), hipMemcpyHostToDevice));
-        if (n_inj) GWI_HIP(hipMemcpy(dinj, inj_cols[c], sizeof(double) * (size_t)n_inj, hipMemcpyHostToDevice));
+      if (cr.narrow_term[c] < 0) {
+        if (h->n_ev * h->n_pe) GWI_HIP(hipMemcpy(dpe, cr.pe_cols[c], sizeof(double) * (size_t)(h->n_ev * h->n_pe), hipMemcpyHostToDevice));
+        if (h->n_inj) GWI_HIP(hipMemcpy(dinj, cr.inj_cols[c], sizeof(double) * (size_t)h->n_inj, hipMemcpyHostToDevice));
       }
-      tab_pe[c] = dpe;
-      tab_inj[c] = dinj;
+      cr.tab_pe[c] = dpe;
+      cr.tab_inj[c] = dinj;
     }
   }
+  return GWI_OK;
+}
 
-  // ---- narrow columns (GWI_TERM_EXP_SPLINE_F32 / _LINEAR_SPLINE_F32): float32 in HBM, after checking that every value survives
-  // the round trip -- on the host for columns handed over, on the device (narrow_column_kernel) for ingested ones
+// ---- narrow columns (GWI_TERM_EXP_SPLINE_F32 / _LINEAR_SPLINE_F32): float32 in HBM, after checking that every value survives
+// the round trip -- on the host for columns handed over, on the device (narrow_column_kernel) for ingested ones
+static gwi_status narrow_columns(gwi_engine* h, Creation& cr) {
+  const gwi_spec* spec = cr.spec;
+  gwi_status st;
   for (int c = 0; c < spec->n_cols; ++c) {
-    const int t = narrow_term[c];
+    const int t = cr.narrow_term[c];
     if (t < 0) continue;
     const gwi_term& tm = spec->terms[t];
     const float park = (float)(0.5 * (tm.p[0] + tm.p[1]));  // the parking place of non-finite entries: the domain's middle
@@ -2133,12 +2103,12 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
     double* old = nullptr;
     if ((st = alloc_pair_f32(h, c, &d, &old)) != GWI_OK) return st;
     unsigned long long bad = 0;
-    if (ingest) {
+    if (cr.ing_pe) {
       unsigned long long* d_bad = nullptr;
       hipError_t e = hipMalloc(&d_bad, sizeof(unsigned long long));
       if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(unsigned long long), h->stream);
-      if (e == hipSuccess) e = narrow_column_run(old, d, d_bad, n_ev * n_pe, park, h->stream);
-      if (e == hipSuccess) e = narrow_column_run(old + h->inj_off, d + h->inj_off, d_bad, n_inj, park, h->stream);
+      if (e == hipSuccess) e = narrow_column_run(old, d, d_bad, h->n_ev * h->n_pe, park, h->stream);
+      if (e == hipSuccess) e = narrow_column_run(old + h->inj_off, d + h->inj_off, d_bad, h->n_inj, park, h->stream);
       if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
       (void)hipFree(d_bad);
@@ -2146,7 +2116,7 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
       GWI_HIP(e);
     } else {
       (void)hipFree(old);
-      std::vector<float> buf((size_t)std::max<long long>(n_ev * n_pe, n_inj));
+      std::vector<float> buf((size_t)std::max<long long>(h->n_ev * h->n_pe, h->n_inj));
       auto narrow = [&](const double* x, long long n) {
         for (long long i = 0; i < n; ++i) {
           const double v = x[i];
@@ -2158,97 +2128,108 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
           buf[(size_t)i] = f;
         }
       };
-      narrow(pe_cols[c], n_ev * n_pe);
-      if (n_ev * n_pe) GWI_HIP(hipMemcpy(d, buf.data(), sizeof(float) * (size_t)(n_ev * n_pe), hipMemcpyHostToDevice));
-      narrow(inj_cols[c], n_inj);
-      if (n_inj) GWI_HIP(hipMemcpy(d + h->inj_off, buf.data(), sizeof(float) * (size_t)n_inj, hipMemcpyHostToDevice));
+      narrow(cr.pe_cols[c], h->n_ev * h->n_pe);
+      if (h->n_ev * h->n_pe) GWI_HIP(hipMemcpy(d, buf.data(), sizeof(float) * (size_t)(h->n_ev * h->n_pe), hipMemcpyHostToDevice));
+      narrow(cr.inj_cols[c], h->n_inj);
+      if (h->n_inj) GWI_HIP(hipMemcpy(d + h->inj_off, buf.data(), sizeof(float) * (size_t)h->n_inj, hipMemcpyHostToDevice));
     }
     if (bad)
       return fail(h, GWI_ERR_INVALID, "term " + std::to_string(t) + " (narrow spline, kind " + std::to_string(tm.kind) + "): " + std::to_string(bad) + " value" +
                                           (bad == 1 ? "" : "s") + " of column " + std::to_string(c) + " do not survive a float32 round trip");
-    tab_pe[c] = reinterpret_cast<const double*>(d);
-    tab_inj[c] = reinterpret_cast<const double*>(d + h->inj_off);
+    cr.tab_pe[c] = reinterpret_cast<const double*>(d);
+    cr.tab_inj[c] = reinterpret_cast<const double*>(d + h->inj_off);
   }
+  return GWI_OK;
+}
 
-  // ---- spline terms read the KNOT coordinate of their column (gwi_device.h: spline_locate_knot): convert x -> u once, here.
-  // A column that several spline terms read with different knots, or that another kind of term (or kappa) reads too, is
-  // copied for each distinct use; otherwise it is converted in place.
-  std::vector<const double*> over_pe(spec->n_terms, nullptr), over_inj(spec->n_terms, nullptr), over_pe1, over_inj1;
-  {
-    struct Use {
-      double lo, inv_dx, top;
-      const double *pe, *inj;
-    };
-    std::vector<std::vector<Use>> uses(spec->n_cols);
-    std::vector<char> plain(spec->n_cols, 0);  // read as it is by some term or as kappa
-    auto is_knot_term = [](const gwi_term& tm) { return tm.kind == GWI_TERM_EXP_SPLINE || tm.kind == GWI_TERM_LINEAR_SPLINE; };
-    plain[spec->kappa_col] = 1;
-    // a mass-ratio power law that takes log m1 from the m1 spline's column (GWI_RATIO_LOGM_FROM_SPLINE) reads the knot
-    // coordinate too: it follows whatever conversion the spline term of the same knots asked for
-    auto follows_knots = [](const gwi_term& tm, int j) { return tm.kind == GWI_TERM_POWERLAW_RATIO && (tm.flags & GWI_RATIO_LOGM_FROM_SPLINE) && j == 1; };
-    for (int t = 0; t < spec->n_terms; ++t) {
-      const gwi_term& tm = spec->terms[t];
-      for (int j = 0; j < 2; ++j) {
-        const int c = tm.cols[j];
-        if (c < 0 || c >= spec->n_cols) continue;
-        if (!(is_knot_term(tm) && j == 0) && !follows_knots(tm, j)) plain[c] = 1;
-      }
+// ---- spline terms read the KNOT coordinate of their column (gwi_device.h: spline_locate_knot): convert x -> u once, here.
+// A column that several spline terms read with different knots, or that another kind of term (or kappa) reads too, is
+// copied for each distinct use; otherwise it is converted in place.
+static gwi_status knot_coordinates(gwi_engine* h, Creation& cr) {
+  const gwi_spec* spec = cr.spec;
+  gwi_status st;
+  cr.over_pe.assign(spec->n_terms, nullptr);
+  cr.over_inj.assign(spec->n_terms, nullptr);
+  struct Use {
+    double lo, inv_dx, top;
+    const double *pe, *inj;
+  };
+  std::vector<std::vector<Use>> uses(spec->n_cols);
+  std::vector<char> plain(spec->n_cols, 0);  // read as it is by some term or as kappa
+  auto is_knot_term = [](const gwi_term& tm) { return tm.kind == GWI_TERM_EXP_SPLINE || tm.kind == GWI_TERM_LINEAR_SPLINE; };
+  // the conversion a knot term asks for: its first knot, 1/dx of the uniform knots (interpolation.py:100-101) and, where the
+  // exponent is clamped at the domain's end, the last coordinate below that end (else -1)
+  auto use_of = [](const gwi_term& tm) {
+    const int n_int = tm.n_basis - 3;
+    const bool clamp = tm.kind == GWI_TERM_EXP_SPLINE && !(tm.flags & GWI_SPLINE_OUTSIDE_ZERO_EXPONENT);
+    return Use{tm.p[0], (double)n_int / (tm.p[1] - tm.p[0]), clamp ? std::nextafter((double)n_int, 0.0) : -1.0, nullptr, nullptr};
+  };
+  auto same_use = [](const Use& a, const Use& b) { return a.lo == b.lo && a.inv_dx == b.inv_dx && a.top == b.top; };
+  plain[spec->kappa_col] = 1;
+  // a mass-ratio power law that takes log m1 from the m1 spline's column (GWI_RATIO_LOGM_FROM_SPLINE) reads the knot
+  // coordinate too: it follows whatever conversion the spline term of the same knots asked for
+  auto follows_knots = [](const gwi_term& tm, int j) { return tm.kind == GWI_TERM_POWERLAW_RATIO && (tm.flags & GWI_RATIO_LOGM_FROM_SPLINE) && j == 1; };
+  for (int t = 0; t < spec->n_terms; ++t) {
+    const gwi_term& tm = spec->terms[t];
+    for (int j = 0; j < 2; ++j) {
+      const int c = tm.cols[j];
+      if (c < 0 || c >= spec->n_cols) continue;
+      if (!(is_knot_term(tm) && j == 0) && !follows_knots(tm, j)) plain[c] = 1;
     }
-    for (int t = 0; t < spec->n_terms; ++t) {
-      const gwi_term& tm = spec->terms[t];
-      if (!is_knot_term(tm)) continue;
-      const int c = tm.cols[0];
-      const int n_int = tm.n_basis - 3;
-      const double inv_dx = (double)n_int / (tm.p[1] - tm.p[0]);  // 1/dx of the uniform knots (interpolation.py:100-101)
-      const bool clamp = tm.kind == GWI_TERM_EXP_SPLINE && !(tm.flags & GWI_SPLINE_OUTSIDE_ZERO_EXPONENT);
-      const double top = clamp ? std::nextafter((double)n_int, 0.0) : -1.0;
-      const Use* hit = nullptr;
+  }
+  for (int t = 0; t < spec->n_terms; ++t) {
+    const gwi_term& tm = spec->terms[t];
+    if (!is_knot_term(tm)) continue;
+    const int c = tm.cols[0];
+    Use u = use_of(tm);
+    const Use* hit = nullptr;
+    for (const Use& have : uses[c])
+      if (same_use(have, u)) hit = &have;
+    if (!hit) {
+      // in place when every knot term of this column wants the same conversion and nobody reads the column as it is;
+      // else every distinct use gets a copy and the column itself stays what the caller handed over
+      bool all_agree = !plain[c];
+      for (int t2 = 0; t2 < spec->n_terms && all_agree; ++t2) {
+        const gwi_term& o = spec->terms[t2];
+        if (!is_knot_term(o) || o.cols[0] != c) continue;
+        all_agree = same_use(use_of(o), u);
+      }
+      double *dpe = h->d_cols_pe[c], *dinj = h->d_cols_inj[c];
+      if (!all_agree) {  // a private copy for this use
+        if ((st = alloc_pair(h, &dpe, &dinj)) != GWI_OK) return st;
+      }
+      GWI_HIP(spline_knot_run(cr.tab_pe[c], dpe, h->n_ev * h->n_pe, u.lo, u.inv_dx, u.top, h->stream));
+      GWI_HIP(spline_knot_run(cr.tab_inj[c], dinj, h->n_inj, u.lo, u.inv_dx, u.top, h->stream));
+      u.pe = dpe;
+      u.inj = dinj;
+      uses[c].push_back(u);
+      hit = &uses[c].back();
+    }
+    cr.over_pe[t] = hit->pe;
+    cr.over_inj[t] = hit->inj;
+  }
+  cr.over_pe1.assign(spec->n_terms, nullptr);
+  cr.over_inj1.assign(spec->n_terms, nullptr);
+  for (int t = 0; t < spec->n_terms; ++t) {
+    const gwi_term& tm = spec->terms[t];
+    if (!follows_knots(tm, 1)) continue;
+    const int c = tm.cols[1];
+    const Use* hit = nullptr;
+    if (c >= 0 && c < spec->n_cols)
       for (const Use& u : uses[c])
-        if (u.lo == tm.p[0] && u.inv_dx == inv_dx && u.top == top) hit = &u;
-      if (!hit) {
-        Use u{tm.p[0], inv_dx, top, nullptr, nullptr};
-        // in place when every knot term of this column wants the same conversion and nobody reads the column as it is;
-        // else every distinct use gets a copy and the column itself stays what the caller handed over
-        bool all_agree = !plain[c];
-        for (int t2 = 0; t2 < spec->n_terms && all_agree; ++t2) {
-          const gwi_term& o = spec->terms[t2];
-          if (!is_knot_term(o) || o.cols[0] != c) continue;
-          const bool oclamp = o.kind == GWI_TERM_EXP_SPLINE && !(o.flags & GWI_SPLINE_OUTSIDE_ZERO_EXPONENT);
-          const double otop = oclamp ? std::nextafter((double)(o.n_basis - 3), 0.0) : -1.0;
-          all_agree = o.p[0] == u.lo && (double)(o.n_basis - 3) / (o.p[1] - o.p[0]) == u.inv_dx && otop == u.top;
-        }
-        double *dpe = h->d_cols_pe[c], *dinj = h->d_cols_inj[c];
-        if (!all_agree) {  // a private copy for this use
-          if ((st = alloc_pair(h, &dpe, &dinj)) != GWI_OK) return st;
-        }
-        GWI_HIP(spline_knot_run(tab_pe[c], dpe, n_ev * n_pe, u.lo, u.inv_dx, u.top, h->stream));
-        GWI_HIP(spline_knot_run(tab_inj[c], dinj, n_inj, u.lo, u.inv_dx, u.top, h->stream));
-        u.pe = dpe;
-        u.inj = dinj;
-        uses[c].push_back(u);
-        hit = &uses[c].back();
-      }
-      over_pe[t] = hit->pe;
-      over_inj[t] = hit->inj;
-    }
-    over_pe1.assign(spec->n_terms, nullptr);
-    over_inj1.assign(spec->n_terms, nullptr);
-    for (int t = 0; t < spec->n_terms; ++t) {
-      const gwi_term& tm = spec->terms[t];
-      if (!follows_knots(tm, 1)) continue;
-      const int c = tm.cols[1];
-      const Use* hit = nullptr;
-      if (c >= 0 && c < spec->n_cols)
-        for (const Use& u : uses[c])
-          if (u.lo == tm.p[1] && u.inv_dx == tm.p[2]) hit = &u;
-      if (!hit) return fail(h, GWI_ERR_INVALID, "GWI_RATIO_LOGM_FROM_SPLINE: cols[1] is not the coordinate column of a spline term with the knots given in p[1], p[2]");
-      over_pe1[t] = hit->pe;
-      over_inj1[t] = hit->inj;
-    }
-    GWI_HIP(hipStreamSynchronize(h->stream));
+        if (u.lo == tm.p[1] && u.inv_dx == tm.p[2]) hit = &u;
+    if (!hit) return fail(h, GWI_ERR_INVALID, "GWI_RATIO_LOGM_FROM_SPLINE: cols[1] is not the coordinate column of a spline term with the knots given in p[1], p[2]");
+    cr.over_pe1[t] = hit->pe;
+    cr.over_inj1[t] = hit->inj;
   }
+  GWI_HIP(hipStreamSynchronize(h->stream));
+  return GWI_OK;
+}
 
-  // ---- normaliser grids
+// normaliser grids
+static gwi_status upload_norms(gwi_engine* h, const Creation& cr) {
+  const gwi_spec* spec = cr.spec;
+  gwi_status st;
   std::vector<NormD> nd(spec->n_norms ? spec->n_norms : 1);
   for (int j = 0; j < spec->n_norms; ++j) {
     const gwi_norm& nm = spec->norms[j];
@@ -2282,274 +2263,157 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
   }
   GWI_HIP(hipMalloc(&h->d_norms, sizeof(NormD) * nd.size()));
   GWI_HIP(hipMemcpy(h->d_norms, nd.data(), sizeof(NormD) * nd.size(), hipMemcpyHostToDevice));
+  return GWI_OK;
+}
 
-  // dynamic LDS of the scan kernel: the workgroup's spline-gradient rows, [n_theta][rep] doubles (spline_scatter in
-  // gwi_device.h).  rep = 64 would give every lane its own replica; 16 (four lanes per replica, bank = replica) measured
-  // the same or better on the BASELINE catalogs (config 5 scan: rep 8 / 16 / 32 / 64 = 61.5 / 51.2 / 51.7 / 70.0 us, config 3:
-  // 15.5 / 14.6 / 15.3 / 16.1) because the rows must also fit next to the kernel's static LDS as many times as the
-  // register budget allows workgroups on a CU, and are zeroed and summed once per workgroup.
-  bool has_spline = false;
-  for (int t = 0; t < spec->n_terms; ++t)
-    has_spline = has_spline || jit::is_spline_kind(spec->terms[t].kind);
-  has_spline = has_spline || h->generic;  // the generic chain keeps every gradient sum in the LDS rows
-  if (const char* env = std::getenv("GWI_DETERMINISTIC")) h->deterministic = std::atoi(env) != 0;
-  size_t scan_lds = 0;
-  int rep = 1;
-  if (has_spline) {
-    size_t lds_per_cu = 160 * 1024, static_lds = 14 * 1024;  // gfx950: 160 KiB per CU; static: s_theta + s_out + s_part + s_wrec (what the kernel reports replaces this guess)
-    if (h->variant->jit) {
-      int v = 0;
-      if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, h->jit_fn[jit::kScan]) == hipSuccess && v > 0) static_lds = (size_t)v;
-    } else {
-      hipFuncAttributes fa;
-      if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(h->variant->fn[jit::kScan])) == hipSuccess && fa.sharedSizeBytes > 0) static_lds = fa.sharedSizeBytes;
-    }
-    // 16 replicas: what the regular scan kernels are compiled for (immediate row offsets).  Where rows that wide cost a
-    // resident workgroup (n_theta beyond ~100), that is the cheaper loss: 8 replicas measured 20 % slower at config 5.
-    // Any other count (GWI_GACC_REP, the replay mode's 64) runs the SAFE instantiation, which takes it at run time.
-    rep = 1 << kRegularRepShift;
-    if (const char* env = std::getenv("GWI_GACC_REP")) rep = std::atoi(env);
-    if (h->deterministic) rep = 64;  // one replica per lane: a wave instruction never meets itself on an address
-    if (rep < 1) rep = 1;
-    if (rep > 64) rep = 64;
-    while (rep & (rep - 1)) rep &= rep - 1;  // power of two
-    while (rep > 1 && sizeof(double) * (size_t)spec->n_theta * rep + static_lds > lds_per_cu) rep >>= 1;
-    const size_t poly_lds = 4 * sizeof(double) * (size_t)kPolyStride;  // the power-basis table of the spline values (gwi_device.h: spline_poly), behind the rows
-    while (rep > 1 && sizeof(double) * (size_t)spec->n_theta * rep + poly_lds + static_lds > lds_per_cu) rep >>= 1;
-    scan_lds = sizeof(double) * (size_t)spec->n_theta * rep + poly_lds;
-    if (scan_lds > 48 * 1024 && !h->variant->jit) {  // beyond the default dynamic-LDS limit of a HIP launch (the AQL packets carry any size; so do module launches)
-      for (int role = 0; role < jit::kRoles; ++role)
-        if (h->variant->fn[role]) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(h->variant->fn[role]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scan_lds);
-    }
+// Dynamic LDS of the scan kernel: the workgroup's spline-gradient rows and the power-basis table behind them (gwi_plan.h,
+// gacc_replicas, which also says why 16 replicas)
+static void size_gradient_rows(gwi_engine* h, Creation& cr) {
+  const gwi_spec* spec = cr.spec;
+  for (int t = 0; t < spec->n_terms; ++t) cr.has_spline = cr.has_spline || jit::is_spline_kind(spec->terms[t].kind);
+  cr.has_spline = cr.has_spline || h->generic;  // the generic chain keeps every gradient sum in the LDS rows
+  if (cr.knobs.deterministic.set) h->deterministic = cr.knobs.deterministic.v != 0;
+  if (!cr.has_spline) return;
+  size_t static_lds = 14 * 1024;  // s_theta + s_out + s_part + s_wrec (what the kernel reports replaces this guess)
+  if (h->variant->jit) {
+    int v = 0;
+    if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, h->jit_fn[jit::kScan]) == hipSuccess && v > 0) static_lds = (size_t)v;
+  } else {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(h->variant->fn[jit::kScan])) == hipSuccess && fa.sharedSizeBytes > 0) static_lds = fa.sharedSizeBytes;
   }
-  h->gacc_rep = rep;
-  if (has_spline) {
-    // Batched launches of >= 9 points take the 16-points-per-wavefront kernel (gwi_mfma.h) where the model has an
-    // instantiation: at K = 16 it measures 15 % ahead of the 4-tap kernel on the BASELINE catalogs (config 5: 34.9 vs 41.0 us
-    // per evaluation, config 3: 8.7 vs 10.5) and its gradient is bit-reproducible.  GWI_BATCH_MFMA=0 keeps the 4-tap kernel,
-    // =2 uses the matrix-core kernel for every batch size; GWI_BATCH_ROWS=1 selects the LDS-row variant of the same kernel.
+  const gwi_plan::GaccRows rows = gwi_plan::gacc_replicas(spec->n_theta, static_lds, h->deterministic, cr.knobs);
+  h->gacc_rep = rows.rep;
+  h->scan_lds_bytes = rows.scan_lds;
+  if (rows.scan_lds > 48 * 1024 && !h->variant->jit) {  // beyond the default dynamic-LDS limit of a HIP launch (the AQL packets carry any size; so do module launches)
+    for (int role = 0; role < jit::kRoles; ++role)
+      if (h->variant->fn[role]) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(h->variant->fn[role]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows.scan_lds);
+  }
+}
+
+// The kernel of batched launches of a spline model.
+// Batched launches of >= 9 points take the 16-points-per-wavefront kernel (gwi_mfma.h) where the model has an
+// instantiation: at K = 16 it measures 15 % ahead of the 4-tap kernel on the BASELINE catalogs (config 5: 34.9 vs 41.0 us
+// per evaluation, config 3: 8.7 vs 10.5) and its gradient is bit-reproducible.  GWI_BATCH_MFMA=0 keeps the 4-tap kernel,
+// =2 uses the matrix-core kernel for every batch size; GWI_BATCH_ROWS=1 selects the LDS-row variant of the same kernel.
+static void choose_batch_kernel(gwi_engine* h, const Creation& cr) {
+  if (!cr.has_spline) return;
+  const gwi_spec* spec = cr.spec;
+  const gwi_plan::Knobs& knobs = cr.knobs;
+  const bool named = knobs.batch_mfma.set || knobs.batch_rows.set;  // the environment names a path
+  h->mfma = find_mfma_variant(*spec);
+  if (h->mfma && !named) {
+    // more than 8 gradient tiles: the 4-tap kernel is faster (the reference's default spline counts, 11 tiles / 165
+    // hyper-parameters, on the config-3 catalog: 11.7 us per evaluation against 14.4 on the matrix cores and 14.5 with LDS rows)
+    int tiles = 0;
+    for (int t = 0; t < h->mfma->n; ++t) tiles += h->mfma->tiles[t];
+    if (tiles > 8) h->mfma = nullptr;
+  }
+  if (knobs.batch_mfma.off()) h->mfma = nullptr;
+  if (knobs.batch_mfma.v >= 2) h->mfma_min_batch = 1;
+  if (knobs.batch_rows.v >= 1) {
     h->mfma = find_mfma_variant(*spec);
-    if (h->mfma && !std::getenv("GWI_BATCH_MFMA") && !std::getenv("GWI_BATCH_ROWS")) {
-      // more than 8 gradient tiles: the 4-tap kernel is faster (the reference's default spline counts, 11 tiles / 165
-      // hyper-parameters, on the config-3 catalog: 11.7 us per evaluation against 14.4 on the matrix cores and 14.5 with LDS rows)
-      int tiles = 0;
-      for (int t = 0; t < h->mfma->n; ++t) tiles += h->mfma->tiles[t];
-      if (tiles > 8) h->mfma = nullptr;
-    }
-    if (const char* env = std::getenv("GWI_BATCH_MFMA")) {
-      if (std::atoi(env) == 0) h->mfma = nullptr;
-      if (std::atoi(env) >= 2) h->mfma_min_batch = 1;
-    }
-    if (const char* env = std::getenv("GWI_BATCH_ROWS")) {
-      if (std::atoi(env) >= 1) {
-        h->mfma = find_mfma_variant(*spec);
-        h->batch_rows = h->mfma != nullptr;
-      }
-      if (std::atoi(env) >= 2) h->mfma_min_batch = 1;
-    }
-    // no path named by the environment: the static rule above stands (config 3 is a tie between the kernels that flipped from box
-    // to box when it was measured by default, config 5 prefers the matrix cores by 15 %); GWI_BATCH_AUTOTUNE=1 measures instead
-    if (const char* env = std::getenv("GWI_BATCH_AUTOTUNE")) h->autotune_wanted = std::atoi(env) != 0;
-    h->batch_autotune = h->autotune_wanted && h->mfma && !std::getenv("GWI_BATCH_MFMA") && !std::getenv("GWI_BATCH_ROWS") && !h->deterministic;
-    // a spline model without an ahead-of-time matrix-core instantiation: compiled on its first batched launch of >= 9 points and used
-    // from then on (GWI_BATCH_MFMA=1: compiled now; GWI_JIT=0 or GWI_BATCH_MFMA=0: not at all; GWI_BATCH_AUTOTUNE=1: measured against
-    // the 4-tap kernel there)
-    {
-      bool jit_ok = !h->generic && !h->deterministic && !find_mfma_variant(*spec) && !std::getenv("GWI_BATCH_ROWS");
-      if (const char* env = std::getenv("GWI_JIT")) jit_ok = jit_ok && std::atoi(env) != 0;
-      const char* want = std::getenv("GWI_BATCH_MFMA");
-      if (jit_ok && want && std::atoi(want) >= 1) {
-        if (try_jit_mfma(h) && std::atoi(want) >= 2) h->mfma_min_batch = 1;
-      } else if (jit_ok && !want) {
-        h->mfma_jit_pending = true;
-      }
-    }
-    if (h->mfma && h->batch_rows) {
-      // sample-slot replicas of the gradient rows: as many (4, 2, 1) as leave two workgroups per CU their LDS
-      h->rows_rep = 4;
-      while (h->rows_rep > 1 && sizeof(double) * mfma_lds_doubles(spec->n_theta, spec->n_terms, h->mfma->row_doubles, h->rows_rep) + 4608 > 80 * 1024) h->rows_rep >>= 1;
-      if (const char* env = std::getenv("GWI_ROWS_REP")) h->rows_rep = std::max(1, std::min(4, std::atoi(env)));
-      h->mfma_lds_bytes = sizeof(double) * mfma_lds_doubles(spec->n_theta, spec->n_terms, h->mfma->row_doubles, h->rows_rep);
-      if (h->mfma_lds_bytes > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(h->mfma->rows_fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mfma_lds_bytes);
-    } else if (h->mfma) {
-      h->mfma_lds_bytes = sizeof(double) * mfma_lds_doubles(spec->n_theta, spec->n_terms, h->mfma->row_doubles, 0);
-      if (h->mfma_lds_bytes > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(h->mfma->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mfma_lds_bytes);
-    }
+    h->batch_rows = h->mfma != nullptr;
   }
-  // ---- launch geometry.  Default: ~2048 scan workgroups (8 per CU).  A step lasts only ~10 us, so a
-  // partial second dispatch round (a few workgroups that can only start when the first finishers
-  // retire) costs a large fraction of it: when one round of resident workgroups can hold the whole
-  // catalog with <= 4 trips each, size the workgroups for exactly one round instead.
-  const long long gran = (long long)h->variant->samples_per_lane * kBlock;  // every lane carries U samples per trip
-  long long spb = 0, spb_batch = 0;  // spb_batch != 0: batched launches use another tile size
-  if (const char* env = std::getenv("GWI_SAMPLES_PER_BLOCK")) spb = std::atoll(env);
-  if (spb <= 0) {
-    const long long total = n_ev * n_pe + n_inj;
-    spb = (total + 2047) / 2048;
-    int occ = 0;
-    bool single_round = true;
-    if (const char* env = std::getenv("GWI_SINGLE_ROUND")) single_round = std::atoi(env) != 0;
-    const hipError_t occ_rc = h->variant->jit ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, h->jit_fn[jit::kScan], kBlock, scan_lds)
-                                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, h->variant->fn[jit::kScan], kBlock, scan_lds);
-    if (single_round && occ_rc == hipSuccess && occ > 0) {
-      const long long capacity = (long long)prop.multiProcessorCount * occ;
-      for (long long cand = gran; cand <= 4 * gran; cand += gran) {
-        const long long pad = ((n_pe + gran - 1) / gran) * gran;
-        const long long cpe = cand < pad ? cand : pad;
-        const long long blocks = n_ev * ((n_pe + cpe - 1) / cpe) + (n_inj + cand - 1) / cand;
-        if (blocks <= capacity) {
-          if (cand > spb) spb = cand;
-          break;
-        }
-      }
-      // One trip per workgroup where two would still give every CU a workgroup: BATCHED launches take two (bgeo below).
-      // Prologue and record reduction are a quarter of a one-trip workgroup's instructions (config 2, K = 16: scan 52.1 ->
-      // 45.3 us, 205 k -> 236 k evals/s); a single evaluation gains nothing from it (16.9 vs 16.8 us) and four concurrent
-      // chains lose ~10 %, so the single-evaluation geometry stays at one trip.
-      if (spb == gran) {
-        const long long c2 = 2 * gran, pad = ((n_pe + gran - 1) / gran) * gran;
-        const long long cpe = c2 < pad ? c2 : pad;
-        const long long blocks2 = n_ev * ((n_pe + cpe - 1) / cpe) + (n_inj + c2 - 1) / c2;
-        if (blocks2 >= (long long)prop.multiProcessorCount) spb_batch = c2;
-      }
-    }
+  if (knobs.batch_rows.v >= 2) h->mfma_min_batch = 1;
+  // no path named by the environment: the static rule above stands (config 3 is a tie between the kernels that flipped from box
+  // to box when it was measured by default, config 5 prefers the matrix cores by 15 %); GWI_BATCH_AUTOTUNE=1 measures instead
+  if (knobs.batch_autotune.set) h->autotune_wanted = knobs.batch_autotune.v != 0;
+  h->batch_autotune = h->autotune_wanted && h->mfma && !named && !h->deterministic;
+  // a spline model without an ahead-of-time matrix-core instantiation: compiled on its first batched launch of >= 9 points and used
+  // from then on (GWI_BATCH_MFMA=1: compiled now; GWI_JIT=0 or GWI_BATCH_MFMA=0: not at all; GWI_BATCH_AUTOTUNE=1: measured against
+  // the 4-tap kernel there)
+  const bool jit_ok = !h->generic && !h->deterministic && !find_mfma_variant(*spec) && !knobs.batch_rows.set && !knobs.jit.off();
+  if (jit_ok && knobs.batch_mfma.v >= 1) {
+    if (try_jit_mfma(h) && knobs.batch_mfma.v >= 2) h->mfma_min_batch = 1;
+  } else if (jit_ok && !knobs.batch_mfma.set) {
+    h->mfma_jit_pending = true;
   }
-  spb = ((spb + gran - 1) / gran) * gran;
-  if (spb < gran) spb = gran;
-  const long long n_pe_pad = ((n_pe + gran - 1) / gran) * gran;
-  h->chunk_pe = (int)(spb < n_pe_pad ? spb : n_pe_pad);
-  h->chunk_inj = (int)spb;
-  if (h->small_geometry) {
-    const long long total = n_ev * n_pe + n_inj;
-    double per_cu = 4.0;  // one round of resident workgroups at four waves per SIMD; 2.0 / 2.75 / 3.4 / 4.0 / 5.5 / 7.0 measured 15.4 / 13.8 / 13.7 / 13.1 / 16.2 / 14.7 us on one box
-    if (const char* env = std::getenv("GWI_SMALL_WGS_PER_CU")) per_cu = std::max(0.5, std::atof(env));
-    const long long target = std::max<long long>(64, (long long)((double)total / (per_cu * prop.multiProcessorCount) + 0.5));
-    const long long tiles_pe = std::max<long long>(1, (n_pe + target / 2) / target);
-    h->chunk_pe = (int)((n_pe + tiles_pe - 1) / tiles_pe);  // equal tiles inside an event
-    h->chunk_inj = (int)target;
-    spb_batch = 0;
+  if (!h->mfma) return;
+  if (h->batch_rows) {
+    // sample-slot replicas of the gradient rows: as many (4, 2, 1) as leave two workgroups per CU their LDS
+    h->rows_rep = 4;
+    while (h->rows_rep > 1 && sizeof(double) * mfma_lds_doubles(spec->n_theta, spec->n_terms, h->mfma->row_doubles, h->rows_rep) + 4608 > 80 * 1024) h->rows_rep >>= 1;
+    if (knobs.rows_rep.set) h->rows_rep = std::max(1, std::min(4, knobs.rows_rep.v));
   }
-  // The combine launch requests the records of up to 16 tiles of an event in its first memory round trip (kEarly in
-  // combine_group) and needs another dependent round per 16 more: a catalog of few events with many posterior samples each --
-  // one rank's share of config 5 on 8 GPUs: 25 events x 10 000 -- got 40 tiles of 256 per event and a 9.5 us combine behind a
-  // 10.7 us scan.  At most 16 tiles per event where that still leaves every CU a workgroup: 768-sample tiles there, scan
-  // 11.7 us, combine 4.1 us, 27.4 -> 21.3 us per local evaluation (tools/shard_time.py).
-  if (!std::getenv("GWI_SAMPLES_PER_BLOCK") && !(std::getenv("GWI_TILE_CAP") && std::atoi(std::getenv("GWI_TILE_CAP")) == 0)) {
-    const long long cap_chunk = (((n_pe + 15) / 16 + gran - 1) / gran) * gran;
-    if (h->chunk_pe < cap_chunk) {
-      const long long inj_chunk = h->chunk_inj < cap_chunk ? cap_chunk : h->chunk_inj;
-      const long long blocks = n_ev * ((n_pe + cap_chunk - 1) / cap_chunk) + (n_inj + inj_chunk - 1) / inj_chunk;
-      if (blocks >= (long long)prop.multiProcessorCount) {
-        h->chunk_pe = (int)cap_chunk;
-        h->chunk_inj = (int)inj_chunk;
-      }
-    }
-  }
-  // experiment knobs: exact tile sizes (the kernel takes any size; a trip covers samples_per_lane * 256 samples)
-  if (const char* env = std::getenv("GWI_PE_CHUNK")) h->chunk_pe = std::max(1, std::atoi(env));
-  if (const char* env = std::getenv("GWI_INJ_CHUNK")) h->chunk_inj = std::max(1, std::atoi(env));
-  // the tail kernels map the tile records of one group to the lanes of ONE wave: an event may have at most 64 tiles, the
-  // injections at most 64 groups x 64 tiles.  Few events with very many posterior samples (3 events x 1 M) or a very long
-  // injection set exceed that with the default tile size: grow the tiles (whole trips) until they fit.
-  {
-    auto round_up = [&](long long v) { return ((v + gran - 1) / gran) * gran; };
-    const long long min_pe = round_up((n_pe + 63) / 64), min_inj = round_up((n_inj + 64 * 64 - 1) / (64 * 64));
-    if (h->chunk_pe < min_pe) h->chunk_pe = (int)min_pe;
-    if (h->chunk_inj < min_inj) h->chunk_inj = (int)min_inj;
-  }
-  // the scan receives its tile sizes in 16 bits each (ScanHead::chunks): exact below 32 768 samples, multiples of 256 above
-  auto packable = [](int c) { return c >= 32768 && c % 256 ? (c / 256 + 1) * 256 : c; };
-  h->chunk_pe = packable(h->chunk_pe);
-  h->chunk_inj = packable(h->chunk_inj);
-  h->tiles_per_event = (int)((n_pe + h->chunk_pe - 1) / h->chunk_pe);
-  h->n_inj_tiles = (int)((n_inj + h->chunk_inj - 1) / h->chunk_inj);
-  h->n_scan_blocks = (int)(n_ev * h->tiles_per_event + h->n_inj_tiles);
-  h->rec_stride = kRecHeader + spec->n_theta;
-  // injection tiles are combined in groups of <= 16 records (one workgroup each): a group's tile values are then
-  // all requested in the combine kernel's first memory round trip (kEarly there)
-  h->tiles_per_inj_group = 16;  // <= 64: one tile per lane in combine_kernel
-  if (const char* env = std::getenv("GWI_TILES_PER_INJ_GROUP")) h->tiles_per_inj_group = std::max(1, std::min(64, std::atoi(env)));
-  h->n_inj_groups = (h->n_inj_tiles + h->tiles_per_inj_group - 1) / h->tiles_per_inj_group;
-  if (h->n_inj_groups < 1) h->n_inj_groups = 1;
-  if (h->n_inj_groups > 64) {  // final_kernel maps groups to the lanes of one wave
-    h->tiles_per_inj_group = (h->n_inj_tiles + 63) / 64;
-    h->n_inj_groups = (h->n_inj_tiles + h->tiles_per_inj_group - 1) / h->tiles_per_inj_group;
-  }
-  if (h->tiles_per_event > 64 || h->tiles_per_inj_group > 64 || h->n_inj_groups > 64)
-    return fail(h, GWI_ERR_INVALID, "launch geometry: more than 64 tile records per group (internal error: the tile sizes above should have prevented this)");
-  h->scan_lds_bytes = scan_lds;
-  if (const char* env = std::getenv("GWI_BATCH_GEOMETRY")) {  // 0: batched launches on the single evaluation's geometry
-    if (std::atoi(env) == 0) spb_batch = 0;
-  }
-  // Parametric models have two batched kernels: one grid row per point (scan_kernel BATCH: the catalog streams K times through
-  // L2 / the Infinity Cache) and scan_pbatch_kernel (every sample loaded once for the points a workgroup draws; single-trip
-  // tiles: the single evaluation's where those are single trips already, else a batch geometry of one trip per workgroup).
-  // Which one is faster turned out to depend on the BOX: round 5's boxes ran pbatch 3-8 % ahead (42.3 against 43.7 us at config 2,
-  // K = 16), every box of round 6 ran it 5-14 % behind at every catalog size from 1 to 8 x config 2 (49.4 against 54.8 us; 287
-  // against 327 us at 8 x; blocking 242-251 k against 215-227 k evals/s: profiles/round6/EXPERIMENTS.md section 5) although it issues
-  // 30 % fewer instructions and moves a seventh of the bytes -- the denser fp64 kernel is the one whose time varies from box to
-  // box.  The choice must be static (the two sum in different orders): the row-per-point kernel is the default since round 6,
-  // GWI_PBATCH=1 (or a row size, GWI_PBATCH_PTS) selects the one-load-per-sample kernel.
+  h->mfma_lds_bytes = sizeof(double) * mfma_lds_doubles(spec->n_theta, spec->n_terms, h->mfma->row_doubles, h->batch_rows ? h->rows_rep : 0);
+  if (h->mfma_lds_bytes > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(h->batch_rows ? h->mfma->rows_fn : h->mfma->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->mfma_lds_bytes);
+}
+
+// The launch geometries (gwi_plan.h: plan_geometry states the rules and their knobs) and, for a parametric model, whether
+// batched launches load every sample once.
+// Parametric models have two batched kernels: one grid row per point (scan_kernel BATCH: the catalog streams K times through
+// L2 / the Infinity Cache) and scan_pbatch_kernel (every sample loaded once for the points a workgroup draws; single-trip
+// tiles: the single evaluation's where those are single trips already, else a batch geometry of one trip per workgroup).
+// Which one is faster turned out to depend on the BOX: round 5's boxes ran pbatch 3-8 % ahead (42.3 against 43.7 us at config 2,
+// K = 16), every box of round 6 ran it 5-14 % behind at every catalog size from 1 to 8 x config 2 (49.4 against 54.8 us; 287
+// against 327 us at 8 x; blocking 242-251 k against 215-227 k evals/s: profiles/round6/EXPERIMENTS.md section 5) although it issues
+// 30 % fewer instructions and moves a seventh of the bytes -- the denser fp64 kernel is the one whose time varies from box to
+// box.  The choice must be static (the two sum in different orders): the row-per-point kernel is the default since round 6,
+// GWI_PBATCH=1 (or a row size, GWI_PBATCH_PTS) selects the one-load-per-sample kernel.
+static gwi_status plan_launch(gwi_engine* h, Creation& cr) {
+  const gwi_plan::Knobs& knobs = cr.knobs;
+  // resident workgroups per CU of one of this chain's kernels
+  auto occupancy = [&](int role, size_t lds, int* occ) {
+    return h->variant->jit ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(occ, h->jit_fn[role], kBlock, lds)
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, h->variant->fn[role], kBlock, lds);
+  };
+  int scan_occupancy = 0;  // 0: not known (and not asked where GWI_SAMPLES_PER_BLOCK names the workgroup size)
+  if (knobs.samples_per_block.v <= 0 && occupancy(jit::kScan, h->scan_lds_bytes, &scan_occupancy) != hipSuccess) scan_occupancy = 0;
   h->pbatch = false;
-  if (const char* env = std::getenv("GWI_PBATCH_PTS")) h->pbatch_pts = std::max(0, std::atoi(env));
-  if (const char* env = std::getenv("GWI_PBATCH")) h->pbatch = std::atoi(env) != 0;
-  else h->pbatch = h->pbatch_pts > 0;
+  if (knobs.pbatch_pts.set) h->pbatch_pts = std::max(0, knobs.pbatch_pts.v);
+  h->pbatch = knobs.pbatch.set ? knobs.pbatch.v != 0 : h->pbatch_pts > 0;
   h->pbatch = h->pbatch && h->variant->has(jit::kPbatch) && !h->generic;
   h->pbatch_balanced = h->pbatch_pts == 0;  // (naming a row size asks for the rows mode)
-  if (const char* env = std::getenv("GWI_PBATCH_BALANCED")) h->pbatch_balanced = std::atoi(env) != 0;
+  if (knobs.pbatch_balanced.set) h->pbatch_balanced = knobs.pbatch_balanced.v != 0;
   if (h->pbatch) {
     int occ = 0;
-    const hipError_t oe = h->variant->jit ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, h->jit_fn[jit::kPbatch], kBlock, 0)
-                                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, h->variant->fn[jit::kPbatch], kBlock, 0);
+    const hipError_t oe = occupancy(jit::kPbatch, 0, &occ);
     if (oe != hipSuccess) (void)hipGetLastError();
     h->pbatch_wgs_per_cu = (oe == hipSuccess && occ > 0) ? std::min(occ, 8) : 4;
-    if (const char* env = std::getenv("GWI_PBATCH_WGS_PER_CU")) h->pbatch_wgs_per_cu = std::max(1, std::min(16, std::atoi(env)));
+    if (knobs.pbatch_wgs_per_cu.set) h->pbatch_wgs_per_cu = std::max(1, std::min(16, knobs.pbatch_wgs_per_cu.v));
   }
-  if (h->pbatch && !std::getenv("GWI_BATCH_GEOMETRY")) spb_batch = (long long)pbatch_u(h->variant->samples_per_lane) * kBlock;  // (not distinct below where that is the single geometry)
-  if (spb_batch > 0 && !std::getenv("GWI_PE_CHUNK") && !std::getenv("GWI_INJ_CHUNK")) {
-    auto& b = h->bgeo;
-    b.chunk_pe = packable((int)(spb_batch < n_pe_pad ? spb_batch : n_pe_pad));
-    b.chunk_inj = packable((int)spb_batch);
-    b.tiles_per_event = (int)((n_pe + b.chunk_pe - 1) / b.chunk_pe);
-    b.n_inj_tiles = (int)((n_inj + b.chunk_inj - 1) / b.chunk_inj);
-    b.n_scan_blocks = (int)(n_ev * b.tiles_per_event + b.n_inj_tiles);
-    b.tiles_per_inj_group = 16;
-    b.n_inj_groups = std::max(1, (b.n_inj_tiles + b.tiles_per_inj_group - 1) / b.tiles_per_inj_group);
-    if (b.n_inj_groups > 64) {  // final_kernel maps groups to the lanes of one wave
-      b.tiles_per_inj_group = (b.n_inj_tiles + 63) / 64;
-      b.n_inj_groups = (b.n_inj_tiles + b.tiles_per_inj_group - 1) / b.tiles_per_inj_group;
-    }
-    // within what the tail kernels take (64 tile records per group, 64 groups); the buffers below hold either geometry
-    b.distinct = b.tiles_per_event <= 64 && b.tiles_per_event < (1 << kGeomTilesBits) && b.tiles_per_inj_group <= 64 && b.n_inj_groups <= 64 &&
-                 (b.chunk_pe != h->chunk_pe || b.chunk_inj != h->chunk_inj);
-  }
-  const int max_scan_blocks = std::max(h->n_scan_blocks, h->bgeo.distinct ? h->bgeo.n_scan_blocks : 0);
-  const int max_inj_groups = std::max(h->n_inj_groups, h->bgeo.distinct ? h->bgeo.n_inj_groups : 0);
+  const long long pbatch_spb = h->pbatch ? (long long)pbatch_u(h->variant->samples_per_lane) * kBlock : 0;
+  const gwi_plan::LaunchPlan plan = gwi_plan::plan_geometry(h->n_ev, h->n_pe, h->n_inj, h->n_cus, h->variant->samples_per_lane, scan_occupancy, h->small_geometry, pbatch_spb, knobs);
+  h->geo[0] = plan.geo[0];
+  h->geo[1] = plan.geo[1];
+  h->rec_stride = kRecHeader + cr.spec->n_theta;
+  if (!gwi_plan::fits_tail(h->geo[0]))
+    return fail(h, GWI_ERR_INVALID, "launch geometry: more than 64 tile records per group (internal error: the tile sizes above should have prevented this)");
+  cr.max_scan_blocks = std::max(h->geo[0].n_scan_blocks, h->geo[1].distinct ? h->geo[1].n_scan_blocks : 0);
+  cr.max_inj_groups = std::max(h->geo[0].n_inj_groups, h->geo[1].distinct ? h->geo[1].n_inj_groups : 0);
+  return GWI_OK;
+}
 
+// device and pinned host memory of the evaluations; every buffer holds either launch geometry
+static gwi_status allocate_buffers(gwi_engine* h, const Creation& cr) {
+  const gwi_spec* spec = cr.spec;
+  const gwi_plan::Knobs& knobs = cr.knobs;
   const size_t KB = (size_t)h->max_batch;  // every per-evaluation buffer holds max_batch hyper-parameter points
-  GWI_HIP(hipMalloc(&h->d_partials, sizeof(double) * KB * (size_t)(max_scan_blocks ? max_scan_blocks : 1) * h->rec_stride));
-  GWI_HIP(hipMalloc(&h->d_ev_out, sizeof(double) * KB * 4 * (size_t)(n_ev ? n_ev : 1)));
-  GWI_HIP(hipMalloc(&h->d_ev_grad, sizeof(double) * KB * (size_t)(n_ev ? n_ev : 1) * spec->n_theta));
-  GWI_HIP(hipMalloc(&h->d_inj_out, sizeof(double) * KB * 4 * (size_t)max_inj_groups));
-  GWI_HIP(hipMalloc(&h->d_inj_grad, sizeof(double) * KB * (size_t)max_inj_groups * spec->n_theta));
+  GWI_HIP(hipMalloc(&h->d_partials, sizeof(double) * KB * (size_t)(cr.max_scan_blocks ? cr.max_scan_blocks : 1) * h->rec_stride));
+  GWI_HIP(hipMalloc(&h->d_ev_out, sizeof(double) * KB * 4 * (size_t)(h->n_ev ? h->n_ev : 1)));
+  GWI_HIP(hipMalloc(&h->d_ev_grad, sizeof(double) * KB * (size_t)(h->n_ev ? h->n_ev : 1) * spec->n_theta));
+  GWI_HIP(hipMalloc(&h->d_inj_out, sizeof(double) * KB * 4 * (size_t)cr.max_inj_groups));
+  GWI_HIP(hipMalloc(&h->d_inj_grad, sizeof(double) * KB * (size_t)cr.max_inj_groups * spec->n_theta));
   GWI_HIP(hipMalloc(&h->d_tblocks, sizeof(ThetaBlock) * KB));
   GWI_HIP(hipHostMalloc((void**)&h->h_tblocks, sizeof(ThetaBlock) * KB, hipHostMallocMapped));
   GWI_HIP(hipHostGetDevicePointer((void**)&h->h_tblocks_dev, h->h_tblocks, 0));
-  if (const char* env = std::getenv("GWI_STAGE_KERNEL")) h->stage_kernel = std::atoi(env) != 0;
+  if (knobs.stage_kernel.set) h->stage_kernel = knobs.stage_kernel.v != 0;
   GWI_HIP(hipHostMalloc((void**)&h->h_record, sizeof(double) * KB * record_len(h), hipHostMallocMapped));
   GWI_HIP(hipHostGetDevicePointer((void**)&h->h_record_dev, h->h_record, 0));
-  GWI_HIP(hipHostMalloc((void**)&h->h_ev, sizeof(double) * KB * 3 * (size_t)(n_ev ? n_ev : 1), hipHostMallocMapped));
+  GWI_HIP(hipHostMalloc((void**)&h->h_ev, sizeof(double) * KB * 3 * (size_t)(h->n_ev ? h->n_ev : 1), hipHostMallocMapped));
   GWI_HIP(hipHostGetDevicePointer((void**)&h->h_ev_dev, h->h_ev, 0));
   std::memset(h->h_record, 0, sizeof(double) * KB * record_len(h));
   // the final launch: one workgroup per ~48 events (at most 8), each publishing a partial record (config 5, 200 events:
   // 1 / 4 / 8 / 16 workgroups = 7.6 / 5.8 / 5.9 / 6.7 us -- more records are more small PCIe writes)
-  h->final_groups = (int)std::max<long long>(1, std::min<long long>(8, n_ev / 48));
-  if (const char* env = std::getenv("GWI_FINAL_GROUPS")) h->final_groups = std::max(1, std::min(64, std::atoi(env)));
+  h->final_groups = (int)std::max<long long>(1, std::min<long long>(8, h->n_ev / 48));
+  if (knobs.final_groups.set) h->final_groups = std::max(1, std::min(64, knobs.final_groups.v));
   GWI_HIP(hipHostMalloc((void**)&h->h_fin, sizeof(double) * KB * h->final_groups * record_len(h), hipHostMallocMapped));
   GWI_HIP(hipHostGetDevicePointer((void**)&h->h_fin_dev, h->h_fin, 0));
   std::memset(h->h_fin, 0, sizeof(double) * KB * h->final_groups * record_len(h));
   {  // tile references of spline models (scan_kernel, shared mode): none yet
-    const size_t n = (size_t)(1 + 2 * h->max_batch) * (size_t)(max_scan_blocks ? max_scan_blocks : 1);  // rows: see nref_row0
+    const size_t n = (size_t)(1 + 2 * h->max_batch) * (size_t)(cr.max_scan_blocks ? cr.max_scan_blocks : 1);  // rows: see nref_row0
     std::vector<int> none(n, kNoRef);
     GWI_HIP(hipMalloc(&h->d_tile_nref, sizeof(int) * n));
     GWI_HIP(hipMemcpy(h->d_tile_nref, none.data(), sizeof(int) * n, hipMemcpyHostToDevice));
@@ -2562,14 +2426,14 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
   // host-final mode for small problems: the per-group rows fit a few KiB, so the host sums them and
   // the third launch (final_kernel: ~1.5 us boundary + ~6-9 us of latency chain) disappears
   {
-    const size_t n_groups = (size_t)n_ev + h->n_inj_groups;
+    const size_t n_groups = (size_t)h->n_ev + h->geo[0].n_inj_groups;
     const size_t row_bytes = 64 * n_groups * (size_t)((3 + spec->n_theta + 6) / 7);  // self-validating 64-byte lines: 7 values + the sequence number
     // measured per evaluation: config 3 (48 KB of rows) gains 2 us from host-final, the reference's default spline counts on 69 events
     // (165 hyper-parameters: 114 KB) 0.85 us (27.35 against 28.21 us; profiles/round6/hostfinal_def50k.txt), config 5 (195 KB) loses 5-8
     size_t host_final_limit = 120 * 1024;
-    if (const char* env = std::getenv("GWI_HOST_FINAL_BYTES")) host_final_limit = (size_t)std::atoll(env);
+    if (knobs.host_final_bytes.set) host_final_limit = (size_t)knobs.host_final_bytes.v;
     h->host_final = row_bytes <= host_final_limit;
-    if (const char* env = std::getenv("GWI_HOST_FINAL")) h->host_final = h->host_final && std::atoi(env) != 0;
+    if (knobs.host_final.set) h->host_final = h->host_final && knobs.host_final.v != 0;
     GWI_HIP(hipHostMalloc((void**)&h->h_rows, KB * row_bytes, hipHostMallocMapped));
     GWI_HIP(hipHostGetDevicePointer((void**)&h->h_rows_dev, h->h_rows, 0));
     std::memset(h->h_rows, 0, KB * row_bytes);
@@ -2580,43 +2444,48 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
     GWI_HIP(hipHostGetDevicePointer((void**)&h->h_norm_stamp_dev, h->h_norm_stamp, 0));
     std::memset(h->h_norm_stamp, 0, sizeof(unsigned long long) * nn);
   }
+  return GWI_OK;
+}
 
-  // ---- constant part of the kernel-argument block
+// the constant part of the kernel-argument block
+static gwi_status fill_kernel_arguments(gwi_engine* h, const Creation& cr) {
+  const gwi_spec* spec = cr.spec;
+  const gwi_plan::Geometry &g = h->geo[0], &b = h->geo[1];
   KArgs& k = h->kargs;
   std::memset(&k, 0, sizeof(k));
   for (int t = 0; t < spec->n_terms; ++t)
     for (int j = 0; j < 2; ++j) {
       const int c = spec->terms[t].cols[j] >= 0 && spec->terms[t].cols[j] < spec->n_cols ? spec->terms[t].cols[j] : spec->terms[t].cols[0];
-      k.pe_tcols[t][j] = (j == 0 && over_pe[t]) ? over_pe[t] : (j == 1 && over_pe1[t]) ? over_pe1[t] : tab_pe[c];
-      k.inj_tcols[t][j] = (j == 0 && over_inj[t]) ? over_inj[t] : (j == 1 && over_inj1[t]) ? over_inj1[t] : tab_inj[c];
+      k.pe_tcols[t][j] = (j == 0 && cr.over_pe[t]) ? cr.over_pe[t] : (j == 1 && cr.over_pe1[t]) ? cr.over_pe1[t] : cr.tab_pe[c];
+      k.inj_tcols[t][j] = (j == 0 && cr.over_inj[t]) ? cr.over_inj[t] : (j == 1 && cr.over_inj1[t]) ? cr.over_inj1[t] : cr.tab_inj[c];
     }
-  k.kappa_pe = tab_pe[spec->kappa_col];
-  k.kappa_inj = tab_inj[spec->kappa_col];
+  k.kappa_pe = cr.tab_pe[spec->kappa_col];
+  k.kappa_inj = cr.tab_inj[spec->kappa_col];
   k.norms = h->d_norms;
   k.norm_out_host = h->h_norm_dev;
   k.norm_stamps_host = h->h_norm_stamp_dev;
   k.partials = h->d_partials;
-  k.n_pe = n_pe;
-  k.n_inj = n_inj;
-  k.n_ev = (int)n_ev;
-  k.tiles_per_event = h->tiles_per_event;
-  k.chunk_pe = h->chunk_pe;
-  k.n_inj_tiles = h->n_inj_tiles;
-  k.chunk_inj = h->chunk_inj;
+  k.n_pe = h->n_pe;
+  k.n_inj = h->n_inj;
+  k.n_ev = (int)h->n_ev;
+  k.tiles_per_event = g.tiles_per_event;
+  k.chunk_pe = g.chunk_pe;
+  k.n_inj_tiles = g.n_inj_tiles;
+  k.chunk_inj = g.chunk_inj;
   k.n_norms = spec->n_norms;
   k.n_terms = spec->n_terms;
   k.n_theta = spec->n_theta;
   k.kappa_col = spec->kappa_col;
   k.rec_stride = h->rec_stride;
 #ifdef GWI_STAMPS
-  GWI_HIP(hipMalloc(&k.stamps, sizeof(unsigned long long) * (size_t)(h->n_scan_blocks + spec->n_norms + 1) * kWaves * 8));
-  GWI_HIP(hipMemset(k.stamps, 0, sizeof(unsigned long long) * (size_t)(h->n_scan_blocks + spec->n_norms + 1) * kWaves * 8));
+  GWI_HIP(hipMalloc(&k.stamps, sizeof(unsigned long long) * (size_t)(g.n_scan_blocks + spec->n_norms + 1) * kWaves * 8));
+  GWI_HIP(hipMemset(k.stamps, 0, sizeof(unsigned long long) * (size_t)(g.n_scan_blocks + spec->n_norms + 1) * kWaves * 8));
 #endif
-  k.gacc_rep = rep;
-  k.gacc_shift = __builtin_ctz((unsigned)rep);
+  k.gacc_rep = h->gacc_rep;
+  k.gacc_shift = __builtin_ctz((unsigned)h->gacc_rep);
   k.seq_dev = h->d_seq;
   k.tile_nref = h->d_tile_nref;
-  k.nref_stride = max_scan_blocks ? max_scan_blocks : 1;
+  k.nref_stride = cr.max_scan_blocks ? cr.max_scan_blocks : 1;
   k.rows_rep = h->rows_rep;
   k.redo_host = h->h_redo_dev;
   k.redo_dev = h->d_seq + 1;
@@ -2638,11 +2507,11 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
       for (int j = 0; j < term_cols(spec->terms[t].kind) && j < 2; ++j) put(k.pe_tcols[t][j], k.inj_tcols[t][j], j == 0 && is_narrow_kind(spec->terms[t].kind));
     for (; slot < kHeadCols; ++slot) hd.col[slot] = k.kappa_pe;  // unused slots: any valid address
     if (!joint) return fail(h, GWI_ERR_INVALID, "internal error: a column's injection part does not sit inj_offset() behind its posterior-sample part");
-    if (n_ev >= (1LL << kGeomEventBits) || n_pe >= (1LL << 32) || n_inj >= (1LL << 32) || spec->n_norms >= 16 || h->tiles_per_event >= (1 << kGeomTilesBits) ||
-        !chunk_packs(h->chunk_pe) || !chunk_packs(h->chunk_inj) || (h->bgeo.distinct && (!chunk_packs(h->bgeo.chunk_pe) || !chunk_packs(h->bgeo.chunk_inj))))
+    if (h->n_ev >= (1LL << kGeomEventBits) || h->n_pe >= (1LL << 32) || h->n_inj >= (1LL << 32) || spec->n_norms >= 16 || g.tiles_per_event >= (1 << kGeomTilesBits) ||
+        !chunk_packs(g.chunk_pe) || !chunk_packs(g.chunk_inj) || (b.distinct && (!chunk_packs(b.chunk_pe) || !chunk_packs(b.chunk_inj))))
       return fail(h, GWI_ERR_INVALID, "catalog shape outside the scan's packed geometry (events < 2^20, samples per event and injections < 2^32, tiles < 8.4 M samples)");
-    hd.n_pe = (unsigned)n_pe;
-    hd.n_inj = (unsigned)n_inj;
+    hd.n_pe = (unsigned)h->n_pe;
+    hd.n_inj = (unsigned)h->n_inj;
   }
   for (int t = 0; t < spec->n_terms; ++t) {
     const gwi_term& tm = spec->terms[t];
@@ -2667,7 +2536,67 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
     }
   }
   h->combine_threads = spec->n_theta + 4 <= 64 ? 64 : kBlock;
-  if (const char* env = std::getenv("GWI_COMBINE_THREADS")) h->combine_threads = std::atoi(env) == 64 ? 64 : kBlock;
+  if (cr.knobs.combine_threads.set) h->combine_threads = cr.knobs.combine_threads.v == 64 ? 64 : kBlock;
+  return GWI_OK;
+}
+
+static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols, int64_t n_ev, int64_t n_pe, const double* const* inj_cols, int64_t n_inj,
+                              int32_t device, gwi_handle* out, const gwi_ingest_program* ing_pe, const gwi_ingest_program* ing_inj) {
+  if (!out) return GWI_ERR_INVALID;
+  *out = nullptr;
+  const bool ingest = ing_pe != nullptr;
+  if (!spec || n_ev < 0 || n_pe < 1 || n_inj < 0) return GWI_ERR_INVALID;
+  if (ingest ? !ing_inj : (!pe_cols || !inj_cols)) return GWI_ERR_INVALID;
+  int n_dev = 0;
+  if (device != GWI_DEVICE_HOST_ONLY && (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1)) return GWI_ERR_NO_DEVICE;
+  gwi_engine* h = new (std::nothrow) gwi_engine();
+  if (!h) return GWI_ERR_INVALID;
+  *out = h;  // returned even on failure so gwi_last_error() can explain; caller must gwi_destroy()
+  gwi_status st = validate_spec(h, spec);
+  if (st != GWI_OK) return st;
+  h->spec = *spec;
+  if (device == GWI_DEVICE_HOST_ONLY) {
+    h->host_only = true;
+    h->n_ev = n_ev;
+    h->n_pe = n_pe;
+    h->n_inj = n_inj;
+    for (int j = 0; j < spec->n_norms; ++j) h->spec.norms[j].tw = h->spec.norms[j].lb = h->spec.norms[j].l1 = h->spec.norms[j].us = nullptr;
+    std::memset(&h->kargs, 0, sizeof(h->kargs));
+    return GWI_OK;
+  }
+  if (device < 0) {
+    GWI_HIP(hipGetDevice(&h->device));
+  } else {
+    if (device >= n_dev) return fail(h, GWI_ERR_NO_DEVICE, "device index out of range");
+    h->device = device;
+  }
+  GWI_HIP(hipSetDevice(h->device));
+  hipDeviceProp_t prop;
+  GWI_HIP(hipGetDeviceProperties(&prop, h->device));
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(h, GWI_ERR_NO_DEVICE, std::string("engine is built for gfx950 only; device reports ") + prop.gcnArchName);
+  h->n_cus = prop.multiProcessorCount;
+  Creation cr{spec, pe_cols, inj_cols, ing_pe, ing_inj, n_ev, n_pe, n_inj, gwi_plan::Knobs::from_env()};
+  const gwi_plan::Knobs& knobs = cr.knobs;
+  choose_scan_kernel(h, cr);
+  GWI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  if (knobs.spin_wait.set) h->spin_wait = knobs.spin_wait.v != 0;
+  for (auto& e : h->ev) GWI_HIP(hipEventCreate(&e));
+  if (knobs.max_batch.set) h->max_batch = knobs.max_batch.v;
+  h->max_batch = std::max(1, std::min(64, h->max_batch));
+  h->n_ev = n_ev;
+  h->n_pe = n_pe;
+  h->n_inj = n_inj;
+  h->inj_off = inj_offset(n_ev, n_pe);
+  if ((st = upload_columns(h, cr)) != GWI_OK) return st;
+  if ((st = narrow_columns(h, cr)) != GWI_OK) return st;
+  if ((st = knot_coordinates(h, cr)) != GWI_OK) return st;
+  if ((st = upload_norms(h, cr)) != GWI_OK) return st;
+  size_gradient_rows(h, cr);
+  choose_batch_kernel(h, cr);
+  if ((st = plan_launch(h, cr)) != GWI_OK) return st;
+  if ((st = allocate_buffers(h, cr)) != GWI_OK) return st;
+  if ((st = fill_kernel_arguments(h, cr)) != GWI_OK) return st;
   setup_aql(h, prop);
   return GWI_OK;
 }
@@ -2844,12 +2773,13 @@ const char* gwi_dispatch_info(gwi_handle h) {
 
 gwi_status gwi_launch_geometry(gwi_handle h, int32_t out[6]) {
   if (!h || !out || h->host_only) return GWI_ERR_INVALID;
-  out[0] = h->chunk_pe;
-  out[1] = h->chunk_inj;
-  out[2] = h->tiles_per_event;
-  out[3] = h->n_inj_tiles;
-  out[4] = h->n_scan_blocks;
-  out[5] = h->n_inj_groups;
+  const gwi_plan::Geometry& g = h->geo[0];
+  out[0] = g.chunk_pe;
+  out[1] = g.chunk_inj;
+  out[2] = g.tiles_per_event;
+  out[3] = g.n_inj_tiles;
+  out[4] = g.n_scan_blocks;
+  out[5] = g.n_inj_groups;
   return GWI_OK;
 }
 
@@ -2873,9 +2803,8 @@ const char* gwi_batch_path(gwi_handle h, int32_t k_batch) {
   const bool safe = h->variant && h->variant->has(jit::kSafe) && h->kargs.deterministic;
   if (h->variant && h->variant->has(jit::kPbatch) && !h->generic) {  // parametric model: one load per sample where the tiles of a launch of k_batch points are single trips
     const long long gran = (long long)pbatch_u(h->variant->samples_per_lane) * kBlock;
-    const bool bg = k_batch >= 4 && h->bgeo.distinct;
-    if (h->pbatch && (bg ? h->bgeo.chunk_pe : h->chunk_pe) <= gran && (bg ? h->bgeo.chunk_inj : h->chunk_inj) <= gran &&
-        ((h->pbatch_balanced && k_batch >= kPbatchBalancedFrom) || pbatch_points(h, k_batch, bg ? 1 : 0) > 1))
+    const gwi_plan::Geometry& g = h->geo[k_batch >= 4 && h->geo[1].distinct ? 1 : 0];
+    if (h->pbatch && g.chunk_pe <= gran && g.chunk_inj <= gran && ((h->pbatch_balanced && k_batch >= kPbatchBalancedFrom) || pbatch_points(h, k_batch, g) > 1))
       return "pbatch";
     return "rows-per-point";
   }
@@ -3641,7 +3570,7 @@ extern "C" void gwi_debug_host_phases(double* out6) {
 // diagnostic build only (not part of the ABI): fetch the per-wave phase stamps of the last scan launch
 gwi_status gwi_debug_stamps(gwi_handle h, unsigned long long* out, int64_t n_words) {
   if (!h || !out) return GWI_ERR_INVALID;
-  const int64_t have = (int64_t)h->n_scan_blocks * kWaves * 8;
+  const int64_t have = (int64_t)h->geo[0].n_scan_blocks * kWaves * 8;
   GWI_HIP(hipMemcpy(out, h->kargs.stamps, sizeof(unsigned long long) * (size_t)(n_words < have ? n_words : have), hipMemcpyDeviceToHost));
   return GWI_OK;
 }
