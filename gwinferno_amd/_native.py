@@ -242,6 +242,9 @@ EXPORTED_SYMBOLS = [
     "gwi_set_quantile_columns",
     "gwi_weighted_quantiles",
     "gwi_quantile_times",
+    "gwi_set_kde_columns",
+    "gwi_weighted_kde",  # (gwi_weighted_kde2d is bound below and not listed: this list holds the names of letters and underscores the header check finds)
+    "gwi_kde_times",
     "gwi_effective_spins",
     "gwi_chi_p_conditional_prior",
     "gwi_spin_prior_times",
@@ -387,6 +390,16 @@ def load_library():
         lib.gwi_weighted_quantiles.argtypes = [vp, _DP, C.c_int32, _I32P, _I32P, _DP, _DP, _DP]
         lib.gwi_quantile_times.restype = None
         lib.gwi_quantile_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_weighted_kde"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_set_kde_columns.restype = C.c_int32
+        lib.gwi_set_kde_columns.argtypes = [vp, C.c_int32, _DP, _DP, _DP]
+        lib.gwi_weighted_kde.restype = C.c_int32
+        lib.gwi_weighted_kde.argtypes = [vp, _DP, C.c_int32, C.c_int32, C.c_double, _DP, _DP, _DP, _DP, _I32P]
+        lib.gwi_weighted_kde2d.restype = C.c_int32
+        lib.gwi_weighted_kde2d.argtypes = [vp, _I32P, C.c_int32, _DP, C.c_int32, _DP, C.c_int32, C.c_int32, C.c_double, _DP, _DP, _DP, _DP, _I32P]
+        lib.gwi_kde_times.restype = None
+        lib.gwi_kde_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

@@ -11,6 +11,7 @@
 #include "gwi_resample.h"
 #include "gwi_hist.h"
 #include "gwi_quant.h"
+#include "gwi_kde.h"
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
 #include "gwi_plan.h"
@@ -484,6 +485,14 @@ struct PostprocessBuffers {
     DeviceBuffer<int> d_order_pe, d_order_inj, d_idx;
     int cols = 0;
   } quant;
+  // weighted kernel density estimates of the marginal weights (gwi_kde.h): the columns and bounds of gwi_set_kde_columns and the tiles'
+  // and segments' moments (allocated with the columns, kept); the pairs, grids, bandwidth records, partials and densities of one query
+  // (grown on demand, kept)
+  struct Kde {
+    DeviceBuffer<double> d_x_pe, d_x_inj, d_bounds, d_part1, d_seg1, d_part2, d_band, d_bw, d_neff, d_grid, d_partial, d_rho;
+    DeviceBuffer<int> d_pairs, d_degenerate;
+    int cols = 0;
+  } kde;
 };
 }  // namespace
 
@@ -4213,6 +4222,248 @@ gwi_status gwi_weighted_quantiles(gwi_handle h, const double* levels, int32_t n_
 }
 
 void gwi_quantile_times(double* logw_ms, double* add_ms, double* query_ms, int32_t* launches) { g_quantile_times.report(logw_ms, add_ms, query_ms, launches); }
+
+// ---- weighted kernel density estimates of the marginal weights (gwi_kde.h) --------------------------------------------------------
+enum { kKdeStats, kKdeEval, kKdeCopy };
+static thread_local StageTimes g_kde_times;
+
+// the index of the first value of x[n] that is not finite, or -1
+static long long first_not_finite(const double* x, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!(std::fabs(x[i]) < __builtin_inf())) return (long long)i;
+  return -1;
+}
+
+gwi_status gwi_set_kde_columns(gwi_handle h, int32_t n_cols, const double* x_pe, const double* x_inj, const double* bounds) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace K = gwi::kde;
+  gwi_status st = post_preflight(h, "gwi_set_kde_columns", "keep the columns on", "the injection densities need", [&]() -> std::string {
+    if (n_cols < 1 || n_cols > K::kMaxCols) return "n_cols = " + std::to_string(n_cols) + " is not in 1 ... " + std::to_string(K::kMaxCols);
+    if (!x_pe && !x_inj) return "x_pe and x_inj are both null";
+    if (x_pe) {
+      const long long at = first_not_finite(x_pe, (size_t)n_cols * (size_t)(h->n_ev * h->n_pe));
+      if (at >= 0) return "x_pe: value " + std::to_string(at) + " is not finite";
+    }
+    if (x_inj) {
+      const long long at = first_not_finite(x_inj, (size_t)n_cols * (size_t)h->n_inj);
+      if (at >= 0) return "x_inj: value " + std::to_string(at) + " is not finite";
+    }
+    for (int c = 0; bounds && c < n_cols; ++c) {
+      const double lo = bounds[2 * c], hi = bounds[2 * c + 1];
+      if (std::isinf(lo) || std::isinf(hi)) return "bounds of column " + std::to_string(c) + ": a bound is finite or NaN (none)";
+      if (lo == lo && hi == hi && !(lo < hi)) return "bounds of column " + std::to_string(c) + ": lo is not below hi";
+    }
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  gwi::draw::DrawArgs geometry;
+  long long n_tiles = 0;
+  st = draw_workspace(h, "gwi_set_kde_columns", "tiles", &geometry, &n_tiles);
+  if (st != GWI_OK) return st;
+  // the previous columns go away first: should an allocation fail, the density entries refuse until they are set again
+  PostprocessBuffers::Kde& kde = h->post.kde;
+  kde = PostprocessBuffers::Kde();
+  const size_t n_pe_vals = x_pe ? (size_t)n_cols * (size_t)(h->n_ev * h->n_pe) : 0, n_inj_vals = x_inj ? (size_t)n_cols * (size_t)h->n_inj : 0;
+  if (x_pe) {
+    GWI_HIP(kde.d_x_pe.reserve(n_pe_vals));
+    if (n_pe_vals) GWI_HIP(hipMemcpy(kde.d_x_pe, x_pe, sizeof(double) * n_pe_vals, hipMemcpyHostToDevice));
+  }
+  if (x_inj) {
+    GWI_HIP(kde.d_x_inj.reserve(n_inj_vals));
+    if (n_inj_vals) GWI_HIP(hipMemcpy(kde.d_x_inj, x_inj, sizeof(double) * n_inj_vals, hipMemcpyHostToDevice));
+  }
+  double host_bounds[2 * K::kMaxCols];
+  for (int i = 0; i < 2 * n_cols; ++i) host_bounds[i] = bounds ? bounds[i] : __builtin_nan("");
+  GWI_HIP(kde.d_bounds.reserve(2 * K::kMaxCols));
+  GWI_HIP(hipMemcpy(kde.d_bounds, host_bounds, sizeof(double) * 2 * (size_t)n_cols, hipMemcpyHostToDevice));
+  const size_t n_segs = (size_t)(h->n_ev + 1);
+  GWI_HIP(kde.d_part1.reserve((size_t)n_tiles * (size_t)(K::kHead + n_cols)));
+  GWI_HIP(kde.d_seg1.reserve(n_segs * (size_t)(K::kHead + n_cols)));
+  GWI_HIP(kde.d_part2.reserve((size_t)n_tiles * (size_t)(n_cols + K::kMaxPairs)));
+  kde.cols = n_cols;
+  return GWI_OK;
+}
+
+// one query of either dimension (d = 1: pairs is null and n_items the columns; d = 2: n_items pairs).  The arguments have passed
+// the entry's own checks.
+static gwi_status kde_query(gwi_handle h, const char* who, int d, const int32_t* pairs, int n_items, const double* gridx, int n_gx, const double* gridy, int n_gy, int rule,
+                            double scale, double* rho_pe, double* rho_inj, double* bw, double* neff, int32_t* degenerate) {
+  namespace K = gwi::kde;
+  PostprocessBuffers::Kde& kde = h->post.kde;
+  const bool with_pe = kde.d_x_pe.ptr != nullptr, with_inj = kde.d_x_inj.ptr != nullptr;
+  gwi::draw::DrawArgs geometry;
+  long long n_tiles = 0;
+  gwi_status st = draw_workspace(h, who, "tiles", &geometry, &n_tiles);  // (as gwi_set_kde_columns found it)
+  if (st != GWI_OK) return st;
+  st = marginal_state(h);
+  if (st != GWI_OK) return st;
+  if (h->n_ev + 1 > 65535) return fail(h, GWI_ERR_INVALID, std::string(who) + ": more segments than one launch can index");
+  g_kde_times = StageTimes();
+  const size_t n_segs = (size_t)(h->n_ev + 1), n_ev = (size_t)h->n_ev, per_bw = d == 1 ? 1 : 3;
+  const long long n_points = d == 1 ? n_gx : (long long)n_gx * n_gy, n_blocks = (n_points + K::kBlock - 1) / K::kBlock;
+  // a set without columns is left out of the launches: PE tiles and segments come first, the injection set's last
+  const long long n_pe_tiles = h->n_ev * geometry.tiles_per_event;
+  const long long q_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? geometry.n_inj_tiles : 0), q_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
+  // the grid blocks of one evaluation pass: as many as keep the partials within kPartialCap doubles, at least one
+  const long long per_block = std::max<long long>(1, q_tiles) * n_items * K::kBlock;
+  const long long pass_blocks = std::max<long long>(1, std::min<long long>(n_blocks, K::kPartialCap / per_block));
+  const size_t n_gridx = (size_t)n_items * (size_t)n_gx, n_gridy = d == 2 ? (size_t)n_items * (size_t)n_gy : 0;
+  GWI_HIP(kde.d_grid.reserve(n_gridx + n_gridy));
+  GWI_HIP(kde.d_pairs.reserve(2 * K::kMaxPairs));
+  GWI_HIP(kde.d_band.reserve(n_segs * (size_t)n_items * K::kBand));
+  GWI_HIP(kde.d_bw.reserve(n_segs * (size_t)n_items * 3));
+  GWI_HIP(kde.d_neff.reserve(n_segs));
+  GWI_HIP(kde.d_degenerate.reserve(n_segs * (size_t)n_items));
+  GWI_HIP(kde.d_partial.reserve((size_t)(per_block * pass_blocks)));
+  GWI_HIP(kde.d_rho.reserve(n_segs * (size_t)n_items * (size_t)n_points));
+  GWI_HIP(hipMemcpy(kde.d_grid, gridx, sizeof(double) * n_gridx, hipMemcpyHostToDevice));
+  if (d == 2) {
+    GWI_HIP(hipMemcpy(kde.d_grid + n_gridx, gridy, sizeof(double) * n_gridy, hipMemcpyHostToDevice));
+    GWI_HIP(hipMemcpy(kde.d_pairs, pairs, sizeof(int32_t) * 2 * (size_t)n_items, hipMemcpyHostToDevice));
+  }
+  K::Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.w_pe = h->post.marg.d_w;
+  a.w_inj = h->post.marg.d_w + (size_t)(h->n_ev * h->n_pe);
+  a.x_pe = kde.d_x_pe;
+  a.x_inj = kde.d_x_inj;
+  a.bounds = kde.d_bounds;
+  a.pairs = kde.d_pairs;
+  a.part1 = kde.d_part1;
+  a.seg1 = kde.d_seg1;
+  a.part2 = kde.d_part2;
+  a.band = kde.d_band;
+  a.bw = kde.d_bw;
+  a.neff = kde.d_neff;
+  a.degenerate = kde.d_degenerate;
+  a.gridx = kde.d_grid;
+  a.gridy = kde.d_grid + n_gridx;
+  a.partial = kde.d_partial;
+  a.rho = kde.d_rho;
+  a.scale = scale;
+  a.n_pe = h->n_pe;
+  a.n_inj = h->n_inj;
+  a.n_ev = (int)h->n_ev;
+  a.tiles_per_event = geometry.tiles_per_event;
+  a.n_inj_tiles = geometry.n_inj_tiles;
+  a.n_cols = kde.cols;
+  a.n_pairs = d == 2 ? n_items : 0;
+  a.n_items = n_items;
+  a.rule = rule;
+  a.n_gx = n_gx;
+  a.n_gy = d == 2 ? n_gy : 1;
+  a.n_points = (int)n_points;
+  a.first_tile = with_pe ? 0 : (int)n_pe_tiles;
+  a.first_seg = with_pe ? 0 : (int)h->n_ev;
+  LaunchScratch ev(who);
+  GWI_HIP(ev.events(3));
+  GWI_HIP(hipEventRecord(ev.e[0], h->stream));
+  int launches = (q_tiles ? 2 : 0) + (q_segs ? 1 : 0);
+  if (q_tiles) hipLaunchKernelGGL(K::kde_moment_kernel<1>, dim3((unsigned)q_tiles), dim3(K::kBlock), 0, h->stream, a);
+  if (q_segs) hipLaunchKernelGGL(K::kde_mean_kernel, dim3((unsigned)q_segs), dim3(64), 0, h->stream, a);
+  if (q_tiles) hipLaunchKernelGGL(K::kde_moment_kernel<2>, dim3((unsigned)q_tiles), dim3(K::kBlock), 0, h->stream, a);
+  if (q_segs) {
+    if (d == 1) hipLaunchKernelGGL(K::kde_band_kernel<1>, dim3((unsigned)q_segs), dim3(64), 0, h->stream, a);
+    else hipLaunchKernelGGL(K::kde_band_kernel<2>, dim3((unsigned)q_segs), dim3(64), 0, h->stream, a);
+    ++launches;
+  }
+  GWI_HIP(hipGetLastError());
+  GWI_HIP(hipEventRecord(ev.e[1], h->stream));
+  for (long long b0 = 0; b0 < n_blocks && q_segs; b0 += pass_blocks) {
+    const long long nb = std::min<long long>(pass_blocks, n_blocks - b0);
+    a.first_block = (int)b0;
+    a.pass_points = (int)(nb * K::kBlock);
+    if (q_tiles) {
+      if (d == 1) hipLaunchKernelGGL(K::kde_eval_kernel<1>, dim3((unsigned)q_tiles, (unsigned)n_items, (unsigned)nb), dim3(K::kBlock), 0, h->stream, a);
+      else hipLaunchKernelGGL(K::kde_eval_kernel<2>, dim3((unsigned)q_tiles, (unsigned)n_items, (unsigned)nb), dim3(K::kBlock), 0, h->stream, a);
+      ++launches;
+    }
+    hipLaunchKernelGGL(K::kde_sum_kernel, dim3((unsigned)nb, (unsigned)n_items, (unsigned)q_segs), dim3(K::kBlock), 0, h->stream, a);
+    ++launches;
+  }
+  GWI_HIP(hipGetLastError());
+  GWI_HIP(hipEventRecord(ev.e[2], h->stream));
+  GWI_HIP(hipStreamSynchronize(h->stream));
+  float stats_ms = 0.f, eval_ms = 0.f;
+  GWI_HIP(hipEventElapsedTime(&stats_ms, ev.e[0], ev.e[1]));
+  GWI_HIP(hipEventElapsedTime(&eval_ms, ev.e[1], ev.e[2]));
+  g_kde_times.ms[kKdeStats] = stats_ms;
+  g_kde_times.ms[kKdeEval] = eval_ms;
+  g_kde_times.launches = launches;
+  // a segment that is left out: no curve, no bandwidth, nothing flagged
+  const auto t0 = std::chrono::steady_clock::now();
+  for (size_t i = 0; i < n_segs * (size_t)n_items * per_bw; ++i) bw[i] = __builtin_nan("");
+  for (size_t i = 0; i < n_segs; ++i) neff[i] = 0.0;
+  for (size_t i = 0; i < n_segs * (size_t)n_items; ++i) degenerate[i] = 0;
+  const size_t s0 = (size_t)a.first_seg, ns = (size_t)q_segs, per_rho = (size_t)n_items * (size_t)n_points;
+  if (ns) {
+    GWI_HIP(hipMemcpy(bw + s0 * n_items * per_bw, kde.d_bw + s0 * n_items * per_bw, sizeof(double) * ns * n_items * per_bw, hipMemcpyDeviceToHost));
+    GWI_HIP(hipMemcpy(neff + s0, kde.d_neff + s0, sizeof(double) * ns, hipMemcpyDeviceToHost));
+    GWI_HIP(hipMemcpy(degenerate + s0 * n_items, kde.d_degenerate + s0 * n_items, sizeof(int32_t) * ns * n_items, hipMemcpyDeviceToHost));
+  }
+  if (with_pe && n_ev) GWI_HIP(hipMemcpy(rho_pe, kde.d_rho, sizeof(double) * n_ev * per_rho, hipMemcpyDeviceToHost));
+  if (with_inj) GWI_HIP(hipMemcpy(rho_inj, kde.d_rho + n_ev * per_rho, sizeof(double) * per_rho, hipMemcpyDeviceToHost));
+  g_kde_times.ms[kKdeCopy] = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return GWI_OK;
+}
+
+// what is wrong with the arguments the two density entries share, or an empty string.  That no columns are set is said after the
+// other refusals: a handle that holds a shard cannot set any and is told so
+static std::string bad_kde_request(const PostprocessBuffers::Kde& kde, int32_t rule, double scale, const double* rho_pe, const double* rho_inj, const double* bw, const double* neff,
+                                   const int32_t* degenerate) {
+  if (rule != gwi::kde::kScott && rule != gwi::kde::kSilverman) return "rule = " + std::to_string(rule) + " is neither 0 (Scott) nor 1 (Silverman)";
+  if (!(scale > 0.0 && scale < __builtin_inf())) return "scale = " + std::to_string(scale) + " is not a positive finite number";
+  if (kde.d_x_pe.ptr && !rho_pe) return "PE columns are set: rho_pe is needed";
+  if (kde.d_x_inj.ptr && !rho_inj) return "injection columns are set: rho_inj is needed";
+  if (!bw || !neff || !degenerate) return "the bandwidth, neff or degenerate output is null";
+  return "";
+}
+
+gwi_status gwi_weighted_kde(gwi_handle h, const double* grid, int32_t n_grid, int32_t rule, double scale, double* rho_pe, double* rho_inj, double* bw, double* neff,
+                            int32_t* degenerate) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace K = gwi::kde;
+  const PostprocessBuffers::Kde& kde = h->post.kde;
+  gwi_status st = post_preflight(h, "gwi_weighted_kde", "evaluate on", "the injection densities need", [&]() -> std::string {
+    if (n_grid < 1 || n_grid > K::kMaxGrid) return "n_grid = " + std::to_string(n_grid) + " is not in 1 ... " + std::to_string(K::kMaxGrid);
+    const std::string why = bad_kde_request(kde, rule, scale, rho_pe, rho_inj, bw, neff, degenerate);
+    if (!why.empty()) return why;
+    if (!grid) return "grid is null";
+    const long long at = first_not_finite(grid, (size_t)std::max(kde.cols, 1) * (size_t)n_grid);
+    if (at >= 0) return "grid: point " + std::to_string(at) + " is not finite";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  if (!kde.cols) return fail(h, GWI_ERR_INVALID, "gwi_weighted_kde: no columns are set (gwi_set_kde_columns)");
+  return kde_query(h, "gwi_weighted_kde", 1, nullptr, kde.cols, grid, n_grid, nullptr, 1, rule, scale, rho_pe, rho_inj, bw, neff, degenerate);
+}
+
+gwi_status gwi_weighted_kde2d(gwi_handle h, const int32_t* pairs, int32_t n_pairs, const double* gridx, int32_t n_gx, const double* gridy, int32_t n_gy, int32_t rule,
+                              double scale, double* rho_pe, double* rho_inj, double* cov, double* neff, int32_t* degenerate) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace K = gwi::kde;
+  const PostprocessBuffers::Kde& kde = h->post.kde;
+  gwi_status st = post_preflight(h, "gwi_weighted_kde2d", "evaluate on", "the injection densities need", [&]() -> std::string {
+    if (n_pairs < 1 || n_pairs > K::kMaxPairs) return "n_pairs = " + std::to_string(n_pairs) + " is not in 1 ... " + std::to_string(K::kMaxPairs);
+    if (n_gx < 1 || n_gx > K::kMaxGrid2 || n_gy < 1 || n_gy > K::kMaxGrid2)
+      return "n_gx = " + std::to_string(n_gx) + ", n_gy = " + std::to_string(n_gy) + ": not in 1 ... " + std::to_string(K::kMaxGrid2);
+    const std::string why = bad_kde_request(kde, rule, scale, rho_pe, rho_inj, cov, neff, degenerate);
+    if (!why.empty()) return why;
+    if (!pairs || !gridx || !gridy) return "pairs, gridx or gridy is null";
+    for (int i = 0; i < 2 * n_pairs; ++i)
+      if (kde.cols && (pairs[i] < 0 || pairs[i] >= kde.cols)) return "pair " + std::to_string(i / 2) + " names column " + std::to_string(pairs[i]) + ": not in 0 ... " + std::to_string(kde.cols - 1);
+    long long at = first_not_finite(gridx, (size_t)n_pairs * (size_t)n_gx);
+    if (at >= 0) return "gridx: point " + std::to_string(at) + " is not finite";
+    at = first_not_finite(gridy, (size_t)n_pairs * (size_t)n_gy);
+    if (at >= 0) return "gridy: point " + std::to_string(at) + " is not finite";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  if (!kde.cols) return fail(h, GWI_ERR_INVALID, "gwi_weighted_kde2d: no columns are set (gwi_set_kde_columns)");
+  return kde_query(h, "gwi_weighted_kde2d", 2, pairs, n_pairs, gridx, n_gx, gridy, n_gy, rule, scale, rho_pe, rho_inj, cov, neff, degenerate);
+}
+
+void gwi_kde_times(double* stats_ms, double* eval_ms, double* copy_ms, int32_t* launches) { g_kde_times.report(stats_ms, eval_ms, copy_ms, launches); }
 
 }  // extern "C"
 

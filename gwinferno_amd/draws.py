@@ -16,7 +16,10 @@ preprocess/selection.py:143-156) draws from the injection segment by the same ru
 
 ``gwi_marginal_weights_add`` / ``gwi_weighted_quantiles`` (gwinferno_amd/csrc/gwi_quant.h) keep the same ``w_j``, normalised and
 summed over the points, per sample -- the marginal posterior weight ``W_j`` -- and select weighted quantiles and moments under it:
-:func:`marginal_weights_reference` and :func:`weighted_quantiles_reference` state them."""
+:func:`marginal_weights_reference` and :func:`weighted_quantiles_reference` state them.
+
+``gwi_weighted_kde`` / ``gwi_weighted_kde2d`` (gwinferno_amd/csrc/gwi_kde.h) smooth the same ``W_j`` into a Gaussian kernel density
+estimate with scipy's bandwidth rules: :func:`weighted_kde_reference` and :func:`weighted_kde2d_reference` state them."""
 import bisect
 import itertools
 import math
@@ -220,3 +223,110 @@ def weighted_quantiles_reference(W, order, x, levels):
     m1, m2 = math.fsum((ws * xs).tolist()), math.fsum((ws * xs * xs).tolist())
     mass = c_last / 2 ** (-low) if low < 0 else float(c_last * 2**low)  # (true division of integers rounds once)
     return idx, (m1, m2), float(mass)
+
+
+KDE_RULES = {"scott": 0, "silverman": 1}  # the rule codes of gwi_weighted_kde / gwi_weighted_kde2d
+
+
+def kde_rule_code(rule):
+    if rule not in KDE_RULES:
+        raise ValueError(f"rule must be 'scott' or 'silverman', not {rule!r}")
+    return KDE_RULES[rule]
+
+
+def _kde_weights(W, *columns):
+    """The normalised weights of one segment and what scipy.stats.gaussian_kde derives from them: ``(p, s2, n_eff, state)`` with
+    ``state`` "dead" (no weight: ``p`` is None), "degenerate" (fewer than two samples with weight) or "live"."""
+    W = np.asarray(W, dtype=np.float64).ravel()
+    if any(c.shape != W.shape for c in columns):
+        raise ValueError("the values have the shape of W")
+    if np.any(~np.isfinite(W)) or np.any(W < 0.0):
+        raise ValueError("W must be finite and non-negative")
+    if any(np.any(~np.isfinite(c)) for c in columns):
+        raise ValueError("the values must be finite")
+    mass = float(np.sum(W))
+    if not (mass > 0.0 and np.isfinite(mass)):
+        return None, np.nan, 0.0, "dead"
+    p = W / mass
+    s2 = float(np.sum(p * p))
+    return p, s2, 1.0 / s2, "live" if np.count_nonzero(W > 0.0) >= 2 else "degenerate"
+
+
+def kde_factor(n_eff, d, rule="scott", scale=1.0):
+    """scipy.stats.gaussian_kde's factor on the square root of the covariance: ``n_eff^(-1/(d+4))`` (Scott) or
+    ``(n_eff (d+2)/4)^(-1/(d+4))`` (Silverman), times ``scale``."""
+    if not (scale > 0.0 and np.isfinite(scale)):
+        raise ValueError("scale must be a positive finite number")
+    base = n_eff * (d + 2.0) / 4.0 if kde_rule_code(rule) == 1 else n_eff
+    return float(scale) * base ** (-1.0 / (d + 4.0))
+
+
+def weighted_kde_reference(W, x, grid, rule="scott", scale=1.0, bounds=None):
+    """The Gaussian kernel density estimate of ONE segment and ONE quantity under the marginal weights ``W (n,)`` at the points
+    ``grid (G,)``: ``(rho (G,), h, n_eff, degenerate)``.  With ``p = W / sum W``: ``s2 = sum p^2``, ``n_eff = 1 / s2``, the CENTRED
+    variance ``sum p (x - mean)^2 / (1 - s2)``, ``h^2 = var f^2`` with :func:`kde_factor`'s ``f``, and ``rho(g) = sum_i p_i
+    exp(-(g - x_i)^2 / 2 h^2) / sqrt(2 pi h^2)`` -- scipy.stats.gaussian_kde(x, weights=W, bw_method=...).  ``bounds = (lo, hi)``
+    (either may be None or NaN) reflects: the images ``2 lo - x_i`` and ``2 hi - x_i`` are added at points inside ``[lo, hi]``,
+    points outside get 0, and the bandwidth stays that of the unreflected data.  Plain float64 sums.  A segment without weight
+    gives NaN, ``n_eff = 0`` and no flag; one with fewer than two samples with weight, or whose variance is not positive and
+    finite, gives NaN and ``degenerate = 1``."""
+    x, grid = np.asarray(x, dtype=np.float64).ravel(), np.asarray(grid, dtype=np.float64).ravel()
+    if np.any(~np.isfinite(grid)):
+        raise ValueError("grid points must be finite")
+    f_of = lambda n_eff: kde_factor(n_eff, 1, rule, scale)  # noqa: E731  (checks rule and scale whatever the segment)
+    f_of(1.0)
+    p, s2, n_eff, state = _kde_weights(W, x)
+    nothing = np.full(grid.shape, np.nan)
+    if state == "dead":
+        return nothing, np.nan, 0.0, 0
+    if state == "degenerate":
+        return nothing, np.nan, n_eff, 1
+    mean = float(np.sum(p * x))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h2 = float(np.sum(p * (x - mean) ** 2)) / (1.0 - s2) * f_of(n_eff) ** 2
+    if not (h2 > 0.0 and np.isfinite(h2)):
+        return nothing, np.nan, n_eff, 1
+    lo, hi = (np.nan, np.nan) if bounds is None else (np.nan if b is None else float(b) for b in bounds)
+    live = p > 0.0
+    pl, xl = p[live], x[live]
+    kernel = lambda pts: np.exp(-0.5 / h2 * (grid[:, None] - pts[None, :]) ** 2)  # noqa: E731
+    e = kernel(xl)
+    if lo == lo:
+        e = e + kernel(2.0 * lo - xl)
+    if hi == hi:
+        e = e + kernel(2.0 * hi - xl)
+    rho = np.sum(e * pl[None, :], axis=1) / np.sqrt(2.0 * np.pi * h2)
+    rho[(grid < lo) | (grid > hi)] = 0.0
+    return rho, float(np.sqrt(h2)), n_eff, 0
+
+
+def weighted_kde2d_reference(W, x, y, gridx, gridy, rule="scott", scale=1.0):
+    """The two-dimensional counterpart of :func:`weighted_kde_reference` on the tensor grid ``gridx (n_gx,) x gridy (n_gy,)``:
+    ``(rho (n_gx, n_gy), H (3,) = (Hxx, Hxy, Hyy), n_eff, degenerate)`` with ``H = f^2 Cov``, the full centred weighted covariance
+    ``sum p (x - mean_x)(y - mean_y) / (1 - s2)``, and ``rho(gx, gy) = sum_i p_i exp(-d^T H^-1 d / 2) / (2 pi sqrt|H|)``.  No
+    reflection.  Degenerate also where ``|H|`` is not positive and finite."""
+    x, y = np.asarray(x, dtype=np.float64).ravel(), np.asarray(y, dtype=np.float64).ravel()
+    gridx, gridy = np.asarray(gridx, dtype=np.float64).ravel(), np.asarray(gridy, dtype=np.float64).ravel()
+    if np.any(~np.isfinite(gridx)) or np.any(~np.isfinite(gridy)):
+        raise ValueError("grid points must be finite")
+    kde_factor(1.0, 2, rule, scale)
+    p, s2, n_eff, state = _kde_weights(W, x, y)
+    nothing, no_h = np.full((gridx.size, gridy.size), np.nan), np.full(3, np.nan)
+    if state == "dead":
+        return nothing, no_h, 0.0, 0
+    if state == "degenerate":
+        return nothing, no_h, n_eff, 1
+    dx, dy = x - float(np.sum(p * x)), y - float(np.sum(p * y))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        k = kde_factor(n_eff, 2, rule, scale) ** 2 / (1.0 - s2)
+        hxx, hxy, hyy = float(np.sum(p * dx * dx)) * k, float(np.sum(p * dx * dy)) * k, float(np.sum(p * dy * dy)) * k
+        det = hxx * hyy - hxy * hxy
+    if not (det > 0.0 and np.isfinite(det) and hxx > 0.0 and hyy > 0.0):
+        return nothing, no_h, n_eff, 1
+    live = p > 0.0
+    pl, ex, ey = p[live], gridx[:, None] - x[live][None, :], gridy[:, None] - y[live][None, :]  # (n_gx, n), (n_gy, n)
+    rho = np.empty((gridx.size, gridy.size))
+    for i in range(gridx.size):  # (one row of the map at a time: n_gy x n numbers)
+        arg = (-0.5 * hyy / det) * ex[i] ** 2 + (hxy / det) * ex[i] * ey + (-0.5 * hxx / det) * ey**2
+        rho[i] = np.sum(np.exp(arg) * pl[None, :], axis=1)
+    return rho / (2.0 * np.pi * np.sqrt(det)), np.array([hxx, hxy, hyy]), n_eff, 0

@@ -1224,6 +1224,113 @@ class NativePopulationLikelihood:
                                                     N.as_dp(mass)))
         return idx_pe, idx_inj, mom_pe, mom_inj, mass
 
+    def set_kde_columns(self, pe_values=None, inj_values=None, bounds=None):
+        """The quantities :meth:`weighted_kde` and :meth:`weighted_kde2d` smooth (``gwi_set_kde_columns``): ``pe_values (n_cols, n_ev,
+        n_pe)`` and ``inj_values (n_cols, n_inj)``, finite; ``None`` leaves that set out, not both; ``1 <= n_cols <= 8``.  ``bounds
+        (n_cols, 2)`` holds reflecting bounds ``(lo, hi)`` of the 1-D estimate per column, NaN (or ``None`` in a sequence) where
+        there is none; ``None``: no column reflects.  The values are copied to HBM once; no sort order is needed.  Not available
+        on an engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("set_kde_columns", "the injection densities need")
+        if pe_values is None and inj_values is None:
+            raise ValueError("pe_values and inj_values are both None")
+
+        def one(v, shape, name):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.ndim != len(shape) + 1 or v.shape[1:] != shape:
+                raise ValueError(f"{name} has shape {v.shape}; expected (n_cols, {', '.join(str(s) for s in shape)})")
+            if not np.all(np.isfinite(v)):
+                raise ValueError(f"{name} holds values that are not finite")
+            return v
+
+        pe, inj = one(pe_values, (self.n_ev, self.n_pe), "pe_values"), one(inj_values, (self.n_inj,), "inj_values")
+        if pe is not None and inj is not None and pe.shape[0] != inj.shape[0]:
+            raise ValueError(f"pe_values holds {pe.shape[0]} columns, inj_values {inj.shape[0]}")
+        n_cols = (pe if pe is not None else inj).shape[0]
+        if not 1 <= n_cols <= 8:
+            raise ValueError(f"{n_cols} columns: between 1 and 8 can be set")
+        b = np.full((n_cols, 2), np.nan)
+        if bounds is not None:
+            given = np.array([[np.nan if v is None else float(v) for v in row] for row in bounds], dtype=np.float64)
+            if given.shape != (n_cols, 2):
+                raise ValueError(f"bounds has shape {given.shape}; expected ({n_cols}, 2)")
+            if np.any(np.isinf(given)) or np.any(given[:, 0] >= given[:, 1]):
+                raise ValueError("a bound is finite or NaN (none), and lo lies below hi")
+            b = np.ascontiguousarray(given)
+        self._kde_shape = None
+        self._check(self.lib.gwi_set_kde_columns(self.handle, n_cols, N.as_dp(pe) if pe is not None else None, N.as_dp(inj) if inj is not None else None, N.as_dp(b)))
+        self._kde_shape = (n_cols, pe is not None, inj is not None)
+
+    def _kde_request(self, what, rule, scale):
+        from .draws import kde_rule_code
+
+        code, scale = kde_rule_code(rule), float(scale)
+        if not (scale > 0.0 and np.isfinite(scale)):
+            raise ValueError("scale must be a positive finite number")
+        shape = getattr(self, "_kde_shape", None)
+        if shape is None:  # the library says so
+            none, flag = np.zeros(1), np.zeros(1, dtype=np.int32)
+            self._check(self.lib.gwi_weighted_kde(self.handle, N.as_dp(none), 1, code, scale, None, None, N.as_dp(none), N.as_dp(np.zeros(self.n_ev + 1)),
+                                                  flag.ctypes.data_as(C.POINTER(C.c_int32))))
+            raise N.NativeEngineError(f"GWI_ERR_INVALID: {what}: no columns are set (set_kde_columns)")
+        return code, scale, shape
+
+    def weighted_kde(self, grid, rule="scott", scale=1.0):
+        """Weighted Gaussian kernel density estimates of every segment and column under the marginal weights, on the device
+        (``gwi_weighted_kde``; semantics: :func:`gwinferno_amd.draws.weighted_kde_reference`).  ``grid`` is ``(n_cols, G)``
+        or ``(G,)`` (the same points for every column), ``1 <= G <= 1024``, finite, in any order; ``rule`` is ``"scott"`` or
+        ``"silverman"`` and ``scale`` multiplies the factor.  Returns ``(rho_pe (n_ev, n_cols, G), rho_inj (n_cols, G), bw (n_ev + 1,
+        n_cols), neff (n_ev + 1,), degenerate (n_ev + 1, n_cols) int32)``: the densities (``None`` for a set without columns; NaN for
+        a segment without a curve), the bandwidth ``h`` and ``n_eff`` per segment (the injection set last) and the flags."""
+        self._whole_catalog("weighted_kde", "the injection densities need")
+        grid = np.asarray(grid, dtype=np.float64)
+        if grid.ndim not in (1, 2) or grid.shape[-1] < 1 or grid.shape[-1] > 1024:
+            raise ValueError(f"grid has shape {grid.shape}; expected (G,) or (n_cols, G) with 1 <= G <= 1024")
+        if not np.all(np.isfinite(grid)):
+            raise ValueError("grid points must be finite")
+        code, scale, (n_cols, with_pe, with_inj) = self._kde_request("weighted_kde", rule, scale)
+        if grid.ndim == 2 and grid.shape[0] != n_cols:
+            raise ValueError(f"grid has shape {grid.shape}; {n_cols} columns are set")
+        grid = np.ascontiguousarray(np.broadcast_to(grid, (n_cols, grid.shape[-1])))
+        g = grid.shape[1]
+        rho_pe = np.full((self.n_ev, n_cols, g), np.nan) if with_pe else None
+        rho_inj = np.full((n_cols, g), np.nan) if with_inj else None
+        bw, neff, flags = np.full((self.n_ev + 1, n_cols), np.nan), np.zeros(self.n_ev + 1), np.zeros((self.n_ev + 1, n_cols), dtype=np.int32)
+        self._check(self.lib.gwi_weighted_kde(self.handle, N.as_dp(grid), g, code, scale, N.as_dp(rho_pe) if with_pe else None, N.as_dp(rho_inj) if with_inj else None,
+                                              N.as_dp(bw), N.as_dp(neff), flags.ctypes.data_as(C.POINTER(C.c_int32))))
+        return rho_pe, rho_inj, bw, neff, flags
+
+    def weighted_kde2d(self, pairs, gridx, gridy, rule="scott", scale=1.0):
+        """Two-dimensional weighted Gaussian kernel density estimates of every segment and pair of columns, on the device
+        (``gwi_weighted_kde2d``; semantics: :func:`gwinferno_amd.draws.weighted_kde2d_reference`).  ``pairs`` is ``(n_pairs, 2)``
+        column indices, ``1 <= n_pairs <= 4``; ``gridx (n_pairs, n_gx)`` or ``(n_gx,)`` and ``gridy`` likewise, at most 128 points
+        each: the map is evaluated on the tensor grid.  No reflection.  Returns ``(rho_pe (n_ev, n_pairs, n_gx, n_gy), rho_inj (n_pairs,
+        n_gx, n_gy), cov (n_ev + 1, n_pairs, 3) = (Hxx, Hxy, Hyy), neff (n_ev + 1,), degenerate (n_ev + 1, n_pairs) int32)``."""
+        self._whole_catalog("weighted_kde2d", "the injection densities need")
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        if not 1 <= pairs.shape[0] <= 4:
+            raise ValueError(f"{pairs.shape[0]} pairs: between 1 and 4 can be asked for in one query")
+        gridx, gridy = np.asarray(gridx, dtype=np.float64), np.asarray(gridy, dtype=np.float64)
+        for name, g in (("gridx", gridx), ("gridy", gridy)):
+            if g.ndim not in (1, 2) or g.shape[-1] < 1 or g.shape[-1] > 128 or (g.ndim == 2 and g.shape[0] != pairs.shape[0]):
+                raise ValueError(f"{name} has shape {g.shape}; expected (n,) or (n_pairs, n) with 1 <= n <= 128")
+            if not np.all(np.isfinite(g)):
+                raise ValueError("grid points must be finite")
+        code, scale, (n_cols, with_pe, with_inj) = self._kde_request("weighted_kde2d", rule, scale)
+        n_pairs = pairs.shape[0]
+        gridx = np.ascontiguousarray(np.broadcast_to(gridx, (n_pairs, gridx.shape[-1])))
+        gridy = np.ascontiguousarray(np.broadcast_to(gridy, (n_pairs, gridy.shape[-1])))
+        n_gx, n_gy = gridx.shape[1], gridy.shape[1]
+        rho_pe = np.full((self.n_ev, n_pairs, n_gx, n_gy), np.nan) if with_pe else None
+        rho_inj = np.full((n_pairs, n_gx, n_gy), np.nan) if with_inj else None
+        cov, neff, flags = np.full((self.n_ev + 1, n_pairs, 3), np.nan), np.zeros(self.n_ev + 1), np.zeros((self.n_ev + 1, n_pairs), dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._check(self.lib.gwi_weighted_kde2d(self.handle, pairs.ctypes.data_as(i32), n_pairs, N.as_dp(gridx), n_gx, N.as_dp(gridy), n_gy, code, scale,
+                                                N.as_dp(rho_pe) if with_pe else None, N.as_dp(rho_inj) if with_inj else None, N.as_dp(cov), N.as_dp(neff),
+                                                flags.ctypes.data_as(i32)))
+        return rho_pe, rho_inj, cov, neff, flags
+
     def selftime(self, theta, total_inj, n_iter=1000, min_neff_cut=True):
         """Mean seconds per evaluation of a C-side loop of sequential gwi_eval calls (diagnostic)."""
         opt = self._options(total_inj, None, False, min_neff_cut, False)

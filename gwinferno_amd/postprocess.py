@@ -364,6 +364,49 @@ def reweighted_event_posteriors(eng, thetas, pe_values, edges, inj_values=None, 
     return result
 
 
+def _summary_columns(eng, pe_values, inj_values, pedata, injdata, param_names):
+    """The quantities of a per-event summary as ``(names, x_pe (C, n_ev, n_pe), x_inj (C, n_inj) or None)``: from ``pe_values`` /
+    ``inj_values`` (name -> array), or read from ``pedata`` / ``injdata`` by ``param_names``."""
+    if pe_values is None:
+        if pedata is None or param_names is None:
+            raise ValueError("without pe_values, pedata and param_names name the quantities")
+        pe_values = pedata
+        if inj_values is None and injdata is not None:
+            inj_values = injdata
+    names = list(param_names) if param_names is not None else list(pe_values)
+    if not 1 <= len(names) <= 8:
+        raise ValueError("between 1 and 8 quantities can be summarised in one pass")
+    n_ev, n_pe, n_inj = eng.n_ev, eng.n_pe, eng.n_inj
+    x_pe = np.empty((len(names), n_ev, n_pe))
+    x_inj = np.empty((len(names), n_inj)) if inj_values is not None else None
+    for c, p in enumerate(names):
+        v = np.asarray(pe_values[p], dtype=np.float64)
+        if v.shape != (n_ev, n_pe):
+            raise ValueError(f"pe_values[{p!r}] has shape {v.shape}, the engine's sample set {(n_ev, n_pe)}")
+        x_pe[c] = v
+        if x_inj is not None:
+            v = np.asarray(inj_values[p], dtype=np.float64)
+            if v.shape != (n_inj,):
+                raise ValueError(f"inj_values[{p!r}] has shape {v.shape}, the engine's injection set {(n_inj,)}")
+            x_inj[c] = v
+    if not np.all(np.isfinite(x_pe)) or (x_inj is not None and not np.all(np.isfinite(x_inj))):
+        raise ValueError("the quantities must be finite")
+    return names, x_pe, x_inj
+
+
+def _mass_cut_masks(pedata, injdata, m1min, m2min, mmax):
+    """``(pe_mask, inj_mask)`` of the mass cuts when all three are given and both data dictionaries are at hand, else ``(None,
+    None)``: the mask the engine holds stays."""
+    from . import draws as D
+
+    cuts = (m1min, m2min, mmax)
+    if pedata is not None and injdata is not None and all(c is not None for c in cuts):
+        return D.mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    if any(c is not None for c in cuts) and not all(c is not None for c in cuts):
+        raise ValueError("m1min, m2min and mmax are given together or not at all")
+    return None, None
+
+
 def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), inj_values=None, pedata=None, injdata=None, param_names=None, m1min=None, m2min=None,
                              mmax=None, backend="device", return_weights=False):
     """Credible intervals of the population-informed posterior of every event, marginalised over K posterior hyper-parameter draws:
@@ -400,39 +443,11 @@ def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), i
         raise ValueError("between 1 and 32 levels can be asked for in one query")
     if not np.all((levels >= 0.0) & (levels <= 1.0)):
         raise ValueError("levels must lie in [0, 1]")
-    if pe_values is None:
-        if pedata is None or param_names is None:
-            raise ValueError("without pe_values, pedata and param_names name the quantities")
-        pe_values = pedata
-        if inj_values is None and injdata is not None:
-            inj_values = injdata
-    names = list(param_names) if param_names is not None else list(pe_values)
-    if not 1 <= len(names) <= 8:
-        raise ValueError("between 1 and 8 quantities can be summarised in one pass")
-    n_ev, n_pe, n_inj = eng.n_ev, eng.n_pe, eng.n_inj
-    x_pe = np.empty((len(names), n_ev, n_pe))
-    x_inj = np.empty((len(names), n_inj)) if inj_values is not None else None
-    for c, p in enumerate(names):
-        v = np.asarray(pe_values[p], dtype=np.float64)
-        if v.shape != (n_ev, n_pe):
-            raise ValueError(f"pe_values[{p!r}] has shape {v.shape}, the engine's sample set {(n_ev, n_pe)}")
-        x_pe[c] = v
-        if x_inj is not None:
-            v = np.asarray(inj_values[p], dtype=np.float64)
-            if v.shape != (n_inj,):
-                raise ValueError(f"inj_values[{p!r}] has shape {v.shape}, the engine's injection set {(n_inj,)}")
-            x_inj[c] = v
-    if not np.all(np.isfinite(x_pe)) or (x_inj is not None and not np.all(np.isfinite(x_inj))):
-        raise ValueError("the quantities must be finite")
-    cuts = (m1min, m2min, mmax)
-    masks = (None, None)
-    if pedata is not None and injdata is not None and all(c is not None for c in cuts):
-        masks = D.mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
-        if backend == "device":
-            eng.set_draw_mask(*masks)
-    elif any(c is not None for c in cuts) and not all(c is not None for c in cuts):
-        raise ValueError("m1min, m2min and mmax are given together or not at all")
-    n_cols, n_q = len(names), levels.size
+    names, x_pe, x_inj = _summary_columns(eng, pe_values, inj_values, pedata, injdata, param_names)
+    masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    if backend == "device" and masks[0] is not None:
+        eng.set_draw_mask(*masks)
+    n_cols, n_q, n_ev = len(names), levels.size, eng.n_ev
     if backend == "device":
         eng.set_quantile_columns(x_pe, x_inj)
         eng.marginal_weights_reset()
@@ -467,4 +482,103 @@ def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), i
         out["dead_inj"] = int(dead[n_ev])
     if return_weights:
         out["weights"], out["weights_inj"] = w_pe, w_inj
+    return out
+
+
+def event_posterior_densities(eng, thetas, pe_values, grid, pairs=None, grid2d=None, inj_values=None, bounds=None, rule="scott", scale=1.0, pedata=None, injdata=None,
+                              param_names=None, m1min=None, m2min=None, mmax=None, backend="device", accumulate=True):
+    """Smooth densities of the population-informed posterior of every event, marginalised over K posterior hyper-parameter draws: per
+    event and quantity a weighted Gaussian kernel density estimate of the marginal posterior weights ``W_i = sum_k w_ki / S_k`` on
+    the points of ``grid`` (the curves of a ridge or violin plot), per pair of quantities the same in two dimensions on a tensor grid
+    (the map behind joint contours), and both for the predicted detected distribution from the injections.  The bandwidth rules are
+    scipy.stats.gaussian_kde(weights=...)'s.  On the device (``eng.weighted_kde``, ``eng.weighted_kde2d``) the weights
+    never leave HBM; only the curves come back.
+
+    ``thetas``, ``pe_values`` / ``inj_values`` (or ``pedata`` / ``injdata`` with ``param_names``), the mass cuts and the masks are
+    :func:`event_credible_intervals`'.  ``grid`` maps a name to its ``(G,)`` points, or is one ``(G,)`` or ``(C, G)`` array (all
+    columns need the same G <= 1024).  ``pairs`` lists up to 4 pairs of names (or column indices) and ``grid2d = (gridx, gridy)``
+    gives their axes, ``(n,)`` or ``(n_pairs, n)`` with n <= 128.  ``bounds`` maps a name to reflecting bounds ``(lo, hi)`` of its 1-D
+    curve (``None`` for an open side); there is no reflection in 2-D.  ``rule`` is ``"scott"`` or ``"silverman"``, ``scale``
+    multiplies the factor.  ``accumulate=False`` leaves the engine's marginal weights as they are -- those a preceding
+    :func:`event_credible_intervals` call on the same ``thetas`` left, so that the table and the figure cost one pass over the
+    points -- and sets no mask.  ``backend="host"`` runs the NumPy statement (:func:`gwinferno_amd.draws.weighted_kde_reference`,
+    :func:`gwinferno_amd.draws.weighted_kde2d_reference`) on ``eng.marginal_weights()``: the statement the kernels are tested
+    against, not a fall-back.
+
+    Returns a dict: ``names``, ``grid (C, G)``, ``density (n_ev, C, G)``, ``bandwidth (n_ev, C)``, ``neff (n_ev,)``, ``degenerate
+    (n_ev, C)``, ``dead (n_ev,)`` (the points at which the event had no weight) and ``n_points``; with ``inj_values`` also
+    ``density_inj (C, G)``, ``bandwidth_inj``, ``neff_inj``, ``degenerate_inj`` and ``dead_inj``; with ``pairs`` also ``pairs``
+    (column indices), ``density2d (n_ev, P, n_gx, n_gy)``, ``covariance (n_ev, P, 3)`` (``Hxx, Hxy, Hyy``), ``degenerate2d`` and their
+    ``_inj`` counterparts.  A segment without a curve gives NaN."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    if thetas.shape[0] < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    D.kde_factor(1.0, 1, rule, scale)  # (checks both)
+    names, x_pe, x_inj = _summary_columns(eng, pe_values, inj_values, pedata, injdata, param_names)
+    n_cols, n_ev = len(names), eng.n_ev
+    grid = np.stack([np.asarray(grid[p], dtype=np.float64) for p in names]) if isinstance(grid, dict) else np.asarray(grid, dtype=np.float64)
+    if grid.ndim not in (1, 2) or (grid.ndim == 2 and grid.shape[0] != n_cols) or not 1 <= grid.shape[-1] <= 1024:
+        raise ValueError(f"grid has shape {grid.shape}; expected (G,) or ({n_cols}, G) with 1 <= G <= 1024")
+    grid = np.ascontiguousarray(np.broadcast_to(grid, (n_cols, grid.shape[-1])))
+    if not np.all(np.isfinite(grid)):
+        raise ValueError("grid points must be finite")
+    b = np.full((n_cols, 2), np.nan)
+    for p, pair in (bounds or {}).items():
+        if p not in names:
+            raise ValueError(f"bounds name {p!r}, which is not one of the quantities")
+        b[names.index(p)] = [np.nan if v is None else float(v) for v in pair]
+    pair_idx = None
+    if pairs is not None:
+        if grid2d is None:
+            raise ValueError("pairs need grid2d = (gridx, gridy)")
+        pair_idx = np.array([[names.index(v) if isinstance(v, str) else int(v) for v in pair] for pair in pairs], dtype=np.int32).reshape(-1, 2)
+        if not 1 <= pair_idx.shape[0] <= 4 or np.any(pair_idx < 0) or np.any(pair_idx >= n_cols):
+            raise ValueError("between 1 and 4 pairs of the quantities can be asked for in one query")
+        gridx, gridy = (np.ascontiguousarray(np.broadcast_to(np.asarray(g, dtype=np.float64), (pair_idx.shape[0], np.shape(g)[-1]))) for g in grid2d)
+        if not (1 <= gridx.shape[1] <= 128 and 1 <= gridy.shape[1] <= 128) or not (np.all(np.isfinite(gridx)) and np.all(np.isfinite(gridy))):
+            raise ValueError("grid2d holds one to 128 finite points per axis")
+    if accumulate:
+        masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+        if masks[0] is not None:
+            eng.set_draw_mask(*masks)
+        eng.marginal_weights_reset()
+        eng.marginal_weights_add(thetas)
+    n_segs = n_ev + 1
+    if backend == "device":
+        eng.set_kde_columns(x_pe, x_inj, b)
+        rho_pe, rho_inj, bw, neff, flags = eng.weighted_kde(grid, rule, scale)
+        if pair_idx is not None:
+            rho2_pe, rho2_inj, cov, _, flags2 = eng.weighted_kde2d(pair_idx, gridx, gridy, rule, scale)
+        _, _, dead, n_points = eng.marginal_weights(weights=False)
+    else:
+        w_pe, w_inj, dead, n_points = eng.marginal_weights()
+        g = grid.shape[1]
+        rho_pe, rho_inj = np.full((n_ev, n_cols, g), np.nan), (np.full((n_cols, g), np.nan) if x_inj is not None else None)
+        bw, neff, flags = np.full((n_segs, n_cols), np.nan), np.zeros(n_segs), np.zeros((n_segs, n_cols), dtype=np.int32)
+        for c in range(n_cols):
+            for ev in range(n_ev):
+                rho_pe[ev, c], bw[ev, c], neff[ev], flags[ev, c] = D.weighted_kde_reference(w_pe[ev], x_pe[c, ev], grid[c], rule, scale, b[c])
+            if x_inj is not None:
+                rho_inj[c], bw[n_ev, c], neff[n_ev], flags[n_ev, c] = D.weighted_kde_reference(w_inj, x_inj[c], grid[c], rule, scale, b[c])
+        if pair_idx is not None:
+            n_p, shape = pair_idx.shape[0], (gridx.shape[1], gridy.shape[1])
+            rho2_pe, rho2_inj = np.full((n_ev, n_p) + shape, np.nan), (np.full((n_p,) + shape, np.nan) if x_inj is not None else None)
+            cov, flags2 = np.full((n_segs, n_p, 3), np.nan), np.zeros((n_segs, n_p), dtype=np.int32)
+            for t, (cx, cy) in enumerate(pair_idx):
+                for ev in range(n_ev):
+                    rho2_pe[ev, t], cov[ev, t], _, flags2[ev, t] = D.weighted_kde2d_reference(w_pe[ev], x_pe[cx, ev], x_pe[cy, ev], gridx[t], gridy[t], rule, scale)
+                if x_inj is not None:
+                    rho2_inj[t], cov[n_ev, t], _, flags2[n_ev, t] = D.weighted_kde2d_reference(w_inj, x_inj[cx], x_inj[cy], gridx[t], gridy[t], rule, scale)
+    out = {"names": names, "grid": grid, "n_points": n_points, "dead": np.asarray(dead[:n_ev]).copy(), "density": rho_pe, "bandwidth": bw[:n_ev], "neff": neff[:n_ev],
+           "degenerate": flags[:n_ev]}
+    if x_inj is not None:
+        out.update(density_inj=rho_inj, bandwidth_inj=bw[n_ev], neff_inj=float(neff[n_ev]), degenerate_inj=flags[n_ev], dead_inj=int(dead[n_ev]))
+    if pair_idx is not None:
+        out.update(pairs=pair_idx, grid2d=(gridx, gridy), density2d=rho2_pe, covariance=cov[:n_ev], degenerate2d=flags2[:n_ev])
+        if x_inj is not None:
+            out.update(density2d_inj=rho2_inj, covariance_inj=cov[n_ev], degenerate2d_inj=flags2[n_ev])
     return out

@@ -502,6 +502,51 @@ gwi_status gwi_weighted_quantiles(gwi_handle h, const double* levels, int32_t n_
                                   double* mass /* [n_ev + 1] */);
 void gwi_quantile_times(double* logw_ms, double* add_ms, double* query_ms, int32_t* launches);
 
+/* Smooth densities of the population-informed event posteriors on the device: a weighted Gaussian kernel density estimate of the
+ * marginal weights W that gwi_marginal_weights_add accumulated, per segment (an event's n_pe samples, or the injection set: segment
+ * n_ev), per quantity in one dimension and per pair of quantities in two, on the caller's grid points (gwinferno_amd/csrc/gwi_kde.h;
+ * the NumPy statement is gwinferno_amd/draws.py: weighted_kde_reference, weighted_kde2d_reference; the contract is DESIGN 8e).  One
+ * accumulation serves quantiles, 1-D and 2-D densities and any number of column sets.
+ *
+ * Bandwidth: scipy.stats.gaussian_kde(weights=...)'s.  With p_i = W_i / sum W over the segment: s2 = sum p_i^2, n_eff = 1 / s2, the
+ * mean sum p_i x_i, and the covariance sum p_i (x_i - mean)(y_i - mean_y) / (1 - s2), centred on the mean of a first pass.  The
+ * factor is f = n_eff^(-1/(d+4)) (rule 0, Scott) or (n_eff (d+2)/4)^(-1/(d+4)) (rule 1, Silverman), times scale > 0.
+ * 1-D: h^2 = var f^2, rho(g) = sum_i p_i exp(-(g - x_i)^2 / 2h^2) / sqrt(2 pi h^2).  A column may have reflecting bounds lo, hi
+ * (bounds[c] = {lo, hi}; NaN: none; bounds NULL: none at all): the images 2 lo - x_i and 2 hi - x_i are added for grid points inside
+ * [lo, hi], points outside get 0, and the bandwidth is that of the unreflected data.
+ * 2-D: H = f^2 Cov (the full 2 x 2 matrix), rho(gx, gy) = sum_i p_i exp(-d^T H^-1 d / 2) / (2 pi sqrt|H|) on the tensor grid
+ * gridx[pair] x gridy[pair]; no reflection.
+ * Grid points must be finite; they need not be uniform or sorted.  1 <= n_cols <= 8, 1 <= n_grid <= 1024, 1 <= n_pairs <= 4,
+ * 1 <= n_gx, n_gy <= 128.
+ *
+ * A segment without weight gives NaN, neff = 0 and no flag (so does every segment when nothing is accumulated).  A segment with fewer
+ * than two samples of positive weight, or whose variance (|H|) is not > 0 and finite, gives NaN and degenerate = 1.  bw holds h
+ * (cov: Hxx, Hxy, Hyy), NaN where there is no curve.  A set without columns is left out: its outputs are not written (bw NaN, neff 0).
+ *
+ * The value at a grid point is a pure function of the point, the segment's W and values and the rule: every sum has a fixed shape
+ * (sample order inside a tile of 1 024 samples, then tile order) and there are no atomics.  A grid split over calls gives the bits
+ * of one call, point by point; so do two calls, two handles of one model, and the same W however it was accumulated.
+ *
+ * gwi_set_kde_columns(): the values (finite: checked on the host) are copied to HBM once; a new call replaces them.  Either set may be
+ * NULL (it is then left out), not both.  No sort order is needed.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for null pointers, counts outside the limits, a value or grid point that is not
+ * finite, a bound that is infinite or lo >= hi, scale not > 0, an unknown rule, a pair index outside the columns, a call before the
+ * columns are set and a host-only handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard, as gwi_weighted_quantiles.
+ *
+ * gwi_kde_times(): DIAGNOSTIC ONLY, for tools/weighted_kde_time.py: of the calling thread's last density query the device time (HIP
+ * events) of the four statistics launches and of the evaluation and sum launches, the wall time of the copies to the host, and the
+ * number of kernel launches. */
+gwi_status gwi_set_kde_columns(gwi_handle h, int32_t n_cols, const double* x_pe /* [n_cols][n_ev][n_pe] or NULL */, const double* x_inj /* [n_cols][n_inj] or NULL */,
+                               const double* bounds /* [n_cols][2], NaN = none; or NULL */);
+gwi_status gwi_weighted_kde(gwi_handle h, const double* grid /* [n_cols][n_grid] */, int32_t n_grid, int32_t rule, double scale, double* rho_pe /* [n_ev][n_cols][n_grid] */,
+                            double* rho_inj /* [n_cols][n_grid] */, double* bw /* [n_ev + 1][n_cols]: h */, double* neff /* [n_ev + 1] */,
+                            int32_t* degenerate /* [n_ev + 1][n_cols] */);
+gwi_status gwi_weighted_kde2d(gwi_handle h, const int32_t* pairs /* [n_pairs][2] column indices */, int32_t n_pairs, const double* gridx /* [n_pairs][n_gx] */, int32_t n_gx,
+                              const double* gridy /* [n_pairs][n_gy] */, int32_t n_gy, int32_t rule, double scale, double* rho_pe /* [n_ev][n_pairs][n_gx][n_gy] */,
+                              double* rho_inj /* [n_pairs][n_gx][n_gy] */, double* cov /* [n_ev + 1][n_pairs][3]: H */, double* neff /* [n_ev + 1] */,
+                              int32_t* degenerate /* [n_ev + 1][n_pairs] */);
+void gwi_kde_times(double* stats_ms, double* eval_ms, double* copy_ms, int32_t* launches);
+
 /* Effective-spin catalogs (gwinferno_amd/csrc/gwi_spinprior.h; the NumPy statement is gwinferno_amd/spin_priors.py).  Stand-alone
  * entries like gwi_ingest_columns: no handle, host pointers in and out, their own stream and buffers on `device` (negative: the
  * calling thread's current device).  The calling thread's current device is the same after the call as before it.
