@@ -235,9 +235,12 @@ EXPORTED_SYMBOLS = [
     "gwi_resample_times",
     "gwi_set_histogram_bins",
     "gwi_weighted_histograms",
+    "gwi_weighted_histograms_weighted",
     "gwi_histogram_times",
     "gwi_marginal_weights_reset",
     "gwi_marginal_weights_add",
+    "gwi_marginal_weights_add_weighted",
+    "gwi_marginal_point_weights",
     "gwi_marginal_weights_read",
     "gwi_set_quantile_columns",
     "gwi_weighted_quantiles",
@@ -400,6 +403,14 @@ def load_library():
         lib.gwi_weighted_kde2d.argtypes = [vp, _I32P, C.c_int32, _DP, C.c_int32, _DP, C.c_int32, C.c_int32, C.c_double, _DP, _DP, _DP, _DP, _I32P]
         lib.gwi_kde_times.restype = None
         lib.gwi_kde_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_marginal_weights_add_weighted"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_marginal_weights_add_weighted.restype = C.c_int32
+        lib.gwi_marginal_weights_add_weighted.argtypes = [vp, _DP, C.c_int32, _DP]
+        lib.gwi_marginal_point_weights.restype = C.c_int32
+        lib.gwi_marginal_point_weights.argtypes = [vp, _DP, _DP]
+        lib.gwi_weighted_histograms_weighted.restype = C.c_int32
+        lib.gwi_weighted_histograms_weighted.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _DP, _I32P, _DP]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

@@ -454,6 +454,7 @@ struct DeviceBuffer {
 // device memory is freed; gwi_set_histogram_bins does the same with `hist`.
 struct PostprocessBuffers {
   DeviceBuffer<double> d_logw_pe, d_logw_inj;  // the log-weight role of the scan chain (fill_log_weights)
+  DeviceBuffer<double> d_point_w;              // the points' weights [k][n_ev + 1] of one weighted call (grown on demand, kept)
   // index draws (gwi_draw.h): the caller's masks, the tiles' (max, sum, mass, prefix) + the segments' maxima, and the uniforms /
   // indices of one gwi_draw_indices call (grown on demand, kept)
   DeviceBuffer<unsigned char> d_draw_mask_pe, d_draw_mask_inj;
@@ -464,17 +465,19 @@ struct PostprocessBuffers {
   DeviceBuffer<double> d_rs_tiles, d_rs_prefix, d_rs_lw;
   DeviceBuffer<int> d_rs_live, d_rs_idx;
   // weighted histograms (gwi_hist.h): the bin codes of gwi_set_histogram_bins, the tiles' partial histograms, the running sums
-  // [n_ev + 1][n_cols][n_bins] and the dead counts [n_ev + 1] of one gwi_weighted_histograms call (allocated with the bins, kept)
+  // [n_ev + 1][n_cols][n_bins], the dead counts [n_ev + 1] and the sums of the points' weights [n_ev + 1] of one
+  // gwi_weighted_histograms(_weighted) call (allocated with the bins, kept)
   struct Histogram {
     DeviceBuffer<unsigned short> d_bins_pe, d_bins_inj;
-    DeviceBuffer<double> d_partial, d_sums;
+    DeviceBuffer<double> d_partial, d_sums, d_vsum;
     DeviceBuffer<int> d_dead;
     int cols = 0, bins = 0;
   } hist;
   // marginal weights and their quantiles (gwi_quant.h).  The state of the handle: one running double per sample [n_ev n_pe | n_inj],
-  // the dead counts [n_ev + 1] (allocated and zeroed on the first use of any of the entries) and the number of points added
+  // the dead counts [n_ev + 1], the sums of the points' weights and of their squares [2][n_ev + 1] (allocated and zeroed on the
+  // first use of any of the entries) and the number of points added
   struct Marginal {
-    DeviceBuffer<double> d_w;
+    DeviceBuffer<double> d_w, d_vsum;
     DeviceBuffer<int> d_dead;
     long long n_points = 0;
   } marg;
@@ -3858,6 +3861,27 @@ gwi_status gwi_resample_injections(gwi_handle h, const double* theta, uint64_t s
 
 void gwi_resample_times(double* logw_ms, double* prefix_ms, double* select_ms, int32_t* launches) { g_resample_times.report(logw_ms, prefix_ms, select_ms, launches); }
 
+// ---- the points' weights of the weighted post-processing entries ------------------------------------------------------------------
+// what is wrong with v[k][n_segs], or an empty string: every entry a number in [0, 1]
+static std::string bad_point_weights(const double* v, int32_t k, long long n_segs) {
+  if (!v) return "v is null";
+  for (long long i = 0; i < (long long)k * n_segs; ++i)
+    if (!(v[i] >= 0.0 && v[i] <= 1.0))
+      return "v: point " + std::to_string(i / n_segs) + ", segment " + std::to_string(i % n_segs) + " is " + std::to_string(v[i]) + ": not in [0, 1]";
+  return "";
+}
+
+// v[k][n_ev + 1] copied to the engine's device once per call
+static gwi_status upload_point_weights(gwi_handle h, const double* v, int32_t k, const double** d_v) {
+  const size_t n = (size_t)k * (size_t)(h->n_ev + 1);
+  *d_v = nullptr;
+  if (!n) return GWI_OK;
+  GWI_HIP(h->post.d_point_w.reserve(n));
+  GWI_HIP(hipMemcpy(h->post.d_point_w, v, sizeof(double) * n, hipMemcpyHostToDevice));
+  *d_v = h->post.d_point_w;
+  return GWI_OK;
+}
+
 // ---- weighted histograms (gwi_hist.h) ---------------------------------------------------------------------------------------
 enum { kHistLogw, kHistTile, kHistMerge };
 static thread_local StageTimes g_histogram_times;
@@ -3900,24 +3924,28 @@ gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, 
   GWI_HIP(hist.d_partial.reserve((size_t)n_tiles * per_seg));
   GWI_HIP(hist.d_sums.reserve((size_t)(h->n_ev + 1) * per_seg));
   GWI_HIP(hist.d_dead.reserve((size_t)(h->n_ev + 1)));
+  GWI_HIP(hist.d_vsum.reserve((size_t)(h->n_ev + 1)));
   hist.cols = n_cols;
   hist.bins = n_bins;
   return GWI_OK;
 }
 
-gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k, double* hist_pe, double* hist_inj, int32_t* dead) {
-  if (!h) return GWI_ERR_INVALID;
+// gwi_weighted_histograms (weighted = false: v and vsum are not looked at) and gwi_weighted_histograms_weighted
+static gwi_status weighted_histograms(gwi_handle h, const char* who, bool weighted, const double* thetas, int32_t k, const double* v, double* hist_pe, double* hist_inj,
+                                      int32_t* dead, double* vsum) {
   g_histogram_times = StageTimes();
   const PostprocessBuffers::Histogram& hist = h->post.hist;
   const bool with_pe = hist.d_bins_pe.ptr != nullptr, with_inj = hist.d_bins_inj.ptr != nullptr;
-  gwi_status st = post_preflight(h, "gwi_weighted_histograms", "sum on", "the injection histogram needs", [&]() -> std::string {
+  gwi_status st = post_preflight(h, who, "sum on", "the injection histogram needs", [&]() -> std::string {
     if (!h->variant) return "the engine has no scan kernel";
     if (!hist.cols) return "no bins are set (gwi_set_histogram_bins)";
+    if (weighted && k < 0) return "k < 0";
     if (!thetas || k < 1) return "thetas is null or k < 1";
     if (with_pe && !hist_pe) return "pe_bins are set: hist_pe is needed";
     if (with_inj && !hist_inj) return "inj_bins are set: hist_inj is needed";
     if (!dead) return "dead is null";
-    return "";
+    if (weighted && !vsum) return "vsum is null";
+    return weighted ? bad_point_weights(v, k, h->n_ev + 1) : std::string();
   });
   if (st != GWI_OK) return st;
   namespace D = gwi::draw;
@@ -3925,8 +3953,14 @@ gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k
   H::Args a;
   std::memset(&a, 0, sizeof(a));
   long long n_tiles = 0;
-  st = draw_workspace(h, "gwi_weighted_histograms", "tiles", &a.d, &n_tiles);  // (as gwi_set_histogram_bins found it)
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);  // (as gwi_set_histogram_bins found it)
   if (st != GWI_OK) return st;
+  const double* d_v = nullptr;
+  if (weighted) {
+    st = upload_point_weights(h, v, k, &d_v);
+    if (st != GWI_OK) return st;
+    GWI_HIP(hipMemcpy(hist.d_vsum, vsum, sizeof(double) * (size_t)(h->n_ev + 1), hipMemcpyHostToDevice));
+  }
   const long long n_pe_tiles = h->n_ev * a.d.tiles_per_event;
   const size_t per_seg = (size_t)hist.cols * (size_t)hist.bins, n_pe_out = (size_t)h->n_ev * per_seg;
   // the caller's running sums: the points of this call are added onto them, so a request may be split over calls
@@ -3938,13 +3972,14 @@ gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k
   a.partial = hist.d_partial;
   a.hist = hist.d_sums;
   a.n_dead = hist.d_dead;
+  a.vsum = hist.d_vsum;
   a.n_cols = hist.cols;
   a.n_bins = hist.bins;
   // a set without bins is left out of the two new launches: PE tiles and segments come first, the injection set's last
   a.first_tile = with_pe ? 0 : (int)n_pe_tiles;
   a.first_seg = with_pe ? 0 : (int)h->n_ev;
   const long long hist_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? a.d.n_inj_tiles : 0), hist_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
-  LaunchScratch ev("gwi_weighted_histograms");
+  LaunchScratch ev(who);
   GWI_HIP(ev.events(3));
   const int nt = h->spec.n_theta;
   for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
@@ -3959,7 +3994,14 @@ gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k
     hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.d);
     if (hist_tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)hist_tiles), dim3(H::kBlock), 0, h->stream, a);
     GWI_HIP(hipEventRecord(ev.e[1], h->stream));
-    if (hist_segs) hipLaunchKernelGGL(H::hist_merge_kernel, dim3((unsigned)hist_segs, (unsigned)a.n_cols), dim3(H::kBlock), 0, h->stream, a);
+    if (hist_segs) {
+      if (weighted) {
+        a.v = d_v + (size_t)p * (size_t)(h->n_ev + 1);
+        hipLaunchKernelGGL(H::hist_merge_kernel<true>, dim3((unsigned)hist_segs, (unsigned)a.n_cols), dim3(H::kBlock), 0, h->stream, a);
+      } else {
+        hipLaunchKernelGGL(H::hist_merge_kernel<false>, dim3((unsigned)hist_segs, (unsigned)a.n_cols), dim3(H::kBlock), 0, h->stream, a);
+      }
+    }
     GWI_HIP(hipGetLastError());
     GWI_HIP(hipEventRecord(ev.e[2], h->stream));
     // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
@@ -3974,7 +4016,21 @@ gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k
   if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(hist_pe, hist.d_sums, sizeof(double) * n_pe_out, hipMemcpyDeviceToHost));
   if (with_inj) GWI_HIP(hipMemcpy(hist_inj, hist.d_sums + n_pe_out, sizeof(double) * per_seg, hipMemcpyDeviceToHost));
   GWI_HIP(hipMemcpy(dead, hist.d_dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyDeviceToHost));
+  if (weighted) GWI_HIP(hipMemcpy(vsum, hist.d_vsum, sizeof(double) * (size_t)(h->n_ev + 1), hipMemcpyDeviceToHost));
   return GWI_OK;
+}
+
+gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k, double* hist_pe, double* hist_inj, int32_t* dead) {
+  if (!h) return GWI_ERR_INVALID;
+  return weighted_histograms(h, "gwi_weighted_histograms", false, thetas, k, nullptr, hist_pe, hist_inj, dead, nullptr);
+}
+
+gwi_status gwi_weighted_histograms_weighted(gwi_handle h, const double* thetas, int32_t k, const double* v, double* hist_pe, double* hist_inj, int32_t* dead, double* vsum) {
+  if (!h) return GWI_ERR_INVALID;
+  // a handle that holds a shard can have no bins (gwi_set_histogram_bins refuses it): it is told that it holds a shard, not that no bins are set
+  if (!h->host_only && (h->comm_world > 1 || h->shm_world > 1))
+    return fail(h, GWI_ERR_UNSUPPORTED, "gwi_weighted_histograms_weighted: this handle holds one shard of the catalog; the injection histogram needs the global set");
+  return weighted_histograms(h, "gwi_weighted_histograms_weighted", true, thetas, k, v, hist_pe, hist_inj, dead, vsum);
 }
 
 void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) { g_histogram_times.report(logw_ms, tile_ms, merge_ms, launches); }
@@ -3986,13 +4042,15 @@ static thread_local StageTimes g_quantile_times;
 // the handle's marginal weights and dead counts on the engine's device (selected by the caller): allocated and zeroed on first use
 static gwi_status marginal_state(gwi_handle h) {
   PostprocessBuffers::Marginal& m = h->post.marg;
-  if (m.d_w.ptr && m.d_dead.ptr) return GWI_OK;
+  if (m.d_w.ptr && m.d_dead.ptr && m.d_vsum.ptr) return GWI_OK;
   const size_t n_w = (size_t)(h->n_ev * h->n_pe) + (size_t)h->n_inj, n_dead = (size_t)(h->n_ev + 1);
   m = PostprocessBuffers::Marginal();
   GWI_HIP(m.d_w.reserve(n_w));
   GWI_HIP(m.d_dead.reserve(n_dead));
+  GWI_HIP(m.d_vsum.reserve(2 * n_dead));
   GWI_HIP(hipMemsetAsync(m.d_w, 0, sizeof(double) * (n_w ? n_w : 1), h->stream));
   GWI_HIP(hipMemsetAsync(m.d_dead, 0, sizeof(int) * n_dead, h->stream));
+  GWI_HIP(hipMemsetAsync(m.d_vsum, 0, sizeof(double) * 2 * n_dead, h->stream));
   GWI_HIP(hipStreamSynchronize(h->stream));
   return GWI_OK;
 }
@@ -4006,13 +4064,13 @@ gwi_status gwi_marginal_weights_reset(gwi_handle h) {
   return marginal_state(h);
 }
 
-gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t k) {
-  if (!h) return GWI_ERR_INVALID;
+// gwi_marginal_weights_add (weighted = false: v is not looked at) and gwi_marginal_weights_add_weighted
+static gwi_status marginal_weights_add(gwi_handle h, const char* who, bool weighted, const double* thetas, int32_t k, const double* v) {
   g_quantile_times = StageTimes();
-  gwi_status st = post_preflight(h, "gwi_marginal_weights_add", "sum on", "the injection weights need", [&]() -> std::string {
+  gwi_status st = post_preflight(h, who, "sum on", "the injection weights need", [&]() -> std::string {
     if (!h->variant) return "the engine has no scan kernel";
     if (!thetas || k < 0) return "thetas is null or k < 0";
-    return "";
+    return weighted ? bad_point_weights(v, k, h->n_ev + 1) : std::string();
   });
   if (st != GWI_OK) return st;
   namespace D = gwi::draw;
@@ -4020,15 +4078,22 @@ gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t 
   Q::MargArgs a;
   std::memset(&a, 0, sizeof(a));
   long long n_tiles = 0;
-  st = draw_workspace(h, "gwi_marginal_weights_add", "tiles", &a.d, &n_tiles);
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);
   if (st != GWI_OK) return st;
   st = marginal_state(h);
   if (st != GWI_OK) return st;
+  const double* d_v = nullptr;
+  if (weighted) {
+    st = upload_point_weights(h, v, k, &d_v);
+    if (st != GWI_OK) return st;
+  }
   PostprocessBuffers::Marginal& m = h->post.marg;
   a.w_pe = m.d_w;
   a.w_inj = m.d_w + (size_t)(h->n_ev * h->n_pe);
   a.dead = m.d_dead;
-  LaunchScratch ev("gwi_marginal_weights_add");
+  a.vsum = m.d_vsum;
+  a.vsum2 = m.d_vsum + (size_t)(h->n_ev + 1);
+  LaunchScratch ev(who);
   GWI_HIP(ev.events(2));
   const int nt = h->spec.n_theta;
   for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
@@ -4041,7 +4106,14 @@ gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t 
     GWI_HIP(hipEventRecord(ev.e[0], h->stream));
     if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a.d);
     hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.d);
-    if (n_tiles) hipLaunchKernelGGL(Q::marg_add_kernel, dim3((unsigned)n_tiles), dim3(Q::kBlock), 0, h->stream, a);
+    if (n_tiles) {
+      if (weighted) {
+        a.v = d_v + (size_t)p * (size_t)(h->n_ev + 1);
+        hipLaunchKernelGGL(Q::marg_add_kernel<true>, dim3((unsigned)n_tiles), dim3(Q::kBlock), 0, h->stream, a);
+      } else {
+        hipLaunchKernelGGL(Q::marg_add_kernel<false>, dim3((unsigned)n_tiles), dim3(Q::kBlock), 0, h->stream, a);
+      }
+    }
     GWI_HIP(hipGetLastError());
     GWI_HIP(hipEventRecord(ev.e[1], h->stream));
     // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
@@ -4052,6 +4124,33 @@ gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t 
     g_quantile_times.ms[kQuantAdd] += add_ms;
     g_quantile_times.launches += 3;
   }
+  return GWI_OK;
+}
+
+gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t k) {
+  if (!h) return GWI_ERR_INVALID;
+  return marginal_weights_add(h, "gwi_marginal_weights_add", false, thetas, k, nullptr);
+}
+
+gwi_status gwi_marginal_weights_add_weighted(gwi_handle h, const double* thetas, int32_t k, const double* v) {
+  if (!h) return GWI_ERR_INVALID;
+  return marginal_weights_add(h, "gwi_marginal_weights_add_weighted", true, thetas, k, v);
+}
+
+gwi_status gwi_marginal_point_weights(gwi_handle h, double* vsum, double* vsum2) {
+  if (!h) return GWI_ERR_INVALID;
+  gwi_status st = post_preflight(h, "gwi_marginal_point_weights", "keep the weights on", "the injection weights need", [&]() -> std::string {
+    if (!vsum || !vsum2) return "vsum or vsum2 is null";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipSetDevice(h->device));
+  st = marginal_state(h);
+  if (st != GWI_OK) return st;
+  const PostprocessBuffers::Marginal& m = h->post.marg;
+  const size_t n = (size_t)(h->n_ev + 1);
+  GWI_HIP(hipMemcpy(vsum, m.d_vsum, sizeof(double) * n, hipMemcpyDeviceToHost));
+  GWI_HIP(hipMemcpy(vsum2, m.d_vsum + n, sizeof(double) * n, hipMemcpyDeviceToHost));
   return GWI_OK;
 }
 

@@ -15,6 +15,11 @@
 //                       divides by S and adds the quotient onto the running sum H[segment][c][b] in HBM; a segment whose S is 0 or
 //                       not finite adds nothing and is counted in n_dead[segment] (by the workgroup of column 0 alone)
 //
+// A point may carry a linear weight v in [0, 1] per segment (gwi_weighted_histograms_weighted; hist_merge_kernel<true>): the quotient
+// is formed as without it and then multiplied by v, in a product of its own that is not fused into the sum, so v = 1 gives the bits
+// of the unweighted launch; the lane that counts n_dead adds v onto vsum[segment] for a live segment instead.  A point whose v is 0
+// touches nothing of its segment, n_dead[segment] included.  The tile launch does not depend on v.
+//
 // Every sum has a fixed shape -- sample order within a tile and bin, then tile order, then the order of the points (the launches
 // of one point follow those of the previous one on one stream) -- so the bits of H are a pure function of the inputs.  No atomics,
 // nothing depends on which workgroup arrives first, every store is a plain vector store; no scratch.  Adding the +0.0 of a sample
@@ -42,6 +47,8 @@ struct Args {
   double* partial;                // [n_tiles][n_cols][n_bins], tiles numbered as in DrawArgs
   double* hist;                   // [n_ev + 1][n_cols][n_bins] running sums over the points; segment n_ev = the injection set
   int* n_dead;                    // [n_ev + 1]
+  const double* v;                // [n_ev + 1] this point's weight per segment (hist_merge_kernel<true>; not read otherwise)
+  double* vsum;                   // [n_ev + 1] running sum of the weights over the live points (hist_merge_kernel<true>)
   int n_cols, n_bins;
   int first_tile, first_seg;      // the launch covers tiles / segments from here on (a set without bins is left out)
 };
@@ -91,8 +98,20 @@ __global__ __launch_bounds__(kBlock) void hist_tile_kernel(const Args a) {
   }
 }
 
+// v q rounded once on its own: never contracted into the addition that follows
+__device__ inline double scaled(double v, double q) {
+#pragma clang fp contract(off)
+  return v * q;
+}
+
+template <bool kWeighted>
 __global__ __launch_bounds__(kBlock) void hist_merge_kernel(const Args a) {
   const int seg = a.first_seg + (int)blockIdx.x, c = (int)blockIdx.y, b = (int)threadIdx.x;
+  double pv = 1.0;
+  if constexpr (kWeighted) {
+    pv = a.v[seg];
+    if (pv == 0.0) return;  // (the same for every thread of the workgroup)
+  }
   const draw::Segment s = draw::segment_of(a.d, seg);
   const double total = s.n_tiles > 0 ? a.d.tile_prefix[s.first_tile + s.n_tiles - 1] : 0.0;
   const bool live = total > 0.0 && total < __builtin_inf();
@@ -100,6 +119,8 @@ __global__ __launch_bounds__(kBlock) void hist_merge_kernel(const Args a) {
     if (c == 0 && b == 0) a.n_dead[seg] += 1;
     return;
   }
+  if constexpr (kWeighted)
+    if (c == 0 && b == 0) a.vsum[seg] += pv;
   if (b >= a.n_bins) return;
   const long long stride = (long long)a.n_cols * a.n_bins;
   const double* p = a.partial + (long long)s.first_tile * stride + (long long)c * a.n_bins + b;
@@ -107,7 +128,8 @@ __global__ __launch_bounds__(kBlock) void hist_merge_kernel(const Args a) {
 #pragma unroll 8
   for (int t = 0; t < s.n_tiles; ++t) sum += p[(long long)t * stride];
   double* h = a.hist + ((long long)seg * a.n_cols + c) * a.n_bins + b;
-  *h += sum / total;
+  if constexpr (kWeighted) *h += scaled(pv, sum / total);
+  else *h += sum / total;
 }
 
 }  // namespace hist

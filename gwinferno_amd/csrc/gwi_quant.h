@@ -10,9 +10,15 @@
 //
 //   marg_add_kernel      one lane per kDrawPerLane consecutive samples, tiles numbered as in DrawArgs: W_i += w_i / S on the running
 //                        double per sample in HBM.  A segment whose S is 0 or not finite adds nothing; the lane of its first sample
-//                        increments dead[segment]
+//                        increments dead[segment], and otherwise adds the point's weight onto vsum[segment] and its square onto
+//                        vsum2[segment]
 //
-// W_i = sum_k w_{k,i} / S_k is the marginal posterior weight of sample i.  It does not depend on any quantile column and is not
+// A point may carry a linear weight v in [0, 1] per segment (gwi_marginal_weights_add_weighted; marg_add_kernel<true>): the quotient
+// w_i / S is formed as without it and then multiplied by v, in a product of its own that is not fused into the sum, so v = 1 gives the
+// bits of the unweighted launch.  A point whose v is 0 touches nothing of its segment, dead[segment] included.  The unweighted launch
+// counts v = 1: after unweighted points alone vsum[segment] is n_points - dead[segment].
+//
+// W_i = sum_k v_k w_{k,i} / S_k is the marginal posterior weight of sample i.  It does not depend on any quantile column and is not
 // reset when the draw mask changes: a mask applies to the points added while it is set.
 //
 // A quantile column c supplies values x and, per segment, an int32 permutation of the segment's sample indices along which the
@@ -57,6 +63,9 @@ struct MargArgs {
   double* w_pe;      // [n_ev][n_pe] running sums over the points
   double* w_inj;     // [n_inj]
   int* dead;         // [n_ev + 1]
+  double* vsum;      // [n_ev + 1] running sum of the points' weights over the live points (1 per point without weights)
+  double* vsum2;     // [n_ev + 1] ... of their squares
+  const double* v;   // [n_ev + 1] this point's weight per segment (marg_add_kernel<true>; not read otherwise)
 };
 
 struct Args {
@@ -95,14 +104,31 @@ __device__ inline Column column_of(const Args& a, int seg, int c) {
   return Column{a.w_inj, a.x_inj + at, a.order_inj + at, a.n_inj, a.n_ev * a.tiles_per_event, a.n_inj_tiles};
 }
 
+// v q rounded once on its own: never contracted into the addition that follows
+__device__ inline double scaled(double v, double q) {
+#pragma clang fp contract(off)
+  return v * q;
+}
+
+template <bool kWeighted>
 __global__ __launch_bounds__(kBlock) void marg_add_kernel(const MargArgs a) {
   const int tile = blockIdx.x, n_pe_tiles = a.d.n_ev * a.d.tiles_per_event;
   const int seg = tile < n_pe_tiles ? tile / a.d.tiles_per_event : a.d.n_ev;
   const draw::Segment s = draw::segment_of(a.d, seg);
+  double pv = 1.0;
+  if constexpr (kWeighted) {
+    pv = a.v[seg];
+    if (pv == 0.0) return;  // (the same for every thread of the workgroup)
+  }
   const double total = a.d.tile_prefix[s.first_tile + s.n_tiles - 1];  // (n_tiles >= 1: this tile exists)
+  const bool first_lane = tile == s.first_tile && threadIdx.x == 0;    // one lane per segment and point
   if (!(total > 0.0 && total < __builtin_inf())) {
-    if (tile == s.first_tile && threadIdx.x == 0) a.dead[seg] += 1;
+    if (first_lane) a.dead[seg] += 1;
     return;
+  }
+  if (first_lane) {
+    a.vsum[seg] += pv;
+    a.vsum2[seg] += pv * pv;
   }
   const double big = a.d.seg_max[seg];
   double* w = seg < a.d.n_ev ? a.w_pe + (long long)seg * a.d.n_pe : a.w_inj;
@@ -112,7 +138,10 @@ __global__ __launch_bounds__(kBlock) void marg_add_kernel(const MargArgs a) {
     const long long j = start + q;
     if (j < s.n) {
       const double v = draw::live_log_weight(s, j, a.d.log_const);
-      if (v > -__builtin_inf()) w[j] += exp(v - big) / total;  // (a sample without weight would add +0.0)
+      if (v > -__builtin_inf()) {  // (a sample without weight would add +0.0)
+        if constexpr (kWeighted) w[j] += scaled(pv, exp(v - big) / total);
+        else w[j] += exp(v - big) / total;
+      }
     }
   }
 }

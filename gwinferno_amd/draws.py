@@ -19,7 +19,11 @@ summed over the points, per sample -- the marginal posterior weight ``W_j`` -- a
 :func:`marginal_weights_reference` and :func:`weighted_quantiles_reference` state them.
 
 ``gwi_weighted_kde`` / ``gwi_weighted_kde2d`` (gwinferno_amd/csrc/gwi_kde.h) smooth the same ``W_j`` into a Gaussian kernel density
-estimate with scipy's bandwidth rules: :func:`weighted_kde_reference` and :func:`weighted_kde2d_reference` state them."""
+estimate with scipy's bandwidth rules: :func:`weighted_kde_reference` and :func:`weighted_kde2d_reference` state them.
+
+``gwi_marginal_weights_add_weighted`` / ``gwi_weighted_histograms_weighted`` give every (point, segment) a linear weight ``v`` in
+``[0, 1]``: the optional ``v`` of :func:`marginal_weights_reference` and :func:`weighted_histograms_reference` states them, and
+:func:`leave_one_out_summary` the weights, scores and diagnostics of the leave-one-out posteriors made of them."""
 import bisect
 import itertools
 import math
@@ -133,51 +137,131 @@ def weighted_histogram_segment(logw, mask, bins, n_bins):
     return h, True
 
 
-def weighted_histograms_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins, inj_bins, n_bins):
+def point_weights_array(v, k, n_segs):
+    """The linear weights of ``k`` points as a C-contiguous ``(k, n_segs)`` float64 array: ``v`` has that shape, or ``(k,)`` -- one
+    weight per point, the same for every segment.  Every entry is a number in ``[0, 1]``; anything else raises ValueError."""
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape == (k,):
+        v = np.repeat(v[:, None], n_segs, axis=1)
+    if v.shape != (k, n_segs):
+        raise ValueError(f"point weights have shape {v.shape}; expected ({k}, {n_segs}) or ({k},)")
+    if not np.all((v >= 0.0) & (v <= 1.0)):
+        raise ValueError("point weights must be numbers in [0, 1]")
+    return np.ascontiguousarray(v)
+
+
+def weighted_histograms_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins, inj_bins, n_bins, v=None):
     """One hyper-parameter point of ``gwi_weighted_histograms``: ``logw_pe (n_ev, n_pe)``, ``pe_bins (n_cols, n_ev, n_pe)``,
     ``logw_inj (n_inj,)``, ``inj_bins (n_cols, n_inj)`` -> ``(hist_pe (n_ev, n_cols, n_bins), hist_inj (n_cols, n_bins), dead
     (n_ev + 1,) int32)``: what the point adds to the running sums, and 1 in ``dead`` for every segment without weight (the
-    injection set last).  A set whose bins are ``None`` is left out (``None`` in its place, 0 in ``dead``)."""
+    injection set last).  A set whose bins are ``None`` is left out (``None`` in its place, 0 in ``dead``).
+
+    ``v (n_ev + 1,)`` is the point's row of linear weights in ``[0, 1]`` (``gwi_weighted_histograms_weighted``): the point adds ``v
+    h`` -- the quotient as without weights, then one product -- and a fourth value is returned, ``vsum (n_ev + 1,)``: ``v`` for every
+    live segment of a set that is not left out, 0 elsewhere.  A segment whose ``v`` is 0 adds nothing and is not counted in ``dead``."""
     logw_pe = np.asarray(logw_pe, dtype=np.float64)
     n_ev = logw_pe.shape[0]
     dead = np.zeros(n_ev + 1, dtype=np.int32)
+    if v is not None:
+        v = point_weights_array(np.asarray(v, dtype=np.float64).reshape(1, -1), 1, n_ev + 1)[0]
+    vsum = np.zeros(n_ev + 1)
     hist_pe = hist_inj = None
+
+    def one(seg, logw, mask, bins):
+        if v is not None and v[seg] == 0.0:
+            return np.zeros((bins.shape[0], int(n_bins)))
+        h, live = weighted_histogram_segment(logw, mask, bins, n_bins)
+        dead[seg] = 0 if live else 1
+        if v is not None and live:
+            vsum[seg] = v[seg]
+            h = v[seg] * h
+        return h
+
     if pe_bins is not None:
         pe_bins = np.asarray(pe_bins)
         pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(logw_pe.shape)
         hist_pe = np.zeros((n_ev, pe_bins.shape[0], int(n_bins)))
         for ev in range(n_ev):
-            hist_pe[ev], live = weighted_histogram_segment(logw_pe[ev], None if pe_mask is None else pe_mask[ev], pe_bins[:, ev], n_bins)
-            dead[ev] = 0 if live else 1
+            hist_pe[ev] = one(ev, logw_pe[ev], None if pe_mask is None else pe_mask[ev], pe_bins[:, ev])
     if inj_bins is not None:
-        hist_inj, live = weighted_histogram_segment(logw_inj, inj_mask, np.asarray(inj_bins), n_bins)
-        dead[n_ev] = 0 if live else 1
-    return hist_pe, hist_inj, dead
+        hist_inj = one(n_ev, logw_inj, inj_mask, np.asarray(inj_bins))
+    return (hist_pe, hist_inj, dead) if v is None else (hist_pe, hist_inj, dead, vsum)
 
 
-def marginal_weights_reference(logw_pe, logw_inj, pe_mask, inj_mask):
+def marginal_weights_reference(logw_pe, logw_inj, pe_mask, inj_mask, v=None):
     """The state ``gwi_marginal_weights_add`` leaves after the K points of ``logw_pe (K, n_ev, n_pe)`` and ``logw_inj (K, n_inj)``,
     added in order: ``(W_pe (n_ev, n_pe), W_inj (n_inj,), dead (n_ev + 1,) int32, n_points)`` with ``W_j = sum_k w_kj / S_k``,
     ``w`` from :func:`draw_weights` under the masks and ``S_k`` the segment's total by ``math.fsum`` (the exact sum, rounded once);
-    a segment whose total is 0 adds nothing at that point and is counted in ``dead`` (the injection set last)."""
+    a segment whose total is 0 adds nothing at that point and is counted in ``dead`` (the injection set last).
+
+    ``v (K, n_ev + 1)`` (or ``(K,)``: the same for every segment) gives every (point, segment) a linear weight in ``[0, 1]``
+    (``gwi_marginal_weights_add_weighted``): ``W_j = sum_k v_k (w_kj / S_k)`` -- the quotient as without weights, then one product --
+    and two more values are returned, ``vsum`` and ``vsum2 (n_ev + 1,)``: the sums of ``v`` and of ``v v`` over the points at which
+    the segment is live, in point order.  A point whose ``v`` is 0 adds nothing, is counted in ``n_points`` and not in ``dead``."""
     logw_pe, logw_inj = np.asarray(logw_pe, dtype=np.float64), np.asarray(logw_inj, dtype=np.float64)
     if logw_pe.ndim != 3 or logw_inj.ndim != 2 or logw_pe.shape[0] != logw_inj.shape[0]:
         raise ValueError("logw_pe is (K, n_ev, n_pe) and logw_inj (K, n_inj)")
     k, n_ev, n_pe = logw_pe.shape
     pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(n_ev, n_pe)
     w_pe, w_inj, dead = np.zeros((n_ev, n_pe)), np.zeros(logw_inj.shape[1]), np.zeros(n_ev + 1, dtype=np.int32)
+    if v is not None:
+        v = point_weights_array(v, k, n_ev + 1)
+    vsum, vsum2 = np.zeros(n_ev + 1), np.zeros(n_ev + 1)
     for p in range(k):
         for seg in range(n_ev + 1):
+            if v is not None and v[p, seg] == 0.0:
+                continue
             w = draw_weights(logw_pe[p, seg], None if pe_mask is None else pe_mask[seg]) if seg < n_ev else draw_weights(logw_inj[p], inj_mask)
             total = math.fsum(w.tolist())
             if not (total > 0.0 and np.isfinite(total)):
                 dead[seg] += 1
                 continue
+            share = w / total
+            if v is not None:
+                share = v[p, seg] * share
+                vsum[seg] += v[p, seg]
+                vsum2[seg] += v[p, seg] * v[p, seg]
             if seg < n_ev:
-                w_pe[seg] += w / total
+                w_pe[seg] += share
             else:
-                w_inj += w / total
-    return w_pe, w_inj, dead, k
+                w_inj += share
+    return (w_pe, w_inj, dead, k) if v is None else (w_pe, w_inj, dead, k, vsum, vsum2)
+
+
+def leave_one_out_summary(log_l_event):
+    """The leave-one-out weights, scores and diagnostics of ``log_l_event (K, n_ev)``, the table of ``l_ke``: event e's contribution
+    to ``log L`` at hyper-posterior point k.  The points are draws from ``p(theta | all events)``; weighting point k by
+    ``1 / exp(l_ke)`` turns them into draws from ``p(theta | all events but e)``.  Returns a dict:
+
+    ``point_weights (K, n_ev + 1)``: ``exp(-l_ke + min_k l_ke)`` -- linear, the largest of every event exactly 1 -- and a last column
+    of ones for the injection set, which has no event of its own; ``elpd_loo (n_ev,)``: ``-log mean_k exp(-l_ke)``, the logarithm of
+    the event's leave-one-out predictive density (importance sampling; summed over the events it compares two population models
+    fitted to one catalog); ``lpd (n_ev,)``: ``log mean_k exp(l_ke)``, the same without leaving the event out; ``neff_points
+    (n_ev,)``: ``(sum_k v)^2 / sum_k v^2``, the effective number of points -- the only reliability diagnostic (no Pareto smoothing);
+    ``n_bad (n_ev,)``: the points at which ``l_ke`` is not finite: they get weight 0 and the means run over the other points (NaN
+    where there is none)."""
+    ell = np.asarray(log_l_event, dtype=np.float64)
+    if ell.ndim != 2 or ell.shape[0] < 1:
+        raise ValueError("log_l_event is (K, n_ev) with K >= 1")
+    k, n_ev = ell.shape
+    good = np.isfinite(ell)
+    n_good = good.sum(axis=0)
+    n_bad = (k - n_good).astype(np.int64)
+    v = np.ones((k, n_ev + 1))
+    elpd, lpd, neff = np.full(n_ev, np.nan), np.full(n_ev, np.nan), np.zeros(n_ev)
+    for e in range(n_ev):
+        v[:, e] = 0.0
+        if not n_good[e]:
+            continue
+        col = ell[good[:, e], e]
+        lo, hi = col.min(), col.max()
+        ve = np.exp(lo - col)
+        v[good[:, e], e] = ve
+        s1 = math.fsum(ve.tolist())
+        elpd[e] = lo - math.log(s1 / n_good[e])
+        lpd[e] = hi + math.log(math.fsum(np.exp(col - hi).tolist()) / n_good[e])
+        neff[e] = s1 * s1 / math.fsum((ve * ve).tolist())
+    return {"log_l_event": ell, "point_weights": v, "elpd_loo": elpd, "lpd": lpd, "neff_points": neff, "n_bad": n_bad}
 
 
 def _exact_integers(w):

@@ -1101,7 +1101,13 @@ class NativePopulationLikelihood:
                                                     inj.ctypes.data_as(u16) if inj is not None else None))
         self._hist_shape = (n_cols, int(n_bins), pe is not None, inj is not None)
 
-    def weighted_histograms(self, thetas, out=None):
+    def _point_weights(self, point_weights, k):
+        """``point_weights`` -- ``(k, n_ev + 1)``, or ``(k,)`` for one weight per point -- as the ``v[k][n_ev + 1]`` of the C ABI."""
+        from .draws import point_weights_array
+
+        return point_weights_array(point_weights, k, self.n_ev + 1)
+
+    def weighted_histograms(self, thetas, out=None, point_weights=None):
         """Weighted histograms on the device (``gwi_weighted_histograms``; semantics:
         :func:`gwinferno_amd.draws.weighted_histograms_reference`).  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.
         Returns ``(hist_pe (n_ev, n_cols, n_bins), hist_inj (n_cols, n_bins), dead (n_ev + 1,) int32)``: running SUMS over the
@@ -1109,31 +1115,43 @@ class NativePopulationLikelihood:
         the number of points at which nothing had weight -- the mean over the live points is ``hist / (K - dead)``.  ``out``
         is such a triple from an earlier call: the new points are added onto it in place, with the bits one call over all
         points would give.  Only the sums travel back from the device.  Not available on an engine that holds a shard
-        (``world > 1``)."""
+        (``world > 1``).
+
+        ``point_weights`` -- ``(k, n_ev + 1)``, the injection set last, or ``(k,)`` for one weight per point -- gives every (point,
+        segment) a linear weight ``v`` in ``[0, 1]`` (``gwi_weighted_histograms_weighted``): the sums are of ``v`` times the point's
+        normalised histogram, and both ``out`` and the return value are the 4-tuple ``(hist_pe, hist_inj, dead, vsum)`` with ``vsum
+        (n_ev + 1,)`` the sum of ``v`` over the points at which the segment had weight: the weighted mean is ``hist / vsum``.  A
+        point whose ``v`` is 0 adds nothing and is not counted in ``dead``.  ``v = 1`` gives the bits of the call without weights."""
         if self.world > 1:
             raise N.NativeEngineError("GWI_ERR_UNSUPPORTED: weighted_histograms: this engine holds one shard of the catalog; the injection histogram needs the global set")
         thetas = N.f64(thetas)
         if thetas.ndim not in (1, 2) or thetas.shape[-1] != self.n_theta or thetas.size == 0:
             raise ValueError(f"thetas has shape {thetas.shape}; expected ({self.n_theta},) or (k, {self.n_theta})")
         thetas = thetas.reshape(-1, self.n_theta)
+        v = None if point_weights is None else self._point_weights(point_weights, thetas.shape[0])
         shape = getattr(self, "_hist_shape", None)
         i32 = C.POINTER(C.c_int32)
         if shape is None:  # the library says so
             self._check(self.lib.gwi_weighted_histograms(self.handle, N.as_dp(thetas), thetas.shape[0], None, None, None))
             raise N.NativeEngineError("GWI_ERR_INVALID: weighted_histograms: no bins are set (set_histogram_bins)")
         n_cols, n_bins, with_pe, with_inj = shape
-        want = ((self.n_ev, n_cols, n_bins) if with_pe else None, (n_cols, n_bins) if with_inj else None, (self.n_ev + 1,))
+        want = ((self.n_ev, n_cols, n_bins) if with_pe else None, (n_cols, n_bins) if with_inj else None, (self.n_ev + 1,)) + (((self.n_ev + 1,),) if v is not None else ())
+        parts, kinds = ("hist_pe", "hist_inj", "dead", "vsum")[: len(want)], (np.float64, np.float64, np.int32, np.float64)
         if out is None:
-            out = tuple(None if s is None else np.zeros(s, dtype=np.int32 if i == 2 else np.float64) for i, s in enumerate(want))
+            out = tuple(None if s is None else np.zeros(s, dtype=dt) for s, dt in zip(want, kinds))
         else:
-            if len(out) != 3:
-                raise ValueError("out is (hist_pe, hist_inj, dead)")
-            for o, s, name, dt in zip(out, want, ("hist_pe", "hist_inj", "dead"), (np.float64, np.float64, np.int32)):
+            if len(out) != len(want):
+                raise ValueError(f"out is ({', '.join(parts)})")
+            for o, s, name, dt in zip(out, want, parts, kinds):
                 if s is None:
                     continue
                 if not isinstance(o, np.ndarray) or o.shape != s or o.dtype != dt or not o.flags.c_contiguous or not o.flags.writeable:
                     raise ValueError(f"out: {name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape {s}")
-        hist_pe, hist_inj, dead = out
+        hist_pe, hist_inj, dead = out[:3]
+        if v is not None:
+            self._check(self.lib.gwi_weighted_histograms_weighted(self.handle, N.as_dp(thetas), thetas.shape[0], N.as_dp(v), N.as_dp(hist_pe) if with_pe else None,
+                                                                  N.as_dp(hist_inj) if with_inj else None, dead.ctypes.data_as(i32), N.as_dp(out[3])))
+            return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead, out[3]
         self._check(self.lib.gwi_weighted_histograms(self.handle, N.as_dp(thetas), thetas.shape[0], N.as_dp(hist_pe) if with_pe else None, N.as_dp(hist_inj) if with_inj else None,
                                                      dead.ctypes.data_as(i32)))
         return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead
@@ -1147,17 +1165,35 @@ class NativePopulationLikelihood:
         self._whole_catalog("marginal_weights_reset", "the injection weights need")
         self._check(self.lib.gwi_marginal_weights_reset(self.handle))
 
-    def marginal_weights_add(self, thetas):
+    def marginal_weights_add(self, thetas, point_weights=None):
         """Adds the points ``thetas`` -- ``(n_theta,)`` or ``(k, n_theta)``, in order -- onto the marginal weights the engine keeps in
         HBM (``gwi_marginal_weights_add``; semantics: :func:`gwinferno_amd.draws.marginal_weights_reference`): ``W_i += w_i / S`` per
         sample under the masks of :meth:`set_draw_mask`.  Nothing travels back.  The sums stay until :meth:`marginal_weights_reset`;
-        changing the mask does not reset them.  Not available on an engine that holds a shard (``world > 1``)."""
+        changing the mask does not reset them.  Not available on an engine that holds a shard (``world > 1``).
+
+        ``point_weights`` -- ``(k, n_ev + 1)``, the injection set last, or ``(k,)`` for one weight per point -- gives every (point,
+        segment) a linear weight ``v`` in ``[0, 1]`` (``gwi_marginal_weights_add_weighted``): ``W_i += v (w_i / S)``.  A point whose
+        ``v`` is 0 adds nothing and is not counted in ``dead``; ``v = 1`` gives the bits of the call without weights.  The sums of
+        ``v`` and ``v v`` per segment are kept beside ``W`` (:meth:`marginal_point_weights`); calls with and without weights mix."""
         self._whole_catalog("marginal_weights_add", "the injection weights need")
         thetas = N.f64(thetas)
         if thetas.ndim not in (1, 2) or thetas.shape[-1] != self.n_theta:
             raise ValueError(f"thetas has shape {thetas.shape}; expected ({self.n_theta},) or (k, {self.n_theta})")
         thetas = thetas.reshape(-1, self.n_theta)
-        self._check(self.lib.gwi_marginal_weights_add(self.handle, N.as_dp(thetas), thetas.shape[0]))
+        if point_weights is None:
+            self._check(self.lib.gwi_marginal_weights_add(self.handle, N.as_dp(thetas), thetas.shape[0]))
+        else:
+            v = self._point_weights(point_weights, thetas.shape[0])
+            self._check(self.lib.gwi_marginal_weights_add_weighted(self.handle, N.as_dp(thetas), thetas.shape[0], N.as_dp(v)))
+
+    def marginal_point_weights(self):
+        """``(vsum (n_ev + 1,), vsum2 (n_ev + 1,))``: per segment (the injection set last) the sums of the points' weights ``v`` and of
+        ``v v`` over the points at which the segment had weight, since the last reset (``gwi_marginal_point_weights``); a point added
+        without weights counts ``v = 1``.  ``vsum ** 2 / vsum2`` is the segment's effective number of points."""
+        self._whole_catalog("marginal_point_weights", "the injection weights need")
+        vsum, vsum2 = np.zeros(self.n_ev + 1), np.zeros(self.n_ev + 1)
+        self._check(self.lib.gwi_marginal_point_weights(self.handle, N.as_dp(vsum), N.as_dp(vsum2)))
+        return vsum, vsum2
 
     def marginal_weights(self, weights=True):
         """``(W_pe (n_ev, n_pe), W_inj (n_inj,), dead (n_ev + 1,) int32, n_points)``: the marginal weights read back once

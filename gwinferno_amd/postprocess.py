@@ -265,11 +265,74 @@ def posterior_predictive_draws(eng, thetas, n_draws, seed, pedata=None, injdata=
     return out
 
 
+def leave_one_out_weights(eng, thetas, total_inj, nobs=None, marginalize_selection=False):
+    """Leave-one-out weights of the K hyper-posterior points ``thetas (K, n_theta)`` for every event, and the leave-one-out predictive
+    score they give.  The points are draws from ``p(theta | all N events)``, which already contains event e: reweighting
+    e's samples by ``p(x | theta_k)`` would use its data twice.  The posterior of e marginalises over ``p(theta | all events but e)``
+    instead, and the same draws serve with the weight ``v_ke`` proportional to ``L_{-e}(theta_k) / L(theta_k) = exp(-l_ke)``, where
+    ``l_ke = log L_N(theta_k) - log L_{N-1, without e}(theta_k)`` is the event's contribution to the log-likelihood.
+
+    The likelihood is ``log L_n = sum_i logBF_i + f(n)`` over the n events of the catalog.  Without marginalised selection ``f(n) =
+    -n log mu`` with ``mu`` the detection efficiency, so ``l_ke = logBF_e - log mu``.  With it (analysis.py:271) ``f(n) = -n (log mu
+    - (3 + n) / (2 n_eff_inj)) = -n log mu + n (3 + n) / (2 n_eff_inj)``, and ``f(N) - f(N - 1) = -log mu + (N (3 + N) - (N - 1)(2 +
+    N)) / (2 n_eff_inj) = -log mu + (N + 1) / n_eff_inj``: ``l_ke = logBF_e - log mu + (N + 1) / n_eff_inj``.  ``N`` is ``nobs``
+    (default: the engine's events).  ``logBF``, ``log mu`` and ``n_eff_inj`` come from ``eng.evaluate_batch`` without gradients, in
+    chunks of the batch limit; the ``min_neff`` and ``variance`` cuts are not applied (a cut replaces the likelihood by a constant and
+    says nothing about one event).
+
+    Returns :func:`gwinferno_amd.draws.leave_one_out_summary` of the table: ``log_l_event (K, n_ev)``; ``point_weights (K, n_ev +
+    1)`` = ``exp(-l_ke + min_k l_ke)``, at most 1, the injection column all ones -- what ``Engine.marginal_weights_add`` and
+    ``Engine.weighted_histograms`` take; ``elpd_loo (n_ev,)`` = ``-log mean_k exp(-l_ke)``; ``lpd (n_ev,)`` = ``log mean_k exp(l_ke)``;
+    ``neff_points (n_ev,)`` = ``(sum_k v)^2 / sum_k v^2``; ``n_bad (n_ev,)``, the points whose ``l_ke`` is not finite (weight 0)."""
+    from .draws import leave_one_out_summary
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    n_obs = float(eng.n_ev_global if nobs is None else nobs)
+    ell = np.empty((k, eng.n_ev))
+    step = int(eng.max_batch)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k0 in range(0, k, step):
+            res = eng.evaluate_batch(thetas[k0 : k0 + step], total_inj, nobs=nobs, marginalize_selection=marginalize_selection, min_neff_cut=False, max_variance_cut=False,
+                                     want_grad=False)
+            for i, r in enumerate(res):
+                row = r.log_bfs - r.summary.log_det_eff
+                if marginalize_selection:
+                    row = row + (n_obs + 1.0) / np.exp(r.summary.log_nEff_inj)
+                ell[k0 + i] = row
+    return leave_one_out_summary(ell)
+
+
+def _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection):
+    """``(v (K, n_ev + 1) or None, the leave-one-out summary or None)`` of a post-processing call."""
+    from .draws import point_weights_array
+
+    if leave_one_out:
+        if point_weights is not None:
+            raise ValueError("leave_one_out=True makes the point weights itself: point_weights must be None")
+        if total_inj is None:
+            raise ValueError("leave_one_out=True needs total_inj")
+        loo = leave_one_out_weights(eng, thetas, total_inj, nobs=nobs, marginalize_selection=marginalize_selection)
+        return loo["point_weights"], loo
+    if point_weights is None:
+        return None, None
+    return point_weights_array(point_weights, thetas.shape[0], eng.n_ev + 1), None
+
+
+def _point_weight_entries(out, loo, vsum):
+    if vsum is not None:
+        out["point_weight_sum"] = np.asarray(vsum).copy()
+    if loo is not None:
+        out["elpd_loo"], out["neff_points"] = loo["elpd_loo"], loo["neff_points"]
+
+
 HISTOGRAM_CHUNK = 64  # points per gwi_weighted_histograms call of reweighted_event_posteriors (the sums do not depend on it)
 
 
 def reweighted_event_posteriors(eng, thetas, pe_values, edges, inj_values=None, pedata=None, injdata=None, param_names=None, m1min=None, m2min=None, mmax=None,
-                                backend="device", chunk=HISTOGRAM_CHUNK):
+                                backend="device", chunk=HISTOGRAM_CHUNK, point_weights=None, leave_one_out=False, total_inj=None, nobs=None, marginalize_selection=False):
     """The population-informed posterior of every event, marginalised over K posterior hyper-parameter draws, as binned densities,
     and the predicted detected distribution from the injections: per event, quantity and bin the mean over the draws of
     ``(sum of w_i in the bin) / (sum of w_i)`` with ``w_i = p(x_i | theta_k) / prior_i`` -- the exact sums whose Monte-Carlo
@@ -291,7 +354,14 @@ def reweighted_event_posteriors(eng, thetas, pe_values, edges, inj_values=None, 
     Returns a dict per name: ``events (n_ev, B)``, the mean normalised histogram divided by the bin widths (a density: ``events *
     widths`` sums to ``1 - outside``); ``predicted (B,)``, the same for the injection set (when ``inj_values`` is given);
     ``outside``, ``{"events": (n_ev,), "predicted": float}``, the weight fraction outside the edges; and ``n_points``, the same
-    layout, the points at which the segment had weight (NaN densities where that is 0); beside them ``"edges"`` itself."""
+    layout, the points at which the segment had weight (NaN densities where that is 0); beside them ``"edges"`` itself.
+
+    ``point_weights`` -- ``(K, n_ev + 1)``, the injection set last, or ``(K,)`` -- gives every (point, segment) a linear weight in
+    ``[0, 1]``, e.g. to move a finished run to another hyper-prior: the mean over the points becomes the weighted mean, the sums
+    divided by the sum of the weights over the live points (returned as ``"point_weight_sum" (n_ev + 1,)``) instead of by their
+    number.  ``leave_one_out=True`` (``total_inj`` is then required; ``nobs`` and ``marginalize_selection`` as in the likelihood)
+    makes the weights with :func:`leave_one_out_weights`, so that no event's data is used twice, and adds ``"elpd_loo"`` and
+    ``"neff_points"``.  The defaults leave every output as it was."""
     from . import draws as D
 
     thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
@@ -333,12 +403,26 @@ def reweighted_event_posteriors(eng, thetas, pe_values, edges, inj_values=None, 
             eng.set_draw_mask(*masks)
     elif any(c is not None for c in cuts) and not all(c is not None for c in cuts):
         raise ValueError("m1min, m2min and mmax are given together or not at all")
+    v, loo = _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection)
+    vsum = None
     if backend == "device":
         eng.set_histogram_bins(pe_bins, inj_bins, n_bins=n_bins)
         out = None
         for i in range(0, k, chunk):
-            out = eng.weighted_histograms(thetas[i : i + chunk], out=out)
-        hist_pe, hist_inj, dead = out
+            out = eng.weighted_histograms(thetas[i : i + chunk], out=out, **({} if v is None else {"point_weights": v[i : i + chunk]}))
+        hist_pe, hist_inj, dead = out[:3]
+        vsum = out[3] if v is not None else None
+    elif v is not None:
+        hist_pe, hist_inj, dead = np.zeros((n_ev, len(names), n_bins)), (np.zeros((len(names), n_bins)) if inj_bins is not None else None), np.zeros(n_ev + 1, dtype=np.int32)
+        vsum = np.zeros(n_ev + 1)
+        for th, row in zip(thetas, v):
+            lw_pe, lw_inj = eng.log_weights(th)
+            h_pe, h_inj, d, vs = D.weighted_histograms_reference(lw_pe, lw_inj, masks[0], masks[1], pe_bins, inj_bins, n_bins, v=row)
+            hist_pe += h_pe
+            if hist_inj is not None:
+                hist_inj += h_inj
+            dead += d
+            vsum += vs
     else:
         hist_pe, hist_inj, dead = np.zeros((n_ev, len(names), n_bins)), (np.zeros((len(names), n_bins)) if inj_bins is not None else None), np.zeros(n_ev + 1, dtype=np.int32)
         for th in thetas:
@@ -348,8 +432,9 @@ def reweighted_event_posteriors(eng, thetas, pe_values, edges, inj_values=None, 
             if hist_inj is not None:
                 hist_inj += h_inj
             dead += d
-    live = (k - dead).astype(np.float64)
+    live = (k - dead).astype(np.float64) if vsum is None else vsum
     result = {"edges": {p: grid[p] for p in names}}
+    _point_weight_entries(result, loo, vsum)
     with np.errstate(invalid="ignore", divide="ignore"):
         for c, p in enumerate(names):
             widths = np.diff(grid[p])
@@ -408,7 +493,8 @@ def _mass_cut_masks(pedata, injdata, m1min, m2min, mmax):
 
 
 def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), inj_values=None, pedata=None, injdata=None, param_names=None, m1min=None, m2min=None,
-                             mmax=None, backend="device", return_weights=False):
+                             mmax=None, backend="device", return_weights=False, point_weights=None, leave_one_out=False, total_inj=None, nobs=None,
+                             marginalize_selection=False):
     """Credible intervals of the population-informed posterior of every event, marginalised over K posterior hyper-parameter draws:
     per event and quantity the weighted quantiles of ``levels`` (rule "inverted CDF": the value of a sample, never an interpolation),
     the mean and the standard deviation under the marginal posterior weight ``W_i = sum_k w_ki / S_k`` of the event's samples,
@@ -429,7 +515,11 @@ def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), i
     Returns a dict: ``names``; ``levels``; ``quantiles (n_ev, C, Q)``, ``mean`` and ``sd (n_ev, C)``; ``dead (n_ev,)``, the points at
     which the event had no weight; ``n_points``; with ``inj_values`` also ``quantiles_inj (C, Q)``, ``mean_inj``, ``sd_inj (C,)``
     and ``dead_inj``; with ``return_weights=True`` also ``weights`` and ``weights_inj``, the ``W`` arrays.  A segment without weight
-    gives NaN."""
+    gives NaN.
+
+    ``point_weights``, ``leave_one_out``, ``total_inj``, ``nobs`` and ``marginalize_selection`` are
+    :func:`reweighted_event_posteriors`': ``W_i = sum_k v_k w_ki / S_k``; with them the dict also holds ``point_weight_sum (n_ev +
+    1,)`` and, for ``leave_one_out=True``, ``elpd_loo`` and ``neff_points``.  The defaults leave every output as it was."""
     from . import draws as D
 
     thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
@@ -448,15 +538,19 @@ def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), i
     if backend == "device" and masks[0] is not None:
         eng.set_draw_mask(*masks)
     n_cols, n_q, n_ev = len(names), levels.size, eng.n_ev
+    v, loo = _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection)
+    weighted = {} if v is None else {"point_weights": v}
     if backend == "device":
         eng.set_quantile_columns(x_pe, x_inj)
         eng.marginal_weights_reset()
-        eng.marginal_weights_add(thetas)
+        eng.marginal_weights_add(thetas, **weighted)
         idx_pe, idx_inj, mom_pe, mom_inj, mass = eng.weighted_quantiles(levels)
         w_pe, w_inj, dead, n_points = eng.marginal_weights(weights=return_weights)
+        vsum = eng.marginal_point_weights()[0] if v is not None else None
     else:
         lw = [eng.log_weights(th) for th in thetas]
-        w_pe, w_inj, dead, n_points = D.marginal_weights_reference(np.stack([a for a, _ in lw]), np.stack([b for _, b in lw]), masks[0], masks[1])
+        w_pe, w_inj, dead, n_points, *sums = D.marginal_weights_reference(np.stack([a for a, _ in lw]), np.stack([b for _, b in lw]), masks[0], masks[1], v=v)
+        vsum = sums[0] if v is not None else None
         idx_pe, mom_pe, mass = np.full((n_ev, n_cols, n_q), -1, dtype=np.int32), np.zeros((n_ev, n_cols, 2)), np.zeros(n_ev + 1)
         idx_inj, mom_inj = (np.full((n_cols, n_q), -1, dtype=np.int32), np.zeros((n_cols, 2))) if x_inj is not None else (None, None)
         for c in range(n_cols):
@@ -476,6 +570,7 @@ def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), i
         return q, mean, sd
 
     out = {"names": names, "levels": levels, "n_points": n_points, "dead": np.asarray(dead[:n_ev]).copy()}
+    _point_weight_entries(out, loo, vsum)
     out["quantiles"], out["mean"], out["sd"] = summary(idx_pe, np.moveaxis(x_pe, 0, 1), mom_pe, mass[:n_ev])
     if x_inj is not None:
         out["quantiles_inj"], out["mean_inj"], out["sd_inj"] = summary(idx_inj, x_inj, mom_inj, mass[n_ev : n_ev + 1].reshape(()))
@@ -486,7 +581,8 @@ def event_credible_intervals(eng, thetas, pe_values, levels=(0.05, 0.5, 0.95), i
 
 
 def event_posterior_densities(eng, thetas, pe_values, grid, pairs=None, grid2d=None, inj_values=None, bounds=None, rule="scott", scale=1.0, pedata=None, injdata=None,
-                              param_names=None, m1min=None, m2min=None, mmax=None, backend="device", accumulate=True):
+                              param_names=None, m1min=None, m2min=None, mmax=None, backend="device", accumulate=True, point_weights=None, leave_one_out=False, total_inj=None,
+                              nobs=None, marginalize_selection=False):
     """Smooth densities of the population-informed posterior of every event, marginalised over K posterior hyper-parameter draws: per
     event and quantity a weighted Gaussian kernel density estimate of the marginal posterior weights ``W_i = sum_k w_ki / S_k`` on
     the points of ``grid`` (the curves of a ridge or violin plot), per pair of quantities the same in two dimensions on a tensor grid
@@ -509,7 +605,12 @@ def event_posterior_densities(eng, thetas, pe_values, grid, pairs=None, grid2d=N
     (n_ev, C)``, ``dead (n_ev,)`` (the points at which the event had no weight) and ``n_points``; with ``inj_values`` also
     ``density_inj (C, G)``, ``bandwidth_inj``, ``neff_inj``, ``degenerate_inj`` and ``dead_inj``; with ``pairs`` also ``pairs``
     (column indices), ``density2d (n_ev, P, n_gx, n_gy)``, ``covariance (n_ev, P, 3)`` (``Hxx, Hxy, Hyy``), ``degenerate2d`` and their
-    ``_inj`` counterparts.  A segment without a curve gives NaN."""
+    ``_inj`` counterparts.  A segment without a curve gives NaN.
+
+    ``point_weights``, ``leave_one_out``, ``total_inj``, ``nobs`` and ``marginalize_selection`` are
+    :func:`reweighted_event_posteriors`' and apply to the accumulation: with ``accumulate=False`` the weights the engine holds are
+    reused whatever they were made with.  With them the dict also holds ``point_weight_sum (n_ev + 1,)`` (the engine's sum of the
+    weights) and, for ``leave_one_out=True``, ``elpd_loo`` and ``neff_points``.  The defaults leave every output as it was."""
     from . import draws as D
 
     thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
@@ -541,12 +642,14 @@ def event_posterior_densities(eng, thetas, pe_values, grid, pairs=None, grid2d=N
         gridx, gridy = (np.ascontiguousarray(np.broadcast_to(np.asarray(g, dtype=np.float64), (pair_idx.shape[0], np.shape(g)[-1]))) for g in grid2d)
         if not (1 <= gridx.shape[1] <= 128 and 1 <= gridy.shape[1] <= 128) or not (np.all(np.isfinite(gridx)) and np.all(np.isfinite(gridy))):
             raise ValueError("grid2d holds one to 128 finite points per axis")
+    v, loo = _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection)
+    weighted = {} if v is None else {"point_weights": v}
     if accumulate:
         masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
         if masks[0] is not None:
             eng.set_draw_mask(*masks)
         eng.marginal_weights_reset()
-        eng.marginal_weights_add(thetas)
+        eng.marginal_weights_add(thetas, **weighted)
     n_segs = n_ev + 1
     if backend == "device":
         eng.set_kde_columns(x_pe, x_inj, b)
@@ -575,6 +678,7 @@ def event_posterior_densities(eng, thetas, pe_values, grid, pairs=None, grid2d=N
                     rho2_inj[t], cov[n_ev, t], _, flags2[n_ev, t] = D.weighted_kde2d_reference(w_inj, x_inj[cx], x_inj[cy], gridx[t], gridy[t], rule, scale)
     out = {"names": names, "grid": grid, "n_points": n_points, "dead": np.asarray(dead[:n_ev]).copy(), "density": rho_pe, "bandwidth": bw[:n_ev], "neff": neff[:n_ev],
            "degenerate": flags[:n_ev]}
+    _point_weight_entries(out, loo, eng.marginal_point_weights()[0] if v is not None else None)
     if x_inj is not None:
         out.update(density_inj=rho_inj, bandwidth_inj=bw[n_ev], neff_inj=float(neff[n_ev]), degenerate_inj=flags[n_ev], dead_inj=int(dead[n_ev]))
     if pair_idx is not None:

@@ -443,11 +443,23 @@ void gwi_resample_times(double* logw_ms, double* prefix_ms, double* select_ms, i
  *
  * gwi_histogram_times(): DIAGNOSTIC ONLY, for tools/weighted_histograms_time.py: of the calling thread's last call, summed over its
  * points, the wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge / histogram
- * tile launches together and of the histogram merge launches, and the number of kernel launches after the log-weight passes. */
+ * tile launches together and of the histogram merge launches, and the number of kernel launches after the log-weight passes.  It
+ * covers gwi_weighted_histograms_weighted() likewise.
+ *
+ * gwi_weighted_histograms_weighted(): the same sums with a linear weight per (point, segment), v[k][n_ev + 1] in [0, 1] (segment n_ev is
+ * the injection set), uploaded once per call: H[segment][c][b] += v h[c][b] -- the quotient h is formed as without weights and then
+ * multiplied by v in a product of its own, so v = 1 gives the bits of gwi_weighted_histograms() -- and vsum[segment] += v for a live
+ * segment; the weighted mean over the points is H / vsum.  A point whose v is 0 adds nothing and does not touch dead[segment].  vsum
+ * [n_ev + 1] is IN/OUT like the histograms and dead; k >= 1 as there.  Leave-one-out posteriors (v proportional to the reciprocal
+ * of the event's own factor of the likelihood) and a change of hyper-prior (one v per point, the same for every segment) are both
+ * stated this way.  GWI_ERR_INVALID also for a null v or vsum, an entry of v that is NaN, negative or above 1, and k < 0. */
 gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, const uint16_t* pe_bins /* [n_cols][n_ev][n_pe] or NULL */,
                                   const uint16_t* inj_bins /* [n_cols][n_inj] or NULL */);
 gwi_status gwi_weighted_histograms(gwi_handle h, const double* thetas, int32_t k, double* hist_pe /* in/out [n_ev][n_cols][n_bins] */,
                                    double* hist_inj /* in/out [n_cols][n_bins] */, int32_t* dead /* in/out [n_ev + 1] */);
+gwi_status gwi_weighted_histograms_weighted(gwi_handle h, const double* thetas, int32_t k, const double* v /* [k][n_ev + 1] */,
+                                            double* hist_pe /* in/out [n_ev][n_cols][n_bins] */, double* hist_inj /* in/out [n_cols][n_bins] */,
+                                            int32_t* dead /* in/out [n_ev + 1] */, double* vsum /* in/out [n_ev + 1] */);
 void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches);
 
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
@@ -477,6 +489,15 @@ void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int
  * of the points.  A request split over calls (2 + 1, 1 + 1 + 1) gives the bits of one call; two handles of one model give the same.
  *
  * gwi_marginal_weights_add(): adds the k >= 0 points thetas[k][n_theta]; k is not bound by the batch limit.
+ * gwi_marginal_weights_add_weighted(): the same with a linear weight per (point, segment), v[k][n_ev + 1] in [0, 1] (segment n_ev is
+ * the injection set), uploaded once per call: W_i += v (w_i / S) -- the quotient is formed as without weights and then multiplied by v
+ * in a product of its own, so v = 1 gives the bits of gwi_marginal_weights_add().  Two more running doubles per segment are state of
+ * the handle beside dead: vsum[segment] += v and vsum2[segment] += v v at every point at which the segment is live, in point order
+ * (gwi_marginal_weights_add() counts v = 1: after unweighted points alone vsum == n_points - dead exactly).  A point whose v is 0 adds
+ * nothing to W, vsum or vsum2, is counted in n_points and does not touch dead.  Weighted and unweighted calls may be mixed;
+ * gwi_marginal_weights_reset() zeroes vsum and vsum2 too.  Quantiles and densities normalise by the segment's sum of W and need no
+ * weights of their own.  (vsum)^2 / vsum2 is the effective number of points of the segment.
+ * gwi_marginal_point_weights(): copies vsum[n_ev + 1] and vsum2[n_ev + 1] back.
  * gwi_marginal_weights_read(): copies W (pe_w[n_ev][n_pe] and inj_w[n_inj]; either may be NULL), dead[n_ev + 1] and n_points back:
  * 8 bytes per sample, whatever the number of points.
  * gwi_weighted_quantiles(): 1 <= n_levels <= 32 levels; idx_pe[n_ev][n_cols][n_levels] and moments_pe[n_ev][n_cols][2] (ignored
@@ -484,15 +505,17 @@ void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int
  * (0 for a set that is left out).  With nothing accumulated every index is -1 and mass is 0.
  * GWI_ERR_INVALID (with a gwi_last_error message) for null pointers, k < 0, n_cols outside 1 ... 8, n_levels outside 1 ... 32, a level
  * that is NaN or outside [0, 1], an order that is no permutation of its segment, values that are not finite or decrease along the
- * order, a quantile call before the columns are set and a host-only handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard, as
- * gwi_draw_indices.
+ * order, a quantile call before the columns are set, a null v, an entry of v that is NaN, negative or above 1, and a host-only
+ * handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard, as gwi_draw_indices.
  *
- * gwi_quantile_times(): DIAGNOSTIC ONLY, for tools/weighted_quantiles_time.py: of the calling thread's last gwi_marginal_weights_add,
+ * gwi_quantile_times(): DIAGNOSTIC ONLY, for tools/weighted_quantiles_time.py: of the calling thread's last gwi_marginal_weights_add(_weighted),
  * summed over its points, the wall time of the (blocking) log-weight passes and the device time (HIP events) of the draw tile / draw
  * merge / marginal add launches; the device time of the calling thread's last gwi_weighted_quantiles (its three launches); and the
  * number of kernel launches of the last of the two calls. */
 gwi_status gwi_marginal_weights_reset(gwi_handle h);
 gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t k);
+gwi_status gwi_marginal_weights_add_weighted(gwi_handle h, const double* thetas, int32_t k, const double* v /* [k][n_ev + 1] */);
+gwi_status gwi_marginal_point_weights(gwi_handle h, double* vsum /* [n_ev + 1] */, double* vsum2 /* [n_ev + 1] */);
 gwi_status gwi_marginal_weights_read(gwi_handle h, double* pe_w /* [n_ev][n_pe] or NULL */, double* inj_w /* [n_inj] or NULL */, int32_t* dead /* [n_ev + 1] */,
                                      int64_t* n_points);
 gwi_status gwi_set_quantile_columns(gwi_handle h, int32_t n_cols, const double* x_pe /* [n_cols][n_ev][n_pe] or NULL */, const int32_t* order_pe /* like x_pe */,
