@@ -237,6 +237,8 @@ EXPORTED_SYMBOLS = [
     "gwi_weighted_histograms",
     "gwi_weighted_histograms_weighted",
     "gwi_histogram_times",
+    "gwi_point_cdfs",
+    "gwi_point_cdf_times",
     "gwi_marginal_weights_reset",
     "gwi_marginal_weights_add",
     "gwi_marginal_weights_add_weighted",
@@ -411,6 +413,12 @@ def load_library():
         lib.gwi_marginal_point_weights.argtypes = [vp, _DP, _DP]
         lib.gwi_weighted_histograms_weighted.restype = C.c_int32
         lib.gwi_weighted_histograms_weighted.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _DP, _I32P, _DP]
+    if hasattr(lib, "gwi_point_cdfs"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_point_cdfs.restype = C.c_int32
+        lib.gwi_point_cdfs.argtypes = [vp, _DP, C.c_int32, _DP, _I32P]
+        lib.gwi_point_cdf_times.restype = None
+        lib.gwi_point_cdf_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

@@ -10,6 +10,7 @@
 #include "gwi_popdraw.h"
 #include "gwi_resample.h"
 #include "gwi_hist.h"
+#include "gwi_cdf.h"
 #include "gwi_quant.h"
 #include "gwi_kde.h"
 #include "gwi_jit.h"
@@ -471,6 +472,10 @@ struct PostprocessBuffers {
     DeviceBuffer<unsigned short> d_bins_pe, d_bins_inj;
     DeviceBuffer<double> d_partial, d_sums, d_vsum;
     DeviceBuffer<int> d_dead;
+    // ... and of gwi_point_cdfs (gwi_cdf.h): one point's F [n_ev + 1][n_cols][n_bins] and segment flags [n_ev + 1], the staged rows
+    // [64][4][n_cols][n_bins] and live counts [64][2] (allocated on that entry's first call after the bins were set, released with them)
+    DeviceBuffer<double> d_cdf, d_cdf_stage;
+    DeviceBuffer<int> d_cdf_dead, d_cdf_live;
     int cols = 0, bins = 0;
   } hist;
   // marginal weights and their quantiles (gwi_quant.h).  The state of the handle: one running double per sample [n_ev n_pe | n_inj],
@@ -4034,6 +4039,93 @@ gwi_status gwi_weighted_histograms_weighted(gwi_handle h, const double* thetas, 
 }
 
 void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) { g_histogram_times.report(logw_ms, tile_ms, merge_ms, launches); }
+
+// ---- per-point CDFs and the catalog's extremes (gwi_cdf.h) ------------------------------------------------------------------
+enum { kCdfLogw, kCdfTile, kCdfReduce };
+static thread_local StageTimes g_point_cdf_times;
+
+gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double* out, int32_t* live) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_cdfs";
+  g_point_cdf_times = StageTimes();
+  PostprocessBuffers::Histogram& hist = h->post.hist;
+  const bool with_pe = hist.d_bins_pe.ptr != nullptr, with_inj = hist.d_bins_inj.ptr != nullptr;
+  gwi_status st = post_preflight(h, who, "sum on", "the injection CDF needs", [&]() -> std::string {
+    if (!h->variant) return "the engine has no scan kernel";
+    if (!hist.cols) return "no bins are set (gwi_set_histogram_bins)";
+    if (!thetas || k < 1) return "thetas is null or k < 1";
+    if (!out) return "out is null";
+    if (!live) return "live is null";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  namespace D = gwi::draw;
+  namespace H = gwi::hist;
+  namespace F = gwi::cdf;
+  F::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.h.d, &n_tiles);  // (as gwi_set_histogram_bins found it)
+  if (st != GWI_OK) return st;
+  // the workspace of this entry alone, allocated on its first call after the bins were set and released with them
+  const size_t per_seg = (size_t)hist.cols * (size_t)hist.bins, per_point = (size_t)F::kSlots * per_seg;
+  GWI_HIP(hist.d_cdf.reserve((size_t)(h->n_ev + 1) * per_seg));
+  GWI_HIP(hist.d_cdf_dead.reserve((size_t)(h->n_ev + 1)));
+  GWI_HIP(hist.d_cdf_stage.reserve((size_t)F::kStagePoints * per_point));
+  GWI_HIP(hist.d_cdf_live.reserve((size_t)F::kStagePoints * 2));
+  const long long n_pe_tiles = h->n_ev * a.h.d.tiles_per_event;
+  a.h.bins_pe = hist.d_bins_pe;
+  a.h.bins_inj = hist.d_bins_inj;
+  a.h.partial = hist.d_partial;
+  a.h.n_cols = hist.cols;
+  a.h.n_bins = hist.bins;
+  a.h.first_tile = with_pe ? 0 : (int)n_pe_tiles;
+  a.h.first_seg = with_pe ? 0 : (int)h->n_ev;
+  a.cdf = hist.d_cdf;
+  a.seg_dead = hist.d_cdf_dead;
+  a.with_pe = with_pe ? 1 : 0;
+  a.with_inj = with_inj ? 1 : 0;
+  const long long hist_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? a.h.d.n_inj_tiles : 0), hist_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
+  LaunchScratch ev(who);
+  GWI_HIP(ev.events(3));
+  const int nt = h->spec.n_theta;
+  for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
+    const int slot = p % F::kStagePoints;
+    const auto t0 = std::chrono::steady_clock::now();
+    st = fill_log_weights(h, thetas + (size_t)p * nt, &a.h.d.log_const);  // (blocking)
+    if (st != GWI_OK) return st;
+    g_point_cdf_times.ms[kCdfLogw] += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    a.h.d.logw_pe = h->post.d_logw_pe;
+    a.h.d.logw_inj = h->post.d_logw_inj;
+    a.out = hist.d_cdf_stage + (size_t)slot * per_point;
+    a.live = hist.d_cdf_live + (size_t)slot * 2;
+    GWI_HIP(hipEventRecord(ev.e[0], h->stream));
+    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a.h.d);
+    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.h.d);
+    if (hist_tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)hist_tiles), dim3(H::kBlock), 0, h->stream, a.h);
+    GWI_HIP(hipEventRecord(ev.e[1], h->stream));
+    if (hist_segs) hipLaunchKernelGGL(F::cdf_segment_kernel, dim3((unsigned)hist_segs, (unsigned)a.h.n_cols), dim3(F::kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(F::cdf_catalog_kernel, dim3((unsigned)a.h.n_cols), dim3(F::kBlock), 0, h->stream, a);
+    GWI_HIP(hipGetLastError());
+    GWI_HIP(hipEventRecord(ev.e[2], h->stream));
+    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
+    GWI_HIP(hipStreamSynchronize(h->stream));
+    float tile_ms = 0.f, reduce_ms = 0.f;
+    GWI_HIP(hipEventElapsedTime(&tile_ms, ev.e[0], ev.e[1]));
+    GWI_HIP(hipEventElapsedTime(&reduce_ms, ev.e[1], ev.e[2]));
+    g_point_cdf_times.ms[kCdfTile] += tile_ms;
+    g_point_cdf_times.ms[kCdfReduce] += reduce_ms;
+    g_point_cdf_times.launches += 5;
+    if (slot + 1 == F::kStagePoints || p + 1 == k) {  // the staged rows go back: 4 n_cols n_bins doubles and two ints per point
+      const size_t first = (size_t)(p - slot);
+      GWI_HIP(hipMemcpy(out + first * per_point, hist.d_cdf_stage, sizeof(double) * (size_t)(slot + 1) * per_point, hipMemcpyDeviceToHost));
+      GWI_HIP(hipMemcpy(live + first * 2, hist.d_cdf_live, sizeof(int) * (size_t)(slot + 1) * 2, hipMemcpyDeviceToHost));
+    }
+  }
+  return GWI_OK;
+}
+
+void gwi_point_cdf_times(double* logw_ms, double* tile_ms, double* reduce_ms, int32_t* launches) { g_point_cdf_times.report(logw_ms, tile_ms, reduce_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

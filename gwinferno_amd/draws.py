@@ -23,7 +23,11 @@ estimate with scipy's bandwidth rules: :func:`weighted_kde_reference` and :func:
 
 ``gwi_marginal_weights_add_weighted`` / ``gwi_weighted_histograms_weighted`` give every (point, segment) a linear weight ``v`` in
 ``[0, 1]``: the optional ``v`` of :func:`marginal_weights_reference` and :func:`weighted_histograms_reference` states them, and
-:func:`leave_one_out_summary` the weights, scores and diagnostics of the leave-one-out posteriors made of them."""
+:func:`leave_one_out_summary` the weights, scores and diagnostics of the leave-one-out posteriors made of them.
+
+``gwi_point_cdfs`` (gwinferno_amd/csrc/gwi_cdf.h) returns, per point, the running sums of the same normalised bins over cumulative
+codes -- exact CDFs at the grid points -- for the injection set and, reduced over the events, for the catalog: :func:`cdf_codes`
+states the codes, :func:`point_cdfs_reference` one point, and :func:`weighted_percentiles` the bands over the points."""
 import bisect
 import itertools
 import math
@@ -186,6 +190,90 @@ def weighted_histograms_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins,
     if inj_bins is not None:
         hist_inj = one(n_ev, logw_inj, inj_mask, np.asarray(inj_bins))
     return (hist_pe, hist_inj, dead) if v is None else (hist_pe, hist_inj, dead, vsum)
+
+
+MAX_CDF_GRID = 256  # grid points per column of gwi_point_cdfs (gwi_hist.h: kMaxBins)
+
+
+def cdf_codes(values, grid):
+    """uint16 CUMULATIVE codes of ``values`` for the grid ``g_0 < ... < g_{G-1}`` of ``gwi_point_cdfs``: the number of grid points
+    ``< x`` (``np.searchsorted(grid, x, side="left")``), so code ``j < G`` means ``g_{j-1} < x <= g_j`` and ``x == g_j`` gets ``j``;
+    :data:`OUTSIDE_BIN` for a value above ``g_{G-1}`` and for NaN: the sample counts in the segment's total and in no bin.  The
+    running sum of a column's bins up to ``j`` is then exactly the weight share with ``x <= g_j``."""
+    grid = np.asarray(grid, dtype=np.float64).ravel()
+    if not 1 <= grid.size <= MAX_CDF_GRID:
+        raise ValueError(f"the grid holds 1 ... {MAX_CDF_GRID} points")
+    if not np.all(np.isfinite(grid)) or not np.all(np.diff(grid) > 0):
+        raise ValueError("the grid must be finite and strictly increasing")
+    x = np.asarray(values, dtype=np.float64)
+    code = np.searchsorted(grid, x, side="left")  # (NaN sorts past the end)
+    return np.where((code < grid.size) & ~np.isnan(x), code, OUTSIDE_BIN).astype(np.uint16)
+
+
+def point_cdfs_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins, inj_bins, n_bins):
+    """One hyper-parameter point of ``gwi_point_cdfs``: the arguments of :func:`weighted_histograms_reference` with
+    the cumulative codes of :func:`cdf_codes` as bins -> ``(out (4, n_cols, n_bins), live (2,) int32)``.  With ``h`` of
+    :func:`weighted_histogram_segment` and ``F = np.cumsum(h, axis=-1)`` per segment: slot 0 is ``F`` of the injection set (NaN
+    when it has no weight or ``inj_bins`` is None); slot 1 ``(sum of F over the live events, in event order) / n_live`` (NaN when
+    no event is live or ``pe_bins`` is None); slot 2 the sum of ``log F`` over the live events -- the log CDF of the catalog's
+    maximum, ``-inf`` where an event has no weight at or below the grid point; slot 3 the sum of ``log1p(-min(F, 1))`` -- the CDF of
+    the catalog's minimum is ``1 - exp`` of it.  Slots 2 and 3 are NaN without ``pe_bins`` and 0 without a live event.  ``live =
+    (n_live, 1 if the injection set is live else 0)``."""
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    n_ev, n_bins = logw_pe.shape[0], int(n_bins)
+    n_cols = np.asarray(pe_bins if pe_bins is not None else inj_bins).shape[0]
+    out = np.full((4, n_cols, n_bins), np.nan)
+    live = np.zeros(2, dtype=np.int32)
+    if inj_bins is not None:
+        h, alive = weighted_histogram_segment(logw_inj, inj_mask, np.asarray(inj_bins), n_bins)
+        if alive:
+            out[0], live[1] = np.cumsum(h, axis=-1), 1
+    if pe_bins is not None:
+        pe_bins = np.asarray(pe_bins)
+        pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(logw_pe.shape)
+        sum_f, below, above = np.zeros((n_cols, n_bins)), np.zeros((n_cols, n_bins)), np.zeros((n_cols, n_bins))
+        with np.errstate(divide="ignore"):
+            for ev in range(n_ev):
+                h, alive = weighted_histogram_segment(logw_pe[ev], None if pe_mask is None else pe_mask[ev], pe_bins[:, ev], n_bins)
+                if not alive:
+                    continue
+                f = np.cumsum(h, axis=-1)
+                live[0] += 1
+                sum_f += f
+                below += np.log(f)
+                above += np.log1p(-np.minimum(f, 1.0))
+        if live[0]:
+            out[1] = sum_f / float(live[0])
+        out[2], out[3] = below, above
+    return out, live
+
+
+def weighted_percentiles(values, weights, levels):
+    """Percentiles over the FIRST axis of ``values (K, ...)`` under the weights ``(K,)``, rule "inverted CDF" as in
+    :func:`weighted_quantiles_reference`: per trailing index the value at the smallest rank ``r`` (values ascending, ties in point
+    order) with ``C_r >= p C_last`` and weight there -- a value of the input, never an interpolation -- ``(Q, ...)``.  Points whose value
+    is NaN or whose weight is 0 are left out; NaN where none is left.  The prefix is a plain float64 ``cumsum``."""
+    values, weights = np.asarray(values, dtype=np.float64), np.asarray(weights, dtype=np.float64).ravel()
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if values.ndim < 1 or values.shape[0] != weights.size:
+        raise ValueError("one weight per entry of the first axis")
+    if np.any(~np.isfinite(weights)) or np.any(weights < 0.0):
+        raise ValueError("weights must be finite and non-negative")
+    if levels.ndim != 1 or np.any(~((levels >= 0.0) & (levels <= 1.0))):
+        raise ValueError("levels must lie in [0, 1]")
+    k = values.shape[0]
+    flat = values.reshape(k, -1)
+    out = np.full((levels.size, flat.shape[1]), np.nan)
+    for j in range(flat.shape[1]):
+        col = flat[:, j]
+        keep = np.nonzero(~np.isnan(col) & (weights > 0.0))[0]
+        if keep.size == 0:
+            continue
+        keep = keep[np.argsort(col[keep], kind="stable")]
+        cum = np.cumsum(weights[keep])
+        r = np.minimum(np.searchsorted(cum, levels * cum[-1], side="left"), keep.size - 1)
+        out[:, j] = col[keep[r]]
+    return out.reshape((levels.size,) + values.shape[1:])
 
 
 def marginal_weights_reference(logw_pe, logw_inj, pe_mask, inj_mask, v=None):

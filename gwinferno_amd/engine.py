@@ -1156,6 +1156,32 @@ class NativePopulationLikelihood:
                                                      dead.ctypes.data_as(i32)))
         return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead
 
+    def point_cdfs(self, thetas):
+        """Per-point cumulative distributions on the device (``gwi_point_cdfs``; semantics:
+        :func:`gwinferno_amd.draws.point_cdfs_reference`).  The bins of :meth:`set_histogram_bins` are cumulative codes
+        (:func:`gwinferno_amd.draws.cdf_codes`).  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.  Returns ``(out (k, 4,
+        n_cols, n_bins), live (k, 2) int32)``: per point the CDF of the predicted detected distribution (slot 0), the mean of the live
+        events' CDFs (slot 1), the sum of their ``log F`` (slot 2: the log CDF of the catalog's maximum) and of their ``log1p(-F)``
+        (slot 3: the CDF of the catalog's minimum is ``1 - exp`` of it), and ``(live events, injection set live)``.  NaN where a set
+        has no bins or no weight.  ``4 n_cols n_bins`` doubles come back per point; the points may be split over calls without
+        changing a bit.  Not available on an engine that holds a shard (``world > 1``)."""
+        if self.world > 1:
+            raise N.NativeEngineError("GWI_ERR_UNSUPPORTED: point_cdfs: this engine holds one shard of the catalog; the injection CDF needs the global set")
+        thetas = N.f64(thetas)
+        if thetas.ndim not in (1, 2) or thetas.shape[-1] != self.n_theta or thetas.size == 0:
+            raise ValueError(f"thetas has shape {thetas.shape}; expected ({self.n_theta},) or (k, {self.n_theta})")
+        thetas = thetas.reshape(-1, self.n_theta)
+        k = thetas.shape[0]
+        shape = getattr(self, "_hist_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        if shape is None:  # the library says so
+            self._check(self.lib.gwi_point_cdfs(self.handle, N.as_dp(thetas), k, None, None))
+            raise N.NativeEngineError("GWI_ERR_INVALID: point_cdfs: no bins are set (set_histogram_bins)")
+        n_cols, n_bins = shape[:2]
+        out, live = np.empty((k, 4, n_cols, n_bins)), np.empty((k, 2), dtype=np.int32)
+        self._check(self.lib.gwi_point_cdfs(self.handle, N.as_dp(thetas), k, N.as_dp(out), live.ctypes.data_as(i32)))
+        return out, live
+
     def _whole_catalog(self, what, need):
         if self.world > 1:
             raise N.NativeEngineError(f"GWI_ERR_UNSUPPORTED: {what}: this engine holds one shard of the catalog; {need} the global set")

@@ -686,3 +686,106 @@ def event_posterior_densities(eng, thetas, pe_values, grid, pairs=None, grid2d=N
         if x_inj is not None:
             out.update(density2d_inj=rho2_inj, covariance_inj=cov[n_ev], degenerate2d_inj=flags2[n_ev])
     return out
+
+
+def catalog_predictive_check(eng, thetas, pe_values, grid, inj_values=None, levels=(0.05, 0.5, 0.95), n_obs=None, point_weights=None, pedata=None, injdata=None,
+                             param_names=None, m1min=None, m2min=None, mmax=None, backend="device"):
+    """Catalog-level predictive checks over K posterior hyper-parameter draws: per quantity the cumulative distribution of
+    the predicted detected population (from the injections) and the catalog's own population-informed one (the mean over the events
+    of their CDFs), each as percentile bands over the draws, and the extreme-event test -- the CDF of the catalog's largest value,
+    ``P(max_e x_e <= g | theta_k) = prod_e F_ke(g)``, and of its smallest, ``1 - prod_e (1 - F_ke(g))``, against those of a predicted
+    catalog of ``n_obs`` detections, ``F_det,k(g)^n_obs`` and ``1 - (1 - F_det,k(g))^n_obs``.  Bands and products are not linear in
+    the per-point distributions, so on the device (``eng.point_cdfs``) the curves of every point come back, ``4 C G`` doubles per
+    point, and the weights never leave HBM.  A CDF at a grid point is an exact partition sum: it has no bin-width error.
+
+    ``thetas`` is ``(K, n_theta)`` in the engine's layout.  ``pe_values`` / ``inj_values`` (or ``pedata`` / ``injdata`` with
+    ``param_names``), the mass cuts and the masks are :func:`event_credible_intervals`'; without ``inj_values`` there is no predicted
+    side (NaN).  ``grid`` maps a name to its strictly increasing ``(G,)`` points, or is one ``(G,)`` or ``(C, G)`` array; ``1 <= G
+    <= 256``, the same for every quantity.  The device backend replaces the engine's histogram bins with the grid's cumulative
+    codes (:func:`gwinferno_amd.draws.cdf_codes`).  ``n_obs`` is the size of the predicted catalog (default ``eng.n_ev``).
+    ``point_weights (K,)`` -- finite, non-negative, not all 0; default equal -- weight the points in the bands (rule "inverted CDF",
+    :func:`gwinferno_amd.draws.weighted_percentiles`) and in the means; they are applied here, to ``K C G`` numbers, and never go to
+    the device.  With ``leave_one_out_weights(...)["point_weights"][:, e]`` the points stand for ``p(theta | all events but e)``:
+    comparing event e's values with ``cdf_max_predicted`` (or ``cdf_min_predicted``) is then the leave-one-out outlier test of event
+    e, whose own data no longer shapes the population it is held against.  ``backend="host"`` runs the NumPy statement
+    (:func:`gwinferno_amd.draws.point_cdfs_reference`) on ``eng.log_weights`` under the masks given here (none without the cuts):
+    the statement the kernels are tested against, not a fall-back.
+
+    Returns a dict: ``names``; ``grid (C, G)``; ``levels``; the raw per-point arrays ``cdf_detected``, ``cdf_observed``,
+    ``log_cdf_max_observed`` and ``log_sf_min_observed``, each ``(K, C, G)`` (``log_sf_min`` is the log of ``P(min > g)``);
+    ``log_cdf_max_predicted = n_obs log cdf_detected`` and ``log_sf_min_predicted = n_obs log1p(-cdf_detected)``; ``bands_detected``
+    and ``bands_observed (Q, C, G)``; ``cdf_max_observed``, ``cdf_max_predicted``, ``cdf_min_observed`` and ``cdf_min_predicted (C,
+    G)``, the weighted means over the points of the exponentiated quantities, a point without a live event (observed) or without
+    injection weight (predicted) left out; ``n_live (K,)``, the live events per point; ``dead_detected``, the points at which the
+    injection set had no weight; ``n_points``."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or levels.size < 1 or not np.all((levels >= 0.0) & (levels <= 1.0)):
+        raise ValueError("levels must be numbers in [0, 1]")
+    source = pe_values if pe_values is not None else pedata
+    for p in param_names if param_names is not None and source is not None else ():
+        if p not in source:
+            raise ValueError(f"unknown quantity {p!r}")
+    names, x_pe, x_inj = _summary_columns(eng, pe_values, inj_values, pedata, injdata, param_names)
+    n_cols, n_ev = len(names), eng.n_ev
+    if isinstance(grid, dict):
+        missing = [p for p in names if p not in grid]
+        if missing:
+            raise ValueError(f"grid names no points for {missing}")
+        if len({np.size(grid[p]) for p in names}) != 1:
+            raise ValueError("every quantity needs the same number of grid points")
+        grid = np.stack([np.asarray(grid[p], dtype=np.float64).ravel() for p in names])
+    else:
+        grid = np.asarray(grid, dtype=np.float64)
+    if grid.ndim not in (1, 2) or (grid.ndim == 2 and grid.shape[0] != n_cols) or not 1 <= grid.shape[-1] <= D.MAX_CDF_GRID:
+        raise ValueError(f"grid has shape {grid.shape}; expected (G,) or ({n_cols}, G) with 1 <= G <= {D.MAX_CDF_GRID}")
+    grid = np.ascontiguousarray(np.broadcast_to(grid, (n_cols, grid.shape[-1])))
+    n_grid = grid.shape[1]
+    n_obs = float(n_ev if n_obs is None else n_obs)
+    if not (n_obs > 0.0 and np.isfinite(n_obs)):
+        raise ValueError("n_obs must be a positive number")
+    if point_weights is None:
+        v = np.ones(k)
+    else:
+        v = np.asarray(point_weights, dtype=np.float64)
+        if v.shape != (k,) or not np.all(np.isfinite(v)) or np.any(v < 0.0) or not np.any(v > 0.0):
+            raise ValueError(f"point_weights are ({k},) finite non-negative numbers, not all 0")
+    pe_codes = np.stack([D.cdf_codes(x_pe[c], grid[c]) for c in range(n_cols)])
+    inj_codes = np.stack([D.cdf_codes(x_inj[c], grid[c]) for c in range(n_cols)]) if x_inj is not None else None
+    masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    if backend == "device":
+        if masks[0] is not None:
+            eng.set_draw_mask(*masks)
+        eng.set_histogram_bins(pe_codes, inj_codes, n_bins=n_grid)
+        out, live = eng.point_cdfs(thetas)
+    else:
+        out, live = np.empty((k, 4, n_cols, n_grid)), np.empty((k, 2), dtype=np.int32)
+        for i, th in enumerate(thetas):
+            lw_pe, lw_inj = eng.log_weights(th)
+            out[i], live[i] = D.point_cdfs_reference(lw_pe, lw_inj, masks[0], masks[1], pe_codes, inj_codes, n_grid)
+    det, obs, below, above = out[:, 0], out[:, 1], out[:, 2], out[:, 3]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        below_pred, above_pred = n_obs * np.log(det), n_obs * np.log1p(-np.minimum(det, 1.0))
+
+    def mean(values, keep):
+        """the weighted mean over the points of ``keep``; NaN where none has weight"""
+        w = np.where(keep, v, 0.0)
+        total = w.sum()
+        if not total > 0.0:
+            return np.full(values.shape[1:], np.nan)
+        return np.tensordot(w, np.where(keep[:, None, None], values, 0.0), axes=1) / total
+
+    has_obs, has_det = live[:, 0] > 0, live[:, 1] > 0
+    return {"names": names, "grid": grid, "levels": levels, "cdf_detected": det, "cdf_observed": obs, "log_cdf_max_observed": below, "log_sf_min_observed": above,
+            "log_cdf_max_predicted": below_pred, "log_sf_min_predicted": above_pred,
+            "bands_detected": D.weighted_percentiles(det, v, levels), "bands_observed": D.weighted_percentiles(obs, v, levels),
+            "cdf_max_observed": mean(np.exp(below), has_obs), "cdf_max_predicted": mean(np.exp(below_pred), has_det),
+            "cdf_min_observed": mean(-np.expm1(above), has_obs), "cdf_min_predicted": mean(-np.expm1(above_pred), has_det),
+            "n_live": live[:, 0].astype(np.int64), "dead_detected": int(np.count_nonzero(~has_det)) if x_inj is not None else k, "n_points": k}

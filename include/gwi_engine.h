@@ -462,6 +462,43 @@ gwi_status gwi_weighted_histograms_weighted(gwi_handle h, const double* thetas, 
                                             int32_t* dead /* in/out [n_ev + 1] */, double* vsum /* in/out [n_ev + 1] */);
 void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches);
 
+/* Catalog predictive checks on the device: per hyper-parameter point the cumulative distributions that observed-versus-predicted
+ * figures with credible bands and the extreme-event (outlier) test are made of (gwinferno_amd/csrc/gwi_cdf.h; the NumPy statement is
+ * gwinferno_amd/draws.py: point_cdfs_reference; the contract is DESIGN 8g).  A band is a percentile over the points and the CDF of the
+ * catalog's largest value a product over the events, P(max_e x_e <= g | theta_k) = prod_e F_ke(g): neither can be rebuilt from the
+ * sums over points gwi_weighted_histograms returns, so these go back per point.
+ *
+ * The bins are those of gwi_set_histogram_bins, made as CUMULATIVE codes from a grid g_0 < ... < g_{G-1}, 1 <= G = n_bins <= 256
+ * (draws.py: cdf_codes): a sample's code in a column is the number of grid points < x (np.searchsorted(grid, x, side="left")), so code
+ * j < G means g_{j-1} < x <= g_j; code G, or a NaN value, becomes 0xFFFF: the sample counts in S and in no bin.  The sum of
+ * h[c][0 ... j] is then exactly the weight share with x <= g_j, without a bin-width error, and 1 - the last entry the share above the
+ * grid.  The library does not look at the grid: it sums whatever codes were set.
+ *
+ * For one point, with h[seg][c][b] the quotient gwi_weighted_histograms forms (tile order, then / S): F[seg][c][b] = the running sum
+ * of h[seg][c][0 ... b], strictly left to right (the bits of np.cumsum).  A segment is live at the point where S > 0 and finite;
+ * n_live counts the live events.  out[k][4][n_cols][n_bins] holds per point
+ *   slot 0  cdf_det         F of the injection segment (n_ev); NaN if that segment is dead or there are no injection bins
+ *   slot 1  cdf_obs         (sum of F over the live events, in event order) / n_live, one division at the end; NaN if n_live = 0 or
+ *                           there are no PE bins
+ *   slot 2  log_all_below   the sum of log F over the live events, in event order: the log CDF of the catalog's maximum; log 0 = -inf
+ *                           stays
+ *   slot 3  log_all_above   the sum of log1p(-min(F, 1)) over the live events, in event order: the CDF of the catalog's minimum is
+ *                           1 - exp(.)
+ * (slots 2 and 3 are NaN without PE bins and 0, the empty sum, with n_live = 0), and live[k][2] = (n_live, injection segment live ? 1
+ * : 0; n_live is 0 without PE bins).  Nothing is in/out.  k >= 1 is not bound by the batch limit: the points are staged on the device 64
+ * at a time and copied back per chunk, 4 n_cols n_bins doubles per point.  The masks of gwi_set_draw_mask apply.  No point weights go to
+ * the device: a weight on the k axis (leave-one-out, a change of hyper-prior) is applied by the host to the K C G numbers.  Every sum has
+ * a fixed shape and there are no atomics: the bits are a pure function of the arguments, whatever the split of the points over calls.
+ * Not done: sharded handles; the events' own per-point CDFs travelling back (K n_ev C G numbers); more than 256 grid points.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, a host-only handle and a call before the bins are set;
+ * GWI_ERR_UNSUPPORTED on a handle that holds a shard, as gwi_weighted_histograms.
+ *
+ * gwi_point_cdf_times(): DIAGNOSTIC ONLY, for tools/point_cdfs_time.py: of the calling thread's last call, summed over its points, the
+ * wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge / histogram tile launches
+ * together and of the two CDF launches, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double* out /* [k][4][n_cols][n_bins] */, int32_t* live /* [k][2] */);
+void gwi_point_cdf_times(double* logw_ms, double* tile_ms, double* reduce_ms, int32_t* launches);
+
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is
  * gwinferno_amd/draws.py: marginal_weights_reference, weighted_quantiles_reference).
