@@ -448,6 +448,11 @@ struct DeviceBuffer {
     ptr = nullptr;
     cap = 0;
   }
+  // src[n] copied from the host into an allocation that holds it
+  hipError_t upload(const T* src, size_t n) {
+    const hipError_t e = reserve(n);
+    return e != hipSuccess || !n ? e : hipMemcpy(ptr, src, sizeof(T) * n, hipMemcpyHostToDevice);
+  }
   operator T*() const { return ptr; }
 };
 
@@ -3642,8 +3647,7 @@ static gwi_status set_one_draw_mask(gwi_handle h, const unsigned char* src, size
     dst->reset();
     return GWI_OK;
   }
-  GWI_HIP(dst->reserve(n));
-  if (n) GWI_HIP(hipMemcpy(*dst, src, n, hipMemcpyHostToDevice));
+  GWI_HIP(dst->upload(src, n));
   return GWI_OK;
 }
 
@@ -3721,6 +3725,84 @@ static gwi_status resample_workspace(gwi_handle h, gwi::draw::DrawArgs* da, gwi:
   return GWI_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// The tiles and segments of draw_workspace's layout that a query covers.  PE tiles and segments come first, the injection set's
+// last: a set without columns (or bins) is left out of the query's launches.
+struct QueryCover {
+  int first_tile, first_seg;
+  long long tiles, segs;
+  QueryCover(bool with_pe, bool with_inj, long long n_ev, const gwi::draw::DrawArgs& d) {
+    const long long n_pe_tiles = n_ev * d.tiles_per_event;
+    first_tile = with_pe ? 0 : (int)n_pe_tiles;
+    first_seg = with_pe ? 0 : (int)n_ev;
+    tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? d.n_inj_tiles : 0);
+    segs = (with_pe ? n_ev : 0) + (with_inj ? 1 : 0);
+  }
+};
+
+// what the arguments of the queries on the marginal weights (gwi_quant.h, gwi_kde.h) share: the weights, the geometry, the cover
+template <class Args>
+void fill_query_args(gwi_handle h, const gwi::draw::DrawArgs& geometry, const QueryCover& cover, Args* a) {
+  a->w_pe = h->post.marg.d_w;
+  a->w_inj = h->post.marg.d_w + (size_t)(h->n_ev * h->n_pe);
+  a->n_pe = h->n_pe;
+  a->n_inj = h->n_inj;
+  a->n_ev = (int)h->n_ev;
+  a->tiles_per_event = geometry.tiles_per_event;
+  a->n_inj_tiles = geometry.n_inj_tiles;
+  a->first_tile = cover.first_tile;
+  a->first_seg = cover.first_seg;
+}
+
+// The per-point pass of the post-processing entries.  One point after another, in the order of the call, since each needs its own
+// normalisers and its own pass over the catalog: the log-weights at the point (blocking), the two draw launches over the whole
+// catalog (*d and n_tiles as draw_workspace left them; the entry's launches see what they filled in), the entry's own launches
+// stage1(p) and stage2(p), one wait for the stream, then after(p), which returns a status.  With `times` (reset by the entry) the
+// host clock of the log-weights is added to ms[0], the HIP-event time of the draw launches and stage1 to ms[1], that of stage2, of
+// n_stages = 2, to ms[2], and launches_per_point to the launches.  Without, no event is created.  A failure returns at once.
+template <class Stage1, class Stage2, class After>
+gwi_status per_point_pass(gwi_handle h, const char* who, const double* thetas, int k, gwi::draw::DrawArgs* d, long long n_tiles, StageTimes* times, int n_stages,
+                                 int launches_per_point, Stage1&& stage1, Stage2&& stage2, After&& after) {
+  namespace D = gwi::draw;
+  LaunchScratch ev(who);
+  if (times) GWI_HIP(ev.events(n_stages + 1));
+  const int nt = h->spec.n_theta;
+  for (int p = 0; p < k; ++p) {
+    const auto t0 = std::chrono::steady_clock::now();
+    gwi_status st = fill_log_weights(h, thetas + (size_t)p * nt, &d->log_const);
+    if (st != GWI_OK) return st;
+    if (times) times->ms[0] += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    d->logw_pe = h->post.d_logw_pe;
+    d->logw_inj = h->post.d_logw_inj;
+    if (times) GWI_HIP(hipEventRecord(ev.e[0], h->stream));
+    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, *d);
+    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, *d);
+    stage1(p);
+    if (times && n_stages == 2) GWI_HIP(hipEventRecord(ev.e[1], h->stream));
+    stage2(p);
+    GWI_HIP(hipGetLastError());
+    if (times) GWI_HIP(hipEventRecord(ev.e[n_stages], h->stream));
+    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
+    GWI_HIP(hipStreamSynchronize(h->stream));
+    st = after(p);
+    if (st != GWI_OK) return st;
+    for (int s = 0; times && s < n_stages; ++s) {
+      float ms = 0.f;
+      GWI_HIP(hipEventElapsedTime(&ms, ev.e[s], ev.e[s + 1]));
+      times->ms[1 + s] += ms;
+    }
+    if (times) times->launches += launches_per_point;
+  }
+  return GWI_OK;
+}
+const auto no_stage = [](int) {};
+const auto no_step = [](int) { return GWI_OK; };
+}  // namespace
+
+extern "C" {
+
 gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const double* u_pe, int32_t n_draw_pe, const double* u_inj, int32_t n_draw_inj,
                             int32_t* idx_pe, int32_t* idx_inj) {
   if (!h) return GWI_ERR_INVALID;
@@ -3755,23 +3837,15 @@ gwi_status gwi_draw_indices(gwi_handle h, const double* thetas, int32_t k, const
   a.n_draw_pe = n_draw_pe;
   a.n_draw_inj = n_draw_inj;
   a.batches_pe = (int)batches_pe;
-  const int nt = h->spec.n_theta;
-  for (int p = 0; p < k; ++p) {  // one point after another: each needs its own normalisers and its own pass over the catalog
-    st = fill_log_weights(h, thetas + (size_t)p * nt, &a.log_const);
-    if (st != GWI_OK) return st;
-    a.logw_pe = h->post.d_logw_pe;
-    a.logw_inj = h->post.d_logw_inj;
+  const auto select = [&](int p) {  // (the first two launches do not look at the uniforms or the indices)
     a.u_pe = d_u + (size_t)p * pe_point;
     a.u_inj = d_u + pe_all + (size_t)p * (size_t)n_draw_inj;
     a.idx_pe = d_idx + (size_t)p * pe_point;
     a.idx_inj = d_idx + pe_all + (size_t)p * (size_t)n_draw_inj;
-    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a);
-    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a);
     hipLaunchKernelGGL(D::draw_select_kernel, dim3((unsigned)select_blocks), dim3(D::kDrawBlock), 0, h->stream, a);
-    GWI_HIP(hipGetLastError());
-    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
-    GWI_HIP(hipStreamSynchronize(h->stream));
-  }
+  };
+  st = per_point_pass(h, "gwi_draw_indices", thetas, k, &a, n_tiles, nullptr, 1, 3, select, no_stage, no_step);
+  if (st != GWI_OK) return st;
   if (pe_all) GWI_HIP(hipMemcpy(idx_pe, d_idx, sizeof(int) * pe_all, hipMemcpyDeviceToHost));
   if (n_draw_inj) GWI_HIP(hipMemcpy(idx_inj, d_idx + pe_all, sizeof(int) * (size_t)k * (size_t)n_draw_inj, hipMemcpyDeviceToHost));
   return GWI_OK;
@@ -3881,8 +3955,7 @@ static gwi_status upload_point_weights(gwi_handle h, const double* v, int32_t k,
   const size_t n = (size_t)k * (size_t)(h->n_ev + 1);
   *d_v = nullptr;
   if (!n) return GWI_OK;
-  GWI_HIP(h->post.d_point_w.reserve(n));
-  GWI_HIP(hipMemcpy(h->post.d_point_w, v, sizeof(double) * n, hipMemcpyHostToDevice));
+  GWI_HIP(h->post.d_point_w.upload(v, n));
   *d_v = h->post.d_point_w;
   return GWI_OK;
 }
@@ -3918,14 +3991,8 @@ gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, 
   PostprocessBuffers::Histogram& hist = h->post.hist;
   hist = PostprocessBuffers::Histogram();
   const size_t per_seg = (size_t)n_cols * (size_t)n_bins;
-  if (n_pe_codes) {
-    GWI_HIP(hist.d_bins_pe.reserve(n_pe_codes));
-    GWI_HIP(hipMemcpy(hist.d_bins_pe, pe_bins, sizeof(uint16_t) * n_pe_codes, hipMemcpyHostToDevice));
-  }
-  if (n_inj_codes) {
-    GWI_HIP(hist.d_bins_inj.reserve(n_inj_codes));
-    GWI_HIP(hipMemcpy(hist.d_bins_inj, inj_bins, sizeof(uint16_t) * n_inj_codes, hipMemcpyHostToDevice));
-  }
+  if (n_pe_codes) GWI_HIP(hist.d_bins_pe.upload(pe_bins, n_pe_codes));  // (an empty set is one without bins)
+  if (n_inj_codes) GWI_HIP(hist.d_bins_inj.upload(inj_bins, n_inj_codes));
   GWI_HIP(hist.d_partial.reserve((size_t)n_tiles * per_seg));
   GWI_HIP(hist.d_sums.reserve((size_t)(h->n_ev + 1) * per_seg));
   GWI_HIP(hist.d_dead.reserve((size_t)(h->n_ev + 1)));
@@ -3933,6 +4000,21 @@ gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, 
   hist.cols = n_cols;
   hist.bins = n_bins;
   return GWI_OK;
+}
+
+// What the arguments of the histogram and the CDF launches share (a->d is draw_workspace's): the bins, the tiles' partial histograms
+// and the cover of the sets that have bins, which is returned.
+static QueryCover fill_hist_args(gwi_handle h, gwi::hist::Args* a) {
+  const PostprocessBuffers::Histogram& hist = h->post.hist;
+  const QueryCover cover(hist.d_bins_pe.ptr != nullptr, hist.d_bins_inj.ptr != nullptr, h->n_ev, a->d);
+  a->bins_pe = hist.d_bins_pe;
+  a->bins_inj = hist.d_bins_inj;
+  a->partial = hist.d_partial;
+  a->n_cols = hist.cols;
+  a->n_bins = hist.bins;
+  a->first_tile = cover.first_tile;
+  a->first_seg = cover.first_seg;
+  return cover;
 }
 
 // gwi_weighted_histograms (weighted = false: v and vsum are not looked at) and gwi_weighted_histograms_weighted
@@ -3966,58 +4048,29 @@ static gwi_status weighted_histograms(gwi_handle h, const char* who, bool weight
     if (st != GWI_OK) return st;
     GWI_HIP(hipMemcpy(hist.d_vsum, vsum, sizeof(double) * (size_t)(h->n_ev + 1), hipMemcpyHostToDevice));
   }
-  const long long n_pe_tiles = h->n_ev * a.d.tiles_per_event;
   const size_t per_seg = (size_t)hist.cols * (size_t)hist.bins, n_pe_out = (size_t)h->n_ev * per_seg;
   // the caller's running sums: the points of this call are added onto them, so a request may be split over calls
   if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(hist.d_sums, hist_pe, sizeof(double) * n_pe_out, hipMemcpyHostToDevice));
   if (with_inj) GWI_HIP(hipMemcpy(hist.d_sums + n_pe_out, hist_inj, sizeof(double) * per_seg, hipMemcpyHostToDevice));
   GWI_HIP(hipMemcpy(hist.d_dead, dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyHostToDevice));
-  a.bins_pe = hist.d_bins_pe;
-  a.bins_inj = hist.d_bins_inj;
-  a.partial = hist.d_partial;
+  const QueryCover cover = fill_hist_args(h, &a);
   a.hist = hist.d_sums;
   a.n_dead = hist.d_dead;
   a.vsum = hist.d_vsum;
-  a.n_cols = hist.cols;
-  a.n_bins = hist.bins;
-  // a set without bins is left out of the two new launches: PE tiles and segments come first, the injection set's last
-  a.first_tile = with_pe ? 0 : (int)n_pe_tiles;
-  a.first_seg = with_pe ? 0 : (int)h->n_ev;
-  const long long hist_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? a.d.n_inj_tiles : 0), hist_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
-  LaunchScratch ev(who);
-  GWI_HIP(ev.events(3));
-  const int nt = h->spec.n_theta;
-  for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
-    const auto t0 = std::chrono::steady_clock::now();
-    st = fill_log_weights(h, thetas + (size_t)p * nt, &a.d.log_const);  // (blocking)
-    if (st != GWI_OK) return st;
-    g_histogram_times.ms[kHistLogw] += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    a.d.logw_pe = h->post.d_logw_pe;
-    a.d.logw_inj = h->post.d_logw_inj;
-    GWI_HIP(hipEventRecord(ev.e[0], h->stream));
-    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a.d);
-    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.d);
-    if (hist_tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)hist_tiles), dim3(H::kBlock), 0, h->stream, a);
-    GWI_HIP(hipEventRecord(ev.e[1], h->stream));
-    if (hist_segs) {
-      if (weighted) {
-        a.v = d_v + (size_t)p * (size_t)(h->n_ev + 1);
-        hipLaunchKernelGGL(H::hist_merge_kernel<true>, dim3((unsigned)hist_segs, (unsigned)a.n_cols), dim3(H::kBlock), 0, h->stream, a);
-      } else {
-        hipLaunchKernelGGL(H::hist_merge_kernel<false>, dim3((unsigned)hist_segs, (unsigned)a.n_cols), dim3(H::kBlock), 0, h->stream, a);
-      }
+  const auto tile = [&](int) {
+    if (cover.tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)cover.tiles), dim3(H::kBlock), 0, h->stream, a);
+  };
+  const auto merge = [&](int p) {
+    if (!cover.segs) return;
+    if (weighted) {
+      a.v = d_v + (size_t)p * (size_t)(h->n_ev + 1);
+      hipLaunchKernelGGL(H::hist_merge_kernel<true>, dim3((unsigned)cover.segs, (unsigned)a.n_cols), dim3(H::kBlock), 0, h->stream, a);
+    } else {
+      hipLaunchKernelGGL(H::hist_merge_kernel<false>, dim3((unsigned)cover.segs, (unsigned)a.n_cols), dim3(H::kBlock), 0, h->stream, a);
     }
-    GWI_HIP(hipGetLastError());
-    GWI_HIP(hipEventRecord(ev.e[2], h->stream));
-    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
-    GWI_HIP(hipStreamSynchronize(h->stream));
-    float tile_ms = 0.f, merge_ms = 0.f;
-    GWI_HIP(hipEventElapsedTime(&tile_ms, ev.e[0], ev.e[1]));
-    GWI_HIP(hipEventElapsedTime(&merge_ms, ev.e[1], ev.e[2]));
-    g_histogram_times.ms[kHistTile] += tile_ms;
-    g_histogram_times.ms[kHistMerge] += merge_ms;
-    g_histogram_times.launches += 4;
-  }
+  };
+  st = per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_histogram_times, 2, 4, tile, merge, no_step);
+  if (st != GWI_OK) return st;
   if (with_pe && n_pe_out) GWI_HIP(hipMemcpy(hist_pe, hist.d_sums, sizeof(double) * n_pe_out, hipMemcpyDeviceToHost));
   if (with_inj) GWI_HIP(hipMemcpy(hist_inj, hist.d_sums + n_pe_out, sizeof(double) * per_seg, hipMemcpyDeviceToHost));
   GWI_HIP(hipMemcpy(dead, hist.d_dead, sizeof(int) * (size_t)(h->n_ev + 1), hipMemcpyDeviceToHost));
@@ -4073,56 +4126,31 @@ gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double*
   GWI_HIP(hist.d_cdf_dead.reserve((size_t)(h->n_ev + 1)));
   GWI_HIP(hist.d_cdf_stage.reserve((size_t)F::kStagePoints * per_point));
   GWI_HIP(hist.d_cdf_live.reserve((size_t)F::kStagePoints * 2));
-  const long long n_pe_tiles = h->n_ev * a.h.d.tiles_per_event;
-  a.h.bins_pe = hist.d_bins_pe;
-  a.h.bins_inj = hist.d_bins_inj;
-  a.h.partial = hist.d_partial;
-  a.h.n_cols = hist.cols;
-  a.h.n_bins = hist.bins;
-  a.h.first_tile = with_pe ? 0 : (int)n_pe_tiles;
-  a.h.first_seg = with_pe ? 0 : (int)h->n_ev;
+  const QueryCover cover = fill_hist_args(h, &a.h);
   a.cdf = hist.d_cdf;
   a.seg_dead = hist.d_cdf_dead;
   a.with_pe = with_pe ? 1 : 0;
   a.with_inj = with_inj ? 1 : 0;
-  const long long hist_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? a.h.d.n_inj_tiles : 0), hist_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
-  LaunchScratch ev(who);
-  GWI_HIP(ev.events(3));
-  const int nt = h->spec.n_theta;
-  for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
+  const auto tile = [&](int) {
+    if (cover.tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)cover.tiles), dim3(H::kBlock), 0, h->stream, a.h);
+  };
+  const auto reduce = [&](int p) {  // into the point's slot of the stage
     const int slot = p % F::kStagePoints;
-    const auto t0 = std::chrono::steady_clock::now();
-    st = fill_log_weights(h, thetas + (size_t)p * nt, &a.h.d.log_const);  // (blocking)
-    if (st != GWI_OK) return st;
-    g_point_cdf_times.ms[kCdfLogw] += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    a.h.d.logw_pe = h->post.d_logw_pe;
-    a.h.d.logw_inj = h->post.d_logw_inj;
     a.out = hist.d_cdf_stage + (size_t)slot * per_point;
     a.live = hist.d_cdf_live + (size_t)slot * 2;
-    GWI_HIP(hipEventRecord(ev.e[0], h->stream));
-    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a.h.d);
-    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.h.d);
-    if (hist_tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)hist_tiles), dim3(H::kBlock), 0, h->stream, a.h);
-    GWI_HIP(hipEventRecord(ev.e[1], h->stream));
-    if (hist_segs) hipLaunchKernelGGL(F::cdf_segment_kernel, dim3((unsigned)hist_segs, (unsigned)a.h.n_cols), dim3(F::kBlock), 0, h->stream, a);
+    if (cover.segs) hipLaunchKernelGGL(F::cdf_segment_kernel, dim3((unsigned)cover.segs, (unsigned)a.h.n_cols), dim3(F::kBlock), 0, h->stream, a);
     hipLaunchKernelGGL(F::cdf_catalog_kernel, dim3((unsigned)a.h.n_cols), dim3(F::kBlock), 0, h->stream, a);
-    GWI_HIP(hipGetLastError());
-    GWI_HIP(hipEventRecord(ev.e[2], h->stream));
-    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
-    GWI_HIP(hipStreamSynchronize(h->stream));
-    float tile_ms = 0.f, reduce_ms = 0.f;
-    GWI_HIP(hipEventElapsedTime(&tile_ms, ev.e[0], ev.e[1]));
-    GWI_HIP(hipEventElapsedTime(&reduce_ms, ev.e[1], ev.e[2]));
-    g_point_cdf_times.ms[kCdfTile] += tile_ms;
-    g_point_cdf_times.ms[kCdfReduce] += reduce_ms;
-    g_point_cdf_times.launches += 5;
+  };
+  const auto copy_back = [&](int p) -> gwi_status {
+    const int slot = p % F::kStagePoints;
     if (slot + 1 == F::kStagePoints || p + 1 == k) {  // the staged rows go back: 4 n_cols n_bins doubles and two ints per point
       const size_t first = (size_t)(p - slot);
       GWI_HIP(hipMemcpy(out + first * per_point, hist.d_cdf_stage, sizeof(double) * (size_t)(slot + 1) * per_point, hipMemcpyDeviceToHost));
       GWI_HIP(hipMemcpy(live + first * 2, hist.d_cdf_live, sizeof(int) * (size_t)(slot + 1) * 2, hipMemcpyDeviceToHost));
     }
-  }
-  return GWI_OK;
+    return GWI_OK;
+  };
+  return per_point_pass(h, who, thetas, k, &a.h.d, n_tiles, &g_point_cdf_times, 2, 5, tile, reduce, copy_back);
 }
 
 void gwi_point_cdf_times(double* logw_ms, double* tile_ms, double* reduce_ms, int32_t* launches) { g_point_cdf_times.report(logw_ms, tile_ms, reduce_ms, launches); }
@@ -4185,38 +4213,20 @@ static gwi_status marginal_weights_add(gwi_handle h, const char* who, bool weigh
   a.dead = m.d_dead;
   a.vsum = m.d_vsum;
   a.vsum2 = m.d_vsum + (size_t)(h->n_ev + 1);
-  LaunchScratch ev(who);
-  GWI_HIP(ev.events(2));
-  const int nt = h->spec.n_theta;
-  for (int p = 0; p < k; ++p) {  // one point after another, in the order of the call: each needs its own pass over the catalog
-    const auto t0 = std::chrono::steady_clock::now();
-    st = fill_log_weights(h, thetas + (size_t)p * nt, &a.d.log_const);  // (blocking)
-    if (st != GWI_OK) return st;
-    g_quantile_times.ms[kQuantLogw] += 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    a.d.logw_pe = h->post.d_logw_pe;
-    a.d.logw_inj = h->post.d_logw_inj;
-    GWI_HIP(hipEventRecord(ev.e[0], h->stream));
-    if (n_tiles) hipLaunchKernelGGL(D::draw_tile_kernel, dim3((unsigned)n_tiles), dim3(D::kDrawBlock), 0, h->stream, a.d);
-    hipLaunchKernelGGL(D::draw_merge_kernel, dim3((unsigned)(h->n_ev + 1)), dim3(D::kDrawBlock), 0, h->stream, a.d);
-    if (n_tiles) {
-      if (weighted) {
-        a.v = d_v + (size_t)p * (size_t)(h->n_ev + 1);
-        hipLaunchKernelGGL(Q::marg_add_kernel<true>, dim3((unsigned)n_tiles), dim3(Q::kBlock), 0, h->stream, a);
-      } else {
-        hipLaunchKernelGGL(Q::marg_add_kernel<false>, dim3((unsigned)n_tiles), dim3(Q::kBlock), 0, h->stream, a);
-      }
+  const auto add = [&](int p) {
+    if (!n_tiles) return;
+    if (weighted) {
+      a.v = d_v + (size_t)p * (size_t)(h->n_ev + 1);
+      hipLaunchKernelGGL(Q::marg_add_kernel<true>, dim3((unsigned)n_tiles), dim3(Q::kBlock), 0, h->stream, a);
+    } else {
+      hipLaunchKernelGGL(Q::marg_add_kernel<false>, dim3((unsigned)n_tiles), dim3(Q::kBlock), 0, h->stream, a);
     }
-    GWI_HIP(hipGetLastError());
-    GWI_HIP(hipEventRecord(ev.e[1], h->stream));
-    // the next point's evaluation may go through the engine's own queue: this point's launches are over before it starts
-    GWI_HIP(hipStreamSynchronize(h->stream));
+  };
+  const auto count = [&](int) {  // (completed points only)
     ++m.n_points;
-    float add_ms = 0.f;
-    GWI_HIP(hipEventElapsedTime(&add_ms, ev.e[0], ev.e[1]));
-    g_quantile_times.ms[kQuantAdd] += add_ms;
-    g_quantile_times.launches += 3;
-  }
-  return GWI_OK;
+    return GWI_OK;
+  };
+  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_quantile_times, 1, 3, add, no_stage, count);
 }
 
 gwi_status gwi_marginal_weights_add(gwi_handle h, const double* thetas, int32_t k) {
@@ -4313,17 +4323,13 @@ gwi_status gwi_set_quantile_columns(gwi_handle h, int32_t n_cols, const double* 
   PostprocessBuffers::Quantile& quant = h->post.quant;
   quant = PostprocessBuffers::Quantile();
   const size_t n_pe_vals = x_pe ? (size_t)n_cols * (size_t)(h->n_ev * h->n_pe) : 0, n_inj_vals = x_inj ? (size_t)n_cols * (size_t)h->n_inj : 0;
-  if (x_pe) {
-    GWI_HIP(quant.d_x_pe.reserve(n_pe_vals));
-    GWI_HIP(quant.d_order_pe.reserve(n_pe_vals));
-    if (n_pe_vals) GWI_HIP(hipMemcpy(quant.d_x_pe, x_pe, sizeof(double) * n_pe_vals, hipMemcpyHostToDevice));
-    if (n_pe_vals) GWI_HIP(hipMemcpy(quant.d_order_pe, order_pe, sizeof(int32_t) * n_pe_vals, hipMemcpyHostToDevice));
+  if (x_pe) {  // (a set that is given has columns, even where it is empty)
+    GWI_HIP(quant.d_x_pe.upload(x_pe, n_pe_vals));
+    GWI_HIP(quant.d_order_pe.upload(order_pe, n_pe_vals));
   }
   if (x_inj) {
-    GWI_HIP(quant.d_x_inj.reserve(n_inj_vals));
-    GWI_HIP(quant.d_order_inj.reserve(n_inj_vals));
-    if (n_inj_vals) GWI_HIP(hipMemcpy(quant.d_x_inj, x_inj, sizeof(double) * n_inj_vals, hipMemcpyHostToDevice));
-    if (n_inj_vals) GWI_HIP(hipMemcpy(quant.d_order_inj, order_inj, sizeof(int32_t) * n_inj_vals, hipMemcpyHostToDevice));
+    GWI_HIP(quant.d_x_inj.upload(x_inj, n_inj_vals));
+    GWI_HIP(quant.d_order_inj.upload(order_inj, n_inj_vals));
   }
   GWI_HIP(quant.d_partial.reserve((size_t)n_tiles * (size_t)n_cols * Q::kSums));
   GWI_HIP(quant.d_prefix.reserve((size_t)n_tiles * (size_t)n_cols));
@@ -4355,15 +4361,15 @@ gwi_status gwi_weighted_quantiles(gwi_handle h, const double* levels, int32_t n_
   st = marginal_state(h);
   if (st != GWI_OK) return st;
   const size_t n_segs = (size_t)(h->n_ev + 1), per_seg_idx = (size_t)quant.cols * (size_t)n_levels, per_seg_mom = (size_t)quant.cols * 2;
-  GWI_HIP(quant.d_levels.reserve((size_t)n_levels));
   GWI_HIP(quant.d_idx.reserve(n_segs * per_seg_idx));
   GWI_HIP(quant.d_out.reserve(n_segs * per_seg_mom + n_segs));
-  GWI_HIP(hipMemcpy(quant.d_levels, levels, sizeof(double) * (size_t)n_levels, hipMemcpyHostToDevice));
+  GWI_HIP(quant.d_levels.upload(levels, (size_t)n_levels));
   GWI_HIP(hipMemsetAsync(quant.d_out, 0, sizeof(double) * (n_segs * per_seg_mom + n_segs), h->stream));  // (the mass of a set that is left out)
   Q::Args a;
   std::memset(&a, 0, sizeof(a));
-  a.w_pe = h->post.marg.d_w;
-  a.w_inj = h->post.marg.d_w + (size_t)(h->n_ev * h->n_pe);
+  // a set without columns is left out of the launches
+  const QueryCover cover(with_pe, with_inj, h->n_ev, geometry);
+  fill_query_args(h, geometry, cover, &a);
   a.x_pe = quant.d_x_pe;
   a.x_inj = quant.d_x_inj;
   a.order_pe = quant.d_order_pe;
@@ -4374,18 +4380,9 @@ gwi_status gwi_weighted_quantiles(gwi_handle h, const double* levels, int32_t n_
   a.idx = quant.d_idx;
   a.moments = quant.d_out;
   a.mass = quant.d_out + n_segs * per_seg_mom;
-  a.n_pe = h->n_pe;
-  a.n_inj = h->n_inj;
-  a.n_ev = (int)h->n_ev;
-  a.tiles_per_event = geometry.tiles_per_event;
-  a.n_inj_tiles = geometry.n_inj_tiles;
   a.n_cols = quant.cols;
   a.n_levels = n_levels;
-  // a set without columns is left out of the launches: PE tiles and segments come first, the injection set's last
-  const long long n_pe_tiles = h->n_ev * geometry.tiles_per_event;
-  a.first_tile = with_pe ? 0 : (int)n_pe_tiles;
-  a.first_seg = with_pe ? 0 : (int)h->n_ev;
-  const long long q_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? geometry.n_inj_tiles : 0), q_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
+  const long long q_tiles = cover.tiles, q_segs = cover.segs;
   LaunchScratch ev("gwi_weighted_quantiles");
   GWI_HIP(ev.events(2));
   GWI_HIP(hipEventRecord(ev.e[0], h->stream));
@@ -4455,14 +4452,8 @@ gwi_status gwi_set_kde_columns(gwi_handle h, int32_t n_cols, const double* x_pe,
   PostprocessBuffers::Kde& kde = h->post.kde;
   kde = PostprocessBuffers::Kde();
   const size_t n_pe_vals = x_pe ? (size_t)n_cols * (size_t)(h->n_ev * h->n_pe) : 0, n_inj_vals = x_inj ? (size_t)n_cols * (size_t)h->n_inj : 0;
-  if (x_pe) {
-    GWI_HIP(kde.d_x_pe.reserve(n_pe_vals));
-    if (n_pe_vals) GWI_HIP(hipMemcpy(kde.d_x_pe, x_pe, sizeof(double) * n_pe_vals, hipMemcpyHostToDevice));
-  }
-  if (x_inj) {
-    GWI_HIP(kde.d_x_inj.reserve(n_inj_vals));
-    if (n_inj_vals) GWI_HIP(hipMemcpy(kde.d_x_inj, x_inj, sizeof(double) * n_inj_vals, hipMemcpyHostToDevice));
-  }
+  if (x_pe) GWI_HIP(kde.d_x_pe.upload(x_pe, n_pe_vals));  // (a set that is given has columns, even where it is empty)
+  if (x_inj) GWI_HIP(kde.d_x_inj.upload(x_inj, n_inj_vals));
   double host_bounds[2 * K::kMaxCols];
   for (int i = 0; i < 2 * n_cols; ++i) host_bounds[i] = bounds ? bounds[i] : __builtin_nan("");
   GWI_HIP(kde.d_bounds.reserve(2 * K::kMaxCols));
@@ -4492,9 +4483,9 @@ static gwi_status kde_query(gwi_handle h, const char* who, int d, const int32_t*
   g_kde_times = StageTimes();
   const size_t n_segs = (size_t)(h->n_ev + 1), n_ev = (size_t)h->n_ev, per_bw = d == 1 ? 1 : 3;
   const long long n_points = d == 1 ? n_gx : (long long)n_gx * n_gy, n_blocks = (n_points + K::kBlock - 1) / K::kBlock;
-  // a set without columns is left out of the launches: PE tiles and segments come first, the injection set's last
-  const long long n_pe_tiles = h->n_ev * geometry.tiles_per_event;
-  const long long q_tiles = (with_pe ? n_pe_tiles : 0) + (with_inj ? geometry.n_inj_tiles : 0), q_segs = (with_pe ? h->n_ev : 0) + (with_inj ? 1 : 0);
+  // a set without columns is left out of the launches
+  const QueryCover cover(with_pe, with_inj, h->n_ev, geometry);
+  const long long q_tiles = cover.tiles, q_segs = cover.segs;
   // the grid blocks of one evaluation pass: as many as keep the partials within kPartialCap doubles, at least one
   const long long per_block = std::max<long long>(1, q_tiles) * n_items * K::kBlock;
   const long long pass_blocks = std::max<long long>(1, std::min<long long>(n_blocks, K::kPartialCap / per_block));
@@ -4514,8 +4505,7 @@ static gwi_status kde_query(gwi_handle h, const char* who, int d, const int32_t*
   }
   K::Args a;
   std::memset(&a, 0, sizeof(a));
-  a.w_pe = h->post.marg.d_w;
-  a.w_inj = h->post.marg.d_w + (size_t)(h->n_ev * h->n_pe);
+  fill_query_args(h, geometry, cover, &a);
   a.x_pe = kde.d_x_pe;
   a.x_inj = kde.d_x_inj;
   a.bounds = kde.d_bounds;
@@ -4532,11 +4522,6 @@ static gwi_status kde_query(gwi_handle h, const char* who, int d, const int32_t*
   a.partial = kde.d_partial;
   a.rho = kde.d_rho;
   a.scale = scale;
-  a.n_pe = h->n_pe;
-  a.n_inj = h->n_inj;
-  a.n_ev = (int)h->n_ev;
-  a.tiles_per_event = geometry.tiles_per_event;
-  a.n_inj_tiles = geometry.n_inj_tiles;
   a.n_cols = kde.cols;
   a.n_pairs = d == 2 ? n_items : 0;
   a.n_items = n_items;
@@ -4544,8 +4529,6 @@ static gwi_status kde_query(gwi_handle h, const char* who, int d, const int32_t*
   a.n_gx = n_gx;
   a.n_gy = d == 2 ? n_gy : 1;
   a.n_points = (int)n_points;
-  a.first_tile = with_pe ? 0 : (int)n_pe_tiles;
-  a.first_seg = with_pe ? 0 : (int)h->n_ev;
   LaunchScratch ev(who);
   GWI_HIP(ev.events(3));
   GWI_HIP(hipEventRecord(ev.e[0], h->stream));

@@ -1,0 +1,403 @@
+"""The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
+injection resampling, weighted histograms, per-point CDFs, marginal weights and their quantiles and kernel density estimates.
+Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+
+
+class PostprocessMixin:
+    """What an engine that holds the whole catalog can do with it beside evaluating the likelihood.  The class that inherits this
+    has ``lib``, ``handle``, ``_check``, ``world`` and the catalog's sizes ``n_theta``, ``n_ev``, ``n_pe``, ``n_inj``."""
+
+    def _whole_catalog(self, what, need):
+        if self.world > 1:
+            raise N.NativeEngineError(f"GWI_ERR_UNSUPPORTED: {what}: this engine holds one shard of the catalog; {need} the global set")
+
+    def _points(self, thetas, none_allowed=False):
+        """``thetas`` -- one point ``(n_theta,)`` or ``(k, n_theta)`` -- as ``(k, n_theta)``; ``k = 0`` only where ``none_allowed``."""
+        thetas = N.f64(thetas)
+        if thetas.ndim not in (1, 2) or thetas.shape[-1] != self.n_theta or (thetas.size == 0 and not none_allowed):
+            raise ValueError(f"thetas has shape {thetas.shape}; expected ({self.n_theta},) or (k, {self.n_theta})")
+        return thetas.reshape(-1, self.n_theta)
+
+    @staticmethod
+    def _one_set(v, shape, name, codes=False):
+        """One set's columns ``(n_cols, *shape)``: finite float64 values, or with ``codes`` integer bin codes as uint16."""
+        if v is None:
+            return None
+        v = np.asarray(v) if codes else np.ascontiguousarray(v, dtype=np.float64)
+        if v.ndim != len(shape) + 1 or v.shape[1:] != shape:
+            raise ValueError(f"{name} has shape {v.shape}; expected (n_cols, {', '.join(str(s) for s in shape)})")
+        if not codes:
+            if not np.all(np.isfinite(v)):
+                raise ValueError(f"{name} holds values that are not finite")
+            return v
+        if v.dtype.kind not in "iu":
+            raise ValueError(f"{name} holds {v.dtype}, not integer bin codes")
+        if v.size and (v.min() < 0 or v.max() > 0xFFFF):
+            raise ValueError(f"{name} holds codes outside 0 ... 0xFFFF")
+        return np.ascontiguousarray(v, dtype=np.uint16)
+
+    def _two_sets(self, pe, inj, pe_name, inj_name, codes=False):
+        """``(pe (n_cols, n_ev, n_pe), inj (n_cols, n_inj), n_cols)`` of the caller's columns: ``None`` leaves a set out, not both."""
+        if pe is None and inj is None:
+            raise ValueError(f"{pe_name} and {inj_name} are both None")
+        pe, inj = self._one_set(pe, (self.n_ev, self.n_pe), pe_name, codes), self._one_set(inj, (self.n_inj,), inj_name, codes)
+        if pe is not None and inj is not None and pe.shape[0] != inj.shape[0]:
+            raise ValueError(f"{pe_name} holds {pe.shape[0]} columns, {inj_name} {inj.shape[0]}")
+        return pe, inj, (pe if pe is not None else inj).shape[0]
+
+    def _nothing_set(self, what, missing, entry, *args):
+        """Nothing to work on: the library says so (``entry`` is called with nulls for its outputs), and where it does not, this does."""
+        self._check(entry(self.handle, *args))
+        raise N.NativeEngineError(f"GWI_ERR_INVALID: {what}: no {missing}")
+
+    def _point_weights(self, point_weights, k):
+        """``point_weights`` -- ``(k, n_ev + 1)``, or ``(k,)`` for one weight per point -- as the ``v[k][n_ev + 1]`` of the C ABI."""
+        from .draws import point_weights_array
+
+        return point_weights_array(point_weights, k, self.n_ev + 1)
+
+    def log_weights(self, theta):
+        """Per-sample log importance weights (diagnostic; parity with the arrays the reference's
+        model function builds, tests/inference_test.py:174-175)."""
+        theta = N.f64(theta)
+        pe = np.zeros((self.n_ev, self.n_pe))
+        inj = np.zeros(self.n_inj)
+        self._check(self.lib.gwi_log_weights(self.handle, N.as_dp(theta), N.as_dp(pe), N.as_dp(inj)))
+        return pe, inj
+
+    def set_draw_mask(self, pe_mask=None, inj_mask=None):
+        """Which samples :meth:`draw_indices` may draw (``gwi_set_draw_mask``): ``pe_mask (n_ev, n_pe)`` and ``inj_mask
+        (n_inj,)``, non-zero = may be drawn, copied to HBM once; ``None`` = every sample.  The mass cuts of the reference's
+        posterior-predictive branch (pipeline/analysis.py:326-338) belong here: :func:`gwinferno_amd.draws.mass_cut_masks`."""
+
+        def one(m, shape, name):
+            if m is None:
+                return None
+            m = np.asarray(m)
+            if m.shape != shape:
+                raise ValueError(f"{name} has shape {m.shape}, the engine's sample set {shape}")
+            return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+        pe, inj = one(pe_mask, (self.n_ev, self.n_pe), "pe_mask"), one(inj_mask, (self.n_inj,), "inj_mask")
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self.lib.gwi_set_draw_mask(self.handle, pe.ctypes.data_as(u8) if pe is not None else None, inj.ctypes.data_as(u8) if inj is not None else None))
+
+    def draw_indices(self, thetas, u_pe=None, u_inj=None):
+        """Weighted index draws on the device (``gwi_draw_indices``; semantics: :mod:`gwinferno_amd.draws`).  ``thetas``
+        is one point ``(n_theta,)`` or ``(k, n_theta)``; ``u_pe (k, n_ev, n_draw_pe)`` and ``u_inj (k, n_draw_inj)`` are the
+        caller's uniforms in ``[0, 1)`` (the leading axis may be left out for a single point; ``None`` = no draws from that
+        set).  Returns ``(idx_pe, idx_inj)``, int32 arrays of the uniforms' shapes (``None`` where no draws were asked for):
+        indices within the event / within the injection set, -1 where a segment has no sample with weight.  Only the indices
+        travel back from the device.  Not available on an engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("draw_indices", "injection draws need")
+        thetas = N.f64(thetas)
+        single = thetas.ndim == 1
+        thetas = thetas.reshape(-1, self.n_theta)
+        k = thetas.shape[0]
+
+        def uniforms(u, lead, name):
+            if u is None:
+                return None, 0
+            u = N.f64(u)
+            if single and u.ndim == len(lead) + 1:
+                u = u[None]
+            if u.ndim != len(lead) + 2 or u.shape[: len(lead) + 1] != (k, *lead):
+                raise ValueError(f"{name} has shape {u.shape}; expected ({', '.join(str(v) for v in (k, *lead))}, n_draws)")
+            return u, u.shape[-1]
+
+        u_pe, n_pe_draws = uniforms(u_pe, (self.n_ev,), "u_pe")
+        u_inj, n_inj_draws = uniforms(u_inj, (), "u_inj")
+        idx_pe = np.full(u_pe.shape, -1, dtype=np.int32) if n_pe_draws else None
+        idx_inj = np.full(u_inj.shape, -1, dtype=np.int32) if n_inj_draws else None
+        i32 = C.POINTER(C.c_int32)
+        self._check(self.lib.gwi_draw_indices(self.handle, N.as_dp(thetas), k, N.as_dp(u_pe) if n_pe_draws else None, n_pe_draws, N.as_dp(u_inj) if n_inj_draws else None,
+                                              n_inj_draws, idx_pe.ctypes.data_as(i32) if n_pe_draws else None, idx_inj.ctypes.data_as(i32) if n_inj_draws else None))
+        if u_pe is not None and idx_pe is None:
+            idx_pe = np.zeros(u_pe.shape, dtype=np.int32)
+        if u_inj is not None and idx_inj is None:
+            idx_inj = np.zeros(u_inj.shape, dtype=np.int32)
+        if single:
+            idx_pe, idx_inj = (None if idx_pe is None else idx_pe[0]), (None if idx_inj is None else idx_inj[0])
+        return idx_pe, idx_inj
+
+    def resample_injections(self, theta, seed, n_request=None, first_index=0):
+        """Seeded draws from the injection set in proportion to ``w = p(.|theta) / prior`` on the device
+        (``gwi_resample_injections``; preprocess/selection.py:143-156; semantics:
+        :func:`gwinferno_amd.draws.resample_indices_reference`).  ``n_request=None`` makes the reference's
+        ``N = floor((sum w)^2 / sum w^2)`` draws, a number exactly that many; draw ``d`` is draw ``first_index + d`` of the seed's
+        stream, so a request may be split over calls.  The injection mask of :meth:`set_draw_mask` applies.  Returns
+        ``(idx, logw_sel, sums)``: int32 indices, the drawn samples' log-weights (``log_weights(theta)[1][idx]``) and
+        ``{"log_sum_w", "log_sum_w2", "n_eff", "n_live"}``; empty arrays when no injection has weight.  Not available on an
+        engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("resample_injections", "injection draws need")
+        theta = N.f64(theta)
+        if theta.shape != (self.n_theta,):
+            raise ValueError(f"theta has shape {theta.shape}; expected ({self.n_theta},)")
+        n_request = -1 if n_request is None else int(n_request)
+        if n_request < -1:
+            raise ValueError("n_request must be None or >= 0")
+        room = self.n_inj if n_request < 0 else n_request
+        idx, lw = np.full(max(room, 1), -1, dtype=np.int32), np.full(max(room, 1), np.nan)
+        sums, made = np.zeros(4), C.c_int64(0)
+        self._check(self.lib.gwi_resample_injections(self.handle, N.as_dp(theta), int(seed) & (2**64 - 1), int(first_index), n_request, C.byref(made), N.as_dp(sums),
+                                                     idx.ctypes.data_as(C.POINTER(C.c_int32)), N.as_dp(lw)))
+        n = int(made.value)
+        return idx[:n].copy(), lw[:n].copy(), {"log_sum_w": float(sums[0]), "log_sum_w2": float(sums[1]), "n_eff": float(sums[2]), "n_live": int(sums[3])}
+
+    def set_histogram_bins(self, pe_bins=None, inj_bins=None, n_bins=None):
+        """The bin codes :meth:`weighted_histograms` sums into (``gwi_set_histogram_bins``): ``pe_bins (n_cols, n_ev, n_pe)`` and
+        ``inj_bins (n_cols, n_inj)``, integers in ``[0, n_bins)`` or ``0xFFFF`` for a sample outside every bin (it still counts in
+        the segment's total); ``None`` leaves that set out, not both.  ``1 <= n_cols <= 8``, ``1 <= n_bins <= 256``.  The codes
+        depend on the catalog only: they are copied to HBM once, and the workspace is allocated here.  Not available on an engine
+        that holds a shard (``world > 1``)."""
+        self._whole_catalog("set_histogram_bins", "the injection histogram needs")
+        if n_bins is None:
+            raise ValueError("n_bins is needed")
+        pe, inj, n_cols = self._two_sets(pe_bins, inj_bins, "pe_bins", "inj_bins", codes=True)
+        u16 = C.POINTER(C.c_uint16)
+        self._check(self.lib.gwi_set_histogram_bins(self.handle, n_cols, int(n_bins), pe.ctypes.data_as(u16) if pe is not None else None,
+                                                    inj.ctypes.data_as(u16) if inj is not None else None))
+        self._hist_shape = (n_cols, int(n_bins), pe is not None, inj is not None)
+
+    def weighted_histograms(self, thetas, out=None, point_weights=None):
+        """Weighted histograms on the device (``gwi_weighted_histograms``; semantics:
+        :func:`gwinferno_amd.draws.weighted_histograms_reference`).  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.
+        Returns ``(hist_pe (n_ev, n_cols, n_bins), hist_inj (n_cols, n_bins), dead (n_ev + 1,) int32)``: running SUMS over the
+        points of each point's normalised histogram (``None`` for a set without bins), and per segment (the injection set last)
+        the number of points at which nothing had weight -- the mean over the live points is ``hist / (K - dead)``.  ``out``
+        is such a triple from an earlier call: the new points are added onto it in place, with the bits one call over all
+        points would give.  Only the sums travel back from the device.  Not available on an engine that holds a shard
+        (``world > 1``).
+
+        ``point_weights`` -- ``(k, n_ev + 1)``, the injection set last, or ``(k,)`` for one weight per point -- gives every (point,
+        segment) a linear weight ``v`` in ``[0, 1]`` (``gwi_weighted_histograms_weighted``): the sums are of ``v`` times the point's
+        normalised histogram, and both ``out`` and the return value are the 4-tuple ``(hist_pe, hist_inj, dead, vsum)`` with ``vsum
+        (n_ev + 1,)`` the sum of ``v`` over the points at which the segment had weight: the weighted mean is ``hist / vsum``.  A
+        point whose ``v`` is 0 adds nothing and is not counted in ``dead``.  ``v = 1`` gives the bits of the call without weights."""
+        self._whole_catalog("weighted_histograms", "the injection histogram needs")
+        thetas = self._points(thetas)
+        v = None if point_weights is None else self._point_weights(point_weights, thetas.shape[0])
+        shape = getattr(self, "_hist_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        if shape is None:
+            self._nothing_set("weighted_histograms", "bins are set (set_histogram_bins)", self.lib.gwi_weighted_histograms, N.as_dp(thetas), thetas.shape[0], None, None, None)
+        n_cols, n_bins, with_pe, with_inj = shape
+        want = ((self.n_ev, n_cols, n_bins) if with_pe else None, (n_cols, n_bins) if with_inj else None, (self.n_ev + 1,)) + (((self.n_ev + 1,),) if v is not None else ())
+        parts, kinds = ("hist_pe", "hist_inj", "dead", "vsum")[: len(want)], (np.float64, np.float64, np.int32, np.float64)
+        if out is None:
+            out = tuple(None if s is None else np.zeros(s, dtype=dt) for s, dt in zip(want, kinds))
+        else:
+            if len(out) != len(want):
+                raise ValueError(f"out is ({', '.join(parts)})")
+            for o, s, name, dt in zip(out, want, parts, kinds):
+                if s is None:
+                    continue
+                if not isinstance(o, np.ndarray) or o.shape != s or o.dtype != dt or not o.flags.c_contiguous or not o.flags.writeable:
+                    raise ValueError(f"out: {name} must be a writeable C-contiguous {np.dtype(dt).name} array of shape {s}")
+        hist_pe, hist_inj, dead = out[:3]
+        if v is not None:
+            self._check(self.lib.gwi_weighted_histograms_weighted(self.handle, N.as_dp(thetas), thetas.shape[0], N.as_dp(v), N.as_dp(hist_pe) if with_pe else None,
+                                                                  N.as_dp(hist_inj) if with_inj else None, dead.ctypes.data_as(i32), N.as_dp(out[3])))
+            return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead, out[3]
+        self._check(self.lib.gwi_weighted_histograms(self.handle, N.as_dp(thetas), thetas.shape[0], N.as_dp(hist_pe) if with_pe else None, N.as_dp(hist_inj) if with_inj else None,
+                                                     dead.ctypes.data_as(i32)))
+        return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead
+
+    def point_cdfs(self, thetas):
+        """Per-point cumulative distributions on the device (``gwi_point_cdfs``; semantics:
+        :func:`gwinferno_amd.draws.point_cdfs_reference`).  The bins of :meth:`set_histogram_bins` are cumulative codes
+        (:func:`gwinferno_amd.draws.cdf_codes`).  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.  Returns ``(out (k, 4,
+        n_cols, n_bins), live (k, 2) int32)``: per point the CDF of the predicted detected distribution (slot 0), the mean of the live
+        events' CDFs (slot 1), the sum of their ``log F`` (slot 2: the log CDF of the catalog's maximum) and of their ``log1p(-F)``
+        (slot 3: the CDF of the catalog's minimum is ``1 - exp`` of it), and ``(live events, injection set live)``.  NaN where a set
+        has no bins or no weight.  ``4 n_cols n_bins`` doubles come back per point; the points may be split over calls without
+        changing a bit.  Not available on an engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("point_cdfs", "the injection CDF needs")
+        thetas = self._points(thetas)
+        k = thetas.shape[0]
+        shape = getattr(self, "_hist_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        if shape is None:
+            self._nothing_set("point_cdfs", "bins are set (set_histogram_bins)", self.lib.gwi_point_cdfs, N.as_dp(thetas), k, None, None)
+        n_cols, n_bins = shape[:2]
+        out, live = np.empty((k, 4, n_cols, n_bins)), np.empty((k, 2), dtype=np.int32)
+        self._check(self.lib.gwi_point_cdfs(self.handle, N.as_dp(thetas), k, N.as_dp(out), live.ctypes.data_as(i32)))
+        return out, live
+
+    def marginal_weights_reset(self):
+        """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""
+        self._whole_catalog("marginal_weights_reset", "the injection weights need")
+        self._check(self.lib.gwi_marginal_weights_reset(self.handle))
+
+    def marginal_weights_add(self, thetas, point_weights=None):
+        """Adds the points ``thetas`` -- ``(n_theta,)`` or ``(k, n_theta)``, in order -- onto the marginal weights the engine keeps in
+        HBM (``gwi_marginal_weights_add``; semantics: :func:`gwinferno_amd.draws.marginal_weights_reference`): ``W_i += w_i / S`` per
+        sample under the masks of :meth:`set_draw_mask`.  Nothing travels back.  The sums stay until :meth:`marginal_weights_reset`;
+        changing the mask does not reset them.  Not available on an engine that holds a shard (``world > 1``).
+
+        ``point_weights`` -- ``(k, n_ev + 1)``, the injection set last, or ``(k,)`` for one weight per point -- gives every (point,
+        segment) a linear weight ``v`` in ``[0, 1]`` (``gwi_marginal_weights_add_weighted``): ``W_i += v (w_i / S)``.  A point whose
+        ``v`` is 0 adds nothing and is not counted in ``dead``; ``v = 1`` gives the bits of the call without weights.  The sums of
+        ``v`` and ``v v`` per segment are kept beside ``W`` (:meth:`marginal_point_weights`); calls with and without weights mix."""
+        self._whole_catalog("marginal_weights_add", "the injection weights need")
+        thetas = self._points(thetas, none_allowed=True)
+        if point_weights is None:
+            self._check(self.lib.gwi_marginal_weights_add(self.handle, N.as_dp(thetas), thetas.shape[0]))
+        else:
+            v = self._point_weights(point_weights, thetas.shape[0])
+            self._check(self.lib.gwi_marginal_weights_add_weighted(self.handle, N.as_dp(thetas), thetas.shape[0], N.as_dp(v)))
+
+    def marginal_point_weights(self):
+        """``(vsum (n_ev + 1,), vsum2 (n_ev + 1,))``: per segment (the injection set last) the sums of the points' weights ``v`` and of
+        ``v v`` over the points at which the segment had weight, since the last reset (``gwi_marginal_point_weights``); a point added
+        without weights counts ``v = 1``.  ``vsum ** 2 / vsum2`` is the segment's effective number of points."""
+        self._whole_catalog("marginal_point_weights", "the injection weights need")
+        vsum, vsum2 = np.zeros(self.n_ev + 1), np.zeros(self.n_ev + 1)
+        self._check(self.lib.gwi_marginal_point_weights(self.handle, N.as_dp(vsum), N.as_dp(vsum2)))
+        return vsum, vsum2
+
+    def marginal_weights(self, weights=True):
+        """``(W_pe (n_ev, n_pe), W_inj (n_inj,), dead (n_ev + 1,) int32, n_points)``: the marginal weights read back once
+        (``gwi_marginal_weights_read``; 8 bytes per sample, whatever the number of points added), per segment (the injection set
+        last) the number of points at which nothing had weight, and the number of points added since the last reset.
+        ``weights=False`` leaves the two arrays on the device (``None`` in their places)."""
+        self._whole_catalog("marginal_weights", "the injection weights need")
+        pe, inj = (np.zeros((self.n_ev, self.n_pe)), np.zeros(self.n_inj)) if weights else (None, None)
+        dead, n = np.zeros(self.n_ev + 1, dtype=np.int32), C.c_int64(0)
+        self._check(self.lib.gwi_marginal_weights_read(self.handle, N.as_dp(pe), N.as_dp(inj), dead.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        return pe, inj, dead, int(n.value)
+
+    def set_quantile_columns(self, pe_values=None, inj_values=None):
+        """The quantities :meth:`weighted_quantiles` selects from (``gwi_set_quantile_columns``): ``pe_values (n_cols, n_ev, n_pe)``
+        and ``inj_values (n_cols, n_inj)``, finite; ``None`` leaves that set out, not both; ``1 <= n_cols <= 8``.  The sort order of
+        every segment is made here (``np.argsort(kind="stable")``: ties stay in sample order) and copied to HBM with the values,
+        once: it does not depend on theta.  Not available on an engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("set_quantile_columns", "the injection quantiles need")
+        pe, inj, n_cols = self._two_sets(pe_values, inj_values, "pe_values", "inj_values")
+        order_pe, order_inj = (None if v is None else np.ascontiguousarray(np.argsort(v, axis=-1, kind="stable"), dtype=np.int32) for v in (pe, inj))
+        i32 = C.POINTER(C.c_int32)
+        self._quant_shape = None
+        self._check(self.lib.gwi_set_quantile_columns(self.handle, n_cols, N.as_dp(pe) if pe is not None else None, order_pe.ctypes.data_as(i32) if pe is not None else None,
+                                                      N.as_dp(inj) if inj is not None else None, order_inj.ctypes.data_as(i32) if inj is not None else None))
+        self._quant_shape = (n_cols, pe is not None, inj is not None)
+
+    def weighted_quantiles(self, levels):
+        """Weighted quantiles and moments under the marginal weights, on the device (``gwi_weighted_quantiles``; semantics:
+        :func:`gwinferno_amd.draws.weighted_quantiles_reference`).  ``levels`` are 1 to 32 numbers in ``[0, 1]``.  Returns ``(idx_pe
+        (n_ev, n_cols, Q), idx_inj (n_cols, Q), moments_pe (n_ev, n_cols, 2), moments_inj (n_cols, 2), mass (n_ev + 1,))``: int32
+        sample indices within the segment (-1 where nothing has weight; ``None`` for a set without columns), ``(sum W x, sum W
+        x^2)`` and per segment ``sum W`` (the injection set last), so that ``mean = m1 / mass``.  Only these travel back."""
+        self._whole_catalog("weighted_quantiles", "the injection quantiles need")
+        levels = np.ascontiguousarray(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        if levels.ndim != 1:
+            raise ValueError(f"levels has shape {levels.shape}; expected (n_levels,)")
+        shape = getattr(self, "_quant_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        mass = np.zeros(self.n_ev + 1)
+        if shape is None:
+            self._nothing_set("weighted_quantiles", "columns are set (set_quantile_columns)", self.lib.gwi_weighted_quantiles, N.as_dp(levels), levels.size, None, None, None, None,
+                              N.as_dp(mass))
+        n_cols, with_pe, with_inj = shape
+        idx_pe, mom_pe = (np.full((self.n_ev, n_cols, levels.size), -1, dtype=np.int32), np.zeros((self.n_ev, n_cols, 2))) if with_pe else (None, None)
+        idx_inj, mom_inj = (np.full((n_cols, levels.size), -1, dtype=np.int32), np.zeros((n_cols, 2))) if with_inj else (None, None)
+        self._check(self.lib.gwi_weighted_quantiles(self.handle, N.as_dp(levels), levels.size, idx_pe.ctypes.data_as(i32) if with_pe else None,
+                                                    idx_inj.ctypes.data_as(i32) if with_inj else None, N.as_dp(mom_pe) if with_pe else None, N.as_dp(mom_inj) if with_inj else None,
+                                                    N.as_dp(mass)))
+        return idx_pe, idx_inj, mom_pe, mom_inj, mass
+
+    def set_kde_columns(self, pe_values=None, inj_values=None, bounds=None):
+        """The quantities :meth:`weighted_kde` and :meth:`weighted_kde2d` smooth (``gwi_set_kde_columns``): ``pe_values (n_cols, n_ev,
+        n_pe)`` and ``inj_values (n_cols, n_inj)``, finite; ``None`` leaves that set out, not both; ``1 <= n_cols <= 8``.  ``bounds
+        (n_cols, 2)`` holds reflecting bounds ``(lo, hi)`` of the 1-D estimate per column, NaN (or ``None`` in a sequence) where
+        there is none; ``None``: no column reflects.  The values are copied to HBM once; no sort order is needed.  Not available
+        on an engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("set_kde_columns", "the injection densities need")
+        pe, inj, n_cols = self._two_sets(pe_values, inj_values, "pe_values", "inj_values")
+        if not 1 <= n_cols <= 8:
+            raise ValueError(f"{n_cols} columns: between 1 and 8 can be set")
+        b = np.full((n_cols, 2), np.nan)
+        if bounds is not None:
+            given = np.array([[np.nan if v is None else float(v) for v in row] for row in bounds], dtype=np.float64)
+            if given.shape != (n_cols, 2):
+                raise ValueError(f"bounds has shape {given.shape}; expected ({n_cols}, 2)")
+            if np.any(np.isinf(given)) or np.any(given[:, 0] >= given[:, 1]):
+                raise ValueError("a bound is finite or NaN (none), and lo lies below hi")
+            b = np.ascontiguousarray(given)
+        self._kde_shape = None
+        self._check(self.lib.gwi_set_kde_columns(self.handle, n_cols, N.as_dp(pe) if pe is not None else None, N.as_dp(inj) if inj is not None else None, N.as_dp(b)))
+        self._kde_shape = (n_cols, pe is not None, inj is not None)
+
+    def _kde_request(self, what, rule, scale):
+        from .draws import kde_rule_code
+
+        code, scale = kde_rule_code(rule), float(scale)
+        if not (scale > 0.0 and np.isfinite(scale)):
+            raise ValueError("scale must be a positive finite number")
+        shape = getattr(self, "_kde_shape", None)
+        if shape is None:
+            none, flag = np.zeros(1), np.zeros(1, dtype=np.int32)
+            self._nothing_set(what, "columns are set (set_kde_columns)", self.lib.gwi_weighted_kde, N.as_dp(none), 1, code, scale, None, None, N.as_dp(none),
+                              N.as_dp(np.zeros(self.n_ev + 1)), flag.ctypes.data_as(C.POINTER(C.c_int32)))
+        return code, scale, shape
+
+    def weighted_kde(self, grid, rule="scott", scale=1.0):
+        """Weighted Gaussian kernel density estimates of every segment and column under the marginal weights, on the device
+        (``gwi_weighted_kde``; semantics: :func:`gwinferno_amd.draws.weighted_kde_reference`).  ``grid`` is ``(n_cols, G)``
+        or ``(G,)`` (the same points for every column), ``1 <= G <= 1024``, finite, in any order; ``rule`` is ``"scott"`` or
+        ``"silverman"`` and ``scale`` multiplies the factor.  Returns ``(rho_pe (n_ev, n_cols, G), rho_inj (n_cols, G), bw (n_ev + 1,
+        n_cols), neff (n_ev + 1,), degenerate (n_ev + 1, n_cols) int32)``: the densities (``None`` for a set without columns; NaN for
+        a segment without a curve), the bandwidth ``h`` and ``n_eff`` per segment (the injection set last) and the flags."""
+        self._whole_catalog("weighted_kde", "the injection densities need")
+        grid = np.asarray(grid, dtype=np.float64)
+        if grid.ndim not in (1, 2) or grid.shape[-1] < 1 or grid.shape[-1] > 1024:
+            raise ValueError(f"grid has shape {grid.shape}; expected (G,) or (n_cols, G) with 1 <= G <= 1024")
+        if not np.all(np.isfinite(grid)):
+            raise ValueError("grid points must be finite")
+        code, scale, (n_cols, with_pe, with_inj) = self._kde_request("weighted_kde", rule, scale)
+        if grid.ndim == 2 and grid.shape[0] != n_cols:
+            raise ValueError(f"grid has shape {grid.shape}; {n_cols} columns are set")
+        grid = np.ascontiguousarray(np.broadcast_to(grid, (n_cols, grid.shape[-1])))
+        g = grid.shape[1]
+        rho_pe = np.full((self.n_ev, n_cols, g), np.nan) if with_pe else None
+        rho_inj = np.full((n_cols, g), np.nan) if with_inj else None
+        bw, neff, flags = np.full((self.n_ev + 1, n_cols), np.nan), np.zeros(self.n_ev + 1), np.zeros((self.n_ev + 1, n_cols), dtype=np.int32)
+        self._check(self.lib.gwi_weighted_kde(self.handle, N.as_dp(grid), g, code, scale, N.as_dp(rho_pe) if with_pe else None, N.as_dp(rho_inj) if with_inj else None,
+                                              N.as_dp(bw), N.as_dp(neff), flags.ctypes.data_as(C.POINTER(C.c_int32))))
+        return rho_pe, rho_inj, bw, neff, flags
+
+    def weighted_kde2d(self, pairs, gridx, gridy, rule="scott", scale=1.0):
+        """Two-dimensional weighted Gaussian kernel density estimates of every segment and pair of columns, on the device
+        (``gwi_weighted_kde2d``; semantics: :func:`gwinferno_amd.draws.weighted_kde2d_reference`).  ``pairs`` is ``(n_pairs, 2)``
+        column indices, ``1 <= n_pairs <= 4``; ``gridx (n_pairs, n_gx)`` or ``(n_gx,)`` and ``gridy`` likewise, at most 128 points
+        each: the map is evaluated on the tensor grid.  No reflection.  Returns ``(rho_pe (n_ev, n_pairs, n_gx, n_gy), rho_inj (n_pairs,
+        n_gx, n_gy), cov (n_ev + 1, n_pairs, 3) = (Hxx, Hxy, Hyy), neff (n_ev + 1,), degenerate (n_ev + 1, n_pairs) int32)``."""
+        self._whole_catalog("weighted_kde2d", "the injection densities need")
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        if not 1 <= pairs.shape[0] <= 4:
+            raise ValueError(f"{pairs.shape[0]} pairs: between 1 and 4 can be asked for in one query")
+        gridx, gridy = np.asarray(gridx, dtype=np.float64), np.asarray(gridy, dtype=np.float64)
+        for name, g in (("gridx", gridx), ("gridy", gridy)):
+            if g.ndim not in (1, 2) or g.shape[-1] < 1 or g.shape[-1] > 128 or (g.ndim == 2 and g.shape[0] != pairs.shape[0]):
+                raise ValueError(f"{name} has shape {g.shape}; expected (n,) or (n_pairs, n) with 1 <= n <= 128")
+            if not np.all(np.isfinite(g)):
+                raise ValueError("grid points must be finite")
+        code, scale, (n_cols, with_pe, with_inj) = self._kde_request("weighted_kde2d", rule, scale)
+        n_pairs = pairs.shape[0]
+        gridx = np.ascontiguousarray(np.broadcast_to(gridx, (n_pairs, gridx.shape[-1])))
+        gridy = np.ascontiguousarray(np.broadcast_to(gridy, (n_pairs, gridy.shape[-1])))
+        n_gx, n_gy = gridx.shape[1], gridy.shape[1]
+        rho_pe = np.full((self.n_ev, n_pairs, n_gx, n_gy), np.nan) if with_pe else None
+        rho_inj = np.full((n_pairs, n_gx, n_gy), np.nan) if with_inj else None
+        cov, neff, flags = np.full((self.n_ev + 1, n_pairs, 3), np.nan), np.zeros(self.n_ev + 1), np.zeros((self.n_ev + 1, n_pairs), dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        self._check(self.lib.gwi_weighted_kde2d(self.handle, pairs.ctypes.data_as(i32), n_pairs, N.as_dp(gridx), n_gx, N.as_dp(gridy), n_gy, code, scale,
+                                                N.as_dp(rho_pe) if with_pe else None, N.as_dp(rho_inj) if with_inj else None, N.as_dp(cov), N.as_dp(neff),
+                                                flags.ctypes.data_as(i32)))
+        return rho_pe, rho_inj, cov, neff, flags
+
