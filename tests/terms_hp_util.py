@@ -1,6 +1,7 @@
-"""Shared by tests/test_terms_hp_cpu.py (C oracle) and tests/test_gpu_terms_hp.py (engine): the high-precision term fixture
-(tests/golden/terms_hp.npz, written by tests/golden/make_terms_hp.py), the drop-in model call of every term in it, the
-catalogs that make a summed gradient transparent, and the assertions -- the same ones, with the same bars, for both.
+"""Shared by tests/test_terms_hp_cpu.py (C oracle), tests/test_gpu_terms_hp.py and tests/test_gpu_spline_terms_hp.py (engine): the
+high-precision term fixtures (tests/golden/terms_hp.npz, written by tests/golden/make_terms_hp.py; tests/golden/spline_terms_hp_*.npz,
+written by tests/golden/make_spline_terms_hp.py), the drop-in model call of every term in them, the catalogs that make a summed
+gradient transparent, and the assertions -- the same ones, with the same bars, for both.
 
 An EVALUATOR is anything with ``log_weights(theta) -> (n_ev, n_pe) array`` and ``evaluate(theta, total_inj) -> (log_l, grad)``
 on a catalog it was built for; ``make(d_pe, d_inj)`` builds one from a pair of lazy densities and must expose ``.bound``.
@@ -12,6 +13,7 @@ Catalogs (the engine returns only the summed gradient):
   B       events of 3 samples, 5 injections, total_inj = 5; samples that are excluded at some hyper-points ride along with core
           ones.  Reference: the weight-averaged form, assembled from the fixture in np.longdouble.
 """
+import glob
 import os
 
 import numpy as np
@@ -30,11 +32,59 @@ LOGL_CANCELLED = {
     "beta": {"a1/b1"},
 }
 
+# The spline fixture: name -> (basis, number of coefficients, xrange, float32 samples).  tests/test_terms_hp_cpu.py holds this table to
+# the generator's own.
+SPLINE_TERMS = {
+    "logy4": ("LogYBSpline", 4, (0.0, 1.0), False), "logy7": ("LogYBSpline", 7, (-1.0, 1.0), False), "logy16": ("LogYBSpline", 16, (0.0, 1.0), False),
+    "logy17": ("LogYBSpline", 17, (0.0, 1.0), False), "logy20": ("LogYBSpline", 20, (0.0, 1.0), False), "logy7_f32": ("LogYBSpline", 7, (0.0, 1.0), True),
+    "logxlogy4": ("LogXLogYBSpline", 4, (0.1, 1.0), False), "logxlogy17": ("LogXLogYBSpline", 17, (2.0, 100.0), False),
+    "logxlogy20": ("LogXLogYBSpline", 20, (3.0, 100.0), False),
+    "bspline4": ("BSpline", 4, (0.0, 1.0), False), "bspline7": ("BSpline", 7, (-1.0, 1.0), False), "bspline17": ("BSpline", 17, (0.0, 1.0), False),
+    "bspline7_f32": ("BSpline", 7, (0.0, 1.0), True),
+    "logx4": ("LogXBSpline", 4, (0.01, 1.0), False), "logx7": ("LogXBSpline", 7, (0.001, 2.3), False), "logx17": ("LogXBSpline", 17, (0.01, 1.0), False),
+}
+SPLINE_FIXTURE_TERMS = list(SPLINE_TERMS) + ["powerlaw_redshift"]
+# A flat density again: all coefficients zero under the exponential, all coefficients one for a linear spline (the bases sum to one
+# inside the domain).  Every log-density is then the same number -log Z (0 on a domain of length 1), the fixture's log_l is 0 or the
+# rounding of sums that cancel, and the bar is relative to those sums as above.  On a domain of length 1 the sums themselves are 0
+# (every log-density is 0, one sample per event): there the floor is LOGL_RTOL x 1, which is what the VALUE bar already allows a sum of
+# up to 50 log-weights, each within VALUE_ATOL = 1e-11 (the older cancelled tags have sums of 16 to 42 and are not touched by it).
+for _name, (_basis, _, _, _) in SPLINE_TERMS.items():
+    LOGL_CANCELLED[_name] = {"zeros"} if "LogY" in _basis else {"ones"}
+# ``dip`` (all ones but one coefficient at -2) with 17 coefficients, ON CATALOG A ONLY: the samples that are live at EVERY hyper-point,
+# which is all that catalog A is made of, lie outside the four intervals the negative coefficient touches -- among them the spline is
+# flat again.  Catalog B also carries samples inside the dip and is held to the plain relative bar.
+LOGL_CANCELLED_A = {"bspline17": {"dip"}, "logx17": {"dip"}}
+
 MMIN, MMAX = 5.0, 100.0
 
 
 def load():
     return np.load(os.path.join(GOLDEN_DIR, "terms_hp.npz"))
+
+
+def spline_files():
+    return sorted(glob.glob(os.path.join(GOLDEN_DIR, "spline_terms_hp_*.npz")))
+
+
+def load_spline():
+    """The arrays of every tests/golden/spline_terms_hp_*.npz in one dict (one file per term; their keys carry the term's name)."""
+    out = {}
+    for path in spline_files():
+        with np.load(path) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
+_Z_TABLE = []
+
+
+def _z_table():
+    """(z grid, dVc/dz, maximum) of tests/golden/terms.npz: loaded once, the distribution keys its tables on the arrays' identity."""
+    if not _Z_TABLE:
+        with np.load(os.path.join(GOLDEN_DIR, "terms.npz")) as z:
+            _Z_TABLE.extend([z["dist/z_grid"], z["dist/z_dVcdz"], float(z["dist/powerlaw_redshift/maximum"])])
+    return _Z_TABLE
 
 
 class Term:
@@ -54,28 +104,49 @@ class Term:
 
 
 class Product(Term):
-    """Two fixture terms on disjoint columns and parameters as one model: sample i is (a's sample i, b's sample i), hyper-point
-    h is (a's point h, b's point h mod len(b))."""
+    """Fixture terms on disjoint columns and parameters as one model: sample i is every part's sample i, hyper-point h is every part's
+    point h mod its number of points, h running over the longest list."""
 
-    def __init__(self, a, b):
-        n = min(a.n, b.n)
-        hb = np.arange(len(a.theta)) % len(b.theta)
-        self.name = f"{a.name}*{b.name}"
-        self.parts = (a, b)
-        self.params = [f"{a.name}.{p}" for p in a.params] + [f"{b.name}.{p}" for p in b.params]
-        self.cols = [c[:n] for c in a.cols] + [c[:n] for c in b.cols]
-        self.tags = [f"{ta}|{b.tags[j]}" for ta, j in zip(a.tags, hb)]
-        self.theta = np.concatenate([a.theta, b.theta[hb]], axis=1)
-        self.logp = a.logp[:, :n] + b.logp[hb][:, :n]
-        self.dlogp = np.concatenate([a.dlogp[:, :, :n], b.dlogp[hb][:, :, :n]], axis=1)
+    def __init__(self, *parts):
+        n = min(t.n for t in parts)
+        hs = [np.arange(max(len(t.theta) for t in parts)) % len(t.theta) for t in parts]
+        self.name = "*".join(t.name for t in parts)
+        self.parts = parts
+        self.part_points = hs
+        self.params = [f"{t.name}.{p}" for t in parts for p in t.params]
+        self.cols = [c[:n] for t in parts for c in t.cols]
+        self.tags = ["|".join(t.tags[h[k]] for t, h in zip(parts, hs)) for k in range(len(hs[0]))]
+        self.theta = np.concatenate([t.theta[h] for t, h in zip(parts, hs)], axis=1)
+        self.logp = sum(t.logp[h][:, :n] for t, h in zip(parts, hs))
+        self.dlogp = np.concatenate([t.dlogp[h][:, :, :n] for t, h in zip(parts, hs)], axis=1)
         dead = np.isneginf(self.logp)
         self.dlogp = np.where(dead[:, None, :], 0.0, self.dlogp)
 
 
-def density(name, cols, p):
-    """The drop-in model call of fixture term ``name`` on the data arrays ``cols`` (PE- or injection-shaped) at parameters ``p``."""
+def model_of(name, pe, inj):
+    """The model OBJECT of a term whose drop-in call is a method of one (the spline models are constructed on both data arrays and
+    called with ``pe_samples=``); None for the terms that are plain functions."""
+    if name not in SPLINE_TERMS:
+        return None
+    from gwinferno_amd import interpolation as I
     from gwinferno_amd import models as M
 
+    basis, n, xrange, _ = SPLINE_TERMS[name]
+    return M.Base1DBSplineModel(n, pe[0], inj[0], xrange=xrange, basis=getattr(I, basis), normalize=True)
+
+
+def density(name, cols, p, model=None, pe_samples=True):
+    """The drop-in model call of fixture term ``name`` on the data arrays ``cols`` (PE- or injection-shaped) at parameters ``p``;
+    ``model``: what ``model_of`` made on the catalog's two sides, ``pe_samples`` which of them ``cols`` is."""
+    from gwinferno_amd import models as M
+
+    if model is not None:
+        return model(np.asarray(p, dtype=np.float64), pe_samples=pe_samples)
+    if name == "powerlaw_redshift":
+        from gwinferno_amd import numpyro_distributions as D
+
+        zg, dv, maximum = _z_table()
+        return D.PowerlawRedshift(p[0], maximum, zg, dv).log_prob(cols[0])
     if name == "powerlaw":
         return M.powerlaw_pdf(cols[0], p[0], MMIN, MMAX)
     if name == "plpeak":
@@ -109,9 +180,13 @@ class Catalog:
             with np.errstate(all="ignore"):
                 self.pe.append(MMIN / self.pe[1])
                 self.inj.append(MMIN / self.inj[1])
+        parts = term.parts if isinstance(term, Product) else (term,)
+        at = np.cumsum([0] + [len(t.cols) for t in parts])
+        self.models = [model_of(t.name, self.pe[a:b], self.inj[a:b]) for t, a, b in zip(parts, at[:-1], at[1:])]
         p0 = term.theta[0]
         self.ev = make(self._density(self.pe, p0), self._density(self.inj, p0))
-        # theta slot of every named parameter: bind the model once more, lazily, with marker values
+        # theta slot of every named parameter: bind the model once more, lazily, with marker values (distinct and positive: the
+        # coefficients of a spline are one vector parameter, and a linear spline is defined for a positive one)
         marks = np.arange(1.0, len(term.params) + 1.0)
         layout = self.ev.bound.theta_of(self._density(self.pe, marks))
         self.slot = [int(np.flatnonzero(layout == m)[0]) for m in marks]
@@ -119,11 +194,17 @@ class Catalog:
 
     def _density(self, cols, p):
         t = self.term
+        pe = cols is self.pe
         if isinstance(t, Product):
-            a, b = t.parts
-            na, ka = len(a.cols), len(a.params)
-            return density(a.name, cols[:na], p[:ka]) * density(b.name, cols[na:], p[ka:])
-        return density(t.name, cols, p)
+            from gwinferno_amd.lazy import Density
+
+            out, c0, p0 = None, 0, 0
+            for part, model in zip(t.parts, self.models):
+                d = density(part.name, cols[c0:c0 + len(part.cols)], p[p0:p0 + len(part.params)], model, pe)
+                out = d if out is None else Density.__mul__(out, d)
+                c0, p0 = c0 + len(part.cols), p0 + len(part.params)
+            return out
+        return density(t.name, cols, p, self.models[0], pe)
 
     def theta(self, h):
         th = np.zeros(len(self.slot))
@@ -191,6 +272,41 @@ def reference(cat, h):
     return float(sum(parts)), grad.astype(np.float64), float(max(abs(p) for p in parts))
 
 
+def reference_marginalised(cat, h):
+    """``reference`` with the selection function's Monte-Carlo uncertainty marginalised (the reference's analysis.py:270-271): log mu
+    becomes log mu - (3 + n_obs) / (2 n_eff) with the reference's n_eff of the injections (analysis.py:128-134), 1 / n_eff = sum w^2 /
+    (sum w)^2 - 1 / total_inj, so log_l gains n_obs (3 + n_obs) / 2 times that and the gradient n_obs (3 + n_obs) / 2 times
+    2 sum w^2 g / (sum w)^2 - 2 sum w^2 sum w g / (sum w)^3."""
+    L = np.longdouble
+    t = cat.term
+    log_l, grad, scale = reference(cat, h)
+    lp = t.logp[h][cat.inj_idx].astype(L)
+    g = t.dlogp[h][:, cat.inj_idx].astype(L)
+    w = np.exp(lp - np.max(lp))
+    s1, s2 = np.sum(w), np.sum(w * w)
+    n_ev = cat.pe_idx.shape[0]
+    k = L(n_ev * (3 + n_ev)) / 2
+    extra = k * (s2 / s1**2 - 1 / L(len(cat.inj_idx)))
+    d_extra = k * (2 * np.sum(w * w * g, axis=-1) / s1**2 - 2 * s2 * np.sum(w * g, axis=-1) / s1**3)
+    return float(L(log_l) + extra), (grad.astype(L) + d_extra).astype(np.float64), max(scale, float(abs(extra)))
+
+
+def is_cancelled(term, h, cat=None):
+    """Whether hyper-point ``h`` is one of LOGL_CANCELLED (or, on a catalog of one sample per event and one injection -- catalog A -- of
+    LOGL_CANCELLED_A); a product's is where every part's is (a flat density times a flat one)."""
+    if isinstance(term, Product):
+        return all(is_cancelled(t, int(hs[h]), cat) for t, hs in zip(term.parts, term.part_points))
+    only_a = cat is not None and cat.pe_idx.shape[1] == 1 and len(cat.inj_idx) == 1
+    return term.tags[h] in LOGL_CANCELLED.get(term.name, ()) or (only_a and term.tags[h] in LOGL_CANCELLED_A.get(term.name, ()))
+
+
+def marginalised_points(term):
+    """Every hyper-point but the flat ones: with equal weights on all ``total_inj`` injections the reference's Monte-Carlo variance
+    (analysis.py:128) is exactly 0, its n_eff infinite and the derivative of its own expression 0 / 0."""
+    flat = LOGL_CANCELLED.get(term.name, ())
+    return [h for h, tag in enumerate(term.tags) if tag not in flat]
+
+
 class Worst:
     """Largest error seen per (term, path, what), for assertion messages and profiles/near_singular/RESULTS.md."""
 
@@ -226,15 +342,19 @@ def grad_errors(t, got_grad, ref_grad):
     return np.abs(got_grad - ref_grad) / np.maximum(1.0, np.abs(ref_grad))
 
 
-def check_gradients(cat, path, worst, failures, points=None, results=None):
+def check_gradients(cat, path, worst, failures, points=None, results=None, marginalised=False):
+    """``marginalised``: against ``reference_marginalised``, the evaluator called with ``marginalize_selection=True``."""
     t = cat.term
     total = float(len(cat.inj_idx))
     for h in (range(len(t.theta)) if points is None else points):
-        log_l, grad = results[h] if results is not None else cat.ev.evaluate(cat.theta(h), total)
+        if results is not None:
+            log_l, grad = results[h]
+        else:
+            log_l, grad = cat.ev.evaluate(cat.theta(h), total, marginalize_selection=True) if marginalised else cat.ev.evaluate(cat.theta(h), total)
         grad = np.asarray(grad)[cat.slot]
-        ref_l, ref_g, scale_l = reference(cat, h)
-        cancelled = t.tags[h] in LOGL_CANCELLED.get(t.name, ())
-        e_l = 0.0 if log_l == ref_l else abs(log_l - ref_l) / (max(scale_l, abs(ref_l)) if cancelled else (abs(ref_l) or 1e-300))
+        ref_l, ref_g, scale_l = (reference_marginalised if marginalised else reference)(cat, h)
+        cancelled = is_cancelled(t, h, cat)
+        e_l = 0.0 if log_l == ref_l else abs(log_l - ref_l) / (max(scale_l, abs(ref_l), 1.0 if t.name in SPLINE_TERMS else 0.0) if cancelled else (abs(ref_l) or 1e-300))
         worst.note((t.name, path, "log_l (relative)"), e_l, t.tags[h])
         if not e_l < LOGL_RTOL:
             failures.append(f"{t.name} [{path}] {t.tags[h]}: log_l {log_l!r} vs {ref_l!r}: relative {e_l:.3e} >= {LOGL_RTOL:g}{' (of the cancelled sums)' if cancelled else ''}")

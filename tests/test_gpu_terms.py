@@ -121,7 +121,8 @@ def test_redshift_model(terms):
 def test_spline_projection_against_design_matrix():
     """Spline density at the golden sample points == the reference's dense projection (interpolation.py:306-317)
     for all four bases -- exp-splines (LogY / LogXLogY) and linear ones (BSpline / LogXBSpline, where a
-    non-positive spline value counts as zero density) -- incl. domain ends and nextafter points."""
+    non-positive spline value counts as zero density) -- incl. domain ends and nextafter points.  Values only: every
+    coefficient's gradient component is held to an 80-digit fixture in tests/test_gpu_spline_terms_hp.py."""
     from gwinferno_amd import models as M
     from gwinferno_amd.interpolation import BSpline, LogXBSpline, LogXLogYBSpline, LogYBSpline
 
