@@ -239,6 +239,8 @@ EXPORTED_SYMBOLS = [
     "gwi_histogram_times",
     "gwi_point_cdfs",
     "gwi_point_cdf_times",
+    "gwi_point_pits",
+    "gwi_point_pit_times",
     "gwi_marginal_weights_reset",
     "gwi_marginal_weights_add",
     "gwi_marginal_weights_add_weighted",
@@ -419,6 +421,12 @@ def load_library():
         lib.gwi_point_cdfs.argtypes = [vp, _DP, C.c_int32, _DP, _I32P]
         lib.gwi_point_cdf_times.restype = None
         lib.gwi_point_cdf_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_point_pits"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_point_pits.restype = C.c_int32
+        lib.gwi_point_pits.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _I32P]
+        lib.gwi_point_pit_times.restype = None
+        lib.gwi_point_pit_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

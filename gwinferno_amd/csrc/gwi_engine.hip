@@ -11,6 +11,7 @@
 #include "gwi_resample.h"
 #include "gwi_hist.h"
 #include "gwi_cdf.h"
+#include "gwi_pit.h"
 #include "gwi_quant.h"
 #include "gwi_kde.h"
 #include "gwi_jit.h"
@@ -481,6 +482,10 @@ struct PostprocessBuffers {
     // [64][4][n_cols][n_bins] and live counts [64][2] (allocated on that entry's first call after the bins were set, released with them)
     DeviceBuffer<double> d_cdf, d_cdf_stage;
     DeviceBuffer<int> d_cdf_dead, d_cdf_live;
+    // ... and of gwi_point_pits (gwi_pit.h), which shares d_cdf and d_cdf_dead: the staged brackets [64][n_ev][n_cols][2], detected CDFs
+    // [64][n_cols][n_bins] and flags [64][n_ev + 1] (allocated on that entry's first call after the bins were set, released with them)
+    DeviceBuffer<double> d_pit_stage, d_pit_det;
+    DeviceBuffer<int> d_pit_dead;
     int cols = 0, bins = 0;
   } hist;
   // marginal weights and their quantiles (gwi_quant.h).  The state of the handle: one running double per sample [n_ev n_pe | n_inj],
@@ -4154,6 +4159,71 @@ gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double*
 }
 
 void gwi_point_cdf_times(double* logw_ms, double* tile_ms, double* reduce_ms, int32_t* launches) { g_point_cdf_times.report(logw_ms, tile_ms, reduce_ms, launches); }
+
+// ---- per-event calibration: per-point PIT brackets (gwi_pit.h) ---------------------------------------------------------------
+enum { kPitLogw, kPitTile, kPitWalk };
+static thread_local StageTimes g_point_pit_times;
+
+gwi_status gwi_point_pits(gwi_handle h, const double* thetas, int32_t k, double* pit, double* cdf_det, int32_t* dead) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_pits";
+  g_point_pit_times = StageTimes();
+  PostprocessBuffers::Histogram& hist = h->post.hist;
+  const bool with_pe = hist.d_bins_pe.ptr != nullptr, with_inj = hist.d_bins_inj.ptr != nullptr;
+  gwi_status st = post_preflight(h, who, "sum on", "the injection CDF needs", [&]() -> std::string {
+    if (!h->variant) return "the engine has no scan kernel";
+    if (!hist.cols) return "no bins are set (gwi_set_histogram_bins)";
+    if (!with_pe) return "no PE bins are set: an event's PIT needs the bins of both sets (gwi_set_histogram_bins)";
+    if (!with_inj) return "no injection bins are set: an event's PIT needs the bins of both sets (gwi_set_histogram_bins)";
+    if (!thetas || k < 1) return "thetas is null or k < 1";
+    if (!pit) return "pit is null";
+    if (!dead) return "dead is null";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  namespace H = gwi::hist;
+  namespace F = gwi::cdf;
+  namespace P = gwi::pit;
+  P::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.f.h.d, &n_tiles);  // (as gwi_set_histogram_bins found it)
+  if (st != GWI_OK) return st;
+  const size_t n_segs = (size_t)(h->n_ev + 1), per_seg = (size_t)hist.cols * (size_t)hist.bins, per_point = (size_t)h->n_ev * (size_t)hist.cols * 2;
+  GWI_HIP(hist.d_cdf.reserve(n_segs * per_seg));
+  GWI_HIP(hist.d_cdf_dead.reserve(n_segs));
+  GWI_HIP(hist.d_pit_stage.reserve((size_t)P::kStagePoints * per_point));
+  GWI_HIP(hist.d_pit_det.reserve((size_t)P::kStagePoints * per_seg));
+  GWI_HIP(hist.d_pit_dead.reserve((size_t)P::kStagePoints * n_segs));
+  const QueryCover cover = fill_hist_args(h, &a.f.h);  // (both sets have bins: every tile and every segment)
+  a.f.cdf = hist.d_cdf;
+  a.f.seg_dead = hist.d_cdf_dead;
+  a.f.with_pe = a.f.with_inj = 1;
+  const auto tile = [&](int) {
+    if (cover.tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)cover.tiles), dim3(H::kBlock), 0, h->stream, a.f.h);
+  };
+  const auto walk = [&](int p) {  // into the point's slot of the stage
+    const size_t slot = (size_t)(p % P::kStagePoints);
+    a.pit = hist.d_pit_stage + slot * per_point;
+    a.cdf_det = hist.d_pit_det + slot * per_seg;
+    a.dead = hist.d_pit_dead + slot * n_segs;
+    hipLaunchKernelGGL(F::cdf_segment_kernel, dim3((unsigned)cover.segs, (unsigned)a.f.h.n_cols), dim3(F::kBlock), 0, h->stream, a.f);
+    hipLaunchKernelGGL(P::pit_kernel, dim3((unsigned)cover.segs, (unsigned)a.f.h.n_cols), dim3(P::kBlock), 0, h->stream, a);
+  };
+  const auto copy_back = [&](int p) -> gwi_status {
+    const int slot = p % P::kStagePoints;
+    if (slot + 1 == P::kStagePoints || p + 1 == k) {  // the staged rows go back: 2 n_ev n_cols (+ n_cols n_bins) doubles and n_ev + 1 ints per point
+      const size_t first = (size_t)(p - slot), n = (size_t)(slot + 1);
+      if (per_point) GWI_HIP(hipMemcpy(pit + first * per_point, hist.d_pit_stage, sizeof(double) * n * per_point, hipMemcpyDeviceToHost));
+      if (cdf_det) GWI_HIP(hipMemcpy(cdf_det + first * per_seg, hist.d_pit_det, sizeof(double) * n * per_seg, hipMemcpyDeviceToHost));
+      GWI_HIP(hipMemcpy(dead + first * n_segs, hist.d_pit_dead, sizeof(int) * n * n_segs, hipMemcpyDeviceToHost));
+    }
+    return GWI_OK;
+  };
+  return per_point_pass(h, who, thetas, k, &a.f.h.d, n_tiles, &g_point_pit_times, 2, 5, tile, walk, copy_back);
+}
+
+void gwi_point_pit_times(double* logw_ms, double* tile_ms, double* pit_ms, int32_t* launches) { g_point_pit_times.report(logw_ms, tile_ms, pit_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

@@ -27,7 +27,11 @@ estimate with scipy's bandwidth rules: :func:`weighted_kde_reference` and :func:
 
 ``gwi_point_cdfs`` (gwinferno_amd/csrc/gwi_cdf.h) returns, per point, the running sums of the same normalised bins over cumulative
 codes -- exact CDFs at the grid points -- for the injection set and, reduced over the events, for the catalog: :func:`cdf_codes`
-states the codes, :func:`point_cdfs_reference` one point, and :func:`weighted_percentiles` the bands over the points."""
+states the codes, :func:`point_cdfs_reference` one point, and :func:`weighted_percentiles` the bands over the points.
+
+``gwi_point_pits`` (gwinferno_amd/csrc/gwi_pit.h) multiplies, per point, every event's normalised bins into the injection set's CDF: a
+rigorous bracket of the event's probability integral transform under the predicted detected distribution.  :func:`pit_bracket` states
+the loop and :func:`point_pits_reference` one point."""
 import bisect
 import itertools
 import math
@@ -246,6 +250,55 @@ def point_cdfs_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins, inj_bins
             out[1] = sum_f / float(live[0])
         out[2], out[3] = below, above
     return out, live
+
+
+def pit_bracket(q, D):
+    """The loop of ``gwi_point_pits`` alone: ``q (G,)`` the normalised bins of one event and column over cumulative codes,
+    ``D (G,)`` the CDF of the predicted detected distribution at the same grid points -> ``(pit_lo, pit_hi)`` as Python floats.  With
+    ``o = max(0, 1 - cumsum(q)[G-1])``, the share above the grid: a sample with code ``j`` has its ``F_det`` in ``[D[j-1], D[j]]`` (``D[-1]
+    := 0``), one outside in ``[D[G-1], 1]``, so
+
+    ``pit_lo = q[1] D[0] + ... + q[G-1] D[G-2] + o D[G-1]`` and ``pit_hi = q[0] D[0] + ... + q[G-1] D[G-1] + o``
+
+    bracket the un-gridded PIT.  Either is summed from 0.0 strictly left to right, the outside term last, every product and every
+    sum a float64 operation of its own: the kernel's bits."""
+    q, D = np.asarray(q, dtype=np.float64).ravel(), np.asarray(D, dtype=np.float64).ravel()
+    if q.size < 1 or q.size != D.size:
+        raise ValueError("q and D hold the same number (>= 1) of grid points")
+    n = q.size
+    o = max(0.0, 1.0 - float(np.cumsum(q)[-1]))
+    ql, dl = q.tolist() + [o], D.tolist()
+    lo = hi = 0.0
+    for j in range(n):
+        lo = lo + ql[j + 1] * dl[j]
+        hi = hi + ql[j] * dl[j]
+    return lo, hi + o
+
+
+def point_pits_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins, inj_bins, n_bins):
+    """One hyper-parameter point of ``gwi_point_pits``: the arguments of :func:`point_cdfs_reference`, both sets of
+    cumulative codes given -> ``(pit (n_ev, n_cols, 2), cdf_det (n_cols, n_bins), dead (n_ev + 1,) int32)``.  With ``q`` of
+    :func:`weighted_histogram_segment` per event and ``D = np.cumsum`` of the injection set's: ``pit[e][c] =``
+    :func:`pit_bracket` ``(q[c], D[c])``; NaN for an event without weight, and everywhere (``cdf_det`` included) when the injection
+    set has none; ``dead`` flags the segments without weight, the injection set last."""
+    if pe_bins is None or inj_bins is None:
+        raise ValueError("an event's PIT needs the bins of both sets")
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    pe_bins, inj_bins = np.asarray(pe_bins), np.asarray(inj_bins)
+    n_ev, n_bins, n_cols = logw_pe.shape[0], int(n_bins), pe_bins.shape[0]
+    pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(logw_pe.shape)
+    pit, cdf_det, dead = np.full((n_ev, n_cols, 2), np.nan), np.full((n_cols, n_bins), np.nan), np.zeros(n_ev + 1, dtype=np.int32)
+    h, inj_alive = weighted_histogram_segment(logw_inj, inj_mask, inj_bins, n_bins)
+    if inj_alive:
+        cdf_det = np.cumsum(h, axis=-1)
+    dead[n_ev] = 0 if inj_alive else 1
+    for ev in range(n_ev):
+        q, alive = weighted_histogram_segment(logw_pe[ev], None if pe_mask is None else pe_mask[ev], pe_bins[:, ev], n_bins)
+        dead[ev] = 0 if alive else 1
+        if alive and inj_alive:
+            for c in range(n_cols):
+                pit[ev, c] = pit_bracket(q[c], cdf_det[c])
+    return pit, cdf_det, dead
 
 
 def weighted_percentiles(values, weights, levels):

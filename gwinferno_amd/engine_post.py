@@ -1,5 +1,5 @@
 """The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
-injection resampling, weighted histograms, per-point CDFs, marginal weights and their quantiles and kernel density estimates.
+injection resampling, weighted histograms, per-point CDFs and PIT brackets, marginal weights and their quantiles and kernel density estimates.
 Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
 """
 import ctypes as C
@@ -229,6 +229,28 @@ class PostprocessMixin:
         out, live = np.empty((k, 4, n_cols, n_bins)), np.empty((k, 2), dtype=np.int32)
         self._check(self.lib.gwi_point_cdfs(self.handle, N.as_dp(thetas), k, N.as_dp(out), live.ctypes.data_as(i32)))
         return out, live
+
+    def point_pits(self, thetas):
+        """Per-point brackets of every event's probability integral transform under the predicted detected distribution, on the device
+        (``gwi_point_pits``; semantics: :func:`gwinferno_amd.draws.point_pits_reference`).  The bins of
+        :meth:`set_histogram_bins` are cumulative codes (:func:`gwinferno_amd.draws.cdf_codes`) of BOTH sets against one grid per
+        column.  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.  Returns ``(pit (k, n_ev, n_cols, 2), cdf_det (k, n_cols,
+        n_bins), dead (k, n_ev + 1) int32)``: per point, event and column the lower and upper end of the bracket (NaN where the event
+        or the injection set has no weight), the CDF of the predicted detected distribution (the bits of :meth:`point_cdfs` slot 0)
+        and 1 for every segment without weight at the point, the injection set last.  ``2 n_ev n_cols + n_cols n_bins`` doubles come
+        back per point; the points may be split over calls without changing a bit.  Not available on an engine that holds a shard
+        (``world > 1``)."""
+        self._whole_catalog("point_pits", "the injection CDF needs")
+        thetas = self._points(thetas)
+        k = thetas.shape[0]
+        shape = getattr(self, "_hist_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        if shape is None:
+            self._nothing_set("point_pits", "bins are set (set_histogram_bins)", self.lib.gwi_point_pits, N.as_dp(thetas), k, None, None, None)
+        n_cols, n_bins = shape[:2]
+        pit, cdf_det, dead = np.empty((k, self.n_ev, n_cols, 2)), np.empty((k, n_cols, n_bins)), np.empty((k, self.n_ev + 1), dtype=np.int32)
+        self._check(self.lib.gwi_point_pits(self.handle, N.as_dp(thetas), k, N.as_dp(pit), N.as_dp(cdf_det), dead.ctypes.data_as(i32)))
+        return pit, cdf_det, dead
 
     def marginal_weights_reset(self):
         """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""

@@ -789,3 +789,104 @@ def catalog_predictive_check(eng, thetas, pe_values, grid, inj_values=None, leve
             "cdf_max_observed": mean(np.exp(below), has_obs), "cdf_max_predicted": mean(np.exp(below_pred), has_det),
             "cdf_min_observed": mean(-np.expm1(above), has_obs), "cdf_min_predicted": mean(-np.expm1(above_pred), has_det),
             "n_live": live[:, 0].astype(np.int64), "dead_detected": int(np.count_nonzero(~has_det)) if x_inj is not None else k, "n_points": k}
+
+
+def _ks_uniform(u):
+    """The Kolmogorov distance of the sample ``u`` (no NaN) from the uniform distribution on [0, 1]: ``max_i max(i / n - u_(i), u_(i) -
+    (i - 1) / n)`` over the sorted sample; NaN for an empty one."""
+    u = np.sort(np.asarray(u, dtype=np.float64).ravel())
+    n = u.size
+    if n == 0:
+        return np.nan
+    i = np.arange(1, n + 1, dtype=np.float64)
+    return float(max(np.max(i / n - u), np.max(u - (i - 1.0) / n)))
+
+
+def event_calibration(eng, thetas, pe_values, grid, inj_values=None, point_weights=None, leave_one_out=False, total_inj=None, nobs=None, marginalize_selection=False,
+                      pedata=None, injdata=None, param_names=None, m1min=None, m2min=None, mmax=None, backend="device"):
+    """Per-event calibration over K posterior hyper-parameter draws: the probability integral transform (PIT) of every event
+    under the predicted detected distribution, ``PIT_kec = sum_i (w_ki / S_ke) F_det,k(x_i)``, averaged over the draws -- what a P-P plot
+    is made of: flat when the population model describes the catalog, bent where it does not -- and with ``leave_one_out=True`` its
+    leave-one-out form, LOO-PIT, in which event e is held against the population fitted without it.  The PIT is a product of the
+    event's weights and the injection set's CDF at the same point, so on the device (``eng.point_pits``) a rigorous bracket ``[pit_lo,
+    pit_hi]`` per (point, event, quantity) comes back, ``2 n_ev C + C G`` doubles per point, and the weights never leave HBM.  The
+    bracket's width is the grid's resolution alone (at most the largest step of ``F_det`` between neighbouring grid points, plus the
+    event's share above the grid); a finer grid narrows it.
+
+    ``thetas`` is ``(K, n_theta)`` in the engine's layout.  ``pe_values`` / ``inj_values`` (or ``pedata`` / ``injdata`` with
+    ``param_names``), ``grid``, the mass cuts and the masks are :func:`catalog_predictive_check`'s; the injections' values are needed.
+    The device backend replaces the engine's histogram bins with the grid's cumulative codes.  The weights on the k axis are applied
+    here, on the host: equal by default, ``point_weights (K,)`` or ``(K, n_ev + 1)`` (numbers in ``[0, 1]``; the last column is not
+    used), or with ``leave_one_out=True`` those of :func:`leave_one_out_weights` (``total_inj`` is needed; ``nobs`` and
+    ``marginalize_selection`` as there).  A (point, event) at which the event or the injection set has no weight is skipped and
+    counted in ``n_dead``.  ``backend="host"`` runs the NumPy statement (:func:`gwinferno_amd.draws.point_pits_reference`) on
+    ``eng.log_weights`` under the masks given here (none without the cuts): the statement the kernel is tested against, not a fall-back.
+
+    Returns a dict: ``names``; ``grid (C, G)``; ``pit_lo``, ``pit_hi``, ``pit`` (the midpoint) and ``width``, each ``(n_ev, C)``, the
+    weighted means over the points (NaN for an event without a live point of positive weight); ``neff_points (n_ev,)``, ``(sum_k v)^2
+    / sum_k v^2`` over the points that count; ``n_dead (n_ev,)``; the sorted P-P curves ``pp_levels (n,) = (1 ... n) / n``, ``pp_lo``,
+    ``pp_hi`` and ``pp (C, n)`` over the ``n`` events that have a PIT; ``ks_lo``, ``ks_hi`` and ``ks (C,)``, the Kolmogorov distance
+    from uniform of the lower, upper and midpoint PITs; the raw per-point arrays ``point_pits (K, n_ev, C, 2)``, ``cdf_detected (K, C,
+    G)`` and ``dead (K, n_ev + 1)``; ``n_points``; with ``leave_one_out=True`` also ``elpd_loo (n_ev,)``."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    source = pe_values if pe_values is not None else pedata
+    for p in param_names if param_names is not None and source is not None else ():
+        if p not in source:
+            raise ValueError(f"unknown quantity {p!r}")
+    names, x_pe, x_inj = _summary_columns(eng, pe_values, inj_values, pedata, injdata, param_names)
+    if x_inj is None:
+        raise ValueError("the PIT is taken under the predicted detected distribution: inj_values (or injdata) are needed")
+    n_cols, n_ev = len(names), eng.n_ev
+    if isinstance(grid, dict):
+        missing = [p for p in names if p not in grid]
+        if missing:
+            raise ValueError(f"grid names no points for {missing}")
+        if len({np.size(grid[p]) for p in names}) != 1:
+            raise ValueError("every quantity needs the same number of grid points")
+        grid = np.stack([np.asarray(grid[p], dtype=np.float64).ravel() for p in names])
+    else:
+        grid = np.asarray(grid, dtype=np.float64)
+    if grid.ndim not in (1, 2) or (grid.ndim == 2 and grid.shape[0] != n_cols) or not 1 <= grid.shape[-1] <= D.MAX_CDF_GRID:
+        raise ValueError(f"grid has shape {grid.shape}; expected (G,) or ({n_cols}, G) with 1 <= G <= {D.MAX_CDF_GRID}")
+    grid = np.ascontiguousarray(np.broadcast_to(grid, (n_cols, grid.shape[-1])))
+    n_grid = grid.shape[1]
+    pe_codes = np.stack([D.cdf_codes(x_pe[c], grid[c]) for c in range(n_cols)])
+    inj_codes = np.stack([D.cdf_codes(x_inj[c], grid[c]) for c in range(n_cols)])
+    masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    v, loo = _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection)
+    v = np.ones((k, n_ev)) if v is None else np.asarray(v, dtype=np.float64)[:, :n_ev]
+    if backend == "device":
+        if masks[0] is not None:
+            eng.set_draw_mask(*masks)
+        eng.set_histogram_bins(pe_codes, inj_codes, n_bins=n_grid)
+        raw, det, dead = eng.point_pits(thetas)
+    else:
+        raw, det, dead = np.empty((k, n_ev, n_cols, 2)), np.empty((k, n_cols, n_grid)), np.empty((k, n_ev + 1), dtype=np.int32)
+        for i, th in enumerate(thetas):
+            lw_pe, lw_inj = eng.log_weights(th)
+            raw[i], det[i], dead[i] = D.point_pits_reference(lw_pe, lw_inj, masks[0], masks[1], pe_codes, inj_codes, n_grid)
+    gone = (dead[:, :n_ev] != 0) | (dead[:, n_ev:] != 0)  # (K, n_ev): the event or the injection set has no weight at the point
+    w = np.where(gone, 0.0, v)
+    wsum, wsq = w.sum(axis=0), (w * w).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = (w[:, :, None, None] * np.where(gone[:, :, None, None], 0.0, raw)).sum(axis=0) / wsum[:, None, None]  # (n_ev, C, 2); NaN without weight
+        neff = np.where(wsum > 0.0, wsum * wsum / wsq, 0.0)
+    lo, hi = mean[..., 0], mean[..., 1]
+    mid = 0.5 * (lo + hi)
+    has = wsum > 0.0
+    n_has = int(np.count_nonzero(has))
+    curves = [np.sort(a[has], axis=0).T.reshape(n_cols, n_has) for a in (lo, hi, mid)]
+    out = {"names": names, "grid": grid, "pit_lo": lo, "pit_hi": hi, "pit": mid, "width": hi - lo, "neff_points": neff, "n_dead": gone.sum(axis=0).astype(np.int64),
+           "pp_levels": np.arange(1, n_has + 1, dtype=np.float64) / max(n_has, 1), "pp_lo": curves[0], "pp_hi": curves[1], "pp": curves[2],
+           "ks_lo": np.array([_ks_uniform(c) for c in curves[0]]), "ks_hi": np.array([_ks_uniform(c) for c in curves[1]]),
+           "ks": np.array([_ks_uniform(c) for c in curves[2]]), "point_pits": raw, "cdf_detected": det, "dead": dead, "n_points": k}
+    if loo is not None:
+        out["elpd_loo"] = loo["elpd_loo"]
+    return out

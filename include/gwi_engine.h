@@ -499,6 +499,41 @@ void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int
 gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double* out /* [k][4][n_cols][n_bins] */, int32_t* live /* [k][2] */);
 void gwi_point_cdf_times(double* logw_ms, double* tile_ms, double* reduce_ms, int32_t* launches);
 
+/* Per-event calibration on the device: per hyper-parameter point and event a rigorous bracket of the probability integral transform
+ * (PIT) of the event under the predicted detected distribution, PIT_kec = sum_i (w_ki / S_ke) F_det,k(x_i) -- what a P-P plot and its
+ * leave-one-out form (LOO-PIT) are made of (gwinferno_amd/csrc/gwi_pit.h; the NumPy statement is gwinferno_amd/draws.py:
+ * point_pits_reference with the loop pit_bracket; the contract is DESIGN 8h).  The PIT is a product of two per-point objects, the
+ * event's weights and the injection set's CDF: no sum over points that another entry keeps can give it, and leave-one-out needs
+ * another weight on the k axis for every event, so the brackets go back per (point, event).
+ *
+ * The bins are those of gwi_set_histogram_bins for BOTH sets, made as the cumulative codes of gwi_point_cdfs against one grid
+ * g_0 < ... < g_{G-1} per column, 1 <= G = n_bins <= 256.  For one point, event e and column c: q[j] is the event's normalised bin (the
+ * bits of what gwi_weighted_histograms returns for that single point), F_e = the running sum of q (the bits of np.cumsum), D[j] the
+ * injection segment's CDF (the bits of gwi_point_cdfs slot 0) and o = max(0, 1 - F_e[G-1]) the event's share above the grid.  A sample
+ * with code j lies in (g_{j-1}, g_j], so its F_det lies in [D[j-1], D[j]] with D[-1] := 0; a sample outside has F_det in [D[G-1], 1]:
+ *   pit_lo = q[1] D[0] + q[2] D[1] + ... + q[G-1] D[G-2] + o D[G-1]
+ *   pit_hi = q[0] D[0] + q[1] D[1] + ... + q[G-1] D[G-1] + o
+ * bracket the un-gridded PIT; the error is the grid's alone (hi - lo <= max_j (D[j] - D[j-1]) when nothing lies outside).  Either is
+ * summed from 0.0 strictly left to right, the outside term last, every product and every sum rounded on its own (no fused
+ * multiply-add): the bits of a plain Python loop over the same q and D.
+ *
+ * pit[k][n_ev][n_cols][2] holds (lo, hi), NaN for an event or an injection segment without weight at the point; cdf_det[k][n_cols][n_bins]
+ * (optional) holds D, NaN for a dead injection segment; dead[k][n_ev + 1] holds 1 for every segment without weight at the point, the
+ * injection segment last.  Nothing is in/out.  k >= 1 is not bound by the batch limit: the points are staged on the device 64 at a time
+ * and copied back per chunk.  The masks of gwi_set_draw_mask apply.  No point weights go to the device: a weight on the k axis is
+ * applied by the host.  Every sum has a fixed shape and there are no atomics: the bits are a pure function of (theta_k, bins, masks),
+ * whatever the split of the points over calls, and the call changes no state another entry reads.
+ * Not done: sharded handles; the exact un-gridded PIT; the events' own per-point CDFs travelling back; more than 256 grid points.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null thetas, pit or dead, k < 1, a host-only handle, a call before the bins are
+ * set and a call while either set has no bins; GWI_ERR_UNSUPPORTED on a handle that holds a shard, as gwi_point_cdfs.
+ *
+ * gwi_point_pit_times(): DIAGNOSTIC ONLY, for tools/point_pits_time.py: of the calling thread's last call, summed over its points, the
+ * wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge / histogram tile launches
+ * together and of the CDF and PIT launches, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_point_pits(gwi_handle h, const double* thetas, int32_t k, double* pit /* [k][n_ev][n_cols][2]: lo, hi */,
+                          double* cdf_det /* [k][n_cols][n_bins] or NULL */, int32_t* dead /* [k][n_ev + 1] */);
+void gwi_point_pit_times(double* logw_ms, double* tile_ms, double* pit_ms, int32_t* launches);
+
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is
  * gwinferno_amd/draws.py: marginal_weights_reference, weighted_quantiles_reference).
