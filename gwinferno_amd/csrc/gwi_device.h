@@ -255,10 +255,8 @@ __device__ __forceinline__ double fast_rcp(double x) {
 }
 
 // ---- exp / expm1 for the scan loop ---------------------------------------------------------
-// exp(x) = 2^n (1 + r q(r)),  n = rint(x log2 e),  r = x - n ln2 (two-piece ln2),  |r| <= 0.3466,
-// q = Taylor series of (e^r - 1)/r to r^10 (truncation 0.3466^12/12! = 6e-15 relative at the ends of the range, 1e-16 in
-// its middle half: five orders below what the parity bars of this path can see; two Horner steps fewer).  Every Horner
-// step is ONE v_fma_f64 whose addend is a scalar-register constant: left to itself the compiler parks
+// exp(x) = 2^n (1 + r q(r)),  n = rint(x log2 e),  r = x - n ln2,  |r| <= 0.3466,  q a polynomial for (e^r - 1)/r (below).
+// Every Horner step is ONE v_fma_f64 whose addend is a scalar-register constant: left to itself the compiler parks
 // the constants in vector registers and spends a v_mov_b64 + v_fmac_f64 per step (two-address form).
 // The argument is clamped to [-1000, 710]: exp(-inf) = 0 and exp(>709.8) = +inf fall out of ldexp.
 // v_max/v_min return the non-NaN operand, so a NaN argument gives 0: NaN can only enter through a
@@ -279,44 +277,22 @@ __device__ __forceinline__ double fma_sc(double a, double b, double c_uniform) {
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c_uniform));
   return r;
 }
-// Round 6 (GWI_EXP_TAYLOR=0, the default): three vector instructions fewer per exponential, where the parity budget has room --
-//   * q = an eighth-degree MINIMAX polynomial for (e^r - 1)/r on |r| <= 0.3466 instead of the tenth-degree Taylor series: the
-//     relative error of e^r = 1 + r q(r) is <= 1.6e-14 over the whole interval (tools/exp_poly.py; the Taylor series: 6e-15 at its
-//     ends), eight FMAs instead of ten;
+// The two halves of the exponential, as few vector instructions as the parity budget allows:
+//   * q = an eighth-degree MINIMAX polynomial for (e^r - 1)/r on |r| <= 0.3466: the relative error of e^r = 1 + r q(r) is
+//     <= 1.6e-14 over the whole interval (tools/exp_poly.py), eight FMAs;
 //   * r = x - n ln2 in ONE fused multiply-add with ln2 rounded to double (off by 2.3e-17): r is then off by 2.3e-17 |n|, i.e. the
 //     result by 2e-14 relative at |x| = 700 and 1e-13 at the |l| of a few thousand that spline models under the reference's priors
-//     reach -- against a bar of 1e-10 on per-sample log-weights and 1e-9 on log_l (tests: every golden and oracle comparison at
-//     its old tolerance).  The shift of fast_exp_shift stays exact: it is applied to the exponent field.
-#ifndef GWI_EXP_TAYLOR
-#define GWI_EXP_TAYLOR 0
-#endif
+//     reach -- against a bar of 1e-10 on per-sample log-weights and 1e-9 on log_l.  The shift of fast_exp_shift stays exact: it
+//     is applied to the exponent field.
 struct ExpParts {
   double rq;  // e^r - 1
   int n;
 };
 __device__ __forceinline__ double exp_reduce(double x, double nf) {
-#if GWI_EXP_TAYLOR
-  const double r = fma(nf, -6.93147180369123816490e-01, x);
-  return fma(nf, -1.90821492927058770002e-10, r);
-#else
   return fma(nf, -6.93147180559945286227e-01, x);
-#endif
 }
 // (e^r - 1)/r, |r| <= 0.3466
 __device__ __forceinline__ double exp_q(double r) {
-#if GWI_EXP_TAYLOR
-  double q = 1.0 / 39916800.0;            // 1/11!
-  q = fma_sc(q, r, 1.0 / 3628800.0);
-  q = fma_sc(q, r, 1.0 / 362880.0);
-  q = fma_sc(q, r, 1.0 / 40320.0);
-  q = fma_sc(q, r, 1.0 / 5040.0);
-  q = fma_sc(q, r, 1.0 / 720.0);
-  q = fma_sc(q, r, 1.0 / 120.0);
-  q = fma_sc(q, r, 1.0 / 24.0);
-  q = fma_sc(q, r, 1.0 / 6.0);
-  q = fma(q, r, 0.5);
-  return fma(q, r, 1.0);
-#else
   double q = GWI_EXP_C8;
   q = fma_sc(q, r, GWI_EXP_C7);
   q = fma_sc(q, r, GWI_EXP_C6);
@@ -326,7 +302,6 @@ __device__ __forceinline__ double exp_q(double r) {
   q = fma_sc(q, r, GWI_EXP_C2);
   q = fma_sc(q, r, GWI_EXP_C1);
   return fma_sc(q, r, GWI_EXP_C0);
-#endif
 }
 __device__ __forceinline__ ExpParts exp_parts(double x) {
   x = fmin(fmax(x, -1000.0), 710.0);
@@ -381,28 +356,13 @@ __device__ __forceinline__ Taps cubic_taps(double t) {
   r.b3 = t2 * (t * (1.0 / 6.0));
   return r;
 }
-// the same scaled by a weight w, for the gradient numerators (w folded into the 1/6 factors).  The fraction is laundered
-// through an empty asm so that the compiler cannot share sub-expressions with the cubic_taps() of the evaluation: shared,
-// they stay live across the sample's exponential -- 8-10 VGPRs per spline term, config 5: 108 -> 159, a resident wave per
-// SIMD -- for 7 of ~50 vector instructions per term (GWI_KEEP_TAPS=1 builds the other choice, for A/B timing)
-__device__ __forceinline__ Taps cubic_taps_weighted(double t, double w) {
-#ifndef GWI_KEEP_TAPS
-  asm("" : "+v"(t));
-#endif
-  const double v = 1.0 - t;
-  const double t2 = t * t, v2 = v * v;
-  const double w6 = w * (1.0 / 6.0);
-  Taps r;
-  r.b0 = v2 * (v * w6);
-  r.b1 = w * fma(t2, fma(t, 0.5, -1.0), 2.0 / 3.0);
-  r.b2 = w * fma(v2, fma(v, 0.5, -1.0), 2.0 / 3.0);
-  r.b3 = t2 * (t * w6);
-  return r;
-}
-// The same with w/6 and 2w/3 handed in -- they are the SAME for every spline term of a sample, but each term's block sits
-// behind its own exec-mask branch, across which the compiler does not share them -- and the inner taps formed from the
-// outer ones, b1 = 2/3 - t^2 + t^3/2 = 2/3 - t^2 + 3 b3:  w b1 = fma(3, w b3, fma(-w, t^2, 2w/3)): 11 vector instructions per
-// term instead of 14 + the w/6 multiply.  (Cancellation is benign: the three addends are O(w), the result >= w/6.)
+// the same scaled by a weight w, for the gradient numerators.  The fraction is laundered through an empty asm so that the
+// compiler cannot share sub-expressions with the cubic_taps() of the evaluation: shared, they stay live across the sample's
+// exponential -- 8-10 VGPRs per spline term, config 5: 108 -> 159, a resident wave per SIMD -- for 7 of ~50 vector
+// instructions per term.  w/6 and 2w/3 are handed in -- they are the SAME for every spline term of a sample, but each term's
+// block sits behind its own exec-mask branch, across which the compiler does not share them -- and the inner taps are formed
+// from the outer ones, b1 = 2/3 - t^2 + t^3/2 = 2/3 - t^2 + 3 b3:  w b1 = fma(3, w b3, fma(-w, t^2, 2w/3)): 11 vector
+// instructions per term.  (Cancellation is benign: the three addends are O(w), the result >= w/6.)
 struct Weight {
   double w, w6, w23;
 };
@@ -414,12 +374,7 @@ __device__ __forceinline__ Weight make_weight(double w) {
   return r;
 }
 __device__ __forceinline__ Taps cubic_taps_weighted(double t, const Weight& ww) {
-#ifdef GWI_AB_OLD_TAPS
-  return cubic_taps_weighted(t, ww.w);
-#else
-#ifndef GWI_KEEP_TAPS
   asm("" : "+v"(t));
-#endif
   const double v = 1.0 - t;
   const double t2 = t * t, v2 = v * v;
   Taps r;
@@ -428,7 +383,6 @@ __device__ __forceinline__ Taps cubic_taps_weighted(double t, const Weight& ww) 
   r.b1 = fma(3.0, r.b3, fma(-ww.w, t2, ww.w23));
   r.b2 = fma(3.0, r.b0, fma(-ww.w, v2, ww.w23));
   return r;
-#endif
 }
 // The spline VALUE in the local power basis: on knot interval k the uniform cubic B-spline sum is one cubic in t,
 //   sum_i c_{k+i} b_i(t) = A + B t + C t^2 + D t^3,   A = (c0 + 4 c1 + c2)/6, B = (c2 - c0)/2, C = (c0 - 2 c1 + c2)/2, D = (c3 - c0)/6 + (c1 - c2)/2,
@@ -443,11 +397,7 @@ __device__ __forceinline__ Taps cubic_taps_weighted(double t, const Weight& ww) 
 // 257 keeps them four ds_read_b64 at immediate offsets (2 x 32 lanes, ~2.3 cycles each: 9 per term, conflict-free for any
 // mix of knot intervals -- neighbouring intervals are neighbouring 8-byte words).  The LDS pipe is what config 5 waits for
 // (SQ_WAIT_INST_LDS 24 % of its wave cycles in round 3): profiles/round4/EXPERIMENTS.md section 2.
-#ifdef GWI_AB_POLY_STRIDE_256
-constexpr int kPolyStride = GWI_MAX_THETA;
-#else
 constexpr int kPolyStride = GWI_MAX_THETA + 1;
-#endif
 __device__ __forceinline__ void spline_poly(double c0, double c1, double c2, double c3, double* out) {
   out[0] = (c0 + 4.0 * c1 + c2) * (1.0 / 6.0);
   out[kPolyStride] = (c2 - c0) * 0.5;
@@ -518,20 +468,11 @@ struct Ctx {
   int rep_shift;
   const double* const (*tcols)[2];  // per-term column pointers of the sample set this workgroup scans
   mutable Weight wt;                // the weight of the sample being accumulated with w/6 and 2w/3 (set by the scan loop: shared by its spline terms)
-#ifdef GWI_ABL_SCATTER_TO_REG
-  mutable double sink = 0.0;  // timing-only ablation: the weighted taps end up here instead of in the LDS rows
-#endif
 };
 
 __device__ __forceinline__ double spline_value(const Ctx& c, int first, double t) {
-#ifdef GWI_SPLINE_TAPS_VALUE  // A/B: the four-tap form
-  const double* cf = c.coefs + first;
-  const Taps b = cubic_taps(t);
-  return cf[0] * b.b0 + cf[1] * b.b1 + cf[2] * b.b2 + cf[3] * b.b3;
-#else
   const double* q = c.poly + first;
   return fma(fma(fma(q[3 * kPolyStride], t, q[2 * kPolyStride]), t, q[kPolyStride]), t, q[0]);
-#endif
 }
 
 // ---- spline-coefficient gradient numerators ------------------------------------------------------
@@ -544,34 +485,13 @@ __device__ __forceinline__ double spline_value(const Ctx& c, int first, double t
 // random; config 5 spent 30 % of its scan there).  The four waves of the workgroup share the rows (the adds are atomic),
 // which is what makes 64 replicas fit: n_theta x 512 B per WORKGROUP.
 __device__ __forceinline__ void spline_scatter(const Ctx& c, int first, const Taps& b) {
-#ifdef GWI_ABL_NO_SCATTER  // timing-only ablation build (tools/build_ablations.sh): results are wrong by construction
-  return;
-#endif
-#ifdef GWI_ABL_SCATTER_TO_REG  // ... the same with the weighted taps still computed (isolates the cost of the LDS atomics)
-  c.sink += (b.b0 + b.b1) + (b.b2 + b.b3) + (double)first;
-  return;
-#endif
-#ifdef GWI_ABL_ALL_REP64  // timing-only: every lane an address of its own (64 "replicas" that overlap the neighbouring rows): no two lanes of a wave instruction ever meet
-  double* g = c.gacc - (__lane_id() & 15) + __lane_id() + (first << c.rep_shift);
-#else
   double* g = c.gacc + (first << c.rep_shift);
-#endif
   const int step = 1 << c.rep_shift;
   unsafeAtomicAdd(g, b.b0);
   unsafeAtomicAdd(g + step, b.b1);
   unsafeAtomicAdd(g + 2 * step, b.b2);
   unsafeAtomicAdd(g + 3 * step, b.b3);
 }
-#ifdef GWI_ABL_Z_REP64  // timing-only: the same for zero-outside terms alone (the redshift spline of configs 5 / bspline_test)
-__device__ __forceinline__ void spline_scatter_rep64(const Ctx& c, int first, const Taps& b) {
-  double* g = c.gacc - (__lane_id() & 15) + __lane_id() + (first << c.rep_shift);
-  const int step = 1 << c.rep_shift;
-  unsafeAtomicAdd(g, b.b0);
-  unsafeAtomicAdd(g + step, b.b1);
-  unsafeAtomicAdd(g + 2 * step, b.b2);
-  unsafeAtomicAdd(g + 3 * step, b.b3);
-}
-#endif
 // ---- term library --------------------------------------------------------------------------
 // A sample's weight is  w = L * exp(l - m):  each term either adds to the log part l (power laws,
 // splines: already exponents) or multiplies the linear part L (mixtures, the ratio normaliser:
@@ -970,12 +890,7 @@ struct Term<GWI_TERM_EXP_SPLINE> {
   }
   __device__ static void accumulate(const TermD& t, const Ctx& c, double w, const State& s, Acc&) {
     if (s.k >= 0 && w != 0.0) {  // c.wt.w == w
-#ifdef GWI_ABL_Z_REP64
-      if (t.flags & GWI_SPLINE_OUTSIDE_ZERO_EXPONENT)
-        spline_scatter_rep64(c, t.th0 + s.k, cubic_taps_weighted(s.t, c.wt));
-      else
-#endif
-        spline_scatter(c, t.th0 + s.k, cubic_taps_weighted(s.t, c.wt));
+      spline_scatter(c, t.th0 + s.k, cubic_taps_weighted(s.t, c.wt));
     }
   }
   __device__ static void init(Acc&) {}
@@ -1918,11 +1833,7 @@ struct KernargWarm {
   // single evaluations only: a batched launch runs many workgroups per CU one after the other, whose argument lines are in the
   // scalar cache after the first -- there the fourteen extra loads per wave cost the config-2 batch 11 % (4.65 -> 5.2 us per
   // evaluation at K = 16) for nothing
-#ifndef GWI_AB_NO_KERNARG_WARM
   static constexpr int kN = BATCHED ? 0 : count();
-#else
-  static constexpr int kN = 0;
-#endif
   int t[kN > 0 ? kN : 1];
   __device__ __forceinline__ void issue() {
     // the argument block inside the kernel-argument segment (behind the preloaded scalars); not &a: taking the address of the
@@ -1947,7 +1858,6 @@ struct KernargWarm {
 // injections.  Loads are coalesced: lane i of a wave reads element base+i of each column; each lane
 // carries kU samples (256 apart) per trip so polynomial constants, the wave maximum and the loop
 // overhead are shared between them.
-constexpr int kRedChunk = 8;
 constexpr int kRegularRepShift = 4;  // 16 gradient-row replicas in the regular (non-SAFE) scan kernels
 
 #ifndef GWI_SCAN_WAVES_PER_EU
@@ -1975,14 +1885,9 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_kernel(con
   // spline models carry few scalar sums (their gradient lives in the s_gacc rows): a narrower staging
   // area leaves the LDS to those rows
   constexpr int kNVals = 2 + ChainT::kNumAcc;
-#ifdef GWI_AB_OLD_RECORD  // A/B: the scalar sums of a workgroup through a transposed LDS staging area and one row-shift reduction per value
-  constexpr int kChunk = ChainT::kSpline ? (kNVals < 4 ? kNVals : 4) : kRedChunk;
-  __shared__ double s_red[kChunk][kBlock];
-#else
   // the scalar sums of the four waves, eight per butterfly (wave_sum8): [wave][value]
   constexpr int kSumGroups = (kNVals + 7) / 8;
   __shared__ double s_part[kWaves][kSumGroups * 8];
-#endif
   __shared__ double s_wrec[kWaves][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #ifdef GWI_STAMPS
@@ -2292,108 +2197,12 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_kernel(con
   if (WRITE_LOGW) return;
   GWI_STAMP(3);
 
-#ifdef GWI_AB_OLD_RECORD
-  // ---- workgroup record: common exponent M, then a transposed LDS reduction of every scalar sum
-  double M = GWI_NEG_INF, f = 1.0;
-  if (kShared) {
-    // every wave used the tile's reference n_ref; the tile's true maximum decides below whether that was good enough
-    const double mx = wave_max(lane_max);
-    if (lane == 0) s_wrec[wave][2] = mx;
-  } else {
-    if (lane == 0) s_wrec[wave][0] = m;
-    __syncthreads();
-    M = s_wrec[0][0];
-#pragma unroll
-    for (int w_ = 1; w_ < kWaves; ++w_) M = fmax(M, s_wrec[w_][0]);
-    f = (m == GWI_NEG_INF) ? 0.0 : fast_exp(m - M);  // this wave's rescale factor
-    if (a.square) f *= f;
-  }
-
-  GWI_STAMP(6);  // diagnostic build: the waves' references exchanged
-  constexpr int kNV = 2 + ChainT::kNumAcc;
-  double vals[kNV];
-  int th[kNV];
-#ifdef GWI_ABL_SCATTER_TO_REG
-  s1 += 1e-300 * ctx.sink;
-#endif
-  vals[0] = s1 * f;
-  vals[1] = s2 * f * f;
-  th[0] = th[1] = -1;
-  chain.collect(0, ctx, vals + 2, th + 2);
-#pragma unroll
-  for (int v = 2; v < kNV; ++v) vals[v] *= f;
-  double* out = a.partials + ((long long)kb * (n_pe_blocks + a.n_inj_tiles) + b) * a.rec_stride;
-#pragma unroll
-  for (int v0 = 0; v0 < kNV; v0 += kChunk) {
-    if (v0 > 0) __syncthreads();
-#pragma unroll
-    for (int v = v0; v < kNV && v < v0 + kChunk; ++v) s_red[v - v0][tid] = vals[v];
-    __syncthreads();
-    // wave w reduces values v0 + w, v0 + w + 4, ...: 4 strided reads (fixed order) + one DPP sum
-#pragma unroll
-    for (int v = v0; v < kNV && v < v0 + kChunk; ++v) {
-      if (((v - v0) & (kWaves - 1)) != wave) continue;  // wave-uniform
-      const double* row = s_red[v - v0];
-      const double r = wave_sum((row[lane] + row[lane + 64]) + (row[lane + 128] + row[lane + 192]));
-      if (lane == 0) {
-        if (v < 2) {
-          if (kShared)
-            s_wrec[v][3] = r;  // S1 / S2 against n_ref: normalised below, once the whole workgroup can see S1
-          else
-            out[1 + v] = r;
-        } else {
-          unsafeAtomicAdd(&s_out[th[v]], r);  // several accumulators may feed one theta slot
-        }
-      }
-    }
-  }
-  if (!kShared && tid == 0) out[0] = a.square ? 2.0 * M : M;
-  __syncthreads();
-  GWI_STAMP(7);  // diagnostic build: scalar sums reduced
-  // Shared mode: the record is normalised to the tile's own S1 -- S1 in [1, 2), everything else scaled by the same exact
-  // power of two, the exponent M a whole number of binades -- so that it is, to the bit, the record any other reference
-  // n_ref would have produced (see n_ref above).
-  int e_norm = 0;
-  if (kShared) {
-    const double S1 = s_wrec[0][3], S2 = s_wrec[1][3];
-    const bool has_sum = S1 > 0.0 && S1 < GWI_POS_INF;
-    if (has_sum) e_norm = ilogb(S1);
-    if (tid == 0) {
-      const double mm = fmax(fmax(s_wrec[0][2], s_wrec[1][2]), fmax(s_wrec[2][2], s_wrec[3][2]));
-      const int n_max = (mm == GWI_NEG_INF) ? kNoRef : (int)__builtin_rint(fmin(fmax(mm, -7.0e5), 7.0e5) * kLog2e);
-      *nref_slot = n_max;  // the next evaluation's reference (and, if this one has to be repeated, the repeat's: exact)
-      const int dist = n_max - n_ref;
-      if (n_max != kNoRef && (dist > ref_slack || dist < -ref_slack)) {
-        __hip_atomic_store(a.redo_host, a.norm_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(a.redo_dev, a.norm_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      const int n_tot = (a.square ? 2 * n_ref : n_ref) + e_norm;
-      out[0] = has_sum ? (double)n_tot * kLn2 : GWI_NEG_INF;
-      out[1] = has_sum ? ldexp(S1, -e_norm) : 0.0;
-      out[2] = has_sum ? ldexp(S2, -2 * e_norm) : 0.0;
-    }
-  }
-  // gradient numerators: scalar sums from s_out, spline-coefficient sums from the shared rows (replicas in fixed order)
-  for (int p = tid; p < a.n_theta; p += kBlock) {
-    double g = s_out[p];
-    if (kShared) {
-      const double* rows = s_gacc + ((long)p << rep_shift);
-      double gw = 0.0;
-      for (int r = 0; r < rep; ++r) gw += rows[(r + p) & (rep - 1)];  // rotated start: the threads of a wave read different banks
-      g = ldexp(g + gw, -e_norm);
-    }
-    out[kRecHeader + p] = g;
-  }
-#else
   // ---- workgroup record.  Every wave sums its lanes' scalar sums eight at a time (wave_sum8: no LDS, no barrier) and
   // leaves them in s_part[wave][.]; ONE barrier later they are added across the waves in wave order.  (Before: a transposed
   // LDS staging area, three barriers and one row-shift reduction per value -- 1.2 us of config 2's 4.8 us wave lifetime.)
   constexpr int kNV = kNVals;
   double vals[kSumGroups * 8];
   int th[kNV];
-#ifdef GWI_ABL_SCATTER_TO_REG
-  s1 += 1e-300 * ctx.sink;
-#endif
   vals[0] = s1;
   vals[1] = s2;
   th[0] = th[1] = -1;
@@ -2484,7 +2293,6 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_kernel(con
     for (int r = 0; r < rep; ++r) gw += rows[(r + p) & (rep - 1)];  // rotated start: the threads of a wave read different banks
     out[kRecHeader + p] = ldexp(g + gw, -e_norm);
   }
-#endif
   GWI_STAMP(4);
 }
 
@@ -2641,13 +2449,7 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_pbatch_ker
         mx_lane = fmax(mx_lane, ell[u]);
       }
       // the wave's maximum for this point (to single precision, wave_max_coarse): every weight is <= (1 + 1e-7 |m|) x its linear part
-#ifdef GWI_AB_PBATCH_NOMAX  // timing-only ablation: no cross-lane maximum (wrong reference)
-      const double m = uniform(mx_lane);
-#elif defined(GWI_AB_PBATCH_EXACT_MAX)  // A/B: round 5's double-precision maximum
-      const double m = wave_max(mx_lane);
-#else
       const double m = wave_max_coarse(mx_lane);  // within 6e-8 |m| of the wave's maximum: a reference, not a result
-#endif
       double s1 = 0.0, s2 = 0.0;
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
@@ -2677,14 +2479,8 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_pbatch_ker
       for (int v = kNV; v < kSumGroups * 8; ++v) vals[v] = 0.0;
 #pragma unroll
       for (int g = 0; g < kSumGroups; ++g) {
-#ifdef GWI_AB_PBATCH_NOSUM  // timing-only ablation: no butterfly (every value still reaches LDS once: eight stores of 64 lanes)
-#pragma unroll
-        for (int v = 0; v < 8; ++v)
-          if ((lane & 7) == v) s_part[wave][kk][8 * g + (lane >> 3)] = vals[8 * g + v];
-#else
         const double z = wave_sum8(vals + 8 * g);
         if ((lane & 7) == 0) s_part[wave][kk][8 * g + (lane >> 3)] = z;
-#endif
       }
       if (lane == 0) s_m[wave][kk] = m;
     }

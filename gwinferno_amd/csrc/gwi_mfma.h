@@ -88,11 +88,7 @@ struct Stage {  // every kind without spline coefficients: the term's column val
   }
   __device__ static void b_rows(const double* row_, Keep& kp) {
     double* dst = reinterpret_cast<double*>(&kp.in);
-#ifdef GWI_AB_MFMA_READ2
-    const double* row = row_;
-#else
     lds_ro row = (lds_ro)row_;
-#endif
 #pragma unroll
     for (int i = 0; i < kDoubles; ++i) dst[i] = row[i];
   }
@@ -132,35 +128,18 @@ __device__ __forceinline__ void stage_spline(const TermD& t, double x, bool zero
   row[6] = 0.0;
 }
 __device__ __forceinline__ void spline_rows(const double* row_, SplineKeep& kp) {
-#ifdef GWI_AB_MFMA_READ2
-  const double* row = row_;
-#else
   lds_ro row = (lds_ro)row_;
-#endif
   kp.k = __double2loint(row[0]);
-#ifdef GWI_ABL_NO_TAPREAD  // timing-only ablation: the taps not read from the staging row
-  kp.b.b0 = kp.b.b1 = kp.b.b2 = kp.b.b3 = 0.25;
-#else
   kp.b.b0 = row[2];
   kp.b.b1 = row[3];
   kp.b.b2 = row[4];
   kp.b.b3 = row[5];
-#endif
   kp.scale = 1.0;
 }
 __device__ __forceinline__ void spline_coefs(const TermD& t, const Ctx& c, SplineKeep& kp) {
-#ifdef GWI_ABL_NO_COEF  // timing-only ablation: no coefficient gather
-#pragma unroll
-  for (int i = 0; i < 4; ++i) kp.cf[i] = 1.0 + kp.k;
-#else
-#ifdef GWI_AB_MFMA_READ2
-  const double* cf = c.coefs + t.th0 + kp.k;
-#else
   lds_ro cf = (lds_ro)(c.coefs + t.th0 + kp.k);
-#endif
 #pragma unroll
   for (int i = 0; i < 4; ++i) kp.cf[i] = cf[i];
-#endif
 }
 __device__ __forceinline__ double spline_value(SplineKeep& kp) {
   return kp.cf[0] * kp.b.b0 + kp.cf[1] * kp.b.b1 + kp.cf[2] * kp.b.b2 + kp.cf[3] * kp.b.b3;
@@ -334,11 +313,7 @@ struct MChain<ROWS, KT, Rest...> {
       } else {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-#if defined(GWI_ABL_NO_MFMA)  // timing-only ablation (results wrong): the A operand still fetched, no matrix instruction
-          tile[t][0] += aval[t] * bw;
-#else
           tile[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(aval[t], bw, tile[t], 0, 0, 0);
-#endif
         }
       }
     } else {
@@ -498,21 +473,13 @@ __device__ __forceinline__ void scan_points_body(const KArgs& a) {
     //      left to itself it sinks every gather to its matrix instruction (read, full LDS round trip, MFMA, eight times a
     //      round).  A two-stage software pipeline over rounds on top of this measured the same (36.6 vs 36.4 us per evaluation
     //      at config 5) and is not kept.
-#ifdef GWI_ABL_B_NONE  // timing-only ablation: phase A and the staging only
-    constexpr int kRounds = 0;
-#else
     constexpr int kRounds = kStageS / 4;
-#endif
 #pragma unroll 1
     for (int g = 0; g < kRounds; ++g) {
       const double* row = my_rows + (4 * g + q) * kRow;
       const double kappa = row[0];
       double lin = 1.0;
-#ifdef GWI_ABL_NO_FWD  // timing-only ablation: no forward half
-      double ell = kappa;
-#else
       double ell = kappa + chain.forward(0, ctx, row + 1, lin);
-#endif
       chain.commit();
       chain.gather(j, row + 1);
       __builtin_amdgcn_sched_barrier(0);

@@ -13,11 +13,7 @@ namespace gwi_plan {
 constexpr int kBlock = 256;             // threads per scan workgroup
 constexpr unsigned kGeomTilesBits = 7;  // bits of the tiles-per-event field in the scan's packed geometry word (ScanHead::geom)
 constexpr int kRegularRepShift = 4;     // 16 gradient-row replicas in the regular (non-SAFE) scan kernels
-#ifdef GWI_AB_POLY_STRIDE_256
-constexpr int kPolyStride = 256;
-#else
 constexpr int kPolyStride = 256 + 1;  // doubles between the four power-basis arrays of the spline values (GWI_MAX_THETA + 1)
-#endif
 // the scan receives its tile sizes in 16 bits each (ScanHead::chunks): exact below 32 768 samples, multiples of 256 above
 inline bool chunk_packs(long long c) { return c > 0 && (c < 32768 || (c % 256 == 0 && c / 256 < 32768)); }
 

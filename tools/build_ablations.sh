@@ -1,5 +1,7 @@
 #!/bin/bash
-# Timing-only ablation builds of the engine (results are wrong by construction): tools/build_ablations.sh NAME -DFLAG...
+# Side builds of the engine with extra compiler flags, for experiments: tools/build_ablations.sh NAME -DFLAG...
+# (-DGWI_PBATCH_U=..., -DGWI_SCAN_WAVES_PER_EU=..., -DGWI_STAMPS for tools/stamp_phases.py, the short variant tables of
+# gwi_engine.hip for a quick build)
 # -> gwinferno_amd/_lib_NAME/{libgwi_engine.so,gwi_kernels.hsaco}; run with GWI_ENGINE_LIB=gwinferno_amd/_lib_NAME/libgwi_engine.so
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
