@@ -971,10 +971,9 @@ gwi_status launch_scan(gwi_handle h, bool logw, int K = 1, bool batch = false) {
   return GWI_OK;
 }
 
-gwi_status wait_for_stamp(gwi_handle h, double* host_buf, int K = 1, size_t stride = 0);
-void merge_final_records(gwi_handle h, int K);
-gwi_status wait_for_rows(gwi_handle h, int K = 1);
-gwi_status wait_for_norms(gwi_handle h, double* record, int K = 1, size_t stride = 0);
+// (the single evaluation is 16 to 28 us end to end: the helpers on its way fold into their entries, as the code they replace did)
+#define GWI_HOT inline __attribute__((always_inline))
+GWI_HOT gwi_status collect_local(gwi_handle h, int K);
 
 // launches scan -> combine -> final; `record_dev` is where final_kernel publishes (pinned host record
 // or, for the sharded path, the device send buffer); `wait` polls the pinned completion stamp.
@@ -1132,37 +1131,41 @@ gwi_status run_pipeline_once(gwi_handle h, const double* theta, double* record_d
   GWI_PHASE(2);
   if (ta.host_rows) {
     GWI_PHASE(3);
-    const gwi_status sw = wait ? wait_for_rows(h, K) : GWI_OK;
+    const gwi_status sw = wait ? collect_local(h, K) : GWI_OK;
     GWI_PHASE(4);
     return sw;
   }
   launch_timed(h, 2, final_kernel, dim3((unsigned)ta.final_groups, gy), dim3(kFinalThreads), 0, ta);
   GWI_HIP(hipGetLastError());
   h->timed_final = true;
-  if (!wait) return GWI_OK;
-  gwi_status st_ = wait_for_stamp(h, h->h_fin, K * h->final_groups);
-  if (st_ == GWI_OK) merge_final_records(h, K);
-  if (st_ != GWI_OK) return st_;
-  return wait_for_norms(h, h->h_record, K);
+  return wait ? collect_local(h, K) : GWI_OK;
 }
 
 // A scan workgroup whose reference exponent turned out too far from its tile's true maximum (models with spline terms:
 // scan_kernel, shared mode) has stored this evaluation's sequence number in the pinned redo word.
 bool redo_requested(const gwi_engine* h) { return *reinterpret_cast<volatile unsigned long long*>(h->h_redo) == h->seq; }
 
-// launches scan -> combine [-> final]; with `wait`, repeats the evaluation when a workgroup asked for it.  The failed attempt
-// has left every tile's exact maximum in tile_nref, so the repeat is the same (fast) kernel with exact references and cannot
-// miss; should it ever ask again (it never has) the two-pass instantiation finds the maxima in a sweep of its own.
-// Callers that pass wait = false check redo_requested() themselves once their results are in (repeat_after_redo).
-gwi_status repeat_after_redo(gwi_handle h, const double* theta, double* record_dev, int K, bool batch, bool square) {
+// The repeat ladder of every evaluating path: when asked() says that the collected evaluation wants a repeat, count it and
+// run_again().  The failed attempt has left every tile's exact maximum in tile_nref, so the repeat is the same (fast) kernel with
+// exact references and cannot miss; should it ever ask again (it never has) the two-pass instantiation, where the variant has
+// one, finds the maxima in a sweep of its own.
+template <typename Run, typename Asked>
+gwi_status repeat_while_asked(gwi_handle h, Run run_again, Asked asked) {
+  if (!asked()) return GWI_OK;
   ++h->redo_count;
-  gwi_status st = run_pipeline_once(h, theta, record_dev, true, K, batch, square);
-  if (st == GWI_OK && redo_requested(h) && h->variant->has(jit::kSafe)) {
+  gwi_status st = run_again();
+  if (st == GWI_OK && asked() && h->variant->has(jit::kSafe)) {
     h->kargs.two_pass = 1;
-    st = run_pipeline_once(h, theta, record_dev, true, K, batch, square);
+    st = run_again();
     h->kargs.two_pass = 0;
   }
   return st;
+}
+
+// ... of this rank's own launches: scan -> combine [-> final] once more, waited for.  run_pipeline does this itself with `wait`;
+// callers that pass wait = false come here once their results are in (collect_local).
+gwi_status repeat_after_redo(gwi_handle h, const double* theta, double* record_dev, int K, bool batch, bool square) {
+  return repeat_while_asked(h, [&] { return run_pipeline_once(h, theta, record_dev, true, K, batch, square); }, [&] { return redo_requested(h); });
 }
 // The matrix-core batched kernel for a spline model that has no ahead-of-time instantiation of it: scan_mfma_kernel
 // instantiated for this model's kinds and tile counts by hipRTC (gwi_jit.h), loaded as a module.  Returns whether h->mfma is set.
@@ -1252,14 +1255,18 @@ gwi_status calibrate_batch_path(gwi_handle h, const double* theta, int K) {
   return st;
 }
 
+// Before a batched launch of K points: a matrix-core kernel still to be compiled is compiled on the first launch that would use it,
+// and (GWI_BATCH_AUTOTUNE=1 only) measured against the 4-tap kernel.  Blocking.
+gwi_status ensure_batch_kernel(gwi_handle h, const double* thetas, int K) {
+  if (K < h->mfma_min_batch) return GWI_OK;
+  if (h->mfma_jit_pending) h->batch_autotune = try_jit_mfma(h) && h->autotune_wanted;
+  return h->batch_autotune && h->mfma ? calibrate_batch_path(h, thetas, K) : GWI_OK;
+}
+
 gwi_status run_pipeline(gwi_handle h, const double* theta, double* record_dev = nullptr, bool wait = true, int K = 1, bool batch = false, bool square = false) {
-  if (batch && h->mfma_jit_pending && K >= h->mfma_min_batch && wait && !record_dev) h->batch_autotune = try_jit_mfma(h) && h->autotune_wanted;
-  if (batch && h->batch_autotune && h->mfma && K >= h->mfma_min_batch && wait && !record_dev) {
-    const gwi_status sc = calibrate_batch_path(h, theta, K);
-    if (sc != GWI_OK) return sc;
-  }
-  gwi_status st = run_pipeline_once(h, theta, record_dev, wait, K, batch, square);
-  if (st == GWI_OK && wait && redo_requested(h)) st = repeat_after_redo(h, theta, record_dev, K, batch, square);
+  gwi_status st = batch && wait && !record_dev ? ensure_batch_kernel(h, theta, K) : GWI_OK;
+  if (st == GWI_OK) st = run_pipeline_once(h, theta, record_dev, wait, K, batch, square);
+  if (st == GWI_OK && wait) st = repeat_after_redo(h, theta, record_dev, K, batch, square);
   return st;
 }
 
@@ -1314,121 +1321,124 @@ gwi_status aql_wait_slow(gwi_handle h, Ready ready, const char* what) {
   }
 }
 
-// the normaliser launch publishes Z_j + a stamp per normaliser; copy them into rank 0's record slots (point k's at
-// record + k * stride; stride 0: one record per point)
-gwi_status wait_for_norms(gwi_handle h, double* record, int K, size_t stride) {
-  const int n = h->spec.n_norms;
-  if (n == 0) return GWI_OK;
-  const int total = n * K;
+// The skeleton of every wait for results in pinned host memory.  ready() says whether they have all arrived (it may keep a cursor:
+// what has arrived stays).  A bounded quick poll (~2 ms) instead of paying a stream synchronise; then the slow wait of the AQL
+// path, or the blocking call on the stream path (which also surfaces any error) and one more look; then the acquire fence ahead
+// of the caller's reads.  `gated`: the quick poll only without timing and with spin_wait.  `grace`: results that are posted
+// writes behind the stream's completion get that many more polls to land after the synchronise.
+template <typename Ready>
+gwi_status wait_until(gwi_handle h, bool gated, long grace, Ready ready, const char* what, const char* mismatch) {
   bool done = false;
-  for (long spin = 0; spin < 400000 && !done; ++spin) {
-    done = true;
-    for (int j = 0; j < total; ++j) done = done && *reinterpret_cast<volatile unsigned long long*>(h->h_norm_stamp + j) == h->seq;
-    if (!done) __builtin_ia32_pause();
-  }
+  if (!gated || (!h->timing && h->spin_wait))
+    for (long spin = 0; spin < 400000 && !(done = ready()); ++spin) __builtin_ia32_pause();
   if (!done && h->aql_now) {
-    const gwi_status sw = aql_wait_slow(h, [&] {
-      for (int j = 0; j < total; ++j)
-        if (*reinterpret_cast<volatile unsigned long long*>(h->h_norm_stamp + j) != h->seq) return false;
-      return true;
-    }, "normaliser stamps");
+    const gwi_status sw = aql_wait_slow(h, ready, what);
     if (sw != GWI_OK) return sw;
   } else if (!done) {
     GWI_HIP(hipStreamSynchronize(h->stream));
-    for (int j = 0; j < total; ++j)
-      if (h->h_norm_stamp[j] != h->seq) return fail(h, GWI_ERR_HIP, "normaliser stamp mismatch after stream synchronise");
+    for (long spin = 0; spin < grace && !ready(); ++spin) __builtin_ia32_pause();
+    if (!ready()) return fail(h, GWI_ERR_HIP, mismatch);
   }
   std::atomic_thread_fence(std::memory_order_acquire);
+  return GWI_OK;
+}
+
+// with gwi_set_timing: the kernel times of the evaluation just waited for, from the AQL queue's dispatch timestamps or the HIP events
+gwi_status collect_kernel_times(gwi_handle h) {
+  if (!h->timing) return GWI_OK;
+  const int n_launches = h->timed_final ? 3 : 2;
+  h->last_ms[2] = 0.0f;  // host-final mode has no third launch
+  if (h->aql_now) return aql::timed_collect(h->aq, n_launches, h->last_ms) ? GWI_OK : fail(h, GWI_ERR_HIP, "dispatch timestamps of the AQL queue are not available");
+  GWI_HIP(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n_launches; ++i) GWI_HIP(hipEventElapsedTime(&h->last_ms[i], h->ev[2 * i], h->ev[2 * i + 1]));
+  return GWI_OK;
+}
+
+// the normaliser launch publishes Z_j + a stamp per normaliser; copy them into rank 0's record slots (point k's at
+// record + k * stride; stride 0: one record per point)
+gwi_status wait_for_norms(gwi_handle h, double* record, int K = 1, size_t stride = 0) {
+  const int n = h->spec.n_norms;
+  if (n == 0) return GWI_OK;
+  const int total = n * K;
+  const gwi_status sw = wait_until(h, /*gated=*/false, /*grace=*/0, [&] {
+    for (int j = 0; j < total; ++j)
+      if (*reinterpret_cast<volatile unsigned long long*>(h->h_norm_stamp + j) != h->seq) return false;
+    return true;
+  }, "normaliser stamps", "normaliser stamp mismatch after stream synchronise");
+  if (sw != GWI_OK) return sw;
   const size_t step = stride ? stride : (size_t)record_len(h);
   for (int k = 0; k < K; ++k)
     for (int j = 0; j < n; ++j) record[(size_t)k * step + kRecNormOff + j] = h->h_norm[k * n + j];
   return GWI_OK;
 }
 
-// Device-final mode: the G partial records of point k (h_fin) -> one record (h_record), merged exactly as assemble() merges the
-// records of ranks: sums, the minimum, the injection triples brought to their common exponent, gradients in workgroup order.
+// n partial records (one after the other, `len` doubles each) merged into one: sums, the minimum, the injection triples brought
+// to their common exponent M, gradients in record order (g_pe, g_inj: n_theta sums each, overwritten).  Workgroups of one launch
+// and ranks of one exchange are merged by this one loop, so a record means the same whoever summed it.  `marked`: the records
+// are a launch's workgroups', whose event count (slot 7) carries the repeat mark as -(count + 1); a rank's is read as it stands.
+struct MergedRecord {
+  double sum_lse = 0.0, sum_var = 0.0, min_lneff = INFINITY, n_ev = 0.0, M = -INFINITY, S1 = 0.0, S2 = 0.0;
+  bool redo = false;
+};
+GWI_HOT MergedRecord merge_records(const gwi_engine* h, const double* records, int n, bool marked, double* g_pe, double* g_inj) {
+  const int n_theta = h->spec.n_theta, n_norms = h->spec.n_norms;
+  const size_t len = (size_t)record_len(h);
+  MergedRecord m;
+  for (int i = 0; i < n; ++i) {
+    const double* r = records + (size_t)i * len;
+    const bool mark = marked && r[7] < 0.0;
+    m.sum_lse += r[1];
+    m.sum_var += r[2];
+    m.min_lneff = std::fmin(m.min_lneff, r[3]);
+    m.M = std::fmax(m.M, r[4]);
+    m.redo = m.redo || mark;
+    m.n_ev += mark ? -r[7] - 1.0 : r[7];
+  }
+  for (int p = 0; p < n_theta; ++p) g_pe[p] = g_inj[p] = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const double* r = records + (size_t)i * len;
+    const double f = (r[4] == -INFINITY) ? 0.0 : std::exp(r[4] - m.M);
+    m.S1 += f * r[5];
+    m.S2 += f * f * r[6];
+    const double* gp = r + kRecNormOff + n_norms;
+    const double* gi = gp + n_theta;
+    for (int p = 0; p < n_theta; ++p) {
+      g_pe[p] += gp[p];
+      g_inj[p] += f * gi[p];
+    }
+  }
+  return m;
+}
+
+// Device-final mode: the G partial records of point k (h_fin) -> one record (h_record)
 void merge_final_records(gwi_handle h, int K) {
-  const int G = h->final_groups, n_theta = h->spec.n_theta, n_norms = h->spec.n_norms;
+  const int G = h->final_groups;
   const size_t len = (size_t)record_len(h);
   for (int k = 0; k < K; ++k) {
     double* out = h->h_record + (size_t)k * len;
-    const double* in = h->h_fin + (size_t)k * G * len;
-    double sum = 0.0, var = 0.0, mn = INFINITY, n_ev = 0.0, M = -INFINITY;
-    bool redo = false;
-    for (int g = 0; g < G; ++g) {
-      const double* r = in + (size_t)g * len;
-      sum += r[1];
-      var += r[2];
-      mn = std::fmin(mn, r[3]);
-      M = std::fmax(M, r[4]);
-      redo = redo || r[7] < 0.0;
-      n_ev += r[7] < 0.0 ? -r[7] - 1.0 : r[7];
-    }
-    double S1 = 0.0, S2 = 0.0;
-    double* gpe = out + kRecNormOff + n_norms;
-    double* ginj = gpe + n_theta;
-    for (int p = 0; p < n_theta; ++p) gpe[p] = ginj[p] = 0.0;
-    for (int g = 0; g < G; ++g) {
-      const double* r = in + (size_t)g * len;
-      const double f = (r[4] == -INFINITY) ? 0.0 : std::exp(r[4] - M);
-      S1 += f * r[5];
-      S2 += f * f * r[6];
-      const double* rp = r + kRecNormOff + n_norms;
-      const double* ri = rp + n_theta;
-      for (int p = 0; p < n_theta; ++p) {
-        gpe[p] += rp[p];
-        ginj[p] += f * ri[p];
-      }
-    }
-    out[1] = sum;
-    out[2] = var;
-    out[3] = mn;
-    out[4] = M;
-    out[5] = S1;
-    out[6] = S2;
-    out[7] = redo ? -(n_ev + 1.0) : n_ev;
+    double* gpe = out + kRecNormOff + h->spec.n_norms;
+    const MergedRecord m = merge_records(h, h->h_fin + (size_t)k * G * len, G, /*marked=*/true, gpe, gpe + h->spec.n_theta);
+    out[1] = m.sum_lse;
+    out[2] = m.sum_var;
+    out[3] = m.min_lneff;
+    out[4] = m.M;
+    out[5] = m.S1;
+    out[6] = m.S2;
+    out[7] = m.redo ? -(m.n_ev + 1.0) : m.n_ev;
   }
 }
 
-gwi_status wait_for_stamp(gwi_handle h, double* host_buf, int K, size_t stride) {
-  // Completion: final_kernel stores the sequence stamp into pinned host memory LAST (system-scope
-  // release after __threadfence_system), so the host can poll it instead of paying a stream
-  // synchronise; after ~2 ms of polling fall back to the blocking call (and surface any error).
-  // Stamp k sits at host_buf + k * stride (stride 0: one record per stamp).
+// Completion: final_kernel (or the kernel that publishes gathered records) stores the sequence stamp into pinned host memory LAST
+// (system-scope release after __threadfence_system), so the host can poll it.  Stamp k sits at host_buf + k * stride (stride 0:
+// one record per stamp).
+gwi_status wait_for_stamp(gwi_handle h, double* host_buf, int K = 1, size_t stride = 0) {
   const size_t len = stride ? stride : (size_t)record_len(h);
-  auto stamp_of = [&](int k) { return *reinterpret_cast<volatile unsigned long long*>(host_buf + (size_t)k * len); };
-  bool done = false;
-  if (!h->timing && h->spin_wait) {
-    int k = 0;
-    for (long spin = 0; spin < 400000 && !done; ++spin) {
-      while (k < K && stamp_of(k) == h->seq) ++k;
-      done = k == K;
-      if (!done) __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-  }
-  if (!done && h->aql_now) {
-    const gwi_status sw = aql_wait_slow(h, [&] {
-      for (int k = 0; k < K; ++k)
-        if (stamp_of(k) != h->seq) return false;
-      return true;
-    }, "the completion stamp");
-    if (sw != GWI_OK) return sw;
-    std::atomic_thread_fence(std::memory_order_acquire);
-  } else if (!done) {
-    GWI_HIP(hipStreamSynchronize(h->stream));
-    for (int k = 0; k < K; ++k)
-      if (stamp_of(k) != h->seq) return fail(h, GWI_ERR_HIP, "completion stamp mismatch after stream synchronise");
-  }
-  if (h->timing && h->aql_now) {
-    h->last_ms[2] = 0.0f;
-    if (!aql::timed_collect(h->aq, h->timed_final ? 3 : 2, h->last_ms)) return fail(h, GWI_ERR_HIP, "dispatch timestamps of the AQL queue are not available");
-  } else if (h->timing) {
-    GWI_HIP(hipStreamSynchronize(h->stream));
-    h->last_ms[2] = 0.0f;  // host-final mode has no third launch
-    for (int i = 0; i < (h->timed_final ? 3 : 2); ++i) GWI_HIP(hipEventElapsedTime(&h->last_ms[i], h->ev[2 * i], h->ev[2 * i + 1]));
-  }
-  return GWI_OK;
+  int k = 0;  // the stamps before it have been seen
+  const gwi_status sw = wait_until(h, /*gated=*/true, /*grace=*/0, [&] {
+    while (k < K && *reinterpret_cast<volatile unsigned long long*>(host_buf + (size_t)k * len) == h->seq) ++k;
+    return k == K;
+  }, "the completion stamp", "completion stamp mismatch after stream synchronise");
+  return sw == GWI_OK ? collect_kernel_times(h) : sw;
 }
 
 // Assemble the sites of analysis.py:259-319 from gathered per-rank records.
@@ -1439,29 +1449,9 @@ void assemble(const gwi_engine* h, const double* records, int n_ranks, const gwi
   const int n_theta = h->spec.n_theta, n_norms = h->spec.n_norms;
   const int len = record_len(h);
   const double NEG_BIG = -1.7976931348623157e308;  // jnp.nan_to_num(-inf)
-  double sum_lse = 0.0, sum_var = 0.0, min_lneff = INFINITY, n_ev_total = 0.0, M = -INFINITY;
-  for (int r = 0; r < n_ranks; ++r) {
-    const double* rec = records + (size_t)r * len;
-    sum_lse += rec[1];
-    sum_var += rec[2];
-    min_lneff = std::fmin(min_lneff, rec[3]);
-    M = std::fmax(M, rec[4]);
-    n_ev_total += rec[7];
-  }
-  double S1 = 0.0, S2 = 0.0;
-  std::vector<double> g_pe(n_theta, 0.0), g_inj(n_theta, 0.0);
-  for (int r = 0; r < n_ranks; ++r) {
-    const double* rec = records + (size_t)r * len;
-    const double f = (rec[4] == -INFINITY) ? 0.0 : std::exp(rec[4] - M);
-    S1 += f * rec[5];
-    S2 += f * f * rec[6];
-    const double* gp = rec + kRecNormOff + n_norms;
-    const double* gi = gp + n_theta;
-    for (int p = 0; p < n_theta; ++p) {
-      g_pe[p] += gp[p];
-      g_inj[p] += f * gi[p];
-    }
-  }
+  std::vector<double> g_pe(n_theta), g_inj(n_theta);
+  const MergedRecord merged = merge_records(h, records, n_ranks, /*marked=*/false, g_pe.data(), g_inj.data());
+  const double sum_lse = merged.sum_lse, sum_var = merged.sum_var, min_lneff = merged.min_lneff, n_ev_total = merged.n_ev, M = merged.M, S1 = merged.S1, S2 = merged.S2;
   const double* nrm = records + kRecNormOff;  // every rank integrates the same grids
   double log_const = host_const;
   for (int t = 0; t < h->spec.n_terms; ++t)
@@ -1548,41 +1538,14 @@ gwi_status wait_for_rows(gwi_handle h, int K) {
   const int n_theta = h->spec.n_theta, n_lines = (3 + n_theta + 6) / 7, stride = 8 * n_lines;
   const size_t total_lines = (size_t)n_groups * K * n_lines;
   // every 64-byte line carries the evaluation's sequence number in its eighth slot
-  auto line_ok = [&](size_t ln) { return *reinterpret_cast<volatile unsigned long long*>(h->h_rows + ln * 8 + 7) == h->seq; };
-  bool done = false;
-  if (!h->timing && h->spin_wait) {
-    size_t g = 0;
-    for (long spin = 0; spin < 400000 && !done; ++spin) {
-      while (g < total_lines && line_ok(g)) ++g;
-      done = g == total_lines;
-      if (!done) __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-  }
-  auto all_ok = [&] {
-    for (size_t g = 0; g < total_lines; ++g)
-      if (!line_ok(g)) return false;
-    return true;
-  };
-  if (!done && h->aql_now) {
-    const gwi_status sw = aql_wait_slow(h, all_ok, "group result rows");
-    if (sw != GWI_OK) return sw;
-    std::atomic_thread_fence(std::memory_order_acquire);
-  } else if (!done) {
-    GWI_HIP(hipStreamSynchronize(h->stream));
-    // the lines are posted writes behind the stream's completion: give the last ones a moment to land
-    for (long spin = 0; spin < 4000000 && !all_ok(); ++spin) __builtin_ia32_pause();
-    if (!all_ok()) return fail(h, GWI_ERR_HIP, "group row stamp mismatch after stream synchronise");
-    std::atomic_thread_fence(std::memory_order_acquire);
-  }
-  if (h->timing && h->aql_now) {
-    h->last_ms[2] = 0.0f;
-    if (!aql::timed_collect(h->aq, h->timed_final ? 3 : 2, h->last_ms)) return fail(h, GWI_ERR_HIP, "dispatch timestamps of the AQL queue are not available");
-  } else if (h->timing) {
-    GWI_HIP(hipStreamSynchronize(h->stream));
-    h->last_ms[2] = 0.0f;  // host-final mode has no third launch
-    for (int i = 0; i < (h->timed_final ? 3 : 2); ++i) GWI_HIP(hipEventElapsedTime(&h->last_ms[i], h->ev[2 * i], h->ev[2 * i + 1]));
-  }
+  size_t seen = 0;  // the lines before it carry it
+  // (the lines are posted writes behind the stream's completion: after a synchronise the last ones get a moment to land)
+  gwi_status sw = wait_until(h, /*gated=*/true, /*grace=*/4000000, [&] {
+    while (seen < total_lines && *reinterpret_cast<volatile unsigned long long*>(h->h_rows + seen * 8 + 7) == h->seq) ++seen;
+    return seen == total_lines;
+  }, "group result rows", "group row stamp mismatch after stream synchronise");
+  if (sw == GWI_OK) sw = collect_kernel_times(h);
+  if (sw != GWI_OK) return sw;
   const int n_ev = (int)h->n_ev, n_norms = h->spec.n_norms, len = record_len(h);
   for (int k = 0; k < K; ++k) {
     double* r = h->h_record + (size_t)k * len;
@@ -1634,6 +1597,24 @@ gwi_status wait_for_rows(gwi_handle h, int K) {
     r[7] = (double)n_ev;
   }
   return wait_for_norms(h, h->h_record, K);
+}
+
+// The only place that turns this rank's launched evaluation of K points into h_record, h_ev and the normalisers: from the result
+// rows where the launch published rows, else from the final launch's records.
+GWI_HOT gwi_status collect_local(gwi_handle h, int K) {
+  if (h->last_host_rows) return wait_for_rows(h, K);
+  const gwi_status st = wait_for_stamp(h, h->h_fin, K * h->final_groups);
+  if (st != GWI_OK) return st;
+  merge_final_records(h, K);
+  return wait_for_norms(h, h->h_record, K);
+}
+
+// ... and its counterpart behind the in-engine RCCL exchange: the ranks' records of K points in h_gather, [K][world][len]
+gwi_status wait_for_gathered(gwi_handle h, int K) {
+  const size_t stride = (size_t)record_len(h) * (size_t)h->comm_world;
+  const gwi_status st = wait_for_stamp(h, h->h_gather, K, stride);
+  if (st != GWI_OK) return st;
+  return wait_for_norms(h, h->h_gather, K, stride);  // every rank integrates the same grids: rank 0's slots of each point are what assemble() reads
 }
 
 void destroy_impl(gwi_engine* h) {
@@ -1739,6 +1720,70 @@ gwi_status busy_guard(gwi_handle h, const char* who) {
   if (h->poisoned) return fail(h, GWI_ERR_INVALID, std::string(who) + ": an earlier evaluation of this handle timed out or its queue failed; destroy the handle");
   if (h->pending) return fail(h, GWI_ERR_INVALID, std::string(who) + ": an evaluation begun with gwi_eval_begin has not been collected (gwi_eval_end)");
   return GWI_OK;
+}
+
+// What the evaluating entries refuse, in their common order: null arguments (with them the handle without a scan kernel, and a
+// count below 1; no message), a sharded entry without its exchange, a count above max_batch, the options, a host-only handle,
+// a busy or poisoned one.
+gwi_status check_options(gwi_handle h, const gwi_options* opt) {
+  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
+    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
+  return GWI_OK;
+}
+gwi_status check_exchange(gwi_handle h) {
+  return h->nccl_comm || h->shm_base ? GWI_OK : fail(h, GWI_ERR_INVALID, "neither gwi_shm_comm_init nor gwi_comm_init has been called");
+}
+constexpr int kMaxBatchCap = 64;  // what gwi_create clamps max_batch to: the points an entry may hold results of on its stack (finish_points)
+gwi_status check_batch_size(gwi_handle h, int k, const char* name) {
+  return k <= h->max_batch ? GWI_OK : fail(h, GWI_ERR_INVALID, std::string(name) + " exceeds the engine's max_batch (GWI_MAX_BATCH, default 16)");
+}
+// ... its last part; leaves the calling thread on the handle's device
+gwi_status eval_preflight(gwi_handle h, const char* who) {
+  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
+  const gwi_status st = busy_guard(h, who);
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipSetDevice(h->device));
+  return GWI_OK;
+}
+
+// point k's result from records[k][n_ranks][len] (the ranks' records of point k in rank order, as gwi_combine reads them)
+GWI_HOT void assemble_points(gwi_handle h, const double* records, const double* records_sq, int n_ranks, int K, const gwi_options* opt, const double* consts,
+                     gwi_summary* summaries, double* grads, double* norms) {
+  const size_t blk = (size_t)n_ranks * record_len(h);
+  const int n_theta = h->spec.n_theta, n_norms = h->spec.n_norms;
+  for (int k = 0; k < K; ++k) {
+    gwi_summary s;
+    assemble(h, records + k * blk, n_ranks, opt, &s, grads ? grads + (size_t)k * n_theta : nullptr, norms ? norms + (size_t)k * n_norms : nullptr, consts[k],
+             records_sq ? records_sq + k * blk : nullptr);
+    if (summaries) summaries[k] = s;
+  }
+}
+
+// this rank's per-event sites of K collected points (h_ev) into the caller's arrays: with the global constant of point k's assembled
+// summary, logBF_i = logsumexp_i - log N_pe (analysis.py:80); without summaries as they are (the caller adds it after gwi_combine)
+GWI_HOT void local_sites(gwi_handle h, int K, const gwi_summary* summaries, double* log_bfs, double* log_neffs, double* variances) {
+  const size_t n = (size_t)h->n_ev;
+  for (int k = 0; k < K; ++k) {
+    const double* ev = h->h_ev + (size_t)k * 3 * n;
+    if (log_bfs && summaries) {
+      const double shift = summaries[k].log_norm_const - std::log((double)h->n_pe);
+      for (size_t i = 0; i < n; ++i) log_bfs[k * n + i] = ev[i] + shift;
+    } else if (log_bfs) {
+      std::memcpy(log_bfs + k * n, ev, sizeof(double) * n);
+    }
+    if (log_neffs) std::memcpy(log_neffs + k * n, ev + n, sizeof(double) * n);
+    if (variances) std::memcpy(variances + k * n, ev + 2 * n, sizeof(double) * n);
+  }
+}
+
+// The end of every entry that assembles on this handle: K points (at most max_batch <= kMaxBatchCap) from the ranks' records of the last
+// exchange, or this rank's own with n_ranks = 1, under the constants of the last prelude; then this rank's sites.
+GWI_HOT void finish_points(gwi_handle h, const double* records, const double* records_sq, int n_ranks, int K, const gwi_options* opt, gwi_summary* summaries, double* grads,
+                   double* log_bfs, double* log_neffs, double* variances, double* norms) {
+  gwi_summary s[kMaxBatchCap];
+  assemble_points(h, records, records_sq, n_ranks, K, opt, h->host_consts.data(), s, grads, norms);
+  if (summaries) std::memcpy(summaries, s, sizeof(gwi_summary) * K);
+  local_sites(h, K, s, log_bfs, log_neffs, variances);
 }
 
 // ---- the scaffold of the post-processing entries ----------------------------------------------------------------------------------
@@ -2610,7 +2655,7 @@ static gwi_status create_impl(const gwi_spec* spec, const double* const* pe_cols
   if (knobs.spin_wait.set) h->spin_wait = knobs.spin_wait.v != 0;
   for (auto& e : h->ev) GWI_HIP(hipEventCreate(&e));
   if (knobs.max_batch.set) h->max_batch = knobs.max_batch.v;
-  h->max_batch = std::max(1, std::min(64, h->max_batch));
+  h->max_batch = std::max(1, std::min(kMaxBatchCap, h->max_batch));
   h->n_ev = n_ev;
   h->n_pe = n_pe;
   h->n_inj = n_inj;
@@ -2883,25 +2928,18 @@ gwi_status gwi_prepare_combine(gwi_handle h, const double* theta) {
 
 gwi_status gwi_eval_partial(gwi_handle h, const double* theta, double* record_host, double* log_bfs, double* log_neffs, double* variances) {
   if (!h || !theta || !h->variant) return GWI_ERR_INVALID;
-  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
-  gwi_status st = busy_guard(h, "gwi_eval_partial");
-  if (st != GWI_OK) return st;
-  GWI_HIP(hipSetDevice(h->device));
-  st = run_pipeline(h, theta);
+  gwi_status st = eval_preflight(h, "gwi_eval_partial");
+  if (st == GWI_OK) st = run_pipeline(h, theta);
   if (st != GWI_OK) return st;
   if (record_host) std::memcpy(record_host, h->h_record, sizeof(double) * record_len(h));
-  const size_t n = (size_t)h->n_ev;
-  // per-event sites without the global constant (added by the caller after gwi_combine)
-  if (log_bfs) std::memcpy(log_bfs, h->h_ev, sizeof(double) * n);
-  if (log_neffs) std::memcpy(log_neffs, h->h_ev + n, sizeof(double) * n);
-  if (variances) std::memcpy(variances, h->h_ev + 2 * n, sizeof(double) * n);
+  local_sites(h, 1, nullptr, log_bfs, log_neffs, variances);
   return GWI_OK;
 }
 
 gwi_status gwi_combine(gwi_handle h, const double* records, int32_t n_ranks, const gwi_options* opt, gwi_summary* summary, double* grad, double* norms) {
   if (!h || !records || n_ranks < 1 || !opt) return GWI_ERR_INVALID;
-  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
-    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
+  const gwi_status st = check_options(h, opt);
+  if (st != GWI_OK) return st;
   if (opt->marginalize_selection && grad)
     return fail(h, GWI_ERR_UNSUPPORTED, "gradient with marginalize_selection=True needs the squared-weight records, which the caller-exchanged path (gwi_eval_partial / gwi_combine) does not carry: use gwi_eval or gwi_eval_sharded");
   assemble(h, records, n_ranks, opt, summary, grad, norms, h->host_consts[0]);
@@ -2910,13 +2948,12 @@ gwi_status gwi_combine(gwi_handle h, const double* records, int32_t n_ranks, con
 
 gwi_status gwi_eval_begin(gwi_handle h, const double* theta, const gwi_options* opt, int32_t want_grad) {
   if (!h || !theta || !opt || !h->variant) return GWI_ERR_INVALID;
+  gwi_status st = check_options(h, opt);
+  if (st != GWI_OK) return st;
+  // (in this entry's own words; a host-only handle never holds an evaluation, so the common order of the refusals stands)
   if (h->pending) return fail(h, GWI_ERR_INVALID, "gwi_eval_begin: the previous evaluation of this handle has not been collected (gwi_eval_end)");
-  if (h->poisoned) return busy_guard(h, "gwi_eval_begin");
-  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
-    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
-  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
-  GWI_HIP(hipSetDevice(h->device));
-  gwi_status st;
+  st = eval_preflight(h, "gwi_eval_begin");
+  if (st != GWI_OK) return st;
   h->pending_opt = *opt;
   h->pending_sq = opt->marginalize_selection && want_grad;
   if (h->pending_sq) {  // squared-weight pass first: the regular pass then leaves its per-event arrays in place
@@ -2930,35 +2967,28 @@ gwi_status gwi_eval_begin(gwi_handle h, const double* theta, const gwi_options* 
   return GWI_OK;
 }
 
+// gwi_eval_end (one point, batch = false) and gwi_eval_batch_end (the K points of the batch begun)
+static GWI_HOT gwi_status eval_end_impl(gwi_handle h, int K, bool batch, gwi_summary* summaries, double* grads, double* log_bfs, double* log_neffs, double* variances, double* norms) {
+  h->pending = false;
+  h->pending_batch = false;
+  GWI_HIP(hipSetDevice(h->device));
+  gwi_status st = collect_local(h, K);
+  if (st != GWI_OK) return st;
+  if (redo_requested(h)) {  // repeat, blocking (the squared-weight pass, if any, went through run_pipeline already)
+    // a batch kept its points for this; a single evaluation's are in the argument block, which the repeat's prelude rewrites
+    std::vector<double> th;
+    if (!batch) th.assign(h->kargs.theta, h->kargs.theta + h->spec.n_theta);
+    st = repeat_after_redo(h, batch ? h->pending_thetas.data() : th.data(), nullptr, K, batch, false);
+    if (st != GWI_OK) return st;
+  }
+  finish_points(h, h->h_record, (h->pending_sq && grads) ? h->sq_records.data() : nullptr, 1, K, &h->pending_opt, summaries, grads, log_bfs, log_neffs, variances, norms);
+  return GWI_OK;
+}
+
 gwi_status gwi_eval_end(gwi_handle h, gwi_summary* summary, double* grad, double* log_bfs, double* log_neffs, double* variances, double* norms) {
   if (!h) return GWI_ERR_INVALID;
   if (!h->pending || h->pending_batch) return fail(h, GWI_ERR_INVALID, "gwi_eval_end without gwi_eval_begin");
-  h->pending = false;
-  GWI_HIP(hipSetDevice(h->device));
-  gwi_status st;
-  if (h->last_host_rows) {
-    st = wait_for_rows(h, 1);
-  } else {
-    st = wait_for_stamp(h, h->h_fin, h->final_groups);
-    if (st == GWI_OK) merge_final_records(h, 1);
-    if (st == GWI_OK) st = wait_for_norms(h, h->h_record, 1);
-  }
-  if (st != GWI_OK) return st;
-  if (redo_requested(h)) {  // repeat, blocking (the squared-weight pass, if any, ran through run_pipeline already)
-    const std::vector<double> th(h->kargs.theta, h->kargs.theta + h->spec.n_theta);
-    st = repeat_after_redo(h, th.data(), nullptr, 1, false, false);
-    if (st != GWI_OK) return st;
-  }
-  gwi_summary s;
-  assemble(h, h->h_record, 1, &h->pending_opt, &s, grad, norms, h->host_consts[0], (h->pending_sq && grad) ? h->sq_records.data() : nullptr);
-  if (summary) *summary = s;
-  const size_t n = (size_t)h->n_ev;
-  const double shift = s.log_norm_const - std::log((double)h->n_pe);
-  if (log_bfs)
-    for (size_t i = 0; i < n; ++i) log_bfs[i] = h->h_ev[i] + shift;  // logBF_i = logsumexp_i - log N_pe (analysis.py:80)
-  if (log_neffs) std::memcpy(log_neffs, h->h_ev + n, sizeof(double) * n);
-  if (variances) std::memcpy(variances, h->h_ev + 2 * n, sizeof(double) * n);
-  return GWI_OK;
+  return eval_end_impl(h, 1, false, summary, grad, log_bfs, log_neffs, variances, norms);
 }
 
 gwi_status gwi_eval(gwi_handle h, const double* theta, const gwi_options* opt, gwi_summary* summary, double* grad, double* log_bfs, double* log_neffs,
@@ -2970,26 +3000,18 @@ gwi_status gwi_eval(gwi_handle h, const double* theta, const gwi_options* opt, g
 
 gwi_status gwi_eval_batch_begin(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, int32_t want_grad, int32_t want_events) {
   if (!h || !thetas || !opt || !h->variant || k_batch < 1) return GWI_ERR_INVALID;
-  if (k_batch > h->max_batch) return fail(h, GWI_ERR_INVALID, "k_batch exceeds the engine's max_batch (GWI_MAX_BATCH, default 16)");
-  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
-    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
-  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
-  gwi_status st = busy_guard(h, "gwi_eval_batch_begin");
+  gwi_status st = check_batch_size(h, k_batch, "k_batch");
+  if (st == GWI_OK) st = check_options(h, opt);
+  if (st == GWI_OK) st = eval_preflight(h, "gwi_eval_batch_begin");
   if (st != GWI_OK) return st;
-  GWI_HIP(hipSetDevice(h->device));
   const size_t len = (size_t)record_len(h);
   h->pending_opt = *opt;
   h->pending_sq = opt->marginalize_selection && want_grad;
   h->pending_k = k_batch;
   h->pending_thetas.assign(thetas, thetas + (size_t)k_batch * h->spec.n_theta);  // a repeat (reference exponent outrun) needs the points again
   h->batch_events = want_events != 0;
-  // a matrix-core kernel still to be compiled is compiled on the first batched launch, and (GWI_BATCH_AUTOTUNE=1 only) measured
-  // against the 4-tap kernel: blocking, here
-  if (h->mfma_jit_pending && k_batch >= h->mfma_min_batch) h->batch_autotune = try_jit_mfma(h) && h->autotune_wanted;
-  if (h->batch_autotune && h->mfma && k_batch >= h->mfma_min_batch) {
-    st = calibrate_batch_path(h, thetas, k_batch);
-    if (st != GWI_OK) return st;
-  }
+  st = ensure_batch_kernel(h, thetas, k_batch);  // (here, blocking: the launch below is not waited for)
+  if (st != GWI_OK) return st;
   if (h->pending_sq) {  // squared-weight pass first, blocking: the regular pass then leaves its per-event arrays in place
     st = run_pipeline(h, thetas, nullptr, true, k_batch, true, /*square=*/true);
     if (st != GWI_OK) return st;
@@ -3005,40 +3027,7 @@ gwi_status gwi_eval_batch_begin(gwi_handle h, const double* thetas, int32_t k_ba
 gwi_status gwi_eval_batch_end(gwi_handle h, gwi_summary* summaries, double* grads, double* log_bfs, double* log_neffs, double* variances, double* norms) {
   if (!h) return GWI_ERR_INVALID;
   if (!h->pending || !h->pending_batch || h->pending_sharded) return fail(h, GWI_ERR_INVALID, "gwi_eval_batch_end without gwi_eval_batch_begin");
-  h->pending = false;
-  h->pending_batch = false;
-  GWI_HIP(hipSetDevice(h->device));
-  const int K = h->pending_k;
-  gwi_status st;
-  if (h->last_host_rows) {
-    st = wait_for_rows(h, K);
-  } else {
-    st = wait_for_stamp(h, h->h_fin, K * h->final_groups);
-    if (st == GWI_OK) merge_final_records(h, K);
-    if (st == GWI_OK) st = wait_for_norms(h, h->h_record, K);
-  }
-  if (st != GWI_OK) return st;
-  if (redo_requested(h)) {  // repeat, blocking (the squared-weight pass, if any, went through run_pipeline already)
-    st = repeat_after_redo(h, h->pending_thetas.data(), nullptr, K, true, false);
-    if (st != GWI_OK) return st;
-  }
-  const size_t n = (size_t)h->n_ev, len = (size_t)record_len(h);
-  const gwi_options* opt = &h->pending_opt;
-  const bool need_sq = h->pending_sq && grads;
-  const int n_theta = h->spec.n_theta, n_norms = h->spec.n_norms;
-  for (int k = 0; k < K; ++k) {
-    gwi_summary s;
-    assemble(h, h->h_record + k * len, 1, opt, &s, grads ? grads + (size_t)k * n_theta : nullptr, norms ? norms + (size_t)k * n_norms : nullptr, h->host_consts[k],
-             need_sq ? h->sq_records.data() + k * len : nullptr);
-    if (summaries) summaries[k] = s;
-    const double* ev = h->h_ev + (size_t)k * 3 * n;
-    const double shift = s.log_norm_const - std::log((double)h->n_pe);
-    if (log_bfs)
-      for (size_t i = 0; i < n; ++i) log_bfs[k * n + i] = ev[i] + shift;
-    if (log_neffs) std::memcpy(log_neffs + k * n, ev + n, sizeof(double) * n);
-    if (variances) std::memcpy(variances + k * n, ev + 2 * n, sizeof(double) * n);
-  }
-  return GWI_OK;
+  return eval_end_impl(h, h->pending_k, true, summaries, grads, log_bfs, log_neffs, variances, norms);
 }
 
 gwi_status gwi_eval_batch(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, gwi_summary* summaries, double* grads,
@@ -3199,13 +3188,10 @@ gwi_status gwi_shm_exchange_batch(gwi_handle h, const double* records, int32_t k
 gwi_status gwi_eval_sharded(gwi_handle h, const double* theta, const gwi_options* opt, gwi_summary* summary, double* grad, double* log_bfs,
                             double* log_neffs, double* variances, double* norms) {
   if (!h || !theta || !opt || !h->variant) return GWI_ERR_INVALID;
-  if (!h->nccl_comm && !h->shm_base) return fail(h, GWI_ERR_INVALID, "neither gwi_shm_comm_init nor gwi_comm_init has been called");
-  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
-    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
-  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
-  gwi_status st = busy_guard(h, "gwi_eval_sharded");
+  gwi_status st = check_exchange(h);
+  if (st == GWI_OK) st = check_options(h, opt);
+  if (st == GWI_OK) st = eval_preflight(h, "gwi_eval_sharded");
   if (st != GWI_OK) return st;
-  GWI_HIP(hipSetDevice(h->device));
   const size_t len = (size_t)record_len(h);
   const double* const gathered = h->shm_base ? h->shm_gather.data() : h->h_gather;
   auto run = [&](bool square) -> gwi_status {
@@ -3223,29 +3209,20 @@ gwi_status gwi_eval_sharded(gwi_handle h, const double* theta, const gwi_options
     if (rc != 0) return fail(h, GWI_ERR_HIP, std::string("ncclAllGather: ") + (g_nccl.GetErrorString ? g_nccl.GetErrorString(rc) : "error"));
     hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(kBlock), 0, h->stream, h->d_recv, h->h_gather_dev, (int)(len * h->comm_world), h->seq);
     GWI_HIP(hipGetLastError());
-    st_ = wait_for_stamp(h, h->h_gather);
-    if (st_ != GWI_OK) return st_;
-    return wait_for_norms(h, h->h_gather);  // every rank integrates the same grids; rank-0 slots are what assemble() reads
+    return wait_for_gathered(h, 1);
   };
   // in-engine RCCL path: a rank whose scan asked for the two-pass repeat marked its record (negative event count), so
-  // every rank sees the request in the gathered records and all repeat the exchange together
-  auto run_checked = [&](bool square) -> gwi_status {
-    gwi_status st_ = run(square);
-    if (st_ != GWI_OK || h->shm_base) return st_;
+  // every rank sees the request in the gathered records and all repeat the exchange together (the ranks whose tiles were fine
+  // find their references exact as well).  Over shared memory run_pipeline has repeated locally, before publishing.
+  auto marked = [&] {
     bool redo = false;
     for (int r = 0; r < h->comm_world; ++r) redo = redo || h->h_gather[(size_t)r * len + 7] < 0.0;
-    if (!redo) return GWI_OK;
-    // every rank repeats the exchange (the ranks whose tiles were fine find their references exact as well)
-    ++h->redo_count;
-    st_ = run(square);
-    if (st_ != GWI_OK) return st_;
-    redo = false;
-    for (int r = 0; r < h->comm_world; ++r) redo = redo || h->h_gather[(size_t)r * len + 7] < 0.0;
-    if (!redo || !h->variant->has(jit::kSafe)) return GWI_OK;
-    h->kargs.two_pass = 1;
-    st_ = run(square);
-    h->kargs.two_pass = 0;
-    return st_;
+    return redo;
+  };
+  auto run_checked = [&](bool square) -> gwi_status {
+    const gwi_status st_ = run(square);
+    if (st_ != GWI_OK || h->shm_base) return st_;
+    return repeat_while_asked(h, [&] { return run(square); }, marked);
   };
   const bool need_sq = opt->marginalize_selection && grad;
   if (need_sq) {  // a second exchange carries the squared-weight numerators
@@ -3255,15 +3232,7 @@ gwi_status gwi_eval_sharded(gwi_handle h, const double* theta, const gwi_options
   }
   st = run_checked(false);
   if (st != GWI_OK) return st;
-  gwi_summary s;
-  assemble(h, gathered, h->comm_world, opt, &s, grad, norms, h->host_consts[0], need_sq ? h->sq_records.data() : nullptr);
-  if (summary) *summary = s;
-  const size_t n = (size_t)h->n_ev;
-  const double shift = s.log_norm_const - std::log((double)h->n_pe);
-  if (log_bfs)
-    for (size_t i = 0; i < n; ++i) log_bfs[i] = h->h_ev[i] + shift;
-  if (log_neffs) std::memcpy(log_neffs, h->h_ev + n, sizeof(double) * n);
-  if (variances) std::memcpy(variances, h->h_ev + 2 * n, sizeof(double) * n);
+  finish_points(h, gathered, need_sq ? h->sq_records.data() : nullptr, h->comm_world, 1, opt, summary, grad, log_bfs, log_neffs, variances, norms);
   return GWI_OK;
 }
 
@@ -3276,19 +3245,6 @@ static void host_constants(gwi_handle h, const double* thetas, int K, double* co
     prelude(h, thetas + (size_t)k * h->spec.n_theta, th.data(), reinterpret_cast<double (*)[kMaxDerived]>(der.data()), &consts[k]);
 }
 
-// point k's result from records[k][n_ranks][len] (the ranks' records of point k in rank order, as gwi_combine reads them)
-static void assemble_points(gwi_handle h, const double* records, const double* records_sq, int n_ranks, int K, const gwi_options* opt, const double* consts,
-                            gwi_summary* summaries, double* grads, double* norms) {
-  const size_t blk = (size_t)n_ranks * record_len(h);
-  const int n_theta = h->spec.n_theta, n_norms = h->spec.n_norms;
-  for (int k = 0; k < K; ++k) {
-    gwi_summary s;
-    assemble(h, records + k * blk, n_ranks, opt, &s, grads ? grads + (size_t)k * n_theta : nullptr, norms ? norms + (size_t)k * n_norms : nullptr, consts[k],
-             records_sq ? records_sq + k * blk : nullptr);
-    if (summaries) summaries[k] = s;
-  }
-}
-
 // [n_ranks][K][len] -> [K][n_ranks][len]
 static void points_major(const double* in, int n_ranks, int K, size_t len, std::vector<double>& out) {
   out.resize((size_t)n_ranks * K * len);
@@ -3296,46 +3252,24 @@ static void points_major(const double* in, int n_ranks, int K, size_t len, std::
     for (int k = 0; k < K; ++k) std::memcpy(out.data() + ((size_t)k * n_ranks + r) * len, in + ((size_t)r * K + k) * len, sizeof(double) * len);
 }
 
-// this rank's per-event sites of point k with the global constant of the assembled summary
-static void local_sites(gwi_handle h, int K, const gwi_summary* summaries, double* log_bfs, double* log_neffs, double* variances) {
-  const size_t n = (size_t)h->n_ev;
-  for (int k = 0; k < K; ++k) {
-    const double* ev = h->h_ev + (size_t)k * 3 * n;
-    const double shift = summaries[k].log_norm_const - std::log((double)h->n_pe);
-    if (log_bfs)
-      for (size_t i = 0; i < n; ++i) log_bfs[k * n + i] = ev[i] + shift;
-    if (log_neffs) std::memcpy(log_neffs + k * n, ev + n, sizeof(double) * n);
-    if (variances) std::memcpy(variances + k * n, ev + 2 * n, sizeof(double) * n);
-  }
-}
-
 gwi_status gwi_eval_batch_partial(gwi_handle h, const double* thetas, int32_t k, double* records, double* log_bfs, double* log_neffs, double* variances) {
   if (!h || !thetas || !h->variant || k < 1) return GWI_ERR_INVALID;
-  if (k > h->max_batch) return fail(h, GWI_ERR_INVALID, "k exceeds the engine's max_batch (GWI_MAX_BATCH, default 16)");
-  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
-  gwi_status st = busy_guard(h, "gwi_eval_batch_partial");
+  gwi_status st = check_batch_size(h, k, "k");
+  if (st == GWI_OK) st = eval_preflight(h, "gwi_eval_batch_partial");
   if (st != GWI_OK) return st;
-  GWI_HIP(hipSetDevice(h->device));
   h->batch_events = log_bfs || log_neffs || variances;
   st = run_pipeline(h, thetas, nullptr, /*wait=*/true, k, /*batch=*/true);
   if (st != GWI_OK) return st;
   if (records) std::memcpy(records, h->h_record, sizeof(double) * record_len(h) * (size_t)k);
-  const size_t n = (size_t)h->n_ev;
-  // per-event sites without the global constant (added by the caller after gwi_combine_batch)
-  for (int p = 0; p < k; ++p) {
-    const double* ev = h->h_ev + (size_t)p * 3 * n;
-    if (log_bfs) std::memcpy(log_bfs + p * n, ev, sizeof(double) * n);
-    if (log_neffs) std::memcpy(log_neffs + p * n, ev + n, sizeof(double) * n);
-    if (variances) std::memcpy(variances + p * n, ev + 2 * n, sizeof(double) * n);
-  }
+  local_sites(h, k, nullptr, log_bfs, log_neffs, variances);
   return GWI_OK;
 }
 
 gwi_status gwi_combine_batch(gwi_handle h, const double* thetas, int32_t k, const double* records, int32_t n_ranks, const gwi_options* opt, gwi_summary* summaries,
                              double* grads, double* norms) {
   if (!h || !thetas || !records || k < 1 || n_ranks < 1 || !opt) return GWI_ERR_INVALID;
-  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
-    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
+  const gwi_status st = check_options(h, opt);
+  if (st != GWI_OK) return st;
   if (opt->marginalize_selection && grads)
     return fail(h, GWI_ERR_UNSUPPORTED, "gradient with marginalize_selection=True needs the squared-weight records, which the caller-exchanged path (gwi_eval_batch_partial / gwi_combine_batch) does not carry: use gwi_eval_batch_sharded");
   std::vector<double> consts(k), by_point;
@@ -3357,26 +3291,16 @@ static gwi_status rccl_batch_issue(gwi_handle h, const double* thetas, int K, bo
   GWI_HIP(hipGetLastError());
   return GWI_OK;
 }
-static gwi_status rccl_batch_wait(gwi_handle h, int K) {
-  const size_t stride = (size_t)record_len(h) * (size_t)h->comm_world;
-  const gwi_status st = wait_for_stamp(h, h->h_gather, K, stride);
-  if (st != GWI_OK) return st;
-  return wait_for_norms(h, h->h_gather, K, stride);  // every rank integrates the same grids: rank 0's slots of each point
-}
-static bool rccl_batch_redo(const gwi_engine* h) { return *reinterpret_cast<volatile unsigned long long*>(h->h_gather_redo) == h->seq; }
 // after a collected batch: a rank whose scan asked for the two-pass repeat marked its record, every rank sees the mark in the
 // gathered records and all repeat the whole batch together (the single-point path's protocol)
 static gwi_status rccl_batch_repeat(gwi_handle h, const double* thetas, int K, bool square) {
-  if (!rccl_batch_redo(h)) return GWI_OK;
-  ++h->redo_count;
-  gwi_status st = rccl_batch_issue(h, thetas, K, square);
-  if (st == GWI_OK) st = rccl_batch_wait(h, K);
-  if (st != GWI_OK || !rccl_batch_redo(h) || !h->variant->has(jit::kSafe)) return st;
-  h->kargs.two_pass = 1;
-  st = rccl_batch_issue(h, thetas, K, square);
-  if (st == GWI_OK) st = rccl_batch_wait(h, K);
-  h->kargs.two_pass = 0;
-  return st;
+  return repeat_while_asked(
+      h,
+      [&] {
+        const gwi_status st = rccl_batch_issue(h, thetas, K, square);
+        return st == GWI_OK ? wait_for_gathered(h, K) : st;
+      },
+      [&] { return *reinterpret_cast<volatile unsigned long long*>(h->h_gather_redo) == h->seq; });
 }
 
 // Shared memory: this rank's K records through the regular batched path (repeated locally, before publishing, when a scan asks
@@ -3410,31 +3334,24 @@ static gwi_status publish_unexchanged_failure(gwi_handle h, gwi_status st, unsig
 
 static gwi_status sharded_begin_impl(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, int32_t want_grad, int32_t want_events) {
   if (!thetas || !opt || !h->variant || k_batch < 1) return GWI_ERR_INVALID;
-  if (!h->nccl_comm && !h->shm_base) return fail(h, GWI_ERR_INVALID, "neither gwi_shm_comm_init nor gwi_comm_init has been called");
-  if (k_batch > h->max_batch) return fail(h, GWI_ERR_INVALID, "k_batch exceeds the engine's max_batch (GWI_MAX_BATCH, default 16)");
-  if (opt->max_variance_cut && (opt->marginalize_selection || opt->min_neff_cut))
-    return fail(h, GWI_ERR_INVALID, "max_variance_cut requires marginalize_selection and min_neff_cut to be off (analysis.py:237-243)");
-  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
-  gwi_status st = busy_guard(h, "gwi_eval_batch_sharded_begin");
+  gwi_status st = check_exchange(h);
+  if (st == GWI_OK) st = check_batch_size(h, k_batch, "k_batch");
+  if (st == GWI_OK) st = check_options(h, opt);
+  if (st == GWI_OK) st = eval_preflight(h, "gwi_eval_batch_sharded_begin");
   if (st != GWI_OK) return st;
-  GWI_HIP(hipSetDevice(h->device));
   h->pending_opt = *opt;
   h->pending_sq = opt->marginalize_selection && want_grad;
   h->pending_k = k_batch;
   h->pending_thetas.assign(thetas, thetas + (size_t)k_batch * h->spec.n_theta);
   h->batch_events = want_events != 0;
-  // the same batched kernel as gwi_eval_batch would run (a matrix-core kernel still to be compiled is compiled now)
-  if (h->mfma_jit_pending && k_batch >= h->mfma_min_batch) h->batch_autotune = try_jit_mfma(h) && h->autotune_wanted;
-  if (h->batch_autotune && h->mfma && k_batch >= h->mfma_min_batch) {
-    st = calibrate_batch_path(h, thetas, k_batch);
-    if (st != GWI_OK) return st;
-  }
+  st = ensure_batch_kernel(h, thetas, k_batch);  // the same batched kernel as gwi_eval_batch would run
+  if (st != GWI_OK) return st;
   if (h->pending_sq) {  // a first exchange, blocking, carries the K squared-weight records
     if (h->shm_base) {
       st = shm_batch_exchange(h, k_batch, run_pipeline(h, thetas, nullptr, true, k_batch, true, /*square=*/true), h->sq_records);
     } else {
       st = rccl_batch_issue(h, thetas, k_batch, true);
-      if (st == GWI_OK) st = rccl_batch_wait(h, k_batch);
+      if (st == GWI_OK) st = wait_for_gathered(h, k_batch);
       if (st == GWI_OK) st = rccl_batch_repeat(h, thetas, k_batch, true);
       if (st == GWI_OK) h->sq_records.assign(h->h_gather, h->h_gather + (size_t)record_len(h) * h->comm_world * k_batch);
     }
@@ -3469,39 +3386,31 @@ static gwi_status sharded_end_impl(gwi_handle h, gwi_summary* summaries, double*
   const double* recs;
   int n_ranks;
   if (h->shm_base) {
-    if (h->last_host_rows) {
-      st = wait_for_rows(h, K);
-    } else {
-      st = wait_for_stamp(h, h->h_fin, K * h->final_groups);
-      if (st == GWI_OK) merge_final_records(h, K);
-      if (st == GWI_OK) st = wait_for_norms(h, h->h_record, K);
-    }
-    if (st == GWI_OK && redo_requested(h)) st = repeat_after_redo(h, thetas, nullptr, K, true, false);  // before publishing
+    st = collect_local(h, K);
+    if (st == GWI_OK) st = repeat_after_redo(h, thetas, nullptr, K, true, false);  // before publishing
     st = shm_batch_exchange(h, K, st, by_point);
     if (st != GWI_OK) return st;
     recs = by_point.data();
     n_ranks = h->shm_world;
   } else {
-    st = rccl_batch_wait(h, K);
+    st = wait_for_gathered(h, K);
     if (st == GWI_OK) st = rccl_batch_repeat(h, thetas, K, false);
     if (st != GWI_OK) return st;
     recs = h->h_gather;
     n_ranks = h->comm_world;
   }
-  std::vector<double> consts(h->host_consts.begin(), h->host_consts.begin() + K);
-  std::vector<gwi_summary> s(K);
-  assemble_points(h, recs, need_sq ? h->sq_records.data() : nullptr, n_ranks, K, &h->pending_opt, consts.data(), s.data(), grads, norms);
-  if (summaries) std::memcpy(summaries, s.data(), sizeof(gwi_summary) * K);
-  local_sites(h, K, s.data(), log_bfs, log_neffs, variances);
+  finish_points(h, recs, need_sq ? h->sq_records.data() : nullptr, n_ranks, K, &h->pending_opt, summaries, grads, log_bfs, log_neffs, variances, norms);
   return GWI_OK;
 }
 
 gwi_status gwi_eval_batch_sharded_begin(gwi_handle h, const double* thetas, int32_t k_batch, const gwi_options* opt, int32_t want_grad, int32_t want_events) {
   if (!h) return GWI_ERR_INVALID;
-  // (a handle with a batch in flight owes that batch's exchange to gwi_eval_batch_sharded_end: nothing is published for the misuse)
-  if (h->pending) return busy_guard(h, "gwi_eval_batch_sharded_begin");
+  // (a handle with a batch in flight owes that batch's exchange to gwi_eval_batch_sharded_end: the call is refused in the common
+  // order, by its arguments or as busy, and nothing is published for the misuse)
+  const bool in_flight = h->pending;
   const unsigned long long seq0 = h->shm_seq;
-  return publish_unexchanged_failure(h, sharded_begin_impl(h, thetas, k_batch, opt, want_grad, want_events), seq0, k_batch);
+  const gwi_status st = sharded_begin_impl(h, thetas, k_batch, opt, want_grad, want_events);
+  return in_flight ? st : publish_unexchanged_failure(h, st, seq0, k_batch);
 }
 
 gwi_status gwi_eval_batch_sharded_end(gwi_handle h, gwi_summary* summaries, double* grads, double* log_bfs, double* log_neffs, double* variances, double* norms) {
@@ -3627,10 +3536,8 @@ static gwi_status fill_log_weights(gwi_handle h, const double* theta, double* lo
 
 gwi_status gwi_log_weights(gwi_handle h, const double* theta, double* pe_logw, double* inj_logw) {
   if (!h || !theta || !h->variant) return GWI_ERR_INVALID;
-  if (h->host_only) return fail(h, GWI_ERR_NO_DEVICE, "host-only handle: no device to evaluate on");
-  gwi_status st = busy_guard(h, "gwi_log_weights");
+  gwi_status st = eval_preflight(h, "gwi_log_weights");
   if (st != GWI_OK) return st;
-  GWI_HIP(hipSetDevice(h->device));
   const size_t n_pe_tot = (size_t)(h->n_ev * h->n_pe), n_inj = (size_t)h->n_inj;
   double log_const = 0.0;
   st = fill_log_weights(h, theta, &log_const);
