@@ -1852,6 +1852,33 @@ struct KernargWarm {
   }
 };
 
+// ---- what the scan kernels share (scan_kernel and scan_pbatch_kernel below, scan_points_body in gwi_mfma.h) --------------
+// the launch's geometry: normaliser workgroups, tiles per event, events, samples per tile and per sample set
+struct TileGeom {
+  int n_norms, tiles, n_ev, chunk_pe, chunk_inj;
+  long long n_pe, n_inj;
+  // out of the preloaded scalars (ScanHead)
+  __device__ __forceinline__ static TileGeom decode(unsigned h_geom, unsigned h_chunks, unsigned hu_n_pe, unsigned hu_n_inj) {
+    TileGeom g;
+    g.n_norms = (int)(h_geom >> (kGeomEventBits + kGeomTilesBits)), g.tiles = (int)((h_geom >> kGeomEventBits) & ((1u << kGeomTilesBits) - 1u));
+    g.n_ev = (int)(h_geom & ((1u << kGeomEventBits) - 1u));
+    g.chunk_pe = unpack_chunk(h_chunks & 0xffffu), g.chunk_inj = unpack_chunk(h_chunks >> 16);
+    g.n_pe = hu_n_pe, g.n_inj = hu_n_inj;
+    return g;
+  }
+};
+
+// the launch's first thread publishes the evaluation's sequence number: the tail launches stamp their results with it.  (Arguments in
+// the order the assignment reads them -- the value first: the other order swaps two loads from the argument block, and the code
+// of 28 kernels moves with them.)
+__device__ __forceinline__ void stamp_sequence(unsigned long long seq, unsigned long long* seq_dev) { *seq_dev = seq; }
+
+// a tile's maximum exponent in whole binades: the reference exponent fast_exp_shift applies
+__device__ __forceinline__ int binades_of(double mm) { return (int)__builtin_rint(fmin(fmax(mm, -7.0e5), 7.0e5) * kLog2e); }
+
+// a sum of weights a record can be normalised to
+__device__ __forceinline__ bool positive_finite(double s) { return s > 0.0 && s < GWI_POS_INF; }
+
 // ---- the scan kernel -----------------------------------------------------------------------------
 // grid = n_ev*tiles_per_event PE workgroups + n_inj_tiles injection workgroups.  A PE workgroup owns `chunk_pe` consecutive samples of ONE event, so its record
 // belongs to that event's logsumexp; an injection workgroup owns `chunk_inj` consecutive
@@ -1918,14 +1945,11 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_kernel(con
 #endif
   // geometry and the first column pointers arrive in scalar registers (ScanHead); everything else comes from the argument block,
   // whose lines are requested now and waited for only after the first trip's column loads have left
-  const int h_n_norms = (int)(h_geom >> (kGeomEventBits + kGeomTilesBits)), h_tiles = (int)((h_geom >> kGeomEventBits) & ((1u << kGeomTilesBits) - 1u));
-  const int h_n_ev = (int)(h_geom & ((1u << kGeomEventBits) - 1u));
-  const int h_chunk_pe = unpack_chunk(h_chunks & 0xffffu), h_chunk_inj = unpack_chunk(h_chunks >> 16);
-  const long long h_n_pe = hu_n_pe, h_n_inj = hu_n_inj;
+  const TileGeom geom = TileGeom::decode(h_geom, h_chunks, hu_n_pe, hu_n_inj);
   // BATCH: blockIdx.y selects the hyper-parameter point; records of point k follow those of k-1 (a single launch of the SAFE
   // instantiation has one grid row)
   const int kb = (BATCH || SAFE) ? (int)blockIdx.y : 0;
-  const int n_norm_blocks = WRITE_LOGW ? 0 : h_n_norms;
+  const int n_norm_blocks = WRITE_LOGW ? 0 : geom.n_norms;
   // The argument block's lines are requested by hand-written scalar loads the compiler does not track (KernargWarm): their
   // destinations are safe only on a path that reaches warm.settle().  The normaliser workgroups below return without it, so the
   // loads are issued AFTER that branch (one scalar compare later).  Round 6 found them issued ahead of it: on the normaliser
@@ -1935,30 +1959,30 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_kernel(con
   if ((int)blockIdx.x < n_norm_blocks) {  // wave-uniform, whole workgroup
     const bool batch_n = BATCH || (SAFE && a.tblocks != nullptr);
     const int j = blockIdx.x;
-    if (blockIdx.x == 0 && kb == 0 && tid == 0) *a.seq_dev = a.norm_seq;  // the tail launches stamp their results with it
-    norm_block(a.norms, batch_n ? a.tblocks[kb].theta : a.theta, a.n_theta, j, a.norm_out_host + kb * h_n_norms + j, a.norm_stamps_host + kb * h_n_norms + j, a.norm_seq, s_theta, &s_wrec[0][0]);
+    if (blockIdx.x == 0 && kb == 0 && tid == 0) stamp_sequence(a.norm_seq, a.seq_dev);  // the tail launches stamp their results with it
+    norm_block(a.norms, batch_n ? a.tblocks[kb].theta : a.theta, a.n_theta, j, a.norm_out_host + kb * geom.n_norms + j, a.norm_stamps_host + kb * geom.n_norms + j, a.norm_seq, s_theta, &s_wrec[0][0]);
     return;
   }
   KernargWarm<(int)sizeof...(Ks), BATCH> warm;
   warm.issue();
   const int b = (int)blockIdx.x - n_norm_blocks;
-  const int n_pe_blocks = h_n_ev * h_tiles;
+  const int n_pe_blocks = geom.n_ev * geom.tiles;
 
   // ---- this workgroup's tile and its first trip's column loads
   long long start, end, base;
   if (b < n_pe_blocks) {
-    const int e = b / h_tiles;
-    const int t = b - e * h_tiles;
-    start = (long long)t * h_chunk_pe;
-    end = start + h_chunk_pe < h_n_pe ? start + h_chunk_pe : h_n_pe;
-    base = (long long)e * h_n_pe;
+    const int e = b / geom.tiles;
+    const int t = b - e * geom.tiles;
+    start = (long long)t * geom.chunk_pe;
+    end = start + geom.chunk_pe < geom.n_pe ? start + geom.chunk_pe : geom.n_pe;
+    base = (long long)e * geom.n_pe;
   } else {
     const int t = b - n_pe_blocks;
-    start = (long long)t * h_chunk_inj;
-    end = start + h_chunk_inj < h_n_inj ? start + h_chunk_inj : h_n_inj;
+    start = (long long)t * geom.chunk_inj;
+    end = start + geom.chunk_inj < geom.n_inj ? start + geom.chunk_inj : geom.n_inj;
     base = 0;
   }
-  const long long col_base = b < n_pe_blocks ? base : inj_offset(h_n_ev, h_n_pe);  // where this workgroup's sample set starts inside every column
+  const long long col_base = b < n_pe_blocks ? base : inj_offset(geom.n_ev, geom.n_pe);  // where this workgroup's sample set starts inside every column
   // column pointers: the first kHeadCols slots from the preloaded arguments, the rest from the argument block (the generic
   // chain indexes the block's table at run time); one pointer serves both sample sets
   const double* const head_cols[kHeadCols] = {hc0, hc1, hc2, hc3, hc4};
@@ -2003,7 +2027,7 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_kernel(con
   const int h_n_theta = a.n_theta;
   const bool batch = BATCH || (SAFE && a.tblocks != nullptr);
   const double* theta_src = batch ? a.tblocks[kb].theta : a.theta;
-  if (!WRITE_LOGW && n_norm_blocks == 0 && blockIdx.x == 0 && kb == 0 && tid == 0) *a.seq_dev = a.norm_seq;  // (with normaliser workgroups, the first of them does it)
+  if (!WRITE_LOGW && n_norm_blocks == 0 && blockIdx.x == 0 && kb == 0 && tid == 0) stamp_sequence(a.norm_seq, a.seq_dev);  // (with normaliser workgroups, the first of them does it)
   double* const logw = b < n_pe_blocks ? a.logw_pe : a.logw_inj;
 
   // theta -> LDS only where lane-varying indices need it (spline coefficients, normaliser grids): one value per thread
@@ -2190,7 +2214,7 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_kernel(con
       if (lane == 0) s_wrec[wave][2] = mx;
       __syncthreads();
       const double mm = uniform(fmax(fmax(s_wrec[0][2], s_wrec[1][2]), fmax(s_wrec[2][2], s_wrec[3][2])));
-      if (mm != GWI_NEG_INF) n_ref = __builtin_amdgcn_readfirstlane((int)__builtin_rint(fmin(fmax(mm, -7.0e5), 7.0e5) * kLog2e));
+      if (mm != GWI_NEG_INF) n_ref = __builtin_amdgcn_readfirstlane(binades_of(mm));
       __syncthreads();  // s_wrec[.][2] is used again below
     }
   }
@@ -2265,11 +2289,11 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_kernel(con
   // n_ref would have produced (see n_ref above).
   auto total = [&](int v) { return (s_part[0][v] + s_part[1][v]) + (s_part[2][v] + s_part[3][v]); };
   const double S1 = total(0), S2 = total(1);
-  const bool has_sum = S1 > 0.0 && S1 < GWI_POS_INF;
+  const bool has_sum = positive_finite(S1);
   const int e_norm = has_sum ? ilogb(S1) : 0;
   if (tid == 0) {
     const double mm = fmax(fmax(s_wrec[0][2], s_wrec[1][2]), fmax(s_wrec[2][2], s_wrec[3][2]));
-    const int n_max = (mm == GWI_NEG_INF) ? kNoRef : (int)__builtin_rint(fmin(fmax(mm, -7.0e5), 7.0e5) * kLog2e);
+    const int n_max = (mm == GWI_NEG_INF) ? kNoRef : binades_of(mm);
     *nref_slot = n_max;  // the next evaluation's reference (and, if this one has to be repeated, the repeat's: exact)
     const int dist = n_max - n_ref;
     if (n_max != kNoRef && (dist > ref_slack || dist < -ref_slack)) {
@@ -2331,22 +2355,19 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_pbatch_ker
   __shared__ double s_m[kWaves][kPbatchMaxPts];
   __shared__ double s_out[kWaves][GWI_MAX_THETA];  // per wave: theta slots of the record being completed
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h_n_norms = (int)(h_geom >> (kGeomEventBits + kGeomTilesBits)), h_tiles = (int)((h_geom >> kGeomEventBits) & ((1u << kGeomTilesBits) - 1u));
-  const int h_n_ev = (int)(h_geom & ((1u << kGeomEventBits) - 1u));
-  const int h_chunk_pe = unpack_chunk(h_chunks & 0xffffu), h_chunk_inj = unpack_chunk(h_chunks >> 16);
-  const long long h_n_pe = hu_n_pe, h_n_inj = hu_n_inj;
+  const TileGeom geom = TileGeom::decode(h_geom, h_chunks, hu_n_pe, hu_n_inj);
   const int K = a.k_batch;
   // the first n_norms x K workgroups of grid row 0 integrate the normaliser grids, one (normaliser, point) each
-  const int n_norm_blocks = h_n_norms * K;
+  const int n_norm_blocks = geom.n_norms * K;
   if ((int)blockIdx.x < n_norm_blocks) {  // wave-uniform, whole workgroup
     if (blockIdx.y != 0) return;
-    const int kb = (int)blockIdx.x / h_n_norms, j = (int)blockIdx.x - kb * h_n_norms;
-    if (blockIdx.x == 0 && tid == 0) *a.seq_dev = a.norm_seq;  // the tail launches stamp their results with it
-    norm_block(a.norms, a.tblocks[kb].theta, a.n_theta, j, a.norm_out_host + kb * h_n_norms + j, a.norm_stamps_host + kb * h_n_norms + j, a.norm_seq, &s_out[0][0], &s_m[0][0]);
+    const int kb = (int)blockIdx.x / geom.n_norms, j = (int)blockIdx.x - kb * geom.n_norms;
+    if (blockIdx.x == 0 && tid == 0) stamp_sequence(a.norm_seq, a.seq_dev);  // the tail launches stamp their results with it
+    norm_block(a.norms, a.tblocks[kb].theta, a.n_theta, j, a.norm_out_host + kb * geom.n_norms + j, a.norm_stamps_host + kb * geom.n_norms + j, a.norm_seq, &s_out[0][0], &s_m[0][0]);
     return;
   }
   const int g_wg = (int)blockIdx.x - n_norm_blocks;
-  const int n_pe_blocks = h_n_ev * h_tiles;
+  const int n_pe_blocks = geom.n_ev * geom.tiles;
   const long long n_blocks_total = (long long)n_pe_blocks + a.n_inj_tiles;
   // ---- which (tile, point) UNITS this workgroup evaluates, in tile-major order u = tile x K + point.
   // rows mode (pbatch_pts > 0): tile blockIdx.x, the pbatch_pts points of grid row blockIdx.y.  Balanced mode (pbatch_pts = -G < 0,
@@ -2380,7 +2401,7 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_pbatch_ker
   const double* kappa_col = hc0;
   ChainT chain;
   double kap[kU];
-  if (n_norm_blocks == 0 && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *a.seq_dev = a.norm_seq;
+  if (n_norm_blocks == 0 && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) stamp_sequence(a.norm_seq, a.seq_dev);
   for (int p = lane; p < a.n_theta; p += 64) s_out[wave][p] = 0.0;  // wave-private: no barrier needed before its own use
   // theta slot of every scalar sum (the same for every point)
   int th[kNV];
@@ -2403,16 +2424,16 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_pbatch_ker
       b = b_seg;
       long long start, end, col_base;
       if (b < n_pe_blocks) {
-        const int e = b / h_tiles;
-        const int t = b - e * h_tiles;
-        start = (long long)t * h_chunk_pe;
-        end = start + h_chunk_pe < h_n_pe ? start + h_chunk_pe : h_n_pe;
-        col_base = (long long)e * h_n_pe;
+        const int e = b / geom.tiles;
+        const int t = b - e * geom.tiles;
+        start = (long long)t * geom.chunk_pe;
+        end = start + geom.chunk_pe < geom.n_pe ? start + geom.chunk_pe : geom.n_pe;
+        col_base = (long long)e * geom.n_pe;
       } else {
         const int t = b - n_pe_blocks;
-        start = (long long)t * h_chunk_inj;
-        end = start + h_chunk_inj < h_n_inj ? start + h_chunk_inj : h_n_inj;
-        col_base = inj_offset(h_n_ev, h_n_pe);
+        start = (long long)t * geom.chunk_inj;
+        end = start + geom.chunk_inj < geom.n_inj ? start + geom.chunk_inj : geom.n_inj;
+        col_base = inj_offset(geom.n_ev, geom.n_pe);
       }
       n_tile = (int)(end - start);
 #pragma unroll
@@ -2519,7 +2540,7 @@ __global__ __launch_bounds__(kBlock, GWI_SCAN_WAVES_PER_EU) void scan_pbatch_ker
   }  // segments
 }
 
-// ---- the tail as separate launches (GWI_FUSED_TAIL=0, and the reference point for A/B timing) -------
+// ---- the tail launches: combine_kernel, one workgroup per (group of tile records, point): combine_group; final_kernel: final_reduce ----
 __global__ __launch_bounds__(kBlock) void combine_kernel(const TailArgs a) { combine_group(a, blockIdx.x, blockIdx.y, threadIdx.x); }
 
 constexpr int kFinalThreads = 1024;

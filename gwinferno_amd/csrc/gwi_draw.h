@@ -68,6 +68,12 @@ __device__ inline double live_log_weight(const Segment& s, long long j, double l
   return on && fabs(v) < __builtin_inf() ? v : -__builtin_inf();
 }
 
+// v q rounded once on its own: never contracted into the addition that follows
+__device__ inline double scaled(double v, double q) {
+#pragma clang fp contract(off)
+  return v * q;
+}
+
 struct OpMax {
   template <class T>
   __device__ T operator()(T a, T b) const { return a > b ? a : b; }

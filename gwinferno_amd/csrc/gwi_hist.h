@@ -98,12 +98,6 @@ __global__ __launch_bounds__(kBlock) void hist_tile_kernel(const Args a) {
   }
 }
 
-// v q rounded once on its own: never contracted into the addition that follows
-__device__ inline double scaled(double v, double q) {
-#pragma clang fp contract(off)
-  return v * q;
-}
-
 template <bool kWeighted>
 __global__ __launch_bounds__(kBlock) void hist_merge_kernel(const Args a) {
   const int seg = a.first_seg + (int)blockIdx.x, c = (int)blockIdx.y, b = (int)threadIdx.x;
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void hist_merge_kernel(const Args a) {
 #pragma unroll 8
   for (int t = 0; t < s.n_tiles; ++t) sum += p[(long long)t * stride];
   double* h = a.hist + ((long long)seg * a.n_cols + c) * a.n_bins + b;
-  if constexpr (kWeighted) *h += scaled(pv, sum / total);
+  if constexpr (kWeighted) *h += draw::scaled(pv, sum / total);
   else *h += sum / total;
 }
 

@@ -382,7 +382,7 @@ __device__ __forceinline__ void scan_points_body(const KArgs& a) {
   if (ROWS)
     for (int p = tid; p < rows_rep * kPts * th_pad; p += kBlock) s_grad[p] = 0.0;
 
-  if (blockIdx.x == 0 && group == 0 && tid == 0) *a.seq_dev = a.norm_seq;
+  if (blockIdx.x == 0 && group == 0 && tid == 0) stamp_sequence(a.norm_seq, a.seq_dev);
   if ((int)blockIdx.x < a.n_norms) {  // grid normalisers of the group's points, one after the other
     __shared__ double s_ntheta[GWI_MAX_THETA];
     const int jn = blockIdx.x;
@@ -505,7 +505,7 @@ __device__ __forceinline__ void scan_points_body(const KArgs& a) {
     for (int w_ = 0; w_ < kWaves; ++w_)
 #pragma unroll
       for (int q_ = 0; q_ < 4; ++q_) mm = fmax(mm, s_mx[w_][q_ * 16 + tid]);
-    const int n_max = (mm == GWI_NEG_INF) ? kNoRef : (int)__builtin_rint(fmin(fmax(mm, -7.0e5), 7.0e5) * kLog2e);
+    const int n_max = (mm == GWI_NEG_INF) ? kNoRef : binades_of(mm);
     if (kb_raw < a.k_batch) {
       *nref_slot = n_max;
       const int dist = n_max - n_ref;
@@ -548,7 +548,7 @@ __device__ __forceinline__ void scan_points_body(const KArgs& a) {
 #pragma unroll
         for (int q_ = 0; q_ < 4; ++q_) r += s_stage[w_ * 64 + q_ * 16 + tid];
       if (v == 0) {
-        const bool has_sum = r > 0.0 && r < GWI_POS_INF;
+        const bool has_sum = positive_finite(r);
         e_norm = has_sum ? ilogb(r) : 0;
         s_enorm[tid] = e_norm;
         if (kb_raw < a.k_batch) {
@@ -556,7 +556,7 @@ __device__ __forceinline__ void scan_points_body(const KArgs& a) {
           out_j[1] = has_sum ? ldexp(r, -e_norm) : 0.0;
         }
       }
-      if (v == 1 && kb_raw < a.k_batch) out_j[2] = (r > 0.0 && r < GWI_POS_INF) ? ldexp(r, -2 * e_norm) : 0.0;
+      if (v == 1 && kb_raw < a.k_batch) out_j[2] = positive_finite(r) ? ldexp(r, -2 * e_norm) : 0.0;
       if (v >= 2) s_outK[tid * th_pad + th[v]] += r;  // tid == j here; several accumulators may feed one slot (in order)
     }
   }

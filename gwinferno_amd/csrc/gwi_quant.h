@@ -104,12 +104,6 @@ __device__ inline Column column_of(const Args& a, int seg, int c) {
   return Column{a.w_inj, a.x_inj + at, a.order_inj + at, a.n_inj, a.n_ev * a.tiles_per_event, a.n_inj_tiles};
 }
 
-// v q rounded once on its own: never contracted into the addition that follows
-__device__ inline double scaled(double v, double q) {
-#pragma clang fp contract(off)
-  return v * q;
-}
-
 template <bool kWeighted>
 __global__ __launch_bounds__(kBlock) void marg_add_kernel(const MargArgs a) {
   const int tile = blockIdx.x, n_pe_tiles = a.d.n_ev * a.d.tiles_per_event;
@@ -139,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void marg_add_kernel(const MargArgs a) {
     if (j < s.n) {
       const double v = draw::live_log_weight(s, j, a.d.log_const);
       if (v > -__builtin_inf()) {  // (a sample without weight would add +0.0)
-        if constexpr (kWeighted) w[j] += scaled(pv, exp(v - big) / total);
+        if constexpr (kWeighted) w[j] += draw::scaled(pv, exp(v - big) / total);
         else w[j] += exp(v - big) / total;
       }
     }
