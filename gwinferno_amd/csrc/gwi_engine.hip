@@ -12,6 +12,7 @@
 #include "gwi_hist.h"
 #include "gwi_cdf.h"
 #include "gwi_pit.h"
+#include "gwi_rank.h"
 #include "gwi_quant.h"
 #include "gwi_kde.h"
 #include "gwi_jit.h"
@@ -512,6 +513,16 @@ struct PostprocessBuffers {
     int cols = 0;
   } kde;
 };
+// ... and of the exact per-event PITs (gwi_rank.h): the injections' orders and the PE samples' ranks of gwi_set_rank_columns, and the
+// entry's own workspace -- the injection tiles' sums and offsets [2][n_cols][n_inj_tiles], the prefix table P [n_cols][n_inj + 1], the
+// event tiles' partial sums [n_ev tiles_per_event][n_cols][2] and the staged rows [64][n_ev][n_cols][2] and flags [64][n_ev + 1]
+// (allocated with the columns, kept).  A record of its own at the END of the engine: PostprocessBuffers sits in the middle of it, and
+// growing it moved every field the evaluation path reads after it, which the single-evaluation benchmark saw (1.2 % at config 2).
+struct RankBuffers {
+  DeviceBuffer<int> d_order_inj, d_rank_lt, d_rank_le, d_dead;
+  DeviceBuffer<double> d_tiles, d_prefix, d_partial, d_stage;
+  int cols = 0;
+};
 }  // namespace
 
 struct gwi_engine {
@@ -643,6 +654,7 @@ struct gwi_engine {
   KArgs& kargs = sblock.k;
   long long inj_off = 0;     // element offset of the injections inside every column allocation (inj_offset)
   std::vector<char> col_f32;  // per entry of d_cols_pe: a narrow (float32) allocation
+  RankBuffers rank;           // gwi_set_rank_columns / gwi_point_pits_exact (freed with `post`)
 };
 
 namespace {
@@ -1655,6 +1667,7 @@ void destroy_impl(gwi_engine* h) {
   (void)hipFree(h->d_inj_out);
   (void)hipFree(h->d_inj_grad);
   h->post = PostprocessBuffers();
+  h->rank = RankBuffers();
   if (h->nccl_comm && g_nccl.CommDestroy) (void)g_nccl.CommDestroy(h->nccl_comm);
   (void)hipFree(h->d_send);
   (void)hipFree(h->d_recv);
@@ -4131,6 +4144,125 @@ gwi_status gwi_point_pits(gwi_handle h, const double* thetas, int32_t k, double*
 }
 
 void gwi_point_pit_times(double* logw_ms, double* tile_ms, double* pit_ms, int32_t* launches) { g_point_pit_times.report(logw_ms, tile_ms, pit_ms, launches); }
+
+// ---- exact per-event calibration: weighted ranks among the injections (gwi_rank.h) ---------------------------------------------------
+enum { kRankLogw, kRankPrefix, kRankPit };
+static thread_local StageTimes g_point_rank_times;
+
+// what is wrong with the rank columns, or an empty string: every order a permutation of the injections, every rank in [0, n_inj],
+// rank_lt <= rank_le
+static std::string bad_rank_columns(int n_cols, long long n_pe_all, long long n_inj, const int32_t* order_inj, const int32_t* rank_lt, const int32_t* rank_le) {
+  std::vector<unsigned char> seen((size_t)n_inj);
+  for (int c = 0; c < n_cols; ++c) {
+    std::fill(seen.begin(), seen.end(), 0);
+    const int32_t* order = order_inj + (size_t)c * (size_t)n_inj;
+    for (long long r = 0; r < n_inj; ++r) {
+      const long long j = order[r];
+      if (j < 0 || j >= n_inj || seen[(size_t)j])
+        return "order_inj column " + std::to_string(c) + ": rank " + std::to_string(r) + " holds " + std::to_string(j) + ": not a permutation of the " + std::to_string(n_inj) + " injections";
+      seen[(size_t)j] = 1;
+    }
+    const int32_t* lt = rank_lt + (size_t)c * (size_t)n_pe_all;
+    const int32_t* le = rank_le + (size_t)c * (size_t)n_pe_all;
+    for (long long i = 0; i < n_pe_all; ++i) {
+      const std::string where = " column " + std::to_string(c) + ", sample " + std::to_string(i) + ": ";
+      if (lt[i] < 0 || lt[i] > n_inj) return "rank_lt_pe" + where + std::to_string(lt[i]) + " is not in 0 ... n_inj = " + std::to_string(n_inj);
+      if (le[i] < 0 || le[i] > n_inj) return "rank_le_pe" + where + std::to_string(le[i]) + " is not in 0 ... n_inj = " + std::to_string(n_inj);
+      if (lt[i] > le[i]) return "rank_lt_pe" + where + std::to_string(lt[i]) + " exceeds rank_le_pe = " + std::to_string(le[i]);
+    }
+  }
+  return "";
+}
+
+gwi_status gwi_set_rank_columns(gwi_handle h, int32_t n_cols, const int32_t* order_inj, const int32_t* rank_lt_pe, const int32_t* rank_le_pe) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace R = gwi::rank;
+  const char* who = "gwi_set_rank_columns";
+  gwi_status st = post_preflight(h, who, "keep the columns on", "the injection ranks need", [&]() -> std::string {
+    if (n_cols < 1 || n_cols > R::kMaxCols) return "n_cols = " + std::to_string(n_cols) + " is not in 1 ... " + std::to_string(R::kMaxCols);
+    if (!order_inj || !rank_lt_pe || !rank_le_pe) return "order_inj, rank_lt_pe or rank_le_pe is null";
+    if (h->n_pe > 0x7fffffffLL || h->n_inj >= 0x7fffffffLL) return "more samples per segment than an int32 rank can count";
+    return bad_rank_columns(n_cols, h->n_ev * h->n_pe, h->n_inj, order_inj, rank_lt_pe, rank_le_pe);
+  });
+  if (st != GWI_OK) return st;
+  gwi::draw::DrawArgs geometry;
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &geometry, &n_tiles);
+  if (st != GWI_OK) return st;
+  // the previous columns go away first: should an allocation fail, gwi_point_pits_exact refuses until they are set again
+  RankBuffers& rank = h->rank;
+  rank = RankBuffers();
+  const size_t n_pe_all = (size_t)(h->n_ev * h->n_pe), n_inj = (size_t)h->n_inj, cols = (size_t)n_cols;
+  const size_t n_prefix = cols * (n_inj + 1);
+  GWI_HIP(rank.d_order_inj.upload(order_inj, cols * n_inj));
+  GWI_HIP(rank.d_rank_lt.upload(rank_lt_pe, cols * n_pe_all));
+  GWI_HIP(rank.d_rank_le.upload(rank_le_pe, cols * n_pe_all));
+  GWI_HIP(rank.d_tiles.reserve(2 * cols * (size_t)geometry.n_inj_tiles));
+  GWI_HIP(rank.d_prefix.reserve(n_prefix));
+  GWI_HIP(rank.d_partial.reserve((size_t)(h->n_ev * geometry.tiles_per_event) * cols * 2));
+  GWI_HIP(rank.d_stage.reserve((size_t)R::kStagePoints * (size_t)h->n_ev * cols * 2));
+  GWI_HIP(rank.d_dead.reserve((size_t)R::kStagePoints * (size_t)(h->n_ev + 1)));
+  GWI_HIP(hipMemset(rank.d_prefix, 0, sizeof(double) * n_prefix));  // (an empty injection set launches nothing that would store P[c][0])
+  rank.cols = n_cols;
+  return GWI_OK;
+}
+
+gwi_status gwi_point_pits_exact(gwi_handle h, const double* thetas, int32_t k, double* pit, int32_t* dead) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_pits_exact";
+  g_point_rank_times = StageTimes();
+  RankBuffers& rank = h->rank;
+  gwi_status st = post_preflight(h, who, "sum on", "the injection ranks need", [&]() -> std::string {
+    if (!h->variant) return "the engine has no scan kernel";
+    if (!rank.cols) return "no rank columns are set (gwi_set_rank_columns)";
+    if (!thetas || k < 1) return "thetas is null or k < 1";
+    if (!pit) return "pit is null";
+    if (!dead) return "dead is null";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  namespace R = gwi::rank;
+  R::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);  // (as gwi_set_rank_columns found it)
+  if (st != GWI_OK) return st;
+  const size_t n_segs = (size_t)(h->n_ev + 1), per_point = (size_t)h->n_ev * (size_t)rank.cols * 2;
+  const unsigned cols = (unsigned)rank.cols, inj_tiles = (unsigned)a.d.n_inj_tiles, pe_tiles = (unsigned)(h->n_ev * a.d.tiles_per_event);
+  a.order_inj = rank.d_order_inj;
+  a.rank_lt = rank.d_rank_lt;
+  a.rank_le = rank.d_rank_le;
+  a.tile_sum = rank.d_tiles;
+  a.tile_off = rank.d_tiles + (size_t)rank.cols * (size_t)a.d.n_inj_tiles;
+  a.prefix = rank.d_prefix;
+  a.partial = rank.d_partial;
+  a.n_cols = rank.cols;
+  const auto prefix = [&](int) {
+    if (!inj_tiles) return;
+    hipLaunchKernelGGL(R::rank_tile_kernel, dim3(inj_tiles, cols), dim3(R::kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(R::rank_merge_kernel, dim3(cols), dim3(R::kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(R::rank_prefix_kernel, dim3(inj_tiles, cols), dim3(R::kBlock), 0, h->stream, a);
+  };
+  const auto sum = [&](int p) {  // into the point's slot of the stage
+    const size_t slot = (size_t)(p % R::kStagePoints);
+    a.pit = rank.d_stage + slot * per_point;
+    a.dead = rank.d_dead + slot * n_segs;
+    if (pe_tiles) hipLaunchKernelGGL(R::pit_rank_kernel, dim3(pe_tiles, cols), dim3(R::kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(R::pit_rank_merge_kernel, dim3((unsigned)n_segs, cols), dim3(R::kBlock), 0, h->stream, a);
+  };
+  const auto copy_back = [&](int p) -> gwi_status {
+    const int slot = p % R::kStagePoints;
+    if (slot + 1 == R::kStagePoints || p + 1 == k) {  // the staged rows go back: 2 n_ev n_cols doubles and n_ev + 1 ints per point
+      const size_t first = (size_t)(p - slot), n = (size_t)(slot + 1);
+      if (per_point) GWI_HIP(hipMemcpy(pit + first * per_point, rank.d_stage, sizeof(double) * n * per_point, hipMemcpyDeviceToHost));
+      GWI_HIP(hipMemcpy(dead + first * n_segs, rank.d_dead, sizeof(int) * n * n_segs, hipMemcpyDeviceToHost));
+    }
+    return GWI_OK;
+  };
+  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_rank_times, 2, 7, prefix, sum, copy_back);
+}
+
+void gwi_point_rank_times(double* logw_ms, double* prefix_ms, double* pit_ms, int32_t* launches) { g_point_rank_times.report(logw_ms, prefix_ms, pit_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

@@ -31,7 +31,11 @@ states the codes, :func:`point_cdfs_reference` one point, and :func:`weighted_pe
 
 ``gwi_point_pits`` (gwinferno_amd/csrc/gwi_pit.h) multiplies, per point, every event's normalised bins into the injection set's CDF: a
 rigorous bracket of the event's probability integral transform under the predicted detected distribution.  :func:`pit_bracket` states
-the loop and :func:`point_pits_reference` one point."""
+the loop and :func:`point_pits_reference` one point.
+
+``gwi_point_pits_exact`` (gwinferno_amd/csrc/gwi_rank.h) gives the same transform without a grid, as the weighted rank of every PE sample
+among the injections: :func:`rank_codes` states the theta-independent ranks and :func:`point_pits_exact_reference` one point;
+:func:`pareto_smooth` and :func:`pareto_smoothed_summary` smooth the leave-one-out weights on the point axis."""
 import bisect
 import itertools
 import math
@@ -378,7 +382,7 @@ def leave_one_out_summary(log_l_event):
     of ones for the injection set, which has no event of its own; ``elpd_loo (n_ev,)``: ``-log mean_k exp(-l_ke)``, the logarithm of
     the event's leave-one-out predictive density (importance sampling; summed over the events it compares two population models
     fitted to one catalog); ``lpd (n_ev,)``: ``log mean_k exp(l_ke)``, the same without leaving the event out; ``neff_points
-    (n_ev,)``: ``(sum_k v)^2 / sum_k v^2``, the effective number of points -- the only reliability diagnostic (no Pareto smoothing);
+    (n_ev,)``: ``(sum_k v)^2 / sum_k v^2``, the effective number of points -- the reliability diagnostic of these raw weights (:func:`pareto_smoothed_summary` smooths them);
     ``n_bad (n_ev,)``: the points at which ``l_ke`` is not finite: they get weight 0 and the means run over the other points (NaN
     where there is none)."""
     ell = np.asarray(log_l_event, dtype=np.float64)
@@ -555,3 +559,174 @@ def weighted_kde2d_reference(W, x, y, gridx, gridy, rule="scott", scale=1.0):
         arg = (-0.5 * hyy / det) * ex[i] ** 2 + (hxy / det) * ex[i] * ey + (-0.5 * hxx / det) * ey**2
         rho[i] = np.sum(np.exp(arg) * pl[None, :], axis=1)
     return rho / (2.0 * np.pi * np.sqrt(det)), np.array([hxx, hxy, hyy]), n_eff, 0
+
+
+MAX_RANK_COLUMNS = 8  # columns of gwi_set_rank_columns (gwi_rank.h: kMaxCols)
+
+
+def rank_codes(pe_values, inj_values):
+    """The theta-independent setup of ``gwi_point_pits_exact``: ``pe_values (n_cols, n_ev, n_pe)`` and ``inj_values
+    (n_cols, n_inj)``, finite -> ``(order_inj (n_cols, n_inj), rank_lt (n_cols, n_ev, n_pe), rank_le (n_cols, n_ev, n_pe))``, all
+    int32.  Per column ``order_inj`` is a stable argsort of the injection values, ``rank_lt`` the number of injections with ``x_inj <
+    x`` (``np.searchsorted(..., "left")``) and ``rank_le`` the number with ``x_inj <= x`` (``"right"``) of every PE sample: numbers in
+    ``[0, n_inj]`` with ``rank_lt <= rank_le``, equal unless the sample ties with an injection."""
+    pe, inj = np.asarray(pe_values, dtype=np.float64), np.asarray(inj_values, dtype=np.float64)
+    if pe.ndim != 3 or inj.ndim != 2 or pe.shape[0] != inj.shape[0]:
+        raise ValueError(f"pe_values is (n_cols, n_ev, n_pe) and inj_values (n_cols, n_inj); got {pe.shape} and {inj.shape}")
+    if not 1 <= pe.shape[0] <= MAX_RANK_COLUMNS:
+        raise ValueError(f"{pe.shape[0]} columns: between 1 and {MAX_RANK_COLUMNS} can be ranked")
+    if inj.shape[1] >= 2**31 - 1:
+        raise ValueError("more injections than an int32 rank can count")
+    if not np.all(np.isfinite(pe)) or not np.all(np.isfinite(inj)):
+        raise ValueError("the values must be finite")
+    order = np.argsort(inj, axis=-1, kind="stable")
+    lt, le = np.empty(pe.shape, dtype=np.int32), np.empty(pe.shape, dtype=np.int32)
+    for c in range(pe.shape[0]):
+        ascending = inj[c][order[c]]
+        lt[c] = np.searchsorted(ascending, pe[c], side="left")
+        le[c] = np.searchsorted(ascending, pe[c], side="right")
+    return np.ascontiguousarray(order, dtype=np.int32), lt, le
+
+
+def _rounded_prefix(w):
+    """``P (n + 1,)`` with ``P[r] = w[0] + ... + w[r-1]``, every entry the EXACT sum rounded once (integer arithmetic on the doubles'
+    bits, as :func:`weighted_quantiles_reference`'s prefix); ``w`` finite and non-negative."""
+    ints, low = _exact_integers(w)
+    cum = [0] + list(itertools.accumulate(ints))
+    if low < 0:
+        den = 2 ** (-low)
+        return np.array([c / den for c in cum], dtype=np.float64)  # (true division of integers rounds once)
+    return np.array([float(c * 2**low) for c in cum], dtype=np.float64)
+
+
+def point_pits_exact_reference(logw_pe, logw_inj, pe_mask, inj_mask, order_inj, rank_lt, rank_le):
+    """One hyper-parameter point of ``gwi_point_pits_exact``: ``logw_pe (n_ev, n_pe)``, ``logw_inj (n_inj,)``, the masks of
+    ``gwi_set_draw_mask`` (or None) and the arrays of :func:`rank_codes` -> ``(pit (n_ev, n_cols, 2), dead (n_ev + 1,) int32)``.  With
+    ``u`` and ``w`` of :func:`draw_weights` for the injection set and the event, ``P[c][r]`` the sum of ``u`` over the first ``r``
+    injections along ``order_inj[c]`` (exact, rounded once), ``T_c = P[c][n_inj]`` and ``S`` the event's total (``math.fsum``):
+
+    ``pit[e][c] = (fsum_i w_i P[c][rank_lt_i] / S / T_c, fsum_i w_i P[c][rank_le_i] / S / T_c)``
+
+    -- the event's un-gridded probability integral transform under ``F_det(x) = share of detected weight with x_inj < x`` (first) or
+    ``x_inj <= x`` (second); the two differ only through ties between the two sets, and their midpoint is the expectation of the
+    randomised PIT.  NaN for an event whose ``S`` is 0 or not finite, and everywhere when the injection set's total is; ``dead`` flags
+    the segments without weight, the injection set last."""
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    order_inj, rank_lt, rank_le = np.asarray(order_inj), np.asarray(rank_lt), np.asarray(rank_le)
+    n_ev, n_pe = logw_pe.shape
+    n_cols, n_inj = order_inj.shape
+    if rank_lt.shape != (n_cols, n_ev, n_pe) or rank_le.shape != rank_lt.shape:
+        raise ValueError("rank_lt and rank_le are (n_cols, n_ev, n_pe)")
+    if rank_lt.size and (rank_lt.min() < 0 or rank_le.max() > n_inj or np.any(rank_lt > rank_le)):
+        raise ValueError("the ranks lie in [0, n_inj] with rank_lt <= rank_le")
+    pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(n_ev, n_pe)
+    pit, dead = np.full((n_ev, n_cols, 2), np.nan), np.zeros(n_ev + 1, dtype=np.int32)
+    u = draw_weights(logw_inj, inj_mask)
+    t_all = math.fsum(u.tolist())
+    inj_alive = t_all > 0.0 and np.isfinite(t_all)
+    dead[n_ev] = 0 if inj_alive else 1
+    prefix = [_rounded_prefix(u[order_inj[c].astype(np.int64)]) for c in range(n_cols)] if inj_alive else None
+    for ev in range(n_ev):
+        w = draw_weights(logw_pe[ev], None if pe_mask is None else pe_mask[ev])
+        total = math.fsum(w.tolist())
+        alive = total > 0.0 and np.isfinite(total)
+        dead[ev] = 0 if alive else 1
+        if not (alive and inj_alive):
+            continue
+        for c in range(n_cols):
+            p = prefix[c]
+            for i, ranks in enumerate((rank_lt[c, ev], rank_le[c, ev])):
+                pit[ev, c, i] = math.fsum((w * p[ranks]).tolist()) / total / p[n_inj]
+    return pit, dead
+
+
+def pareto_smooth(log_ratios):
+    """Pareto-smoothed importance sampling on the point axis (Vehtari, Simpson, Gelman, Yao & Gabry, *Pareto smoothed importance
+    sampling*; the fit is Zhang & Stephens 2009): ``log_ratios (K, n_seg)`` -> ``(log_weights (K, n_seg), khat (n_seg,))``.  Per column:
+    the maximum is subtracted; the tail is the ``M = min(floor(K / 5), ceil(3 sqrt K))`` largest entries and ``cutoff`` the largest
+    below it; a generalised Pareto distribution is fitted to ``exp(tail) - exp(cutoff)`` (the profile-likelihood posterior mean of
+    Zhang & Stephens over ``30 + floor(sqrt M)`` points, then ``khat = (M k + 5) / (M + 10)``, the weakly informative pull towards
+    0.5); the tail's values are replaced, in ascending order, by ``log(exp(cutoff) + sigma expm1(-khat log1p(-p_i)) / khat)`` with
+    ``p_i = (i - 1/2) / M`` and truncated at the raw maximum, 0 after the shift.  Every entry outside the tail keeps the bits of the
+    shifted input, and the order of the tail's values does not decrease.  With ``M < 5`` or a constant tail nothing is smoothed and
+    ``khat`` is inf.  Every entry must be finite.  ``khat`` below 0.5 is good, up to 0.7 usable, above it the estimate is unreliable;
+    the value is reported and nothing is refitted."""
+    lr = np.array(log_ratios, dtype=np.float64)
+    if lr.ndim != 2 or lr.shape[0] < 1:
+        raise ValueError("log_ratios is (K, n_seg) with K >= 1")
+    if not np.all(np.isfinite(lr)):
+        raise ValueError("log_ratios must be finite")
+    k_pts, n_seg = lr.shape
+    khat = np.full(n_seg, np.inf)
+    m_tail = min(k_pts // 5, int(math.ceil(3.0 * math.sqrt(k_pts))))
+    for s in range(n_seg):
+        col = lr[:, s] - lr[:, s].max()
+        lr[:, s] = col
+        if m_tail < 5:
+            continue
+        order = np.argsort(col, kind="stable")
+        tail_at = order[k_pts - m_tail :]  # ascending
+        cutoff = col[order[k_pts - m_tail - 1]]
+        tail = col[tail_at]
+        if not tail[-1] > tail[0]:
+            continue
+        x = np.exp(tail) - math.exp(cutoff)
+        if not x[int(m_tail / 4.0 + 0.5) - 1] > 0.0:  # (the lowest quarter of the tail ties with the cutoff: the fit has no scale)
+            continue
+        k_fit, sigma = _gpd_fit(x)
+        kh = (m_tail * k_fit + 5.0) / (m_tail + 10.0)
+        khat[s] = kh
+        p = (np.arange(1, m_tail + 1, dtype=np.float64) - 0.5) / m_tail
+        with np.errstate(divide="ignore", invalid="ignore"):
+            q = sigma * np.expm1(-kh * np.log1p(-p)) / kh if kh != 0.0 else -sigma * np.log1p(-p)
+            new = np.log(math.exp(cutoff) + q)
+        lr[tail_at, s] = np.minimum(new, 0.0)
+    return lr, khat
+
+
+def _gpd_fit(x):
+    """Zhang & Stephens' estimate ``(k, sigma)`` of the generalised Pareto distribution for the ascending positive sample ``x (n,)``,
+    without the regularisation of ``k``."""
+    n = x.size
+    m = 30 + int(math.sqrt(n))
+    j = np.arange(1, m + 1, dtype=np.float64)
+    b = 1.0 - np.sqrt(m / (j - 0.5))
+    b = b / (3.0 * x[int(n / 4.0 + 0.5) - 1]) + 1.0 / x[n - 1]
+    k = np.mean(np.log1p(-b[:, None] * x[None, :]), axis=1)
+    big_l = n * (np.log(-b / k) - k - 1.0)
+    omega = 1.0 / np.sum(np.exp(big_l[None, :] - big_l[:, None]), axis=1)
+    b_hat = float(np.sum(b * omega))
+    k_hat = float(np.mean(np.log1p(-b_hat * x)))
+    return k_hat, -k_hat / b_hat
+
+
+def pareto_smoothed_summary(log_l_event):
+    """:func:`leave_one_out_summary` with the leave-one-out weights of every event Pareto-smoothed on the point axis
+    (:func:`pareto_smooth` of ``-l_ke`` over the points at which it is finite): the same dictionary with ``point_weights`` the smoothed
+    weights, each event's largest exactly 1 and the injection column all ones; ``pareto_k (n_ev,)`` (inf where nothing was smoothed,
+    NaN for an event without a finite point); ``elpd_loo = log(sum_k v_k exp(l_ke) / sum_k v_k)``, the self-normalised estimate,
+    which is ``-log mean_k exp(-l_ke)`` when nothing is smoothed; and ``neff_points`` of the smoothed weights.  ``lpd`` and ``n_bad``
+    are unchanged."""
+    out = dict(leave_one_out_summary(log_l_event))
+    ell = out["log_l_event"]
+    k, n_ev = ell.shape
+    good = np.isfinite(ell)
+    v = np.ones((k, n_ev + 1))
+    elpd, neff, khat = np.full(n_ev, np.nan), np.zeros(n_ev), np.full(n_ev, np.nan)
+    for e in range(n_ev):
+        v[:, e] = 0.0
+        rows = np.nonzero(good[:, e])[0]
+        if rows.size == 0:
+            continue
+        col = ell[rows, e]
+        lw, kh = pareto_smooth(-col[:, None])
+        lw = lw[:, 0] - lw[:, 0].max()  # (the largest becomes exactly exp(0) = 1)
+        ve = np.exp(lw)
+        v[rows, e] = ve
+        khat[e] = kh[0]
+        s1 = math.fsum(ve.tolist())
+        hi = col.max()
+        elpd[e] = hi + math.log(math.fsum((ve * np.exp(col - hi)).tolist()) / s1)
+        neff[e] = s1 * s1 / math.fsum((ve * ve).tolist())
+    out.update(point_weights=v, elpd_loo=elpd, neff_points=neff, pareto_k=khat)
+    return out

@@ -1,5 +1,6 @@
 """The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
-injection resampling, weighted histograms, per-point CDFs and PIT brackets, marginal weights and their quantiles and kernel density estimates.
+injection resampling, weighted histograms, per-point CDFs, PIT brackets and exact PITs, marginal weights and their quantiles and kernel density
+estimates.
 Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
 """
 import ctypes as C
@@ -251,6 +252,44 @@ class PostprocessMixin:
         pit, cdf_det, dead = np.empty((k, self.n_ev, n_cols, 2)), np.empty((k, n_cols, n_bins)), np.empty((k, self.n_ev + 1), dtype=np.int32)
         self._check(self.lib.gwi_point_pits(self.handle, N.as_dp(thetas), k, N.as_dp(pit), N.as_dp(cdf_det), dead.ctypes.data_as(i32)))
         return pit, cdf_det, dead
+
+    def set_rank_columns(self, pe_values, inj_values):
+        """The quantities :meth:`point_pits_exact` ranks (``gwi_set_rank_columns``): ``pe_values (n_cols, n_ev, n_pe)`` and
+        ``inj_values (n_cols, n_inj)``, finite, both needed; ``1 <= n_cols <= 8``.  The injections' sort order and every PE sample's
+        ranks among the injections (:func:`gwinferno_amd.draws.rank_codes`) are made here and copied to HBM once: they do not depend
+        on theta.  Not available on an engine that holds a shard (``world > 1``)."""
+        from .draws import MAX_RANK_COLUMNS, rank_codes
+
+        self._whole_catalog("set_rank_columns", "the injection ranks need")
+        if pe_values is None or inj_values is None:
+            raise ValueError("a rank is that of a PE sample among the injections: pe_values and inj_values are both needed")
+        pe, inj, n_cols = self._two_sets(pe_values, inj_values, "pe_values", "inj_values")
+        if not 1 <= n_cols <= MAX_RANK_COLUMNS:
+            raise ValueError(f"{n_cols} columns: between 1 and {MAX_RANK_COLUMNS} can be set")
+        order, lt, le = rank_codes(pe, inj)
+        i32 = C.POINTER(C.c_int32)
+        self._rank_shape = None
+        self._check(self.lib.gwi_set_rank_columns(self.handle, n_cols, order.ctypes.data_as(i32), lt.ctypes.data_as(i32), le.ctypes.data_as(i32)))
+        self._rank_shape = (n_cols,)
+
+    def point_pits_exact(self, thetas):
+        """Every event's un-gridded probability integral transform under the predicted detected distribution, per point, on the device
+        (``gwi_point_pits_exact``; semantics: :func:`gwinferno_amd.draws.point_pits_exact_reference`).  ``thetas`` is one
+        point ``(n_theta,)`` or ``(k, n_theta)``.  Returns ``(pit (k, n_ev, n_cols, 2), dead (k, n_ev + 1) int32)``: per point, event
+        and column of :meth:`set_rank_columns` the PIT with ``<`` and with ``<=`` in the detected CDF (they differ only through ties
+        between the two sets; NaN where the event or the injection set has no weight), and 1 for every segment without weight at the
+        point, the injection set last.  ``2 n_ev n_cols`` doubles come back per point; the points may be split over calls without
+        changing a bit.  Not available on an engine that holds a shard (``world > 1``)."""
+        self._whole_catalog("point_pits_exact", "the injection ranks need")
+        thetas = self._points(thetas)
+        k = thetas.shape[0]
+        shape = getattr(self, "_rank_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        if shape is None:
+            self._nothing_set("point_pits_exact", "rank columns are set (set_rank_columns)", self.lib.gwi_point_pits_exact, N.as_dp(thetas), k, None, None)
+        pit, dead = np.empty((k, self.n_ev, shape[0], 2)), np.empty((k, self.n_ev + 1), dtype=np.int32)
+        self._check(self.lib.gwi_point_pits_exact(self.handle, N.as_dp(thetas), k, N.as_dp(pit), dead.ctypes.data_as(i32)))
+        return pit, dead
 
     def marginal_weights_reset(self):
         """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""

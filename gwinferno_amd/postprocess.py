@@ -890,3 +890,99 @@ def event_calibration(eng, thetas, pe_values, grid, inj_values=None, point_weigh
     if loo is not None:
         out["elpd_loo"] = loo["elpd_loo"]
     return out
+
+
+def pareto_smoothed_loo_weights(eng, thetas, total_inj, nobs=None, marginalize_selection=False):
+    """:func:`leave_one_out_weights` with every event's weights Pareto-smoothed on the point axis (Vehtari et al., *Pareto
+    smoothed importance sampling*; :func:`gwinferno_amd.draws.pareto_smooth`): the raw weights ``exp(-l_ke)`` have a heavy right tail
+    when a single point explains event e badly, and the largest ``M = min(K / 5, 3 sqrt K)`` of them are replaced by the quantiles of
+    a generalised Pareto distribution fitted to them.  Takes what :func:`leave_one_out_weights` takes and returns the same dictionary
+    with ``point_weights (K, n_ev + 1)`` the smoothed weights -- each event's largest exactly 1, the injection column all ones, every
+    entry in ``[0, 1]``: they go straight into the ``point_weights=`` arguments of the weighted entries -- ``pareto_k (n_ev,)``, the
+    fitted shape (below 0.5 good, up to 0.7 usable, above it unreliable; inf where fewer than 25 points leave no tail to fit; nothing
+    is refitted), and ``elpd_loo`` and ``neff_points`` recomputed from the smoothed weights."""
+    from .draws import pareto_smoothed_summary
+
+    return pareto_smoothed_summary(leave_one_out_weights(eng, thetas, total_inj, nobs=nobs, marginalize_selection=marginalize_selection)["log_l_event"])
+
+
+def event_calibration_exact(eng, thetas, pe_values, inj_values=None, point_weights=None, leave_one_out=False, total_inj=None, nobs=None, marginalize_selection=False,
+                            pedata=None, injdata=None, param_names=None, m1min=None, m2min=None, mmax=None, backend="device"):
+    """:func:`event_calibration` without a grid: the un-gridded probability integral transform of every event under the
+    predicted detected distribution, ``PIT_kec = sum_i (w_ki / S_ke) F_det,k(x_i)`` with ``F_det`` the weighted rank of the sample
+    among the injections, averaged over the draws.  On the device (``eng.point_pits_exact``) ``2 n_ev C`` doubles come back per point
+    and the weights never leave HBM; no bracket is left to the resolution of a grid, and values that tie between the two sets are
+    treated exactly: ``pit_le`` counts the injections with ``x_inj <= x``, ``pit_lt`` those with ``x_inj < x``, and ``pit``, their
+    midpoint, is the expectation of the randomised PIT.
+
+    The arguments are :func:`event_calibration`'s without ``grid``.  The device backend replaces the engine's rank columns
+    (``eng.set_rank_columns``).  ``leave_one_out="psis"`` takes the weights of :func:`pareto_smoothed_loo_weights` -- with the exact
+    PIT, what ArviZ calls ``loo_pit`` -- and ``leave_one_out=True`` the raw ones.  ``backend="host"`` runs the NumPy statement
+    (:func:`gwinferno_amd.draws.point_pits_exact_reference`) on ``eng.log_weights``: the statement the kernels are tested against, not
+    a fall-back.
+
+    Returns a dict: ``names``; ``pit_lt``, ``pit_le`` and ``pit``, each ``(n_ev, C)``, the weighted means over the points (NaN for an
+    event without a live point of positive weight); ``neff_points (n_ev,)``; ``n_dead (n_ev,)``, the (point, event) pairs skipped
+    because the event or the injection set had no weight; the sorted P-P curves ``pp_levels (n,)``, ``pp_lt``, ``pp_le`` and ``pp (C,
+    n)``; the Kolmogorov distances ``ks_lt``, ``ks_le`` and ``ks (C,)``; the raw ``point_pits (K, n_ev, C, 2)`` and ``dead (K, n_ev +
+    1)``; ``n_points``; with leave-one-out weights ``elpd_loo (n_ev,)``, and with ``"psis"`` also ``pareto_k (n_ev,)``."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    if not (isinstance(leave_one_out, bool) or leave_one_out == "psis"):
+        raise ValueError(f"leave_one_out must be False, True or 'psis', not {leave_one_out!r}")
+    source = pe_values if pe_values is not None else pedata
+    for p in param_names if param_names is not None and source is not None else ():
+        if p not in source:
+            raise ValueError(f"unknown quantity {p!r}")
+    names, x_pe, x_inj = _summary_columns(eng, pe_values, inj_values, pedata, injdata, param_names)
+    if x_inj is None:
+        raise ValueError("the PIT is taken under the predicted detected distribution: inj_values (or injdata) are needed")
+    n_cols, n_ev = len(names), eng.n_ev
+    masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    if leave_one_out == "psis":
+        if point_weights is not None:
+            raise ValueError("leave_one_out='psis' makes the point weights itself: point_weights must be None")
+        if total_inj is None:
+            raise ValueError("leave_one_out='psis' needs total_inj")
+        loo = pareto_smoothed_loo_weights(eng, thetas, total_inj, nobs=nobs, marginalize_selection=marginalize_selection)
+        v = loo["point_weights"]
+    else:
+        v, loo = _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection)
+    v = np.ones((k, n_ev)) if v is None else np.asarray(v, dtype=np.float64)[:, :n_ev]
+    if backend == "device":
+        if masks[0] is not None:
+            eng.set_draw_mask(*masks)
+        eng.set_rank_columns(x_pe, x_inj)
+        raw, dead = eng.point_pits_exact(thetas)
+    else:
+        order, lt, le = D.rank_codes(x_pe, x_inj)
+        raw, dead = np.empty((k, n_ev, n_cols, 2)), np.empty((k, n_ev + 1), dtype=np.int32)
+        for i, th in enumerate(thetas):
+            lw_pe, lw_inj = eng.log_weights(th)
+            raw[i], dead[i] = D.point_pits_exact_reference(lw_pe, lw_inj, masks[0], masks[1], order, lt, le)
+    gone = (dead[:, :n_ev] != 0) | (dead[:, n_ev:] != 0)  # (K, n_ev): the event or the injection set has no weight at the point
+    w = np.where(gone, 0.0, v)
+    wsum, wsq = w.sum(axis=0), (w * w).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = (w[:, :, None, None] * np.where(gone[:, :, None, None], 0.0, raw)).sum(axis=0) / wsum[:, None, None]  # (n_ev, C, 2); NaN without weight
+        neff = np.where(wsum > 0.0, wsum * wsum / wsq, 0.0)
+    lt_mean, le_mean = mean[..., 0], mean[..., 1]
+    mid = 0.5 * (lt_mean + le_mean)
+    has = wsum > 0.0
+    n_has = int(np.count_nonzero(has))
+    curves = [np.sort(a[has], axis=0).T.reshape(n_cols, n_has) for a in (lt_mean, le_mean, mid)]
+    out = {"names": names, "pit_lt": lt_mean, "pit_le": le_mean, "pit": mid, "neff_points": neff, "n_dead": gone.sum(axis=0).astype(np.int64),
+           "pp_levels": np.arange(1, n_has + 1, dtype=np.float64) / max(n_has, 1), "pp_lt": curves[0], "pp_le": curves[1], "pp": curves[2],
+           "ks_lt": np.array([_ks_uniform(c) for c in curves[0]]), "ks_le": np.array([_ks_uniform(c) for c in curves[1]]),
+           "ks": np.array([_ks_uniform(c) for c in curves[2]]), "point_pits": raw, "dead": dead, "n_points": k}
+    if loo is not None:
+        out["elpd_loo"] = loo["elpd_loo"]
+        if "pareto_k" in loo:
+            out["pareto_k"] = loo["pareto_k"]
+    return out

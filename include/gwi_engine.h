@@ -523,7 +523,8 @@ void gwi_point_cdf_times(double* logw_ms, double* tile_ms, double* reduce_ms, in
  * and copied back per chunk.  The masks of gwi_set_draw_mask apply.  No point weights go to the device: a weight on the k axis is
  * applied by the host.  Every sum has a fixed shape and there are no atomics: the bits are a pure function of (theta_k, bins, masks),
  * whatever the split of the points over calls, and the call changes no state another entry reads.
- * Not done: sharded handles; the exact un-gridded PIT; the events' own per-point CDFs travelling back; more than 256 grid points.
+ * Not done: sharded handles; the events' own per-point CDFs travelling back; more than 256 grid points (the exact un-gridded PIT is
+ * gwi_point_pits_exact's, below).
  * GWI_ERR_INVALID (with a gwi_last_error message) for a null thetas, pit or dead, k < 1, a host-only handle, a call before the bins are
  * set and a call while either set has no bins; GWI_ERR_UNSUPPORTED on a handle that holds a shard, as gwi_point_cdfs.
  *
@@ -533,6 +534,42 @@ void gwi_point_cdf_times(double* logw_ms, double* tile_ms, double* reduce_ms, in
 gwi_status gwi_point_pits(gwi_handle h, const double* thetas, int32_t k, double* pit /* [k][n_ev][n_cols][2]: lo, hi */,
                           double* cdf_det /* [k][n_cols][n_bins] or NULL */, int32_t* dead /* [k][n_ev + 1] */);
 void gwi_point_pit_times(double* logw_ms, double* tile_ms, double* pit_ms, int32_t* launches);
+
+/* Exact per-event calibration on the device: per hyper-parameter point and event the UN-GRIDDED probability integral transform of the
+ * event under the predicted detected distribution -- the weighted rank of every PE sample among the injections (gwinferno_amd/csrc/
+ * gwi_rank.h; the NumPy statement is gwinferno_amd/draws.py: rank_codes, point_pits_exact_reference; the contract is DESIGN 8i).  With
+ * Pareto-smoothed leave-one-out weights on the k axis (draws.py: pareto_smooth, applied by the host) it is what ArviZ calls loo_pit.
+ *
+ * gwi_set_rank_columns(): what does not depend on theta, made by the host once.  Per column c, 1 <= n_cols <= 8: order_inj[c] is a
+ * permutation of the injections along which the column's values do not decrease (the library does not sort), rank_lt_pe[c][e][i] the
+ * number of injections whose value lies below that of PE sample i of event e and rank_le_pe[c][e][i] the number at or below it: int32
+ * in [0, n_inj], rank_lt <= rank_le, equal unless the sample ties with an injection.  The arrays are checked in O(n) (every order a
+ * permutation, every rank in range, rank_lt <= rank_le), copied to HBM, and the entry's own workspace is allocated: the prefix table
+ * P[n_cols][n_inj + 1], the tiles' partial sums and staging rows for 64 points.  The workspaces of gwi_set_histogram_bins and
+ * gwi_set_quantile_columns are neither used nor resized.
+ *
+ * gwi_point_pits_exact(): for one point, u_j = exp(lw_j - M) are the injections' weights and w_i those of an event (0 for a masked or
+ * non-finite sample; the masks of gwi_set_draw_mask apply), S_e the event's total, P[c][r] the sum of u over the first r injections
+ * along order_inj[c] and T_c = P[c][n_inj]:
+ *   pit_lt = sum_i w_i P[c][rank_lt_i] / S_e / T_c        pit_le = sum_i w_i P[c][rank_le_i] / S_e / T_c
+ * pit_le is the PIT under F_det(x) = share of detected weight with x_inj <= x, pit_lt uses <; the two differ only through ties between
+ * the two sets, and their midpoint is the expectation of the randomised PIT.  pit[k][n_ev][n_cols][2] holds (lt, le), NaN for an event
+ * whose S is 0 or not finite and everywhere when the injection segment's is; dead[k][n_ev + 1] holds 1 for every segment without weight
+ * at the point, the injection segment last.  k >= 1 is not bound by the batch limit: the points are staged on the device 64 at a time
+ * and copied back per chunk.  Every sum has a fixed shape (rank order inside a tile of 1 024, then tile order) and there are no atomics:
+ * the bits are a pure function of (theta_k, ranks, masks), whatever the split of the points over calls, and the call changes no state
+ * another entry reads.  Not done: sharded handles; more than 8 columns; leave-one-out for the injection segment.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, n_cols outside 1 ... 8, an order that is no permutation, a
+ * rank outside [0, n_inj], rank_lt > rank_le, a host-only handle and a call before the rank columns are set; GWI_ERR_UNSUPPORTED on a
+ * handle that holds a shard.
+ *
+ * gwi_point_rank_times(): DIAGNOSTIC ONLY, for tools/point_ranks_time.py: of the calling thread's last call, summed over its points, the
+ * wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge / three prefix launches
+ * together and of the two PIT launches, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_set_rank_columns(gwi_handle h, int32_t n_cols, const int32_t* order_inj /* [n_cols][n_inj] */, const int32_t* rank_lt_pe /* [n_cols][n_ev][n_pe] */,
+                                const int32_t* rank_le_pe /* [n_cols][n_ev][n_pe] */);
+gwi_status gwi_point_pits_exact(gwi_handle h, const double* thetas, int32_t k, double* pit /* [k][n_ev][n_cols][2]: lt, le */, int32_t* dead /* [k][n_ev + 1] */);
+void gwi_point_rank_times(double* logw_ms, double* prefix_ms, double* pit_ms, int32_t* launches);
 
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is
