@@ -13,6 +13,7 @@
 #include "gwi_cdf.h"
 #include "gwi_pit.h"
 #include "gwi_rank.h"
+#include "gwi_moment.h"
 #include "gwi_quant.h"
 #include "gwi_kde.h"
 #include "gwi_jit.h"
@@ -523,6 +524,13 @@ struct RankBuffers {
   DeviceBuffer<double> d_tiles, d_prefix, d_partial, d_stage;
   int cols = 0;
 };
+// ... and of the per-point moments (gwi_moment.h), which read the columns of gwi_set_kde_columns where they lie: the tiles' sums
+// [n_tiles][n_cols + P] and the staged rows [64][n_ev + 1][n_cols + P] and flags [64][n_ev + 1] (grown on demand, kept).  At the end of
+// the engine for RankBuffers' reason.
+struct MomentBuffers {
+  DeviceBuffer<double> d_partial, d_stage;
+  DeviceBuffer<int> d_dead;
+};
 }  // namespace
 
 struct gwi_engine {
@@ -655,6 +663,7 @@ struct gwi_engine {
   long long inj_off = 0;     // element offset of the injections inside every column allocation (inj_offset)
   std::vector<char> col_f32;  // per entry of d_cols_pe: a narrow (float32) allocation
   RankBuffers rank;           // gwi_set_rank_columns / gwi_point_pits_exact (freed with `post`)
+  MomentBuffers moment;       // gwi_point_moments (freed with `post`)
 };
 
 namespace {
@@ -1668,6 +1677,7 @@ void destroy_impl(gwi_engine* h) {
   (void)hipFree(h->d_inj_grad);
   h->post = PostprocessBuffers();
   h->rank = RankBuffers();
+  h->moment = MomentBuffers();
   if (h->nccl_comm && g_nccl.CommDestroy) (void)g_nccl.CommDestroy(h->nccl_comm);
   (void)hipFree(h->d_send);
   (void)hipFree(h->d_recv);
@@ -4263,6 +4273,72 @@ gwi_status gwi_point_pits_exact(gwi_handle h, const double* thetas, int32_t k, d
 }
 
 void gwi_point_rank_times(double* logw_ms, double* prefix_ms, double* pit_ms, int32_t* launches) { g_point_rank_times.report(logw_ms, prefix_ms, pit_ms, launches); }
+
+// ---- per-point moments: means and full covariance of the KDE columns (gwi_moment.h) -------------------------------------------------
+enum { kMomentLogw, kMomentMean, kMomentCov };
+static thread_local StageTimes g_point_moment_times;
+
+gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, double* out, int32_t* dead) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_moments";
+  g_point_moment_times = StageTimes();
+  PostprocessBuffers::Kde& kde = h->post.kde;
+  gwi_status st = post_preflight(h, who, "sum on", "the injection moments need", [&]() -> std::string {
+    if (!h->variant) return "the engine has no scan kernel";
+    return "";
+  });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_weighted_kde: a shard cannot be given columns, and says that it is one)
+  if (!kde.cols) return fail(h, GWI_ERR_INVALID, "gwi_point_moments: no columns are set (gwi_set_kde_columns)");
+  if (!thetas || k < 1) return fail(h, GWI_ERR_INVALID, "gwi_point_moments: thetas is null or k < 1");
+  if (!out) return fail(h, GWI_ERR_INVALID, "gwi_point_moments: out is null");
+  if (!dead) return fail(h, GWI_ERR_INVALID, "gwi_point_moments: dead is null");
+  namespace M = gwi::moment;
+  M::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);  // (as gwi_set_kde_columns found it)
+  if (st != GWI_OK) return st;
+  const bool with_pe = kde.d_x_pe.ptr != nullptr, with_inj = kde.d_x_inj.ptr != nullptr;
+  const size_t n_segs = (size_t)(h->n_ev + 1), cols = (size_t)kde.cols, pairs = (size_t)M::pairs_of(kde.cols), per_point = n_segs * (cols + pairs);
+  MomentBuffers& mom = h->moment;
+  GWI_HIP(mom.d_partial.reserve((size_t)n_tiles * (cols + pairs)));
+  GWI_HIP(mom.d_stage.reserve((size_t)M::kStagePoints * per_point));
+  GWI_HIP(mom.d_dead.reserve((size_t)M::kStagePoints * n_segs));
+  // a set without columns is left out of the tile launches; its segments come back NaN
+  const QueryCover cover(with_pe, with_inj, h->n_ev, a.d);
+  a.x_pe = kde.d_x_pe;
+  a.x_inj = kde.d_x_inj;
+  a.part1 = mom.d_partial;
+  a.part2 = mom.d_partial + (size_t)n_tiles * cols;
+  a.n_cols = kde.cols;
+  a.first_tile = cover.first_tile;
+  a.first_seg = cover.first_seg;
+  a.n_seg_covered = (int)cover.segs;
+  const auto means = [&](int p) {  // into the point's slot of the stage
+    const size_t slot = (size_t)(p % M::kStagePoints);
+    a.out = mom.d_stage + slot * per_point;
+    a.dead = mom.d_dead + slot * n_segs;
+    if (cover.tiles) hipLaunchKernelGGL(M::moment_sum_kernel, dim3((unsigned)cover.tiles), dim3(M::kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(M::moment_mean_kernel, dim3((unsigned)n_segs), dim3(64), 0, h->stream, a);
+  };
+  const auto covariances = [&](int) {
+    if (cover.tiles) M::launch_cov((unsigned)cover.tiles, h->stream, a);
+    hipLaunchKernelGGL(M::moment_merge_kernel, dim3((unsigned)n_segs), dim3(64), 0, h->stream, a);
+  };
+  const auto copy_back = [&](int p) -> gwi_status {
+    const int slot = p % M::kStagePoints;
+    if (slot + 1 == M::kStagePoints || p + 1 == k) {  // the staged rows go back: (n_ev + 1)(n_cols + P) doubles and n_ev + 1 ints per point
+      const size_t first = (size_t)(p - slot), n = (size_t)(slot + 1);
+      GWI_HIP(hipMemcpy(out + first * per_point, mom.d_stage, sizeof(double) * n * per_point, hipMemcpyDeviceToHost));
+      GWI_HIP(hipMemcpy(dead + first * n_segs, mom.d_dead, sizeof(int) * n * n_segs, hipMemcpyDeviceToHost));
+    }
+    return GWI_OK;
+  };
+  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_moment_times, 2, 6, means, covariances, copy_back);
+}
+
+void gwi_point_moment_times(double* logw_ms, double* mean_ms, double* cov_ms, int32_t* launches) { g_point_moment_times.report(logw_ms, mean_ms, cov_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

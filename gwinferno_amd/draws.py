@@ -640,6 +640,58 @@ def point_pits_exact_reference(logw_pe, logw_inj, pe_mask, inj_mask, order_inj, 
     return pit, dead
 
 
+MAX_MOMENT_COLUMNS = 8  # columns of gwi_point_moments (gwi_moment.h: kMaxCols)
+
+
+def moments_segment(w, x):
+    """``(mean (C,), cov (C, C), alive)`` of ONE segment with the weights ``w (n,)`` of :func:`draw_weights` and the values ``x (C, n)``,
+    in two passes: ``S = fsum w``, ``m_c = fsum_i (w_i x_ci) / S`` and, centred on those means, ``V_cd = fsum_i ((w_i (x_ci - m_c))
+    (x_di - m_d)) / S`` -- every product rounded on its own, every sum exact and rounded once (``math.fsum``).  NaN and ``alive =
+    False`` where ``S`` is 0 or not finite.  A segment with one live sample has ``w = 1`` and ``S = 1``: the mean is the sample and the
+    covariance exactly 0."""
+    w, x = np.asarray(w, dtype=np.float64).ravel(), np.asarray(x, dtype=np.float64)
+    n_cols = x.shape[0]
+    mean, cov = np.full(n_cols, np.nan), np.full((n_cols, n_cols), np.nan)
+    total = math.fsum(w.tolist())
+    if not (total > 0.0 and np.isfinite(total)):
+        return mean, cov, False
+    live = w > 0.0
+    w, x = w[live], x[:, live]
+    for c in range(n_cols):
+        mean[c] = math.fsum((w * x[c]).tolist()) / total
+    d = x - mean[:, None]
+    for c in range(n_cols):
+        wd = w * d[c]
+        for e in range(c, n_cols):
+            cov[c, e] = cov[e, c] = math.fsum((wd * d[e]).tolist()) / total
+    return mean, cov, True
+
+
+def point_moments_reference(logw_pe, logw_inj, x_pe, x_inj, pe_mask=None, inj_mask=None):
+    """One hyper-parameter point of ``gwi_point_moments``: ``logw_pe (n_ev, n_pe)``, ``logw_inj (n_inj,)``, the values
+    ``x_pe (C, n_ev, n_pe)`` and ``x_inj (C, n_inj)`` (``None``: the set has no columns) and the masks of ``gwi_set_draw_mask`` (or
+    None) -> ``(mean (n_ev + 1, C), cov (n_ev + 1, C, C), dead (n_ev + 1,) int32)``, the injection set last: per segment
+    :func:`moments_segment` on the weights of :func:`draw_weights`.  NaN for a segment without weight, which ``dead`` flags, and for a
+    set without columns."""
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    n_ev, n_pe = logw_pe.shape
+    if x_pe is None and x_inj is None:
+        raise ValueError("x_pe and x_inj are both None")
+    n_cols = (x_pe if x_pe is not None else x_inj).shape[0]
+    if not 1 <= n_cols <= MAX_MOMENT_COLUMNS:
+        raise ValueError(f"{n_cols} columns: between 1 and {MAX_MOMENT_COLUMNS}")
+    pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(n_ev, n_pe)
+    mean, cov, dead = np.full((n_ev + 1, n_cols), np.nan), np.full((n_ev + 1, n_cols, n_cols), np.nan), np.zeros(n_ev + 1, dtype=np.int32)
+    for seg in range(n_ev + 1):
+        w = draw_weights(logw_pe[seg], None if pe_mask is None else pe_mask[seg]) if seg < n_ev else draw_weights(logw_inj, inj_mask)
+        x = (None if x_pe is None else np.asarray(x_pe)[:, seg]) if seg < n_ev else x_inj
+        total = math.fsum(w.tolist())
+        dead[seg] = 0 if total > 0.0 and np.isfinite(total) else 1
+        if x is not None and not dead[seg]:
+            mean[seg], cov[seg], _ = moments_segment(w, x)
+    return mean, cov, dead
+
+
 def pareto_smooth(log_ratios):
     """Pareto-smoothed importance sampling on the point axis (Vehtari, Simpson, Gelman, Yao & Gabry, *Pareto smoothed importance
     sampling*; the fit is Zhang & Stephens 2009): ``log_ratios (K, n_seg)`` -> ``(log_weights (K, n_seg), khat (n_seg,))``.  Per column:

@@ -1,5 +1,5 @@
 """The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
-injection resampling, weighted histograms, per-point CDFs, PIT brackets and exact PITs, marginal weights and their quantiles and kernel density
+injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs and moments, marginal weights and their quantiles and kernel density
 estimates.
 Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
 """
@@ -290,6 +290,32 @@ class PostprocessMixin:
         pit, dead = np.empty((k, self.n_ev, shape[0], 2)), np.empty((k, self.n_ev + 1), dtype=np.int32)
         self._check(self.lib.gwi_point_pits_exact(self.handle, N.as_dp(thetas), k, N.as_dp(pit), dead.ctypes.data_as(i32)))
         return pit, dead
+
+    def point_moments(self, thetas):
+        """Per-point means and full covariance of every segment, on the device (``gwi_point_moments``; semantics:
+        :func:`gwinferno_amd.draws.point_moments_reference`).  The quantities are the columns of :meth:`set_kde_columns`,
+        read where they lie.  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.  Returns ``(mean (k, n_ev + 1, C), cov (k,
+        n_ev + 1, C, C), dead (k, n_ev + 1) int32)``, the injection set last: the weighted means ``sum_i (w_i / S) x_ci``, the
+        symmetric covariance ``sum_i (w_i / S)(x_ci - m_c)(x_di - m_d)`` centred on them (filled from the upper triangle the device
+        returns) and 1 for every segment without weight at the point.  NaN for a segment without weight and for a set without
+        columns; exactly 0 covariance for a segment with one live sample.  ``(n_ev + 1)(C + C (C + 1) / 2)`` doubles come back per
+        point; the points may be split over calls without changing a bit.  Not available on an engine that holds a shard
+        (``world > 1``)."""
+        self._whole_catalog("point_moments", "the injection moments need")
+        thetas = self._points(thetas)
+        k = thetas.shape[0]
+        shape = getattr(self, "_kde_shape", None)
+        i32 = C.POINTER(C.c_int32)
+        if shape is None:
+            self._nothing_set("point_moments", "columns are set (set_kde_columns)", self.lib.gwi_point_moments, N.as_dp(thetas), k, None, None)
+        n_cols = shape[0]
+        iu = np.triu_indices(n_cols)
+        raw, dead = np.empty((k, self.n_ev + 1, n_cols + iu[0].size)), np.empty((k, self.n_ev + 1), dtype=np.int32)
+        self._check(self.lib.gwi_point_moments(self.handle, N.as_dp(thetas), k, N.as_dp(raw), dead.ctypes.data_as(i32)))
+        cov = np.empty((k, self.n_ev + 1, n_cols, n_cols))
+        cov[..., iu[0], iu[1]] = raw[..., n_cols:]
+        cov[..., iu[1], iu[0]] = raw[..., n_cols:]
+        return np.ascontiguousarray(raw[..., :n_cols]), cov, dead
 
     def marginal_weights_reset(self):
         """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""

@@ -986,3 +986,203 @@ def event_calibration_exact(eng, thetas, pe_values, inj_values=None, point_weigh
         if "pareto_k" in loo:
             out["pareto_k"] = loo["pareto_k"]
     return out
+
+
+def _moment_points(eng, thetas, x_pe, x_inj, masks, backend):
+    """``(mean (K, n_ev + 1, C), cov (K, n_ev + 1, C, C), dead (K, n_ev + 1))`` of the points on either backend."""
+    from . import draws as D
+
+    if backend == "device":
+        if masks[0] is not None:
+            eng.set_draw_mask(*masks)
+        eng.set_kde_columns(x_pe, x_inj)
+        return eng.point_moments(thetas)
+    k, n_cols, n_segs = thetas.shape[0], x_pe.shape[0], eng.n_ev + 1
+    mean, cov, dead = np.empty((k, n_segs, n_cols)), np.empty((k, n_segs, n_cols, n_cols)), np.empty((k, n_segs), dtype=np.int32)
+    for i, th in enumerate(thetas):
+        lw_pe, lw_inj = eng.log_weights(th)
+        mean[i], cov[i], dead[i] = D.point_moments_reference(lw_pe, lw_inj, x_pe, x_inj, masks[0], masks[1])
+    return mean, cov, dead
+
+
+def _checked_names(pe_values, pedata, param_names):
+    source = pe_values if pe_values is not None else pedata
+    for p in param_names if param_names is not None and source is not None else ():
+        if p not in source:
+            raise ValueError(f"unknown quantity {p!r}")
+
+
+def catalog_correlation_check(eng, thetas, pe_values, inj_values=None, pairs=None, levels=(0.05, 0.5, 0.95), point_weights=None, pedata=None, injdata=None,
+                              param_names=None, m1min=None, m2min=None, mmax=None, backend="device"):
+    """Does the catalog's correlation between two quantities agree with the one the fitted population predicts for detected sources?
+      Every model the engine evaluates is a product of one-dimensional densities, and the checks of one coordinate at a
+    time cannot see a correlation the data demand.  Per hyper-posterior point k the observed catalog is the equal-weight mixture of its
+    live events' population-informed posteriors, with mean and covariance
+
+    ``mu_obs = mean_e m_ke``        ``Sigma_obs = mean_e [V_ke + (m_ke - mu_obs)(m_ke - mu_obs)^T]``
+
+    from the events' per-point means ``m_ke`` and covariances ``V_ke``; the prediction is the injection segment's ``V_det,k``.  A
+    correlation is a ratio of centred second moments and has to be taken point by point: on the device (``eng.point_moments``) ``(n_ev
+    + 1)(C + C (C + 1) / 2)`` doubles come back per point and the weights never leave HBM.
+
+    ``thetas`` is ``(K, n_theta)``.  ``pe_values`` / ``inj_values`` (or ``pedata`` / ``injdata`` with ``param_names``), the mass cuts
+    and the masks are :func:`catalog_predictive_check`'s; without ``inj_values`` there is no predicted side (NaN).  ``pairs`` holds
+    pairs of names or of column indices (default: every pair ``c < d``).  ``point_weights (K,)`` -- finite, non-negative, not all 0;
+    default equal -- weight the points in the bands (:func:`gwinferno_amd.draws.weighted_percentiles`) and in the shares; they are
+    applied here and never go to the device.  The device backend replaces the engine's KDE columns.  ``backend="host"`` runs the NumPy
+    statement (:func:`gwinferno_amd.draws.point_moments_reference`) on ``eng.log_weights``: the statement the kernels are tested
+    against, not a fall-back.
+
+    Returns a dict: ``names``; ``pairs (n_pairs, 2)`` column indices; ``levels``; per point and pair ``rho_obs``, ``rho_det`` and
+    ``delta = rho_obs - rho_det``, each ``(K, n_pairs)``; ``bands_rho_obs``, ``bands_rho_det`` and ``bands_delta (Q, n_pairs)``;
+    ``p_delta_positive (n_pairs,)``, the weighted share of the points with ``delta > 0`` among those where it is a number, and
+    ``p_two_sided = 2 min(p, 1 - p)``, the tail probability of "no difference"; the same for the covariances themselves, which need no
+    division: ``cov_obs``, ``cov_det``, ``delta_cov``, ``bands_cov_obs``, ``bands_cov_det``, ``bands_delta_cov``,
+    ``p_delta_cov_positive`` and ``p_cov_two_sided``.  A correlation is the covariance standardised by the two variances: where a
+    variance is 0 within rounding (at most ``(64 * 2^-52 mu)^2``) or not finite nothing is divided, the correlation is NaN and ``degenerate_obs`` / ``degenerate_det
+    (K, n_pairs)`` flag it.  Also ``mu_obs (K, C)``, ``sigma_obs (K, C, C)``, ``mu_det``, ``sigma_det``; ``n_live (K,)``, the live
+    events per point; ``dead_detected``, the points at which the injection set had no weight; the raw ``point_mean``, ``point_cov``
+    and ``dead`` of ``eng.point_moments``; ``n_points``."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or levels.size < 1 or not np.all((levels >= 0.0) & (levels <= 1.0)):
+        raise ValueError("levels must be numbers in [0, 1]")
+    _checked_names(pe_values, pedata, param_names)
+    names, x_pe, x_inj = _summary_columns(eng, pe_values, inj_values, pedata, injdata, param_names)
+    n_cols, n_ev = len(names), eng.n_ev
+    if pairs is None:
+        pairs = [(c, d) for c in range(n_cols) for d in range(c + 1, n_cols)]
+    pairs = [tuple(names.index(p) if isinstance(p, str) else int(p) for p in pair) for pair in pairs]
+    if not pairs or any(len(p) != 2 or not all(0 <= c < n_cols for c in p) for p in pairs):
+        raise ValueError(f"pairs are pairs of names or of column indices below {n_cols}, at least one")
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if point_weights is None:
+        v = np.ones(k)
+    else:
+        v = np.asarray(point_weights, dtype=np.float64)
+        if v.shape != (k,) or not np.all(np.isfinite(v)) or np.any(v < 0.0) or not np.any(v > 0.0):
+            raise ValueError(f"point_weights are ({k},) finite non-negative numbers, not all 0")
+    masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    mean, cov, dead = _moment_points(eng, thetas, x_pe, x_inj, masks, backend)
+    live = dead[:, :n_ev] == 0                                    # (K, n_ev)
+    n_live = live.sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        share = live / n_live[:, None]                            # NaN rows where no event is live
+        m = np.where(live[:, :, None], mean[:, :n_ev], 0.0)
+        mu_obs = np.einsum("ke,kec->kc", share, m)
+        dm = np.where(live[:, :, None], mean[:, :n_ev] - mu_obs[:, None, :], 0.0)
+        spread = np.where(live[:, :, None, None], cov[:, :n_ev], 0.0) + dm[:, :, :, None] * dm[:, :, None, :]
+        sigma_obs = np.einsum("ke,kecd->kcd", share, spread)
+    mu_det, sigma_det = mean[:, n_ev], cov[:, n_ev]
+
+    def standardised(sigma, mu):
+        """``(covariance, correlation, flag)`` per point and pair: nothing is divided where a variance is not finite or does not exceed
+        ``(64 * 2^-52 |mu|)^2`` -- a constant column's mean carries a rounding of its own, so its centred values are a few ulps of
+        the mean, not 0, and a standard deviation of that size is what the arithmetic cannot tell from none"""
+        c, d = pairs[:, 0], pairs[:, 1]
+        s_cd, s_cc, s_dd = sigma[:, c, d], sigma[:, c, c], sigma[:, d, d]
+        floor = (64.0 * 2.0**-52 * np.abs(mu)) ** 2
+        with np.errstate(invalid="ignore"):
+            ok = (s_cc > floor[:, c]) & (s_dd > floor[:, d]) & np.isfinite(s_cc) & np.isfinite(s_dd)
+        rho = np.full(s_cd.shape, np.nan)
+        rho[ok] = s_cd[ok] / np.sqrt(s_cc[ok] * s_dd[ok])
+        return s_cd, rho, (~ok & ~np.isnan(s_cc) & ~np.isnan(s_dd)).astype(np.int32)
+
+    def shares(delta):
+        """the weighted share of the points with delta > 0 among those where delta is a number, and the two-sided tail"""
+        has = ~np.isnan(delta)
+        den = (v[:, None] * has).sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p = (v[:, None] * (has & (np.where(has, delta, 0.0) > 0.0))).sum(axis=0) / den
+        return p, 2.0 * np.minimum(p, 1.0 - p)
+
+    cov_obs, rho_obs, flag_obs = standardised(sigma_obs, mu_obs)
+    cov_det, rho_det, flag_det = standardised(sigma_det, mu_det)
+    delta, delta_cov = rho_obs - rho_det, cov_obs - cov_det
+    p_rho, p_cov = shares(delta), shares(delta_cov)
+    out = {"names": names, "pairs": pairs, "levels": levels, "rho_obs": rho_obs, "rho_det": rho_det, "delta": delta, "cov_obs": cov_obs, "cov_det": cov_det,
+           "delta_cov": delta_cov, "p_delta_positive": p_rho[0], "p_two_sided": p_rho[1], "p_delta_cov_positive": p_cov[0], "p_cov_two_sided": p_cov[1],
+           "degenerate_obs": flag_obs, "degenerate_det": flag_det, "mu_obs": mu_obs, "sigma_obs": sigma_obs, "mu_det": mu_det, "sigma_det": sigma_det,
+           "n_live": n_live.astype(np.int64), "dead_detected": int(np.count_nonzero(dead[:, n_ev])) if x_inj is not None else k, "point_mean": mean, "point_cov": cov,
+           "dead": dead, "n_points": k}
+    for key in ("rho_obs", "rho_det", "delta", "cov_obs", "cov_det", "delta_cov"):
+        out["bands_" + key] = D.weighted_percentiles(out[key], v, levels)
+    return out
+
+
+def event_variance_split(eng, thetas, pe_values, point_weights=None, leave_one_out=False, total_inj=None, nobs=None, marginalize_selection=False, pedata=None,
+                         injdata=None, param_names=None, m1min=None, m2min=None, mmax=None, backend="device"):
+    """How much of an event's population-informed variance is hyper-posterior uncertainty and how much its own measurement?  (DESIGN
+    8j.)  :func:`event_credible_intervals` reports the standard deviation under the marginal weights, which is the total.  With the
+    per-point means ``m_k`` and variances ``V_cc,k`` of the event (``eng.point_moments``) and normalised point weights ``v_k``, the law
+    of total variance splits it:
+
+    ``within = sum_k v_k V_cc,k``    ``between = sum_k v_k (m_k - mbar)^2``, ``mbar = sum_k v_k m_k``    ``total = within + between``
+
+    ``within`` is the event's measurement under a fixed population, ``between`` what moving the population moves.
+
+    ``thetas`` is ``(K, n_theta)``.  ``pe_values`` (or ``pedata`` with ``param_names``), the mass cuts and the masks are
+    :func:`event_credible_intervals`'.  The weights on the k axis are applied here, on the host: equal by default, ``point_weights
+    (K,)`` or ``(K, n_ev + 1)`` (the last column is not used), with ``leave_one_out=True`` those of :func:`leave_one_out_weights` and
+    with ``leave_one_out="psis"`` those of :func:`pareto_smoothed_loo_weights` (``total_inj`` is needed; ``nobs`` and
+    ``marginalize_selection`` as there).  A (point, event) at which the event has no weight is skipped and counted in ``n_dead``.  The
+    device backend replaces the engine's KDE columns.  ``backend="host"`` runs the NumPy statement
+    (:func:`gwinferno_amd.draws.point_moments_reference`) on ``eng.log_weights``: the statement the kernels are tested against, not a
+    fall-back.
+
+    Returns a dict: ``names``; ``mean``, ``within``, ``between``, ``total`` and ``fraction_between = between / total``, each ``(n_ev,
+    C)`` (NaN for an event without a live point of positive weight; ``fraction_between`` also where ``total`` is 0); ``neff_points
+    (n_ev,)``, ``(sum_k v)^2 / sum_k v^2`` over the points that count; ``n_dead (n_ev,)``; the raw ``point_mean (K, n_ev + 1, C)``,
+    ``point_cov (K, n_ev + 1, C, C)`` and ``dead (K, n_ev + 1)``; ``n_points``; with leave-one-out weights ``elpd_loo (n_ev,)``, and
+    with ``"psis"`` also ``pareto_k (n_ev,)``."""
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    if not (isinstance(leave_one_out, bool) or leave_one_out == "psis"):
+        raise ValueError(f"leave_one_out must be False, True or 'psis', not {leave_one_out!r}")
+    _checked_names(pe_values, pedata, param_names)
+    names, x_pe, _ = _summary_columns(eng, pe_values, None, pedata, None, param_names)
+    n_cols, n_ev = len(names), eng.n_ev
+    masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    if leave_one_out == "psis":
+        if point_weights is not None:
+            raise ValueError("leave_one_out='psis' makes the point weights itself: point_weights must be None")
+        if total_inj is None:
+            raise ValueError("leave_one_out='psis' needs total_inj")
+        loo = pareto_smoothed_loo_weights(eng, thetas, total_inj, nobs=nobs, marginalize_selection=marginalize_selection)
+        v = loo["point_weights"]
+    else:
+        v, loo = _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection)
+    v = np.ones((k, n_ev)) if v is None else np.asarray(v, dtype=np.float64)[:, :n_ev]
+    mean, cov, dead = _moment_points(eng, thetas, x_pe, None, masks, backend)
+    gone = dead[:, :n_ev] != 0                                    # (K, n_ev): the event has no weight at the point
+    w = np.where(gone, 0.0, v)
+    wsum, wsq = w.sum(axis=0), (w * w).sum(axis=0)
+    diag = np.arange(n_cols)
+    m = np.where(gone[:, :, None], 0.0, mean[:, :n_ev])          # (K, n_ev, C)
+    var = np.where(gone[:, :, None], 0.0, cov[:, :n_ev][..., diag, diag])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vn = w / wsum                                             # NaN columns where an event has no point that counts
+        mbar = (vn[:, :, None] * m).sum(axis=0)
+        within = (vn[:, :, None] * var).sum(axis=0)
+        between = (vn[:, :, None] * np.where(gone[:, :, None], 0.0, m - mbar) ** 2).sum(axis=0)
+        total = within + between
+        fraction = np.where(total > 0.0, between / total, np.nan)
+        neff = np.where(wsum > 0.0, wsum * wsum / wsq, 0.0)
+    out = {"names": names, "mean": mbar, "within": within, "between": between, "total": total, "fraction_between": fraction, "neff_points": neff,
+           "n_dead": gone.sum(axis=0).astype(np.int64), "point_mean": mean, "point_cov": cov, "dead": dead, "n_points": k}
+    if loo is not None:
+        out["elpd_loo"] = loo["elpd_loo"]
+        if "pareto_k" in loo:
+            out["pareto_k"] = loo["pareto_k"]
+    return out

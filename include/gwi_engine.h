@@ -571,6 +571,30 @@ gwi_status gwi_set_rank_columns(gwi_handle h, int32_t n_cols, const int32_t* ord
 gwi_status gwi_point_pits_exact(gwi_handle h, const double* thetas, int32_t k, double* pit /* [k][n_ev][n_cols][2]: lt, le */, int32_t* dead /* [k][n_ev + 1] */);
 void gwi_point_rank_times(double* logw_ms, double* prefix_ms, double* pit_ms, int32_t* launches);
 
+/* Per-point moments on the device: per hyper-parameter point and segment the weighted means and the full weighted covariance of the
+ * columns of gwi_set_kde_columns -- what a correlation between two quantities, taken point by point, is made of (gwinferno_amd/csrc/
+ * gwi_moment.h; the NumPy statement is gwinferno_amd/draws.py: point_moments_reference; the contract is DESIGN 8j).
+ *
+ * gwi_point_moments(): the columns (C of them, 1 <= C <= 8) are read where gwi_set_kde_columns left them; nothing is copied and there is
+ * no setter of this entry's own.  Segments, lw_i, the masks of gwi_set_draw_mask, M, w_i = exp(lw_i - M) and the segment total S are
+ * gwi_draw_indices'.  For point k and segment s (the injection segment last), with P = C (C + 1) / 2:
+ *   m_c  = sum_i w_i x_ci / S                                   out[k][s][c]
+ *   V_cd = sum_i w_i (x_ci - m_c)(x_di - m_d) / S,  c <= d      out[k][s][C + t], t counting the upper triangle row by row
+ * in two passes over the samples, the second centred on the means of the first.  A segment whose S is 0 or not finite gives NaN and
+ * dead[k][s] = 1; the segments of a set that was given no columns give NaN (dead still tells whether they had weight); a segment with one
+ * live sample gives that sample and a covariance of exactly 0.  k >= 1 is not bound by the batch limit: the points are staged on the
+ * device 64 at a time and copied back per chunk.  Every sum has a fixed shape (sample order inside a tile of 1 024, then tile order)
+ * and there are no atomics: the bits are a pure function of (theta_k, columns, masks), whatever the split of the points over calls, and
+ * the call changes no state another entry reads.  Not done: sharded handles; more than 8 columns; rank correlation; conditional means.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, a host-only handle and a call before columns are set;
+ * GWI_ERR_UNSUPPORTED on a handle that holds a shard.
+ *
+ * gwi_point_moment_times(): DIAGNOSTIC ONLY, for tools/point_moments_time.py: of the calling thread's last call, summed over its points,
+ * the wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge / two mean launches
+ * together and of the two covariance launches, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, double* out /* [k][n_ev + 1][C + C(C+1)/2] */, int32_t* dead /* [k][n_ev + 1] */);
+void gwi_point_moment_times(double* logw_ms, double* mean_ms, double* cov_ms, int32_t* launches);
+
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is
  * gwinferno_amd/draws.py: marginal_weights_reference, weighted_quantiles_reference).
