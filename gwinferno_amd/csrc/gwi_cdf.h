@@ -37,7 +37,6 @@ namespace cdf {
 
 constexpr int kBlock = hist::kBlock;
 constexpr int kSlots = 4;        // cdf_det, cdf_obs, log_all_below, log_all_above
-constexpr int kStagePoints = 64;  // points per copy back to the host
 
 struct Args {
   hist::Args h;     // the segments, S, the tiles' partial histograms, n_cols, n_bins, first_seg of this point (hist and n_dead are not touched)

@@ -3734,6 +3734,54 @@ gwi_status per_point_pass(gwi_handle h, const char* who, const double* thetas, i
 }
 const auto no_stage = [](int) {};
 const auto no_step = [](int) { return GWI_OK; };
+
+// The rows an entry hands back per point go through a stage on the device: kStagePoints points' rows of every array, copied to the
+// caller when the stage is full or the call ends.  An entry registers (caller's array, stage, elements per point) in the order of
+// the copies, points its launches of point p at slot(i, p) of array i and passes after(p) to per_point_pass.  Built per call from the
+// entry's own buffers: it owns nothing.  An array the caller left out (null) or whose rows are empty is not copied.
+constexpr int kStagePoints = 64;
+struct StagedRows {
+  struct Array {
+    char *to, *stage;
+    size_t bytes;  // per point
+  };
+  gwi_handle h;
+  int k, n = 0;  // points of the call, arrays
+  Array arrays[3];
+  StagedRows(gwi_handle h, int k) : h(h), k(k) {}
+  template <class T>
+  void add(T* to, T* stage, size_t per_point) {
+    arrays[n++] = Array{(char*)to, (char*)stage, sizeof(T) * per_point};
+  }
+  template <class T>
+  T* slot(int i, int p) const {
+    return (T*)(arrays[i].stage + (size_t)(p % kStagePoints) * arrays[i].bytes);
+  }
+  gwi_status after(int p) const {
+    const int last = p % kStagePoints;
+    if (last + 1 != kStagePoints && p + 1 != k) return GWI_OK;
+    for (int i = 0; i < n; ++i) {
+      const Array& a = arrays[i];
+      if (a.to && a.bytes) GWI_HIP(hipMemcpy(a.to + (size_t)(p - last) * a.bytes, a.stage, (size_t)(last + 1) * a.bytes, hipMemcpyDeviceToHost));
+    }
+    return GWI_OK;
+  }
+};
+
+// What the per-point entries refuse of their arguments, in their common order, or an empty string: an engine without a scan kernel,
+// `unset` (what the entry works on is not set; empty when it is), no points, an output that is null.
+struct NamedOutput {
+  const char* name;
+  const void* ptr;
+};
+std::string bad_point_args(gwi_handle h, const char* unset, const double* thetas, int k, std::initializer_list<NamedOutput> outputs) {
+  if (!h->variant) return "the engine has no scan kernel";
+  if (*unset) return unset;
+  if (!thetas || k < 1) return "thetas is null or k < 1";
+  for (const NamedOutput& o : outputs)
+    if (!o.ptr) return std::string(o.name) + " is null";
+  return "";
+}
 }  // namespace
 
 extern "C" {
@@ -3896,7 +3944,6 @@ static gwi_status upload_point_weights(gwi_handle h, const double* v, int32_t k,
 }
 
 // ---- weighted histograms (gwi_hist.h) ---------------------------------------------------------------------------------------
-enum { kHistLogw, kHistTile, kHistMerge };
 static thread_local StageTimes g_histogram_times;
 
 gwi_status gwi_set_histogram_bins(gwi_handle h, int32_t n_cols, int32_t n_bins, const uint16_t* pe_bins, const uint16_t* inj_bins) {
@@ -4029,7 +4076,6 @@ gwi_status gwi_weighted_histograms_weighted(gwi_handle h, const double* thetas, 
 void gwi_histogram_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) { g_histogram_times.report(logw_ms, tile_ms, merge_ms, launches); }
 
 // ---- per-point CDFs and the catalog's extremes (gwi_cdf.h) ------------------------------------------------------------------
-enum { kCdfLogw, kCdfTile, kCdfReduce };
 static thread_local StageTimes g_point_cdf_times;
 
 gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double* out, int32_t* live) {
@@ -4038,14 +4084,8 @@ gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double*
   g_point_cdf_times = StageTimes();
   PostprocessBuffers::Histogram& hist = h->post.hist;
   const bool with_pe = hist.d_bins_pe.ptr != nullptr, with_inj = hist.d_bins_inj.ptr != nullptr;
-  gwi_status st = post_preflight(h, who, "sum on", "the injection CDF needs", [&]() -> std::string {
-    if (!h->variant) return "the engine has no scan kernel";
-    if (!hist.cols) return "no bins are set (gwi_set_histogram_bins)";
-    if (!thetas || k < 1) return "thetas is null or k < 1";
-    if (!out) return "out is null";
-    if (!live) return "live is null";
-    return "";
-  });
+  gwi_status st = post_preflight(h, who, "sum on", "the injection CDF needs",
+                                 [&] { return bad_point_args(h, hist.cols ? "" : "no bins are set (gwi_set_histogram_bins)", thetas, k, {{"out", out}, {"live", live}}); });
   if (st != GWI_OK) return st;
   namespace D = gwi::draw;
   namespace H = gwi::hist;
@@ -4059,8 +4099,11 @@ gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double*
   const size_t per_seg = (size_t)hist.cols * (size_t)hist.bins, per_point = (size_t)F::kSlots * per_seg;
   GWI_HIP(hist.d_cdf.reserve((size_t)(h->n_ev + 1) * per_seg));
   GWI_HIP(hist.d_cdf_dead.reserve((size_t)(h->n_ev + 1)));
-  GWI_HIP(hist.d_cdf_stage.reserve((size_t)F::kStagePoints * per_point));
-  GWI_HIP(hist.d_cdf_live.reserve((size_t)F::kStagePoints * 2));
+  GWI_HIP(hist.d_cdf_stage.reserve((size_t)kStagePoints * per_point));
+  GWI_HIP(hist.d_cdf_live.reserve((size_t)kStagePoints * 2));
+  StagedRows rows(h, k);  // 4 n_cols n_bins doubles and two ints per point
+  rows.add(out, hist.d_cdf_stage.ptr, per_point);
+  rows.add(live, hist.d_cdf_live.ptr, 2);
   const QueryCover cover = fill_hist_args(h, &a.h);
   a.cdf = hist.d_cdf;
   a.seg_dead = hist.d_cdf_dead;
@@ -4070,28 +4113,17 @@ gwi_status gwi_point_cdfs(gwi_handle h, const double* thetas, int32_t k, double*
     if (cover.tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)cover.tiles), dim3(H::kBlock), 0, h->stream, a.h);
   };
   const auto reduce = [&](int p) {  // into the point's slot of the stage
-    const int slot = p % F::kStagePoints;
-    a.out = hist.d_cdf_stage + (size_t)slot * per_point;
-    a.live = hist.d_cdf_live + (size_t)slot * 2;
+    a.out = rows.slot<double>(0, p);
+    a.live = rows.slot<int>(1, p);
     if (cover.segs) hipLaunchKernelGGL(F::cdf_segment_kernel, dim3((unsigned)cover.segs, (unsigned)a.h.n_cols), dim3(F::kBlock), 0, h->stream, a);
     hipLaunchKernelGGL(F::cdf_catalog_kernel, dim3((unsigned)a.h.n_cols), dim3(F::kBlock), 0, h->stream, a);
   };
-  const auto copy_back = [&](int p) -> gwi_status {
-    const int slot = p % F::kStagePoints;
-    if (slot + 1 == F::kStagePoints || p + 1 == k) {  // the staged rows go back: 4 n_cols n_bins doubles and two ints per point
-      const size_t first = (size_t)(p - slot);
-      GWI_HIP(hipMemcpy(out + first * per_point, hist.d_cdf_stage, sizeof(double) * (size_t)(slot + 1) * per_point, hipMemcpyDeviceToHost));
-      GWI_HIP(hipMemcpy(live + first * 2, hist.d_cdf_live, sizeof(int) * (size_t)(slot + 1) * 2, hipMemcpyDeviceToHost));
-    }
-    return GWI_OK;
-  };
-  return per_point_pass(h, who, thetas, k, &a.h.d, n_tiles, &g_point_cdf_times, 2, 5, tile, reduce, copy_back);
+  return per_point_pass(h, who, thetas, k, &a.h.d, n_tiles, &g_point_cdf_times, 2, 5, tile, reduce, [&](int p) { return rows.after(p); });
 }
 
 void gwi_point_cdf_times(double* logw_ms, double* tile_ms, double* reduce_ms, int32_t* launches) { g_point_cdf_times.report(logw_ms, tile_ms, reduce_ms, launches); }
 
 // ---- per-event calibration: per-point PIT brackets (gwi_pit.h) ---------------------------------------------------------------
-enum { kPitLogw, kPitTile, kPitWalk };
 static thread_local StageTimes g_point_pit_times;
 
 gwi_status gwi_point_pits(gwi_handle h, const double* thetas, int32_t k, double* pit, double* cdf_det, int32_t* dead) {
@@ -4100,16 +4132,11 @@ gwi_status gwi_point_pits(gwi_handle h, const double* thetas, int32_t k, double*
   g_point_pit_times = StageTimes();
   PostprocessBuffers::Histogram& hist = h->post.hist;
   const bool with_pe = hist.d_bins_pe.ptr != nullptr, with_inj = hist.d_bins_inj.ptr != nullptr;
-  gwi_status st = post_preflight(h, who, "sum on", "the injection CDF needs", [&]() -> std::string {
-    if (!h->variant) return "the engine has no scan kernel";
-    if (!hist.cols) return "no bins are set (gwi_set_histogram_bins)";
-    if (!with_pe) return "no PE bins are set: an event's PIT needs the bins of both sets (gwi_set_histogram_bins)";
-    if (!with_inj) return "no injection bins are set: an event's PIT needs the bins of both sets (gwi_set_histogram_bins)";
-    if (!thetas || k < 1) return "thetas is null or k < 1";
-    if (!pit) return "pit is null";
-    if (!dead) return "dead is null";
-    return "";
-  });
+  const char* unset = !hist.cols  ? "no bins are set (gwi_set_histogram_bins)"
+                      : !with_pe  ? "no PE bins are set: an event's PIT needs the bins of both sets (gwi_set_histogram_bins)"
+                      : !with_inj ? "no injection bins are set: an event's PIT needs the bins of both sets (gwi_set_histogram_bins)"
+                                  : "";
+  gwi_status st = post_preflight(h, who, "sum on", "the injection CDF needs", [&] { return bad_point_args(h, unset, thetas, k, {{"pit", pit}, {"dead", dead}}); });
   if (st != GWI_OK) return st;
   namespace H = gwi::hist;
   namespace F = gwi::cdf;
@@ -4122,9 +4149,13 @@ gwi_status gwi_point_pits(gwi_handle h, const double* thetas, int32_t k, double*
   const size_t n_segs = (size_t)(h->n_ev + 1), per_seg = (size_t)hist.cols * (size_t)hist.bins, per_point = (size_t)h->n_ev * (size_t)hist.cols * 2;
   GWI_HIP(hist.d_cdf.reserve(n_segs * per_seg));
   GWI_HIP(hist.d_cdf_dead.reserve(n_segs));
-  GWI_HIP(hist.d_pit_stage.reserve((size_t)P::kStagePoints * per_point));
-  GWI_HIP(hist.d_pit_det.reserve((size_t)P::kStagePoints * per_seg));
-  GWI_HIP(hist.d_pit_dead.reserve((size_t)P::kStagePoints * n_segs));
+  GWI_HIP(hist.d_pit_stage.reserve((size_t)kStagePoints * per_point));
+  GWI_HIP(hist.d_pit_det.reserve((size_t)kStagePoints * per_seg));
+  GWI_HIP(hist.d_pit_dead.reserve((size_t)kStagePoints * n_segs));
+  StagedRows rows(h, k);  // 2 n_ev n_cols (+ n_cols n_bins where the caller takes cdf_det) doubles and n_ev + 1 ints per point
+  rows.add(pit, hist.d_pit_stage.ptr, per_point);
+  rows.add(cdf_det, hist.d_pit_det.ptr, per_seg);
+  rows.add(dead, hist.d_pit_dead.ptr, n_segs);
   const QueryCover cover = fill_hist_args(h, &a.f.h);  // (both sets have bins: every tile and every segment)
   a.f.cdf = hist.d_cdf;
   a.f.seg_dead = hist.d_cdf_dead;
@@ -4133,30 +4164,18 @@ gwi_status gwi_point_pits(gwi_handle h, const double* thetas, int32_t k, double*
     if (cover.tiles) hipLaunchKernelGGL(H::hist_tile_kernel, dim3((unsigned)cover.tiles), dim3(H::kBlock), 0, h->stream, a.f.h);
   };
   const auto walk = [&](int p) {  // into the point's slot of the stage
-    const size_t slot = (size_t)(p % P::kStagePoints);
-    a.pit = hist.d_pit_stage + slot * per_point;
-    a.cdf_det = hist.d_pit_det + slot * per_seg;
-    a.dead = hist.d_pit_dead + slot * n_segs;
+    a.pit = rows.slot<double>(0, p);
+    a.cdf_det = rows.slot<double>(1, p);
+    a.dead = rows.slot<int>(2, p);
     hipLaunchKernelGGL(F::cdf_segment_kernel, dim3((unsigned)cover.segs, (unsigned)a.f.h.n_cols), dim3(F::kBlock), 0, h->stream, a.f);
     hipLaunchKernelGGL(P::pit_kernel, dim3((unsigned)cover.segs, (unsigned)a.f.h.n_cols), dim3(P::kBlock), 0, h->stream, a);
   };
-  const auto copy_back = [&](int p) -> gwi_status {
-    const int slot = p % P::kStagePoints;
-    if (slot + 1 == P::kStagePoints || p + 1 == k) {  // the staged rows go back: 2 n_ev n_cols (+ n_cols n_bins) doubles and n_ev + 1 ints per point
-      const size_t first = (size_t)(p - slot), n = (size_t)(slot + 1);
-      if (per_point) GWI_HIP(hipMemcpy(pit + first * per_point, hist.d_pit_stage, sizeof(double) * n * per_point, hipMemcpyDeviceToHost));
-      if (cdf_det) GWI_HIP(hipMemcpy(cdf_det + first * per_seg, hist.d_pit_det, sizeof(double) * n * per_seg, hipMemcpyDeviceToHost));
-      GWI_HIP(hipMemcpy(dead + first * n_segs, hist.d_pit_dead, sizeof(int) * n * n_segs, hipMemcpyDeviceToHost));
-    }
-    return GWI_OK;
-  };
-  return per_point_pass(h, who, thetas, k, &a.f.h.d, n_tiles, &g_point_pit_times, 2, 5, tile, walk, copy_back);
+  return per_point_pass(h, who, thetas, k, &a.f.h.d, n_tiles, &g_point_pit_times, 2, 5, tile, walk, [&](int p) { return rows.after(p); });
 }
 
 void gwi_point_pit_times(double* logw_ms, double* tile_ms, double* pit_ms, int32_t* launches) { g_point_pit_times.report(logw_ms, tile_ms, pit_ms, launches); }
 
 // ---- exact per-event calibration: weighted ranks among the injections (gwi_rank.h) ---------------------------------------------------
-enum { kRankLogw, kRankPrefix, kRankPit };
 static thread_local StageTimes g_point_rank_times;
 
 // what is wrong with the rank columns, or an empty string: every order a permutation of the injections, every rank in [0, n_inj],
@@ -4210,8 +4229,8 @@ gwi_status gwi_set_rank_columns(gwi_handle h, int32_t n_cols, const int32_t* ord
   GWI_HIP(rank.d_tiles.reserve(2 * cols * (size_t)geometry.n_inj_tiles));
   GWI_HIP(rank.d_prefix.reserve(n_prefix));
   GWI_HIP(rank.d_partial.reserve((size_t)(h->n_ev * geometry.tiles_per_event) * cols * 2));
-  GWI_HIP(rank.d_stage.reserve((size_t)R::kStagePoints * (size_t)h->n_ev * cols * 2));
-  GWI_HIP(rank.d_dead.reserve((size_t)R::kStagePoints * (size_t)(h->n_ev + 1)));
+  GWI_HIP(rank.d_stage.reserve((size_t)kStagePoints * (size_t)h->n_ev * cols * 2));
+  GWI_HIP(rank.d_dead.reserve((size_t)kStagePoints * (size_t)(h->n_ev + 1)));
   GWI_HIP(hipMemset(rank.d_prefix, 0, sizeof(double) * n_prefix));  // (an empty injection set launches nothing that would store P[c][0])
   rank.cols = n_cols;
   return GWI_OK;
@@ -4222,14 +4241,8 @@ gwi_status gwi_point_pits_exact(gwi_handle h, const double* thetas, int32_t k, d
   const char* who = "gwi_point_pits_exact";
   g_point_rank_times = StageTimes();
   RankBuffers& rank = h->rank;
-  gwi_status st = post_preflight(h, who, "sum on", "the injection ranks need", [&]() -> std::string {
-    if (!h->variant) return "the engine has no scan kernel";
-    if (!rank.cols) return "no rank columns are set (gwi_set_rank_columns)";
-    if (!thetas || k < 1) return "thetas is null or k < 1";
-    if (!pit) return "pit is null";
-    if (!dead) return "dead is null";
-    return "";
-  });
+  gwi_status st = post_preflight(h, who, "sum on", "the injection ranks need",
+                                 [&] { return bad_point_args(h, rank.cols ? "" : "no rank columns are set (gwi_set_rank_columns)", thetas, k, {{"pit", pit}, {"dead", dead}}); });
   if (st != GWI_OK) return st;
   namespace R = gwi::rank;
   R::Args a;
@@ -4247,6 +4260,9 @@ gwi_status gwi_point_pits_exact(gwi_handle h, const double* thetas, int32_t k, d
   a.prefix = rank.d_prefix;
   a.partial = rank.d_partial;
   a.n_cols = rank.cols;
+  StagedRows rows(h, k);  // 2 n_ev n_cols doubles and n_ev + 1 ints per point
+  rows.add(pit, rank.d_stage.ptr, per_point);
+  rows.add(dead, rank.d_dead.ptr, n_segs);
   const auto prefix = [&](int) {
     if (!inj_tiles) return;
     hipLaunchKernelGGL(R::rank_tile_kernel, dim3(inj_tiles, cols), dim3(R::kBlock), 0, h->stream, a);
@@ -4254,28 +4270,17 @@ gwi_status gwi_point_pits_exact(gwi_handle h, const double* thetas, int32_t k, d
     hipLaunchKernelGGL(R::rank_prefix_kernel, dim3(inj_tiles, cols), dim3(R::kBlock), 0, h->stream, a);
   };
   const auto sum = [&](int p) {  // into the point's slot of the stage
-    const size_t slot = (size_t)(p % R::kStagePoints);
-    a.pit = rank.d_stage + slot * per_point;
-    a.dead = rank.d_dead + slot * n_segs;
+    a.pit = rows.slot<double>(0, p);
+    a.dead = rows.slot<int>(1, p);
     if (pe_tiles) hipLaunchKernelGGL(R::pit_rank_kernel, dim3(pe_tiles, cols), dim3(R::kBlock), 0, h->stream, a);
     hipLaunchKernelGGL(R::pit_rank_merge_kernel, dim3((unsigned)n_segs, cols), dim3(R::kBlock), 0, h->stream, a);
   };
-  const auto copy_back = [&](int p) -> gwi_status {
-    const int slot = p % R::kStagePoints;
-    if (slot + 1 == R::kStagePoints || p + 1 == k) {  // the staged rows go back: 2 n_ev n_cols doubles and n_ev + 1 ints per point
-      const size_t first = (size_t)(p - slot), n = (size_t)(slot + 1);
-      if (per_point) GWI_HIP(hipMemcpy(pit + first * per_point, rank.d_stage, sizeof(double) * n * per_point, hipMemcpyDeviceToHost));
-      GWI_HIP(hipMemcpy(dead + first * n_segs, rank.d_dead, sizeof(int) * n * n_segs, hipMemcpyDeviceToHost));
-    }
-    return GWI_OK;
-  };
-  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_rank_times, 2, 7, prefix, sum, copy_back);
+  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_rank_times, 2, 7, prefix, sum, [&](int p) { return rows.after(p); });
 }
 
 void gwi_point_rank_times(double* logw_ms, double* prefix_ms, double* pit_ms, int32_t* launches) { g_point_rank_times.report(logw_ms, prefix_ms, pit_ms, launches); }
 
 // ---- per-point moments: means and full covariance of the KDE columns (gwi_moment.h) -------------------------------------------------
-enum { kMomentLogw, kMomentMean, kMomentCov };
 static thread_local StageTimes g_point_moment_times;
 
 gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, double* out, int32_t* dead) {
@@ -4283,16 +4288,11 @@ gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, doub
   const char* who = "gwi_point_moments";
   g_point_moment_times = StageTimes();
   PostprocessBuffers::Kde& kde = h->post.kde;
-  gwi_status st = post_preflight(h, who, "sum on", "the injection moments need", [&]() -> std::string {
-    if (!h->variant) return "the engine has no scan kernel";
-    return "";
-  });
+  gwi_status st = post_preflight(h, who, "sum on", "the injection moments need", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
   if (st != GWI_OK) return st;
   // (after the shard refusal, as gwi_weighted_kde: a shard cannot be given columns, and says that it is one)
-  if (!kde.cols) return fail(h, GWI_ERR_INVALID, "gwi_point_moments: no columns are set (gwi_set_kde_columns)");
-  if (!thetas || k < 1) return fail(h, GWI_ERR_INVALID, "gwi_point_moments: thetas is null or k < 1");
-  if (!out) return fail(h, GWI_ERR_INVALID, "gwi_point_moments: out is null");
-  if (!dead) return fail(h, GWI_ERR_INVALID, "gwi_point_moments: dead is null");
+  const std::string why = bad_point_args(h, kde.cols ? "" : "no columns are set (gwi_set_kde_columns)", thetas, k, {{"out", out}, {"dead", dead}});
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, std::string(who) + ": " + why);
   namespace M = gwi::moment;
   M::Args a;
   std::memset(&a, 0, sizeof(a));
@@ -4303,8 +4303,11 @@ gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, doub
   const size_t n_segs = (size_t)(h->n_ev + 1), cols = (size_t)kde.cols, pairs = (size_t)M::pairs_of(kde.cols), per_point = n_segs * (cols + pairs);
   MomentBuffers& mom = h->moment;
   GWI_HIP(mom.d_partial.reserve((size_t)n_tiles * (cols + pairs)));
-  GWI_HIP(mom.d_stage.reserve((size_t)M::kStagePoints * per_point));
-  GWI_HIP(mom.d_dead.reserve((size_t)M::kStagePoints * n_segs));
+  GWI_HIP(mom.d_stage.reserve((size_t)kStagePoints * per_point));
+  GWI_HIP(mom.d_dead.reserve((size_t)kStagePoints * n_segs));
+  StagedRows rows(h, k);  // (n_ev + 1)(n_cols + P) doubles and n_ev + 1 ints per point
+  rows.add(out, mom.d_stage.ptr, per_point);
+  rows.add(dead, mom.d_dead.ptr, n_segs);
   // a set without columns is left out of the tile launches; its segments come back NaN
   const QueryCover cover(with_pe, with_inj, h->n_ev, a.d);
   a.x_pe = kde.d_x_pe;
@@ -4316,9 +4319,8 @@ gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, doub
   a.first_seg = cover.first_seg;
   a.n_seg_covered = (int)cover.segs;
   const auto means = [&](int p) {  // into the point's slot of the stage
-    const size_t slot = (size_t)(p % M::kStagePoints);
-    a.out = mom.d_stage + slot * per_point;
-    a.dead = mom.d_dead + slot * n_segs;
+    a.out = rows.slot<double>(0, p);
+    a.dead = rows.slot<int>(1, p);
     if (cover.tiles) hipLaunchKernelGGL(M::moment_sum_kernel, dim3((unsigned)cover.tiles), dim3(M::kBlock), 0, h->stream, a);
     hipLaunchKernelGGL(M::moment_mean_kernel, dim3((unsigned)n_segs), dim3(64), 0, h->stream, a);
   };
@@ -4326,16 +4328,7 @@ gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, doub
     if (cover.tiles) M::launch_cov((unsigned)cover.tiles, h->stream, a);
     hipLaunchKernelGGL(M::moment_merge_kernel, dim3((unsigned)n_segs), dim3(64), 0, h->stream, a);
   };
-  const auto copy_back = [&](int p) -> gwi_status {
-    const int slot = p % M::kStagePoints;
-    if (slot + 1 == M::kStagePoints || p + 1 == k) {  // the staged rows go back: (n_ev + 1)(n_cols + P) doubles and n_ev + 1 ints per point
-      const size_t first = (size_t)(p - slot), n = (size_t)(slot + 1);
-      GWI_HIP(hipMemcpy(out + first * per_point, mom.d_stage, sizeof(double) * n * per_point, hipMemcpyDeviceToHost));
-      GWI_HIP(hipMemcpy(dead + first * n_segs, mom.d_dead, sizeof(int) * n * n_segs, hipMemcpyDeviceToHost));
-    }
-    return GWI_OK;
-  };
-  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_moment_times, 2, 6, means, covariances, copy_back);
+  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_moment_times, 2, 6, means, covariances, [&](int p) { return rows.after(p); });
 }
 
 void gwi_point_moment_times(double* logw_ms, double* mean_ms, double* cov_ms, int32_t* launches) { g_point_moment_times.report(logw_ms, mean_ms, cov_ms, launches); }

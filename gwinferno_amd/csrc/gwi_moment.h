@@ -35,7 +35,6 @@ constexpr int kBlock = draw::kDrawBlock;
 constexpr int kTile = draw::kDrawTile;
 constexpr int kMaxCols = 8;
 constexpr int kMaxPairs = kMaxCols * (kMaxCols + 1) / 2;
-constexpr int kStagePoints = 64;  // points per copy back to the host
 
 constexpr int pairs_of(int n_cols) { return n_cols * (n_cols + 1) / 2; }
 

@@ -33,7 +33,6 @@ namespace gwi {
 namespace pit {
 
 constexpr int kBlock = cdf::kBlock;
-constexpr int kStagePoints = cdf::kStagePoints;  // points per copy back to the host
 
 struct Args {
   cdf::Args f;      // what cdf_segment_kernel saw and left: the tiles' partial histograms, S, F and the segments' flags of this point

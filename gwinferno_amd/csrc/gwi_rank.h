@@ -40,7 +40,6 @@ namespace rank {
 constexpr int kBlock = draw::kDrawBlock;
 constexpr int kTile = draw::kDrawTile;
 constexpr int kMaxCols = 8;
-constexpr int kStagePoints = 64;  // points per copy back to the host
 
 struct Args {
   draw::DrawArgs d;       // the segments, the masks, log_const, seg_max and tile_prefix of this point

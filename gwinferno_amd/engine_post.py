@@ -210,6 +210,19 @@ class PostprocessMixin:
                                                      dead.ctypes.data_as(i32)))
         return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead
 
+    def _per_point(self, what, need, shape_attr, missing, dtypes, shapes, thetas):
+        """One per-point entry: the library's ``gwi_<what>`` fills one array per dtype, float64 or int32, of the shapes ``shapes(k, shape)``,
+        where ``shape`` is what the setter left in ``shape_attr``; the arrays are returned.  ``need`` and ``missing`` word the refusals."""
+        self._whole_catalog(what, need)
+        thetas = self._points(thetas)
+        k, entry = thetas.shape[0], getattr(self.lib, "gwi_" + what)
+        shape = getattr(self, shape_attr, None)
+        if shape is None:
+            self._nothing_set(what, missing, entry, N.as_dp(thetas), k, *(None for _ in dtypes))
+        out = [np.empty(s, dtype=dt) for s, dt in zip(shapes(k, shape), dtypes)]
+        self._check(entry(self.handle, N.as_dp(thetas), k, *(N.as_dp(o) if o.dtype == np.float64 else o.ctypes.data_as(C.POINTER(C.c_int32)) for o in out)))
+        return out
+
     def point_cdfs(self, thetas):
         """Per-point cumulative distributions on the device (``gwi_point_cdfs``; semantics:
         :func:`gwinferno_amd.draws.point_cdfs_reference`).  The bins of :meth:`set_histogram_bins` are cumulative codes
@@ -219,16 +232,8 @@ class PostprocessMixin:
         (slot 3: the CDF of the catalog's minimum is ``1 - exp`` of it), and ``(live events, injection set live)``.  NaN where a set
         has no bins or no weight.  ``4 n_cols n_bins`` doubles come back per point; the points may be split over calls without
         changing a bit.  Not available on an engine that holds a shard (``world > 1``)."""
-        self._whole_catalog("point_cdfs", "the injection CDF needs")
-        thetas = self._points(thetas)
-        k = thetas.shape[0]
-        shape = getattr(self, "_hist_shape", None)
-        i32 = C.POINTER(C.c_int32)
-        if shape is None:
-            self._nothing_set("point_cdfs", "bins are set (set_histogram_bins)", self.lib.gwi_point_cdfs, N.as_dp(thetas), k, None, None)
-        n_cols, n_bins = shape[:2]
-        out, live = np.empty((k, 4, n_cols, n_bins)), np.empty((k, 2), dtype=np.int32)
-        self._check(self.lib.gwi_point_cdfs(self.handle, N.as_dp(thetas), k, N.as_dp(out), live.ctypes.data_as(i32)))
+        out, live = self._per_point("point_cdfs", "the injection CDF needs", "_hist_shape", "bins are set (set_histogram_bins)",
+                                    (np.float64, np.int32), lambda k, s: ((k, 4, s[0], s[1]), (k, 2)), thetas)
         return out, live
 
     def point_pits(self, thetas):
@@ -241,16 +246,8 @@ class PostprocessMixin:
         and 1 for every segment without weight at the point, the injection set last.  ``2 n_ev n_cols + n_cols n_bins`` doubles come
         back per point; the points may be split over calls without changing a bit.  Not available on an engine that holds a shard
         (``world > 1``)."""
-        self._whole_catalog("point_pits", "the injection CDF needs")
-        thetas = self._points(thetas)
-        k = thetas.shape[0]
-        shape = getattr(self, "_hist_shape", None)
-        i32 = C.POINTER(C.c_int32)
-        if shape is None:
-            self._nothing_set("point_pits", "bins are set (set_histogram_bins)", self.lib.gwi_point_pits, N.as_dp(thetas), k, None, None, None)
-        n_cols, n_bins = shape[:2]
-        pit, cdf_det, dead = np.empty((k, self.n_ev, n_cols, 2)), np.empty((k, n_cols, n_bins)), np.empty((k, self.n_ev + 1), dtype=np.int32)
-        self._check(self.lib.gwi_point_pits(self.handle, N.as_dp(thetas), k, N.as_dp(pit), N.as_dp(cdf_det), dead.ctypes.data_as(i32)))
+        pit, cdf_det, dead = self._per_point("point_pits", "the injection CDF needs", "_hist_shape", "bins are set (set_histogram_bins)",
+                                             (np.float64, np.float64, np.int32), lambda k, s: ((k, self.n_ev, s[0], 2), (k, s[0], s[1]), (k, self.n_ev + 1)), thetas)
         return pit, cdf_det, dead
 
     def set_rank_columns(self, pe_values, inj_values):
@@ -280,15 +277,8 @@ class PostprocessMixin:
         between the two sets; NaN where the event or the injection set has no weight), and 1 for every segment without weight at the
         point, the injection set last.  ``2 n_ev n_cols`` doubles come back per point; the points may be split over calls without
         changing a bit.  Not available on an engine that holds a shard (``world > 1``)."""
-        self._whole_catalog("point_pits_exact", "the injection ranks need")
-        thetas = self._points(thetas)
-        k = thetas.shape[0]
-        shape = getattr(self, "_rank_shape", None)
-        i32 = C.POINTER(C.c_int32)
-        if shape is None:
-            self._nothing_set("point_pits_exact", "rank columns are set (set_rank_columns)", self.lib.gwi_point_pits_exact, N.as_dp(thetas), k, None, None)
-        pit, dead = np.empty((k, self.n_ev, shape[0], 2)), np.empty((k, self.n_ev + 1), dtype=np.int32)
-        self._check(self.lib.gwi_point_pits_exact(self.handle, N.as_dp(thetas), k, N.as_dp(pit), dead.ctypes.data_as(i32)))
+        pit, dead = self._per_point("point_pits_exact", "the injection ranks need", "_rank_shape", "rank columns are set (set_rank_columns)",
+                                    (np.float64, np.int32), lambda k, s: ((k, self.n_ev, s[0], 2), (k, self.n_ev + 1)), thetas)
         return pit, dead
 
     def point_moments(self, thetas):
@@ -301,17 +291,10 @@ class PostprocessMixin:
         columns; exactly 0 covariance for a segment with one live sample.  ``(n_ev + 1)(C + C (C + 1) / 2)`` doubles come back per
         point; the points may be split over calls without changing a bit.  Not available on an engine that holds a shard
         (``world > 1``)."""
-        self._whole_catalog("point_moments", "the injection moments need")
-        thetas = self._points(thetas)
-        k = thetas.shape[0]
-        shape = getattr(self, "_kde_shape", None)
-        i32 = C.POINTER(C.c_int32)
-        if shape is None:
-            self._nothing_set("point_moments", "columns are set (set_kde_columns)", self.lib.gwi_point_moments, N.as_dp(thetas), k, None, None)
-        n_cols = shape[0]
+        raw, dead = self._per_point("point_moments", "the injection moments need", "_kde_shape", "columns are set (set_kde_columns)",
+                                    (np.float64, np.int32), lambda k, s: ((k, self.n_ev + 1, s[0] + s[0] * (s[0] + 1) // 2), (k, self.n_ev + 1)), thetas)
+        k, n_cols = raw.shape[0], self._kde_shape[0]
         iu = np.triu_indices(n_cols)
-        raw, dead = np.empty((k, self.n_ev + 1, n_cols + iu[0].size)), np.empty((k, self.n_ev + 1), dtype=np.int32)
-        self._check(self.lib.gwi_point_moments(self.handle, N.as_dp(thetas), k, N.as_dp(raw), dead.ctypes.data_as(i32)))
         cov = np.empty((k, self.n_ev + 1, n_cols, n_cols))
         cov[..., iu[0], iu[1]] = raw[..., n_cols:]
         cov[..., iu[1], iu[0]] = raw[..., n_cols:]

@@ -5,9 +5,6 @@ only where the whole request would take minutes; the row says how many) and the 
       python tools/population_draws_time.py [--tables 1,64,1024] [--draws 10000,1000000] [--grid 800] [--host-draws 4000000] [--out profiles/population_draws/RESULTS.md]"""
 import argparse
 import os
-import re
-import shutil
-import subprocess
 import sys
 import time
 
@@ -15,27 +12,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from gwinferno_amd import _native  # noqa: E402
+from kernel_resources import kernel_resources  # noqa: E402
 from gwinferno_amd import population_draws as P  # noqa: E402
-
-
-def kernel_resources():
-    """VGPRs, SGPRs, LDS and scratch of the two kernels from the code object's metadata."""
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf")
-    path = os.path.join(os.path.dirname(_native.LIB_PATH), "gwi_kernels.hsaco")
-    if not readelf or not os.path.exists(path):
-        return []
-    notes = subprocess.run([readelf, "--notes", path], capture_output=True, text=True).stdout
-    rows = []
-    for block in re.split(r"\n\s+- \.agpr_count", notes):
-        name = re.search(r"\.name:\s+(\S+)", block)
-        if not name or "popdraw" not in name.group(1):
-            continue
-        get = lambda key: re.search(r"\.%s:\s+(\d+)" % key, block).group(1)  # noqa: E731
-        rows.append((re.search(r"(table_\w+_kernel)", name.group(1)).group(1), get("vgpr_count"), get("sgpr_count"), get("group_segment_fixed_size"), get("private_segment_fixed_size")))
-    return rows
 
 
 def main():
@@ -75,7 +53,7 @@ def main():
             lines.append(f"| {K} | {n} | {1e3 * min(walls):.2f} | {min(cdf_ms):.3f} | {min(draw_ms):.3f} | {launches} | {K * n / (min(draw_ms) * 1e-3):.3e} | {stores:.1f} | {moved:.1f} | "
                          f"{host:.2f} s on {k_host} of {K} tables | {k_host * n / host:.3e} |")
             print(lines[-1], flush=True)
-    res = kernel_resources()
+    res = kernel_resources(r"table_\w+_kernel")
     text = ["# Population draws: measured times", "",
             f"`tools/population_draws_time.py` on one MI355X: K tables of {G} points, n draws per table, no lower bound; the best of {a.repeats} calls.  The wall time is the "
             "whole `gwi_table_draws` call (allocation, upload of the tables, the launches, the copy of the draws back into pageable host memory); the kernel times are HIP "

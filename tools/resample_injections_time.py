@@ -10,9 +10,6 @@ report.
 import argparse
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 import sys
 import time
 
@@ -20,31 +17,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from gwinferno_amd import _native  # noqa: E402
+from kernel_resources import kernel_resources  # noqa: E402
 from gwinferno_amd import catalog as K  # noqa: E402
 from gwinferno_amd.compositions import COMPOSITIONS, draw_params  # noqa: E402
 from gwinferno_amd.synthetic import make_config_catalog  # noqa: E402
 
 COMPOSITION_OF = {"c2": "plpeak", "c3": "bspline_iid", "c5": "bspline_full"}
-
-
-def kernel_resources():
-    """VGPRs, SGPRs, LDS and scratch of the three kernels from the code object's metadata."""
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf")
-    path = os.path.join(os.path.dirname(_native.LIB_PATH), "gwi_kernels.hsaco")
-    if not readelf or not os.path.exists(path):
-        return []
-    notes = subprocess.run([readelf, "--notes", path], capture_output=True, text=True).stdout
-    rows = []
-    for block in re.split(r"\n\s+- \.agpr_count", notes):
-        name = re.search(r"\.name:\s+(\S+)", block)
-        if not name or "resample" not in name.group(1):
-            continue
-        get = lambda key: re.search(r"\.%s:\s+(\d+)" % key, block).group(1)  # noqa: E731
-        rows.append((re.search(r"(resample_\w+_kernel)", name.group(1)).group(1), get("vgpr_count"), get("sgpr_count"), get("group_segment_fixed_size"), get("private_segment_fixed_size")))
-    return rows
 
 
 def device_times(lib):
@@ -84,7 +62,7 @@ def main():
                      f"{8 * (eng.n_inj + eng.n_ev * eng.n_pe) / 1e6:.1f} | {n_d == n_h} | {differ} |")
         print(lines[-1], flush=True)
         eng.close()
-    res = kernel_resources()
+    res = kernel_resources(r"resample_\w+_kernel")
     text = ["# Resampled injection sets: measured times", "",
             f"`tools/resample_injections_time.py` on one MI355X: `Engine.resample_injections(theta, seed)` (the reference's N draws) against the host path "
             f"(`catalog.resample_injections(backend=\"host\")`: `gwi_log_weights`, NumPy `exp`, `cumsum`, `searchsorted`, and the gather of the columns) at one fiducial "

@@ -10,9 +10,6 @@ fixed in advance; what is not measured is named as unmeasured.  Writes a Markdow
 import argparse
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 import sys
 import time
 
@@ -20,7 +17,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from gwinferno_amd import _native  # noqa: E402
+from kernel_resources import kernel_resources  # noqa: E402
 from gwinferno_amd import draws as D  # noqa: E402
 from gwinferno_amd.compositions import COMPOSITIONS, draw_params  # noqa: E402
 from gwinferno_amd.synthetic import make_config_catalog  # noqa: E402
@@ -28,26 +25,6 @@ from gwinferno_amd.synthetic import make_config_catalog  # noqa: E402
 COMPOSITION_OF = {"c2": "plpeak", "c3": "bspline_iid", "c5": "bspline_full"}
 COLUMNS = ("mass_1", "mass_ratio", "redshift")
 N_BINS = 64
-
-
-def kernel_resources():
-    """VGPRs, SGPRs, LDS and scratch of the two kernels from the code object's metadata."""
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf")
-    path = os.path.join(os.path.dirname(_native.LIB_PATH), "gwi_kernels.hsaco")
-    if not readelf or not os.path.exists(path):
-        return []
-    notes = subprocess.run([readelf, "--notes", path], capture_output=True, text=True).stdout
-    rows = []
-    for block in re.split(r"\n\s+- \.agpr_count", notes):
-        name = re.search(r"\.name:\s+(\S+)", block)
-        found = re.search(r"(hist_\w+_kernel)", name.group(1)) if name else None
-        if not found:
-            continue
-        get = lambda key: re.search(r"\.%s:\s+(\d+)" % key, block).group(1)  # noqa: E731
-        rows.append((found.group(1), get("vgpr_count"), get("sgpr_count"), get("group_segment_fixed_size"), get("private_segment_fixed_size")))
-    return rows
 
 
 def device_times(lib):
@@ -105,7 +82,7 @@ def main():
                          f"{back / 1e3:.1f} | {1e3 * min(host) / k:.3f} | {8 * (eng.n_inj + eng.n_ev * eng.n_pe) / 1e6:.1f} | {rel.max():.2e} (dead: {int(dead.sum())}) |")
             print(lines[-1], flush=True)
         eng.close()
-    res = kernel_resources()
+    res = kernel_resources(r"hist_\w+_kernel")
     text = ["# Weighted histograms: measured times", "",
             f"`tools/weighted_histograms_time.py` on one MI355X: `Engine.weighted_histograms(thetas[:K])` with C = {len(COLUMNS)} binned quantities ({', '.join(COLUMNS)}) and "
             f"B = {N_BINS} bins against the host path of the same commit (`Engine.log_weights` per point, then `draws.weighted_histograms_reference`: NumPy `exp`, `bincount`); "

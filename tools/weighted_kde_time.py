@@ -11,9 +11,6 @@ unmeasured.  Writes a Markdown report.
 import argparse
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 import sys
 import time
 
@@ -21,7 +18,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from gwinferno_amd import _native  # noqa: E402
+from kernel_resources import kernel_resources  # noqa: E402
 from gwinferno_amd.compositions import COMPOSITIONS, draw_params  # noqa: E402
 from gwinferno_amd.synthetic import make_config_catalog  # noqa: E402
 
@@ -32,27 +29,6 @@ N_GRID = 256
 MAPS = (64, 128)
 K = 4
 HOST_MAX_TERMS = 3e9  # the host route is not run for a map of more Gaussian evaluations than this (minutes of one CPU)
-
-
-def kernel_resources():
-    """VGPRs, SGPRs, LDS and scratch of the new kernels from the code object's metadata."""
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf")
-    path = os.path.join(os.path.dirname(_native.LIB_PATH), "gwi_kernels.hsaco")
-    if not readelf or not os.path.exists(path):
-        return []
-    notes = subprocess.run([readelf, "--notes", path], capture_output=True, text=True).stdout
-    rows = []
-    for block in re.split(r"\n\s+- \.agpr_count", notes):
-        name = re.search(r"\.name:\s+(\S+)", block)
-        found = re.search(r"(kde_\w+_kernel(?:ILi\d)?)", name.group(1)) if name else None
-        if not found:
-            continue
-        get = lambda key: re.search(r"\.%s:\s+(\d+)" % key, block).group(1)  # noqa: E731
-        rows.append((found.group(1).replace("ILi", "<") + (">" if "ILi" in found.group(1) else ""), get("vgpr_count"), get("sgpr_count"), get("group_segment_fixed_size"),
-                     get("private_segment_fixed_size")))
-    return sorted(set(rows))
 
 
 def kde_times(lib):
@@ -146,7 +122,7 @@ def main():
             t_1d, t_2d = host_route(W[live], cols[:, live], grid, PAIR, MAPS, f"{cfg} {label}")
             host_rows.append(f"| {cfg} ({name}) | {readback} | {label} | {int(live.sum())} | {t_1d:.3f} | " + " | ".join("not run" if t != t else f"{t:.3f}" for t in t_2d) + " |")
         eng.close()
-    res = kernel_resources()
+    res = kernel_resources(r"kde_\w+_kernel")
     text = ["# Weighted kernel density estimates: measured times", "",
             f"`tools/weighted_kde_time.py` on one MI355X, ONE run on ONE box, nothing tuned.  After K = {K} points have been accumulated, every query is called once to load and allocate and "
             f"then {a.repeats} times: the table gives the median and (smallest ... largest) of the wall time of the Python call (host clock; the copies to the host and the allocation of the "

@@ -12,8 +12,6 @@ import argparse
 import ctypes as C
 import json
 import os
-import re
-import shutil
 import subprocess
 import sys
 import time
@@ -22,7 +20,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from gwinferno_amd import _native  # noqa: E402
+from kernel_resources import kernel_resources  # noqa: E402
 from gwinferno_amd import draws as D  # noqa: E402
 from gwinferno_amd.compositions import COMPOSITIONS, draw_params  # noqa: E402
 from gwinferno_amd.synthetic import make_config_catalog  # noqa: E402
@@ -32,26 +30,6 @@ COLUMNS = ("mass_1", "mass_ratio", "redshift")
 LEVELS = (0.05, 0.5, 0.95)
 N_BINS = 64
 KS = (1, 64)
-
-
-def kernel_resources():
-    """VGPRs, SGPRs, LDS and scratch of the new kernels from the code object's metadata."""
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf")
-    path = os.path.join(os.path.dirname(_native.LIB_PATH), "gwi_kernels.hsaco")
-    if not readelf or not os.path.exists(path):
-        return []
-    notes = subprocess.run([readelf, "--notes", path], capture_output=True, text=True).stdout
-    rows = []
-    for block in re.split(r"\n\s+- \.agpr_count", notes):
-        name = re.search(r"\.name:\s+(\S+)", block)
-        found = re.search(r"((?:quant_|marg_)\w+_kernel)", name.group(1)) if name else None
-        if not found:
-            continue
-        get = lambda key: re.search(r"\.%s:\s+(\d+)" % key, block).group(1)  # noqa: E731
-        rows.append((found.group(1), get("vgpr_count"), get("sgpr_count"), get("group_segment_fixed_size"), get("private_segment_fixed_size")))
-    return rows
 
 
 def setup(cfg):
@@ -185,7 +163,7 @@ def main():
                           f"{1e3 * s_wall:.1f} | {same} of {total} | {rel.max():.2e} (dead: {int(dead.sum())}) |")
         print(query_rows[-1], flush=True)
         eng.close()
-    res = kernel_resources()
+    res = kernel_resources(r"(?:quant_|marg_)\w+_kernel")
     text = ["# Marginal weights and weighted quantiles: measured times", "",
             f"`tools/weighted_quantiles_time.py` on one MI355X, ONE run on ONE box, nothing tuned.  `Engine.marginal_weights_add(thetas[:K])`: the best of {a.repeats} calls in each of "
             f"{a.rounds} rounds by the host clock, divided by K; its parts are those of the best call (`gwi_quantile_times`: the blocking log-weight passes by the host clock, the draw tile / "
