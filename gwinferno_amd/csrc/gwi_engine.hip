@@ -531,6 +531,19 @@ struct MomentBuffers {
   DeviceBuffer<double> d_partial, d_stage;
   DeviceBuffer<int> d_dead;
 };
+// ... and of the per-point conditional moments (gwi_cond.h), which read the codes of gwi_set_histogram_bins and the columns of
+// gwi_set_kde_columns where they lie: the tiles' sums [n_tiles][n_pairs][3][n_bins], the bins' weights [n_ev + 1][n_pairs][n_bins] and the
+// staged rows [64][n_ev + 1][n_pairs][3][n_bins] and flags [64][n_ev + 1] (grown on demand, kept).  At the end of the engine for
+// RankBuffers' reason, and there as a pointer: the record is made on the entry's first call and released by release_moment_and_conditional_buffers(),
+// which like the entry and its kernels is defined behind everything the evaluation path runs.  A member by value grew destroy_impl
+// and the engine's destructor, every function behind them moved by 16 bytes, and the single-evaluation benchmark read 1.5 % lower
+// (measured: profiles/point_conditionals/RESULTS.md, "The buffers' place").  The engine's destructor does not know the record: the
+// one path that deletes a device handle without release_moment_and_conditional_buffers() is destroy_impl's poisoned one, which
+// leaks device memory on purpose (a kernel may still run), as it does with `post`.
+struct ConditionalBuffers {
+  DeviceBuffer<double> d_partial, d_bin_w, d_stage;
+  DeviceBuffer<int> d_dead;
+};
 }  // namespace
 
 struct gwi_engine {
@@ -664,6 +677,7 @@ struct gwi_engine {
   std::vector<char> col_f32;  // per entry of d_cols_pe: a narrow (float32) allocation
   RankBuffers rank;           // gwi_set_rank_columns / gwi_point_pits_exact (freed with `post`)
   MomentBuffers moment;       // gwi_point_moments (freed with `post`)
+  ConditionalBuffers* cond = nullptr;  // gwi_point_conditionals (release_moment_and_conditional_buffers, with `post`)
 };
 
 namespace {
@@ -995,6 +1009,7 @@ gwi_status launch_scan(gwi_handle h, bool logw, int K = 1, bool batch = false) {
 // (the single evaluation is 16 to 28 us end to end: the helpers on its way fold into their entries, as the code they replace did)
 #define GWI_HOT inline __attribute__((always_inline))
 GWI_HOT gwi_status collect_local(gwi_handle h, int K);
+void release_moment_and_conditional_buffers(gwi_handle h);
 
 // launches scan -> combine -> final; `record_dev` is where final_kernel publishes (pinned host record
 // or, for the sharded path, the device send buffer); `wait` polls the pinned completion stamp.
@@ -1677,7 +1692,7 @@ void destroy_impl(gwi_engine* h) {
   (void)hipFree(h->d_inj_grad);
   h->post = PostprocessBuffers();
   h->rank = RankBuffers();
-  h->moment = MomentBuffers();
+  release_moment_and_conditional_buffers(h);
   if (h->nccl_comm && g_nccl.CommDestroy) (void)g_nccl.CommDestroy(h->nccl_comm);
   (void)hipFree(h->d_send);
   (void)hipFree(h->d_recv);
@@ -4332,6 +4347,100 @@ gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, doub
 }
 
 void gwi_point_moment_times(double* logw_ms, double* mean_ms, double* cov_ms, int32_t* launches) { g_point_moment_times.report(logw_ms, mean_ms, cov_ms, launches); }
+
+// ---- per-point conditional moments: a bin's share, and the mean and variance of y given the bin of x (gwi_cond.h) ---------------------
+// (the kernels' header is included here and not at the top: their host stubs then lie behind the evaluation path -- ConditionalBuffers)
+}  // extern "C"
+#include "gwi_cond.h"
+namespace {
+__attribute__((noinline)) void release_moment_and_conditional_buffers(gwi_handle h) {
+  h->moment = MomentBuffers();
+  delete h->cond;
+  h->cond = nullptr;
+}
+}  // namespace
+extern "C" {
+static thread_local StageTimes g_point_conditional_times;
+
+gwi_status gwi_point_conditionals(gwi_handle h, const double* thetas, int32_t k, int32_t n_pairs, const int32_t* pairs, double* out, int32_t* dead) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_conditionals";
+  g_point_conditional_times = StageTimes();
+  namespace Q = gwi::cond;
+  const PostprocessBuffers::Histogram& hist = h->post.hist;
+  const PostprocessBuffers::Kde& kde = h->post.kde;
+  gwi_status st = post_preflight(h, who, "sum on", "the injection moments need", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_point_moments: a shard cannot be given bins or columns, and says that it is one)
+  const bool with_pe = hist.d_bins_pe.ptr != nullptr && kde.d_x_pe.ptr != nullptr, with_inj = hist.d_bins_inj.ptr != nullptr && kde.d_x_inj.ptr != nullptr;
+  const char* unset = !hist.cols ? "no bins are set (gwi_set_histogram_bins)" : !kde.cols ? "no columns are set (gwi_set_kde_columns)" : "";
+  std::string why = bad_point_args(h, unset, thetas, k, {{"pairs", pairs}, {"out", out}, {"dead", dead}});
+  if (why.empty() && (n_pairs < 1 || n_pairs > Q::kMaxPairs)) why = "n_pairs = " + std::to_string(n_pairs) + " is not in 1 ... " + std::to_string(Q::kMaxPairs);
+  for (int r = 0; why.empty() && r < n_pairs; ++r) {
+    const int cx = pairs[2 * r], cy = pairs[2 * r + 1];
+    if (cx < 0 || cx >= hist.cols)
+      why = "pair " + std::to_string(r) + ": bin column " + std::to_string(cx) + " is not in 0 ... " + std::to_string(hist.cols - 1) + " (gwi_set_histogram_bins)";
+    else if (cy < 0 || cy >= kde.cols)
+      why = "pair " + std::to_string(r) + ": value column " + std::to_string(cy) + " is not in 0 ... " + std::to_string(kde.cols - 1) + " (gwi_set_kde_columns)";
+  }
+  if (why.empty() && n_pairs * hist.bins > Q::kMaxItems) why = "n_pairs n_bins = " + std::to_string(n_pairs * hist.bins) + " exceeds " + std::to_string(Q::kMaxItems);
+  if (why.empty() && !with_pe && !with_inj) why = "no sample set has both bins and columns: the bins are set for one set, the columns for the other";
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, std::string(who) + ": " + why);
+  Q::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);  // (as the two setters found it)
+  if (st != GWI_OK) return st;
+  const size_t n_segs = (size_t)(h->n_ev + 1), items = (size_t)n_pairs * (size_t)hist.bins, per_point = n_segs * Q::kSlots * items;
+  if (!h->cond) h->cond = new (std::nothrow) ConditionalBuffers();
+  if (!h->cond) return fail(h, GWI_ERR_INVALID, std::string(who) + ": out of host memory");
+  ConditionalBuffers& cb = *h->cond;
+  GWI_HIP(cb.d_partial.reserve((size_t)n_tiles * Q::kSlots * items));
+  GWI_HIP(cb.d_bin_w.reserve(n_segs * items));
+  GWI_HIP(cb.d_stage.reserve((size_t)kStagePoints * per_point));
+  GWI_HIP(cb.d_dead.reserve((size_t)kStagePoints * n_segs));
+  StagedRows rows(h, k);  // 3 (n_ev + 1) n_pairs n_bins doubles and n_ev + 1 ints per point
+  rows.add(out, cb.d_stage.ptr, per_point);
+  rows.add(dead, cb.d_dead.ptr, n_segs);
+  // a set without bins or without columns is left out of the tile launches; its segments come back NaN
+  const QueryCover cover(with_pe, with_inj, h->n_ev, a.d);
+  a.bins_pe = hist.d_bins_pe;
+  a.bins_inj = hist.d_bins_inj;
+  a.x_pe = kde.d_x_pe;
+  a.x_inj = kde.d_x_inj;
+  a.part1 = cb.d_partial;
+  a.part2 = cb.d_partial + (size_t)n_tiles * 2 * items;
+  a.bin_w = cb.d_bin_w;
+  a.n_pairs = n_pairs;
+  a.n_bins = hist.bins;
+  for (int r = 0; r < n_pairs; ++r) {  // the pairs' distinct columns, in the order of their first use
+    const int cx = pairs[2 * r], cy = pairs[2 * r + 1];
+    int ix = 0, iy = 0;
+    while (ix < a.n_x && a.x_col[ix] != cx) ++ix;
+    while (iy < a.n_y && a.y_col[iy] != cy) ++iy;
+    if (ix == a.n_x) a.x_col[a.n_x++] = cx;
+    if (iy == a.n_y) a.y_col[a.n_y++] = cy;
+    a.pair_x[r] = ix;
+    a.pair_y[r] = iy;
+  }
+  a.first_tile = cover.first_tile;
+  a.first_seg = cover.first_seg;
+  a.n_seg_covered = (int)cover.segs;
+  const dim3 merge_grid((unsigned)n_segs, (unsigned)n_pairs);
+  const auto means = [&](int p) {  // into the point's slot of the stage
+    a.out = rows.slot<double>(0, p);
+    a.dead = rows.slot<int>(1, p);
+    if (cover.tiles) Q::launch_tiles<false>((unsigned)cover.tiles, h->stream, a);
+    hipLaunchKernelGGL(Q::cond_mean_kernel, merge_grid, dim3(Q::kBlock), 0, h->stream, a);
+  };
+  const auto variances = [&](int) {
+    if (cover.tiles) Q::launch_tiles<true>((unsigned)cover.tiles, h->stream, a);
+    hipLaunchKernelGGL(Q::cond_var_kernel, merge_grid, dim3(Q::kBlock), 0, h->stream, a);
+  };
+  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_conditional_times, 2, 6, means, variances, [&](int p) { return rows.after(p); });
+}
+
+void gwi_point_conditional_times(double* logw_ms, double* mean_ms, double* var_ms, int32_t* launches) { g_point_conditional_times.report(logw_ms, mean_ms, var_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

@@ -692,6 +692,75 @@ def point_moments_reference(logw_pe, logw_inj, x_pe, x_inj, pe_mask=None, inj_ma
     return mean, cov, dead
 
 
+MAX_CONDITIONAL_PAIRS = 8    # pairs of gwi_point_conditionals (gwi_cond.h: kMaxPairs)
+MAX_CONDITIONAL_ITEMS = 512  # ... and n_pairs n_bins (gwi_cond.h: kMaxItems)
+
+
+def conditionals_segment(w, code, y, n_bins):
+    """``(out (3, B), alive)`` of ONE segment and ONE pair with the weights ``w (n,)`` of :func:`draw_weights`, the bin codes ``code (n,)``
+    of the conditioning quantity and the values ``y (n,)``, in two passes: ``S = fsum w``; per bin ``b``, over the samples coded ``b``,
+    ``W_b = fsum w_i``, ``a_b = W_b / S``, ``m_b = fsum (w_i y_i) / W_b`` and, centred on that mean, ``v_b = fsum ((w_i (y_i - m_b))
+    (y_i - m_b)) / W_b`` -- every product rounded on its own, every sum exact and rounded once (``math.fsum``).  A sample coded
+    :data:`OUTSIDE_BIN` counts in ``S`` and in no bin.  A bin with ``W_b = 0`` gives ``a_b = 0`` and NaN for the other two.  All NaN and
+    ``alive = False`` where ``S`` is 0 or not finite."""
+    w, code, y = np.asarray(w, dtype=np.float64).ravel(), np.asarray(code).ravel().astype(np.int64), np.asarray(y, dtype=np.float64).ravel()
+    out = np.full((3, int(n_bins)), np.nan)
+    total = math.fsum(w.tolist())
+    if not (total > 0.0 and np.isfinite(total)):
+        return out, False
+    live = w > 0.0
+    w, code, y = w[live], code[live], y[live]
+    for b in range(int(n_bins)):
+        sel = code == b
+        wb, yb = w[sel], y[sel]
+        w_bin = math.fsum(wb.tolist())
+        out[0, b] = w_bin / total
+        if w_bin > 0.0:
+            out[1, b] = math.fsum((wb * yb).tolist()) / w_bin
+            d = yb - out[1, b]
+            out[2, b] = math.fsum(((wb * d) * d).tolist()) / w_bin
+    return out, True
+
+
+def point_conditionals_reference(logw_pe, logw_inj, codes_pe, codes_inj, x_pe, x_inj, pairs, n_bins, pe_mask=None, inj_mask=None):
+    """One hyper-parameter point of ``gwi_point_conditionals``: ``logw_pe (n_ev, n_pe)``, ``logw_inj (n_inj,)``, the bin codes
+    ``codes_pe (Cx, n_ev, n_pe)`` and ``codes_inj (Cx, n_inj)`` of ``gwi_set_histogram_bins``, the values ``x_pe (Cy, n_ev, n_pe)`` and
+    ``x_inj (Cy, n_inj)`` of ``gwi_set_kde_columns`` (``None``: the set has none), ``pairs (R, 2)`` of ``(cx, cy)`` and the masks of
+    ``gwi_set_draw_mask`` (or None) -> ``(out (n_ev + 1, R, 3, B), dead (n_ev + 1,) int32)``, the injection set last: per segment and
+    pair :func:`conditionals_segment` on the weights of :func:`draw_weights` -- share, conditional mean, conditional variance per bin.
+    NaN for a segment without weight, which ``dead`` flags, and for a set that lacks codes or values."""
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    n_ev, n_pe = logw_pe.shape
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n_bins = int(n_bins)
+    if not 1 <= pairs.shape[0] <= MAX_CONDITIONAL_PAIRS:
+        raise ValueError(f"{pairs.shape[0]} pairs: between 1 and {MAX_CONDITIONAL_PAIRS}")
+    if n_bins < 1 or pairs.shape[0] * n_bins > MAX_CONDITIONAL_ITEMS:
+        raise ValueError(f"n_pairs n_bins = {pairs.shape[0] * n_bins}: between 1 and {MAX_CONDITIONAL_ITEMS}")
+    if codes_pe is None and codes_inj is None:
+        raise ValueError("codes_pe and codes_inj are both None")
+    if x_pe is None and x_inj is None:
+        raise ValueError("x_pe and x_inj are both None")
+    with_pe, with_inj = codes_pe is not None and x_pe is not None, codes_inj is not None and x_inj is not None
+    if not with_pe and not with_inj:
+        raise ValueError("no sample set has both codes and values")
+    n_x, n_y = (codes_pe if codes_pe is not None else codes_inj).shape[0], (x_pe if x_pe is not None else x_inj).shape[0]
+    if np.any(pairs < 0) or np.any(pairs[:, 0] >= n_x) or np.any(pairs[:, 1] >= n_y):
+        raise ValueError(f"a pair is (bin column below {n_x}, value column below {n_y})")
+    pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(n_ev, n_pe)
+    out, dead = np.full((n_ev + 1, pairs.shape[0], 3, n_bins), np.nan), np.zeros(n_ev + 1, dtype=np.int32)
+    for seg in range(n_ev + 1):
+        w = draw_weights(logw_pe[seg], None if pe_mask is None else pe_mask[seg]) if seg < n_ev else draw_weights(logw_inj, inj_mask)
+        total = math.fsum(w.tolist())
+        dead[seg] = 0 if total > 0.0 and np.isfinite(total) else 1
+        if dead[seg] or not (with_pe if seg < n_ev else with_inj):
+            continue
+        for r, (cx, cy) in enumerate(pairs):
+            code, y = (np.asarray(codes_pe)[cx, seg], np.asarray(x_pe)[cy, seg]) if seg < n_ev else (np.asarray(codes_inj)[cx], np.asarray(x_inj)[cy])
+            out[seg, r], _ = conditionals_segment(w, code, y, n_bins)
+    return out, dead
+
+
 def pareto_smooth(log_ratios):
     """Pareto-smoothed importance sampling on the point axis (Vehtari, Simpson, Gelman, Yao & Gabry, *Pareto smoothed importance
     sampling*; the fit is Zhang & Stephens 2009): ``log_ratios (K, n_seg)`` -> ``(log_weights (K, n_seg), khat (n_seg,))``.  Per column:

@@ -1,6 +1,6 @@
 """The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
-injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs and moments, marginal weights and their quantiles and kernel density
-estimates.
+injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments and conditional moments, marginal weights and their
+quantiles and kernel density estimates.
 Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
 """
 import ctypes as C
@@ -210,17 +210,18 @@ class PostprocessMixin:
                                                      dead.ctypes.data_as(i32)))
         return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead
 
-    def _per_point(self, what, need, shape_attr, missing, dtypes, shapes, thetas):
+    def _per_point(self, what, need, shape_attr, missing, dtypes, shapes, thetas, extra=()):
         """One per-point entry: the library's ``gwi_<what>`` fills one array per dtype, float64 or int32, of the shapes ``shapes(k, shape)``,
-        where ``shape`` is what the setter left in ``shape_attr``; the arrays are returned.  ``need`` and ``missing`` word the refusals."""
+        where ``shape`` is what the setter left in ``shape_attr``; the arrays are returned.  ``need`` and ``missing`` word the refusals;
+        ``extra`` holds the entry's own arguments between ``k`` and the outputs."""
         self._whole_catalog(what, need)
         thetas = self._points(thetas)
         k, entry = thetas.shape[0], getattr(self.lib, "gwi_" + what)
         shape = getattr(self, shape_attr, None)
         if shape is None:
-            self._nothing_set(what, missing, entry, N.as_dp(thetas), k, *(None for _ in dtypes))
+            self._nothing_set(what, missing, entry, N.as_dp(thetas), k, *extra, *(None for _ in dtypes))
         out = [np.empty(s, dtype=dt) for s, dt in zip(shapes(k, shape), dtypes)]
-        self._check(entry(self.handle, N.as_dp(thetas), k, *(N.as_dp(o) if o.dtype == np.float64 else o.ctypes.data_as(C.POINTER(C.c_int32)) for o in out)))
+        self._check(entry(self.handle, N.as_dp(thetas), k, *extra, *(N.as_dp(o) if o.dtype == np.float64 else o.ctypes.data_as(C.POINTER(C.c_int32)) for o in out)))
         return out
 
     def point_cdfs(self, thetas):
@@ -299,6 +300,30 @@ class PostprocessMixin:
         cov[..., iu[0], iu[1]] = raw[..., n_cols:]
         cov[..., iu[1], iu[0]] = raw[..., n_cols:]
         return np.ascontiguousarray(raw[..., :n_cols]), cov, dead
+
+    def point_conditionals(self, thetas, pairs):
+        """Per-point conditional moments of every segment, on the device (``gwi_point_conditionals``; semantics:
+        :func:`gwinferno_amd.draws.point_conditionals_reference`).  ``pairs`` is ``(R, 2)`` of ``(cx, cy)``: ``cx`` a bin column
+        of :meth:`set_histogram_bins` -- the conditioning quantity -- and ``cy`` a value column of :meth:`set_kde_columns`, both read
+        where they lie; ``1 <= R <= 8`` and ``R n_bins <= 512``.  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.  Returns
+        ``(share (k, n_ev + 1, R, B), mean (k, n_ev + 1, R, B), var (k, n_ev + 1, R, B), dead (k, n_ev + 1) int32)``, the injection set
+        last: per bin ``b`` of ``cx`` the bin's share ``W_b / S`` of the segment's weight (the bits :meth:`weighted_histograms` adds for the
+        point), the weighted mean of ``cy`` among the bin's samples and their weighted variance centred on that mean, and 1 for every
+        segment without weight at the point.  A bin without weight has share 0 and NaN mean and variance; NaN everywhere for a segment
+        without weight and for a set that lacks bins or columns.  ``3 (n_ev + 1) R B`` doubles come back per point; the points may be
+        split over calls without changing a bit.  Not available on an engine that holds a shard (``world > 1``)."""
+        from .draws import MAX_CONDITIONAL_PAIRS
+
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        if not 1 <= pairs.shape[0] <= MAX_CONDITIONAL_PAIRS:
+            raise ValueError(f"{pairs.shape[0]} pairs: between 1 and {MAX_CONDITIONAL_PAIRS} can be asked for in one call")
+        n_pairs = pairs.shape[0]
+        no_bins = getattr(self, "_hist_shape", None) is None
+        raw, dead = self._per_point("point_conditionals", "the injection moments need", "_hist_shape" if no_bins else "_kde_shape",
+                                    "bins are set (set_histogram_bins)" if no_bins else "columns are set (set_kde_columns)", (np.float64, np.int32),
+                                    lambda k, s: ((k, self.n_ev + 1, n_pairs, 3, self._hist_shape[1]), (k, self.n_ev + 1)), thetas,
+                                    extra=(n_pairs, pairs.ctypes.data_as(C.POINTER(C.c_int32))))
+        return np.ascontiguousarray(raw[:, :, :, 0]), np.ascontiguousarray(raw[:, :, :, 1]), np.ascontiguousarray(raw[:, :, :, 2]), dead
 
     def marginal_weights_reset(self):
         """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""

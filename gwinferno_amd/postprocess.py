@@ -1186,3 +1186,178 @@ def event_variance_split(eng, thetas, pe_values, point_weights=None, leave_one_o
         if "pareto_k" in loo:
             out["pareto_k"] = loo["pareto_k"]
     return out
+
+
+def _conditional_points(eng, thetas, x, y, edges, pe_values, inj_values, backend):
+    """``(share, mean, var (K, n_ev + 1, B), dead (K, n_ev + 1), edges (B + 1,))`` of ``y`` given the bin of ``x`` on either backend
+    (DESIGN 8k): ``x`` is binned with ``np.histogram``'s rule (:func:`gwinferno_amd.draws.digitize`)."""
+    from . import draws as D
+
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    for name in (x, y):
+        if name not in pe_values or (inj_values is not None and name not in inj_values):
+            raise ValueError(f"unknown quantity {name!r}")
+    edges = np.asarray(edges, dtype=np.float64).ravel()
+    n_bins = edges.size - 1
+    if not 1 <= n_bins <= min(D.MAX_CDF_GRID, D.MAX_CONDITIONAL_ITEMS):
+        raise ValueError("edges are between 2 and 257 increasing numbers")
+    _, v_pe, v_inj = _summary_columns(eng, pe_values, inj_values, None, None, [x, y])
+    codes_pe, codes_inj = D.digitize(v_pe[0], edges)[None], (None if v_inj is None else D.digitize(v_inj[0], edges)[None])
+    y_pe, y_inj = np.ascontiguousarray(v_pe[1:]), (None if v_inj is None else np.ascontiguousarray(v_inj[1:]))
+    if backend == "device":
+        eng.set_histogram_bins(codes_pe, codes_inj, n_bins=n_bins)
+        eng.set_kde_columns(y_pe, y_inj)
+        share, mean, var, dead = eng.point_conditionals(thetas, [(0, 0)])
+        return share[:, :, 0], mean[:, :, 0], var[:, :, 0], dead, edges
+    k, n_segs = thetas.shape[0], eng.n_ev + 1
+    out, dead = np.empty((k, n_segs, 3, n_bins)), np.empty((k, n_segs), dtype=np.int32)
+    for i, th in enumerate(thetas):
+        lw_pe, lw_inj = eng.log_weights(th)
+        one, dead[i] = D.point_conditionals_reference(lw_pe, lw_inj, codes_pe, codes_inj, y_pe, y_inj, [(0, 0)], n_bins)
+        out[i] = one[:, 0]
+    return out[:, :, 0], out[:, :, 1], out[:, :, 2], dead, edges
+
+
+def catalog_conditional_check(eng, thetas, x, y, edges, *, pe_values, inj_values, point_weights=None, backend="device", levels=(5, 50, 95)):
+    """Do the catalog's conditional mean and width of ``y`` given ``x`` agree with what the fitted population predicts for detected
+    sources?    A covariance (:func:`catalog_correlation_check`) sees the linear part of a dependence only; the known
+    departures from a separable model are a mean of ``chi_eff`` that drifts with mass ratio and a width that grows with redshift or mass:
+    statements about ``E[y | x]`` and ``Var[y | x]`` as functions of ``x``.  Per hyper-posterior point k and bin b of ``x`` the device
+    (``eng.point_conditionals``) returns every segment's share ``a``, conditional mean ``m`` and conditional variance ``v``; the observed
+    catalog is the equal-weight mixture of its live events e:
+
+    ``A_b = mean_e a_eb``    ``mu_b = sum_e a_eb m_eb / sum_e a_eb``    ``sigma2_b = sum_e a_eb [v_eb + (m_eb - mu_b)^2] / sum_e a_eb``
+
+    (events with ``a_eb = 0`` are left out of a bin's sums), held against the injection segment's ``m_b`` and ``v_b``.
+
+    ``thetas`` is ``(K, n_theta)``.  ``x`` and ``y`` name quantities of ``pe_values`` (name -> ``(n_ev, n_pe)``) and ``inj_values``
+    (name -> ``(n_inj,)``; ``None``: no predicted side, NaN); ``edges`` are the ``B + 1 <= 257`` increasing bin edges of ``x``
+    (``np.histogram``'s rule).  ``point_weights (K,)`` -- finite, non-negative, not all 0; default equal -- weight the points in the bands
+    and in the shares; they are applied here and never go to the device.  ``levels`` are percentiles in ``[0, 100]``.  The device
+    backend replaces the engine's histogram bins and KDE columns; the draw mask the engine holds stays.  ``backend="host"`` runs the NumPy
+    statement (:func:`gwinferno_amd.draws.point_conditionals_reference`) on ``eng.log_weights``, without a mask: the statement the
+    kernels are tested against, not a fall-back.
+
+    Returns a dict: ``x``, ``y``, ``edges``, ``levels``; per point and bin ``share_obs``, ``mean_obs``, ``var_obs``, ``std_obs``,
+    ``share_det``, ``mean_det``, ``var_det``, ``std_det``, ``delta_mean = mean_obs - mean_det`` and ``delta_std = std_obs - std_det``,
+    each ``(K, B)``; ``bands_<key> (Q, B)`` of each, the weighted percentiles over the points
+    (:func:`gwinferno_amd.draws.weighted_percentiles`); ``p_delta_mean_positive`` and ``p_delta_std_positive (B,)``, the weighted share
+    of the points with ``delta > 0`` among those where it is a number, and ``p_mean_two_sided``, ``p_std_two_sided = 2 min(p, 1 - p)``.
+    A (point, bin) with no observed or no predicted weight is skipped (NaN) and counted in ``n_skipped (B,)``.  Also ``n_live (K,)``, the
+    live events per point; the raw ``point_share``, ``point_mean``, ``point_var (K, n_ev + 1, B)`` and ``dead``; ``n_points``."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k, n_ev = thetas.shape[0], eng.n_ev
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or levels.size < 1 or not np.all((levels >= 0.0) & (levels <= 100.0)):
+        raise ValueError("levels must be percentiles in [0, 100]")
+    if point_weights is None:
+        v = np.ones(k)
+    else:
+        v = np.asarray(point_weights, dtype=np.float64)
+        if v.shape != (k,) or not np.all(np.isfinite(v)) or np.any(v < 0.0) or not np.any(v > 0.0):
+            raise ValueError(f"point_weights are ({k},) finite non-negative numbers, not all 0")
+    share, mean, var, dead, edges = _conditional_points(eng, thetas, x, y, edges, pe_values, inj_values, backend)
+    live = dead[:, :n_ev] == 0                                    # (K, n_ev)
+    n_live = live.sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = np.where(live[:, :, None], share[:, :n_ev], 0.0)      # (K, n_ev, B); NaN nowhere
+        has = a > 0.0
+        den = a.sum(axis=1)                                       # (K, B)
+        share_obs = den / n_live[:, None]
+        m = np.where(has, mean[:, :n_ev], 0.0)
+        mean_obs = (a * m).sum(axis=1) / den                      # NaN where no event has weight in the bin
+        dm = np.where(has, m - mean_obs[:, None, :], 0.0)
+        var_obs = (a * (np.where(has, var[:, :n_ev], 0.0) + dm * dm)).sum(axis=1) / den
+        std_obs = np.sqrt(var_obs)
+        share_det, mean_det, var_det = share[:, n_ev], mean[:, n_ev], var[:, n_ev]
+        std_det = np.sqrt(var_det)
+        delta_mean, delta_std = mean_obs - mean_det, std_obs - std_det
+
+    def shares(delta):
+        has_delta = ~np.isnan(delta)
+        total = (v[:, None] * has_delta).sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p = (v[:, None] * (has_delta & (np.where(has_delta, delta, 0.0) > 0.0))).sum(axis=0) / total
+        return p, 2.0 * np.minimum(p, 1.0 - p)
+
+    p_mean, p_std = shares(delta_mean), shares(delta_std)
+    out = {"x": x, "y": y, "edges": edges, "levels": levels, "share_obs": share_obs, "mean_obs": mean_obs, "var_obs": var_obs, "std_obs": std_obs,
+           "share_det": share_det, "mean_det": mean_det, "var_det": var_det, "std_det": std_det, "delta_mean": delta_mean, "delta_std": delta_std,
+           "p_delta_mean_positive": p_mean[0], "p_mean_two_sided": p_mean[1], "p_delta_std_positive": p_std[0], "p_std_two_sided": p_std[1],
+           "n_skipped": np.isnan(delta_mean).sum(axis=0).astype(np.int64), "n_live": n_live.astype(np.int64), "point_share": share, "point_mean": mean,
+           "point_var": var, "dead": dead, "n_points": k}
+    for key in ("share_obs", "mean_obs", "std_obs", "share_det", "mean_det", "std_det", "delta_mean", "delta_std"):
+        out["bands_" + key] = D.weighted_percentiles(out[key], v, levels / 100.0)
+    return out
+
+
+def event_conditional_moments(eng, thetas, x, y, edges, *, pe_values, inj_values=None, point_weights=None, leave_one_out=False, total_inj=None, nobs=None,
+                              marginalize_selection=False, backend="device"):
+    """Every event's population-informed conditional mean and variance of ``y`` per bin of ``x``, marginalised over the hyper-posterior
+    points, with the variance split as in :func:`event_variance_split`.  With the per-point shares ``a_kb``, conditional
+    means ``m_kb`` and variances ``v_kb`` of the event (``eng.point_conditionals``) and normalised point weights ``v_k``, the weight of
+    point k in bin b is ``u_kb = v_k a_kb / sum_k v_k a_kb`` and
+
+    ``share_b = sum_k v_k a_kb``   ``mean_b = sum_k u_kb m_kb``   ``within_b = sum_k u_kb v_kb``   ``between_b = sum_k u_kb (m_kb - mean_b)^2``
+
+    ``total = within + between`` is the variance of ``y`` under the marginal weights restricted to the bin (the law of total variance).
+
+    The arguments are :func:`catalog_conditional_check`'s (``inj_values`` is not needed).  The weights on the k axis are applied here, on the
+    host: equal by default, ``point_weights (K,)`` or ``(K, n_ev + 1)`` (the last column is not used), with ``leave_one_out=True`` those of
+    :func:`leave_one_out_weights` and with ``leave_one_out="psis"`` those of :func:`pareto_smoothed_loo_weights` (``total_inj`` is needed;
+    ``nobs`` and ``marginalize_selection`` as there).  A (point, event, bin) without weight -- the event dead at the point or the bin
+    empty -- is skipped and counted in ``n_skipped``.
+
+    Returns a dict: ``x``, ``y``, ``edges``; ``share``, ``mean``, ``within``, ``between`` and ``total``, each ``(n_ev, B)`` (NaN mean
+    and variances for a bin no point gives weight; NaN shares too for an event without a live point of positive weight); ``neff_points
+    (n_ev,)``, ``(sum_k v)^2 / sum_k v^2`` over the points at which the event is live; ``n_skipped (n_ev, B)``; ``n_dead (n_ev,)``; the
+    raw ``point_share``, ``point_mean``, ``point_var (K, n_ev + 1, B)`` and ``dead``; ``n_points``; with leave-one-out weights ``elpd_loo
+    (n_ev,)``, and with ``"psis"`` also ``pareto_k (n_ev,)``."""
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k, n_ev = thetas.shape[0], eng.n_ev
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if not (isinstance(leave_one_out, bool) or leave_one_out == "psis"):
+        raise ValueError(f"leave_one_out must be False, True or 'psis', not {leave_one_out!r}")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    if leave_one_out == "psis":
+        if point_weights is not None:
+            raise ValueError("leave_one_out='psis' makes the point weights itself: point_weights must be None")
+        if total_inj is None:
+            raise ValueError("leave_one_out='psis' needs total_inj")
+        loo = pareto_smoothed_loo_weights(eng, thetas, total_inj, nobs=nobs, marginalize_selection=marginalize_selection)
+        v = loo["point_weights"]
+    else:
+        v, loo = _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection)
+    v = np.ones((k, n_ev)) if v is None else np.asarray(v, dtype=np.float64)[:, :n_ev]
+    share, mean, var, dead, edges = _conditional_points(eng, thetas, x, y, edges, pe_values, inj_values, backend)
+    gone = dead[:, :n_ev] != 0                                    # (K, n_ev): the event has no weight at the point
+    w = np.where(gone, 0.0, v)
+    wsum, wsq = w.sum(axis=0), (w * w).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vn = w / wsum                                             # NaN columns where an event has no point that counts
+        a = np.where(gone[:, :, None], 0.0, share[:, :n_ev])     # (K, n_ev, B)
+        has = (a > 0.0) & (w[:, :, None] > 0.0)
+        mass = vn[:, :, None] * a
+        share_e = mass.sum(axis=0)                                # (n_ev, B)
+        u = np.where(has, mass, 0.0) / np.where(has, mass, 0.0).sum(axis=0)
+        m = np.where(has, mean[:, :n_ev], 0.0)
+        mbar = (u * m).sum(axis=0)
+        mbar = np.where(has.any(axis=0), mbar, np.nan)
+        within = np.where(has.any(axis=0), (u * np.where(has, var[:, :n_ev], 0.0)).sum(axis=0), np.nan)
+        between = np.where(has.any(axis=0), (u * np.where(has, m - mbar, 0.0) ** 2).sum(axis=0), np.nan)
+        neff = np.where(wsum > 0.0, wsum * wsum / wsq, 0.0)
+    out = {"x": x, "y": y, "edges": edges, "share": share_e, "mean": mbar, "within": within, "between": between, "total": within + between, "neff_points": neff,
+           "n_skipped": (~has).sum(axis=0).astype(np.int64), "n_dead": gone.sum(axis=0).astype(np.int64), "point_share": share, "point_mean": mean, "point_var": var,
+           "dead": dead, "n_points": k}
+    if loo is not None:
+        out["elpd_loo"] = loo["elpd_loo"]
+        if "pareto_k" in loo:
+            out["pareto_k"] = loo["pareto_k"]
+    return out

@@ -585,7 +585,7 @@ void gwi_point_rank_times(double* logw_ms, double* prefix_ms, double* pit_ms, in
  * live sample gives that sample and a covariance of exactly 0.  k >= 1 is not bound by the batch limit: the points are staged on the
  * device 64 at a time and copied back per chunk.  Every sum has a fixed shape (sample order inside a tile of 1 024, then tile order)
  * and there are no atomics: the bits are a pure function of (theta_k, columns, masks), whatever the split of the points over calls, and
- * the call changes no state another entry reads.  Not done: sharded handles; more than 8 columns; rank correlation; conditional means.
+ * the call changes no state another entry reads.  Not done: sharded handles; more than 8 columns; rank correlation (conditional means: gwi_point_conditionals).
  * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, a host-only handle and a call before columns are set;
  * GWI_ERR_UNSUPPORTED on a handle that holds a shard.
  *
@@ -594,6 +594,39 @@ void gwi_point_rank_times(double* logw_ms, double* prefix_ms, double* pit_ms, in
  * together and of the two covariance launches, and the number of kernel launches after the log-weight passes. */
 gwi_status gwi_point_moments(gwi_handle h, const double* thetas, int32_t k, double* out /* [k][n_ev + 1][C + C(C+1)/2] */, int32_t* dead /* [k][n_ev + 1] */);
 void gwi_point_moment_times(double* logw_ms, double* mean_ms, double* cov_ms, int32_t* launches);
+
+/* Per-point conditional moments on the device: per hyper-parameter point and segment, for every bin of a conditioning quantity x, the
+ * bin's share of the weight and the weighted mean and variance of another quantity y among the bin's samples -- E[y | x] and Var[y | x]
+ * as functions of x, what a drift of a mean or a growth of a width with another quantity is stated in, and what a covariance (linear only)
+ * does not see (gwinferno_amd/csrc/gwi_cond.h; the NumPy statement is gwinferno_amd/draws.py: point_conditionals_reference; the contract
+ * is DESIGN 8k).
+ *
+ * gwi_point_conditionals(): pairs[r] = (cx, cy): cx a bin column of gwi_set_histogram_bins (n_bins is that setter's), cy a value column
+ * of gwi_set_kde_columns; both are read where they lie, nothing is copied and there is no setter of this entry's own.  1 <= n_pairs <= 8
+ * and n_pairs n_bins <= 512.  A sample set is covered when it has both bins and columns.  Segments, lw_i, the masks of gwi_set_draw_mask,
+ * M, w_i = exp(lw_i - M) and the segment total S are gwi_draw_indices'.  For point k, segment s (the injection segment last), pair r and
+ * bin b, with W_b the sum of w_i over the samples coded b:
+ *   a_b = W_b / S                                  out[k][s][r][0][b]   (a sample coded 0xFFFF counts in S and in no bin)
+ *   m_b = sum_{i in b} w_i y_i / W_b               out[k][s][r][1][b]
+ *   v_b = sum_{i in b} w_i (y_i - m_b)^2 / W_b     out[k][s][r][2][b]
+ * in two passes over the samples, the second centred on the m_b of the first.  Slot 0 has the bits gwi_weighted_histograms adds for this
+ * one point onto a zeroed histogram of column cx.  A bin with W_b = 0 gives a_b = +0.0 and NaN for m_b and v_b: no error, no flag.  A
+ * segment whose S is 0 or not finite gives NaN in all three slots and dead[k][s] = 1; the segments of a set that is not covered give NaN
+ * (dead still tells whether they had weight).  k >= 1 is not bound by the batch limit: the points are staged on the device 64 at a time
+ * and copied back per chunk.  Every sum has a fixed shape (sample order inside a tile of 1 024 and a bin, then tile order) and there are
+ * no atomics: the bits are a pure function of (theta_k, codes, columns, masks, pairs), whatever the split of the points over calls, and
+ * the call changes no state another entry reads.  Not done: sharded handles; rank correlation; more than 8 pairs or 512 (pair, bin)
+ * items; two conditioning quantities at once.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, n_pairs outside 1 ... 8, an index outside the bin columns
+ * or the value columns, n_pairs n_bins > 512, a call before bins are set or before columns are set, no sample set covered by both, and a
+ * host-only handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard.
+ *
+ * gwi_point_conditional_times(): DIAGNOSTIC ONLY, for tools/post_time.py: of the calling thread's last call, summed over its points, the
+ * wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge / two mean launches together
+ * and of the two variance launches, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_point_conditionals(gwi_handle h, const double* thetas, int32_t k, int32_t n_pairs, const int32_t* pairs /* [n_pairs][2] */,
+                                  double* out /* [k][n_ev + 1][n_pairs][3][n_bins] */, int32_t* dead /* [k][n_ev + 1] */);
+void gwi_point_conditional_times(double* logw_ms, double* mean_ms, double* var_ms, int32_t* launches);
 
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is

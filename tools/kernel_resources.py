@@ -29,8 +29,8 @@ def _metadata(hsaco):
 
 
 def _label(mangled):
-    """The kernel's own name without its namespaces and arguments, and its template argument if it has one: ``moment_cov_kernel``, ``<8>``;
-    ``hist_merge_kernel``, ``<true>``."""
+    """The kernel's own name without its namespaces and arguments, and its template arguments if it has any: ``moment_cov_kernel``, ``<8>``;
+    ``hist_merge_kernel``, ``<true>``; ``cond_tile_kernel``, ``<4, false>``."""
     at, name = re.match(r"_ZN?|", mangled).end(), mangled
     while True:
         n = re.match(r"\d+", mangled[at:])
@@ -38,8 +38,9 @@ def _label(mangled):
             break
         at += n.end() + int(n.group())
         name = mangled[at - int(n.group()):at]
-    t = re.match(r"IL([bi])(\d+)E", mangled[at:])
-    return name, "" if not t else f"<{t.group(2)}>" if t.group(1) == "i" else ("<false>", "<true>")[int(t.group(2))]
+    t = re.match(r"I((?:L[bi]\d+E)+)", mangled[at:])
+    args = [d if kind == "i" else ("false", "true")[int(d)] for kind, d in re.findall(r"L([bi])(\d+)E", t.group(1))] if t else []
+    return name, "<" + ", ".join(args) + ">" if args else ""
 
 
 def kernel_resources(pattern, hsaco=None):

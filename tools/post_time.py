@@ -7,7 +7,7 @@ timed on another build of the engine (the parent commit's), in child processes o
 half after, and this build's median is placed against the span of that build's own calls.  No figure is fixed in advance; what is not
 measured is named as unmeasured.  Writes a Markdown report.
 
-      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments} [--configs c2,c5] [--repeats 10]
+      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals} [--configs c2,c5] [--repeats 10]
                                 [--parent-lib PATH] [--out profiles/<entry>/RESULTS.md]
 
 What differs per entry is one record of ENTRIES: the set-up calls, one_round, the host route, the kernels to list and the row labels."""
@@ -392,6 +392,62 @@ def moments_tail(res):
     return [f"Scratch is {max(r[4] for r in res)} bytes in every kernel listed: the {max(r[1] for r in res)} VGPRs of `moment_cov_kernel<8>` hold its 36 running sums without a spill.", ""]
 
 
+# ---- point_conditionals (gwi_cond.h) ----------------------------------------------------------------------------------------
+COND_BINS = 16
+
+
+def conditionals_setup(c, extra, full):
+    from gwinferno_amd import draws as D
+
+    c.edges = [np.quantile(np.concatenate([p.ravel(), i]), np.linspace(0.01, 0.99, COND_BINS + 1)) for p, i in zip(c.x_pe, c.x_inj)]
+    c.codes = tuple(np.stack([D.digitize(v, e) for v, e in zip(x, c.edges)]) for x in (c.x_pe, c.x_inj))
+    c.eng.set_histogram_bins(*c.codes, n_bins=COND_BINS)
+    c.eng.set_kde_columns(c.x_pe, c.x_inj)
+    c.pairs = [(1, 2)]  # chi_eff given the mass-ratio bin
+
+
+def conditionals_round(c, thetas, full):
+    out = {}
+    hist_round(c, thetas, out)
+    t = timed(out, "moment", lambda: c.eng.point_moments(thetas), c.eng.lib.gwi_point_moment_times, thetas)
+    out["moment"] = t[1] + t[2]
+    if full:
+        t = timed(out, "cond", lambda: c.eng.point_conditionals(thetas, c.pairs), c.eng.lib.gwi_point_conditional_times, thetas)
+        out["cond"], out["cond var"], out["cond logw"] = t[1] + t[2], t[2], t[0]
+    return out
+
+
+def conditionals_check(c, extra):
+    from gwinferno_amd import draws as D
+
+    def reference(lw_pe, lw_inj):
+        return D.point_conditionals_reference(lw_pe, lw_inj, c.codes[0], c.codes[1], c.x_pe, c.x_inj, c.pairs, COND_BINS)
+
+    extra["host_ms"], (want, want_dead) = host_route(c, 2, reference)
+    share, mean, var, dead = c.eng.point_conditionals(c.thetas[1], c.pairs)
+    ok = ~np.isnan(want[:, 0, 2]) & (want[:, 0, 2] > 0.0)
+    extra["deviation"] = float(np.max(np.abs(var[0][:, 0][ok] - want[:, 0, 2][ok]) / want[:, 0, 2][ok])) if ok.any() else float("nan")
+    extra["flags"] = bool(np.array_equal(dead[0], want_dead)) and bool(np.array_equal(np.isnan(mean[0][:, 0]), np.isnan(want[:, 0, 1])))
+
+
+def conditionals_notes(cfg, own, extra):
+    back = 8 * 3 * (extra["n_ev"] + 1) * COND_BINS + 4 * (extra["n_ev"] + 1)
+    return [f"- {cfg}: host route (`Engine.log_weights` + `draws.point_conditionals_reference`, {extra['host_mb']:.1f} MB to the host per point against {back} bytes from the device): "
+            f"{extra['host_ms']:.1f} ms per point over 2 points, ONE run, no spread taken.  Largest relative |device - host| conditional variance of the last of them: "
+            f"{extra['deviation']:.2e}; flags and NaN positions {'equal' if extra['flags'] else 'DIFFERENT'}."]
+
+
+def conditionals_intro(repeats, how):
+    return (f"K = {K} points per call, C = 3 columns ({', '.join(MASS_CHI)}) as bin columns (B = {COND_BINS}) and as value columns, one pair (chi_eff given the mass-ratio bin), "
+            f"{repeats} calls per row after two warm-up calls.  Times in ms; device times are HIP-event times of the launches after the log-weight pass (draw tile, draw merge and the "
+            f"entry's own), summed over the call and divided by K.  No ratio was promised in advance.  `parent`: {how}".rstrip())
+
+
+def conditionals_tail(res):
+    return [f"Scratch is {max(r[4] for r in res)} bytes in every kernel listed.  `cond_tile_kernel<N, centred>` holds 8 KB of weights and 10 KB per staged column in LDS (N = 1, 2, 4, 8: the "
+            "larger number of distinct bin / value columns of the pairs, rounded up), the centred pass 4 KB of means more.", ""]
+
+
 QUANTITIES = f"C = 3 quantities ({', '.join(MASS_Z)})"
 WEIGHTED_LABEL = {"hist_merge_kernel<true>": "hist_merge_kernel<true> (weighted)", "marg_add_kernel<true>": "marg_add_kernel<true> (weighted)"}
 COMMON = dict(style="spread", columns=MASS_Z, relabel={}, resources_tail=lambda res: [], check=lambda c, extra: None)
@@ -449,6 +505,14 @@ ENTRIES = {e.name: e for e in (
                  ("moment logw", "`point_moments`, log-weight pass per point (host clock)"), ("moment wall", "`point_moments`, wall time per point of the call"),
                  ("cdf", "`point_cdfs`, device time per point after the log-weight pass"), ("kde", "`weighted_kde`, device time per query")],
            compare=("moment", "cdf", "kde"), spans=[("moment", "`point_moments`", " per point"), ("cdf", "`point_cdfs`", " per point"), ("kde", "`weighted_kde`", " per query")],
+           unmeasured="NOT MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
+    record(style="calls", columns=MASS_CHI, resources_tail=conditionals_tail, name="point_conditionals", symbol="gwi_point_conditionals",
+           title="# Per-point conditional moments: measured times", kernels="cond_tile_kernel|cond_mean_kernel|cond_var_kernel|hist_tile_kernel|draw_tile_kernel|draw_merge_kernel",
+           setup=conditionals_setup, one_round=conditionals_round, notes=conditionals_notes, check=conditionals_check, intro=conditionals_intro,
+           rows=[("cond", "`point_conditionals`, device time per point after the log-weight pass"), ("cond var", "... of which the two variance launches"),
+                 ("cond logw", "`point_conditionals`, log-weight pass per point (host clock)"), ("cond wall", "`point_conditionals`, wall time per point of the call"),
+                 ("moment", "`point_moments`, device time per point after the log-weight pass"), ("hist", "`weighted_histograms`, device time per point after the log-weight pass")],
+           compare=("moment", "hist"), spans=[("moment", "`point_moments` (unchanged code)", " per point"), ("hist", "`weighted_histograms` (unchanged code)", " per point")],
            unmeasured="NOT MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
 )}
 
