@@ -248,6 +248,9 @@ EXPORTED_SYMBOLS = [
     "gwi_point_moment_times",
     "gwi_point_conditionals",
     "gwi_point_conditional_times",
+    "gwi_set_rankcorr_columns",
+    "gwi_point_rank_correlations",
+    "gwi_point_rankcorr_times",
     "gwi_marginal_weights_reset",
     "gwi_marginal_weights_add",
     "gwi_marginal_weights_add_weighted",
@@ -454,6 +457,13 @@ def load_library():
         lib.gwi_point_conditionals.argtypes = [vp, _DP, C.c_int32, C.c_int32, _I32P, _DP, _I32P]
         lib.gwi_point_conditional_times.restype = None
         lib.gwi_point_conditional_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_point_rank_correlations"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        lib.gwi_set_rankcorr_columns.restype = C.c_int32
+        lib.gwi_set_rankcorr_columns.argtypes = [vp, C.c_int32, _I32P, _I32P, _I32P, _I32P, _I32P, _I32P]
+        lib.gwi_point_rank_correlations.restype = C.c_int32
+        lib.gwi_point_rank_correlations.argtypes = [vp, _DP, C.c_int32, _DP, _I32P]
+        lib.gwi_point_rankcorr_times.restype = None
+        lib.gwi_point_rankcorr_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

@@ -544,6 +544,15 @@ struct ConditionalBuffers {
   DeviceBuffer<double> d_partial, d_bin_w, d_stage;
   DeviceBuffer<int> d_dead;
 };
+// ... and of the per-point rank correlations (gwi_rankcorr.h): per rank set (the pooled PE samples, the injections) the orders and the
+// members' ranks of gwi_set_rankcorr_columns, and the entry's own workspace -- the order tiles' sums and offsets [2][n_cols][order
+// tiles of both sets], the prefix tables P [n_cols][n + 1] of either set, the sample tiles' sums [n_tiles][items] and the staged rows
+// [64][2][items] and flags [64][n_ev + 2] (allocated with the columns, kept).  A pointer for ConditionalBuffers' reason, released with it.
+struct RankcorrBuffers {
+  DeviceBuffer<int> d_codes, d_dead;  // order, lt, le of the observed set, then of the detected set
+  DeviceBuffer<double> d_tiles, d_prefix, d_partial, d_stage;
+  int cols = 0;
+};
 }  // namespace
 
 struct gwi_engine {
@@ -678,6 +687,7 @@ struct gwi_engine {
   RankBuffers rank;           // gwi_set_rank_columns / gwi_point_pits_exact (freed with `post`)
   MomentBuffers moment;       // gwi_point_moments (freed with `post`)
   ConditionalBuffers* cond = nullptr;  // gwi_point_conditionals (release_moment_and_conditional_buffers, with `post`)
+  RankcorrBuffers* rankcorr = nullptr;  // gwi_set_rankcorr_columns / gwi_point_rank_correlations (released with `cond`)
 };
 
 namespace {
@@ -4357,6 +4367,8 @@ __attribute__((noinline)) void release_moment_and_conditional_buffers(gwi_handle
   h->moment = MomentBuffers();
   delete h->cond;
   h->cond = nullptr;
+  delete h->rankcorr;
+  h->rankcorr = nullptr;
 }
 }  // namespace
 extern "C" {
@@ -4441,6 +4453,141 @@ gwi_status gwi_point_conditionals(gwi_handle h, const double* thetas, int32_t k,
 }
 
 void gwi_point_conditional_times(double* logw_ms, double* mean_ms, double* var_ms, int32_t* launches) { g_point_conditional_times.report(logw_ms, mean_ms, var_ms, launches); }
+
+// ---- per-point rank correlations: weighted mid-ranks within the pooled PE samples and within the injections (gwi_rankcorr.h) ----------
+// (the header is included here for gwi_cond.h's reason)
+}  // extern "C"
+#include "gwi_rankcorr.h"
+namespace {
+// what is wrong with one rank set's codes, or an empty string: every order a permutation of the set's n members, every rank in [0, n],
+// lt <= position of the member along the order < le
+std::string bad_rankcorr_codes(const char* set, int n_cols, long long n, const int32_t* order, const int32_t* lt, const int32_t* le) {
+  std::vector<int32_t> pos((size_t)n);
+  for (int c = 0; c < n_cols; ++c) {
+    std::fill(pos.begin(), pos.end(), -1);
+    const int32_t* o = order + (size_t)c * (size_t)n;
+    for (long long r = 0; r < n; ++r) {
+      const long long i = o[r];
+      if (i < 0 || i >= n || pos[(size_t)i] >= 0)
+        return std::string("order_") + set + " column " + std::to_string(c) + ": position " + std::to_string(r) + " holds " + std::to_string(i) + ": not a permutation of the set's " +
+               std::to_string(n) + " members";
+      pos[(size_t)i] = (int32_t)r;
+    }
+    const int32_t* below = lt + (size_t)c * (size_t)n;
+    const int32_t* upto = le + (size_t)c * (size_t)n;
+    for (long long i = 0; i < n; ++i) {
+      const std::string where = std::string("_") + set + " column " + std::to_string(c) + ", member " + std::to_string(i) + ": ";
+      if (below[i] < 0 || below[i] > n) return "lt" + where + std::to_string(below[i]) + " is not in 0 ... n = " + std::to_string(n);
+      if (upto[i] < 0 || upto[i] > n) return "le" + where + std::to_string(upto[i]) + " is not in 0 ... n = " + std::to_string(n);
+      if (below[i] > upto[i]) return "lt" + where + std::to_string(below[i]) + " exceeds le = " + std::to_string(upto[i]);
+      if (below[i] > pos[(size_t)i] || pos[(size_t)i] >= upto[i])
+        return "lt" + where + "the member's position " + std::to_string(pos[(size_t)i]) + " along the order is not in lt = " + std::to_string(below[i]) + " ... le - 1 = " + std::to_string(upto[i] - 1);
+    }
+  }
+  return "";
+}
+}  // namespace
+extern "C" {
+static thread_local StageTimes g_point_rankcorr_times;
+
+gwi_status gwi_set_rankcorr_columns(gwi_handle h, int32_t n_cols, const int32_t* order_obs, const int32_t* lt_obs, const int32_t* le_obs, const int32_t* order_det,
+                                    const int32_t* lt_det, const int32_t* le_det) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace R = gwi::rankcorr;
+  const char* who = "gwi_set_rankcorr_columns";
+  gwi_status st = post_preflight(h, who, "keep the columns on", "the rank sets need", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_point_moments: a shard says that it is one)
+  const long long n_obs = h->n_ev * h->n_pe, n_det = h->n_inj;
+  std::string why;
+  if (n_cols < 1 || n_cols > R::kMaxCols) why = "n_cols = " + std::to_string(n_cols) + " is not in 1 ... " + std::to_string(R::kMaxCols);
+  else if (!order_obs || !lt_obs || !le_obs || !order_det || !lt_det || !le_det) why = "order_obs, lt_obs, le_obs, order_det, lt_det or le_det is null";
+  else if (n_obs >= 0x7fffffffLL || n_det >= 0x7fffffffLL) why = "more members of a set than an int32 rank can count";
+  else why = bad_rankcorr_codes("obs", n_cols, n_obs, order_obs, lt_obs, le_obs);
+  if (why.empty()) why = bad_rankcorr_codes("det", n_cols, n_det, order_det, lt_det, le_det);
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, std::string(who) + ": " + why);
+  gwi::draw::DrawArgs geometry;
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &geometry, &n_tiles);
+  if (st != GWI_OK) return st;
+  // the previous columns go away first: should an allocation fail, gwi_point_rank_correlations refuses until they are set again
+  delete h->rankcorr;
+  h->rankcorr = new (std::nothrow) RankcorrBuffers();
+  if (!h->rankcorr) return fail(h, GWI_ERR_INVALID, std::string(who) + ": out of host memory");
+  RankcorrBuffers& rc = *h->rankcorr;
+  const size_t cols = (size_t)n_cols, obs = cols * (size_t)n_obs, det = cols * (size_t)n_det, items = (size_t)R::items_of(n_cols);
+  const size_t order_tiles = (size_t)(gwi::draw::tiles_of(n_obs) + gwi::draw::tiles_of(n_det)), n_prefix = cols * (size_t)(n_obs + 1 + n_det + 1);
+  GWI_HIP(rc.d_codes.reserve(3 * (obs + det)));
+  const int32_t* src[6] = {order_obs, lt_obs, le_obs, order_det, lt_det, le_det};
+  for (int i = 0; i < 6; ++i) {
+    const size_t count = i < 3 ? obs : det, at = i < 3 ? (size_t)i * obs : 3 * obs + (size_t)(i - 3) * det;
+    if (count) GWI_HIP(hipMemcpy(rc.d_codes.ptr + at, src[i], sizeof(int32_t) * count, hipMemcpyHostToDevice));
+  }
+  GWI_HIP(rc.d_tiles.reserve(2 * cols * order_tiles + 1));
+  GWI_HIP(rc.d_prefix.reserve(n_prefix));
+  GWI_HIP(rc.d_partial.reserve((size_t)n_tiles * items + 1));
+  GWI_HIP(rc.d_stage.reserve((size_t)kStagePoints * R::kSets * items));
+  GWI_HIP(rc.d_dead.reserve((size_t)kStagePoints * (size_t)(h->n_ev + 2)));
+  GWI_HIP(hipMemset(rc.d_prefix, 0, sizeof(double) * n_prefix));  // (an empty set launches nothing that would store P[c][0])
+  rc.cols = n_cols;
+  return GWI_OK;
+}
+
+gwi_status gwi_point_rank_correlations(gwi_handle h, const double* thetas, int32_t k, double* out, int32_t* dead) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_rank_correlations";
+  g_point_rankcorr_times = StageTimes();
+  gwi_status st = post_preflight(h, who, "sum on", "the rank sets need", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_point_moments)
+  const bool set = h->rankcorr && h->rankcorr->cols;
+  const std::string why = bad_point_args(h, set ? "" : "no rank-correlation columns are set (gwi_set_rankcorr_columns)", thetas, k, {{"out", out}, {"dead", dead}});
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, std::string(who) + ": " + why);
+  namespace R = gwi::rankcorr;
+  RankcorrBuffers& rc = *h->rankcorr;
+  R::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);  // (as gwi_set_rankcorr_columns found it)
+  if (st != GWI_OK) return st;
+  const size_t cols = (size_t)rc.cols, items = (size_t)R::items_of(rc.cols), n_obs = (size_t)(h->n_ev * h->n_pe), n_det = (size_t)h->n_inj;
+  const size_t obs = cols * n_obs, det = cols * n_det;
+  a.n[R::kObs] = (long long)n_obs;
+  a.n[R::kDet] = (long long)n_det;
+  a.order_tiles[R::kObs] = (int)gwi::draw::tiles_of((long long)n_obs);
+  a.order_tiles[R::kDet] = (int)gwi::draw::tiles_of((long long)n_det);
+  const unsigned order_tiles = (unsigned)(a.order_tiles[R::kObs] + a.order_tiles[R::kDet]);
+  a.order[R::kObs] = rc.d_codes;
+  a.lt[R::kObs] = rc.d_codes + obs;
+  a.le[R::kObs] = rc.d_codes + 2 * obs;
+  a.order[R::kDet] = rc.d_codes + 3 * obs;
+  a.lt[R::kDet] = rc.d_codes + 3 * obs + det;
+  a.le[R::kDet] = rc.d_codes + 3 * obs + 2 * det;
+  a.prefix[R::kObs] = rc.d_prefix;
+  a.prefix[R::kDet] = rc.d_prefix + cols * (n_obs + 1);
+  a.tile_sum = rc.d_tiles;
+  a.tile_off = rc.d_tiles + cols * order_tiles;
+  a.partial = rc.d_partial;
+  a.n_cols = rc.cols;
+  StagedRows rows(h, k);  // 2 (1 + C + C (C + 1) / 2) doubles and n_ev + 2 ints per point
+  rows.add(out, rc.d_stage.ptr, (size_t)R::kSets * items);
+  rows.add(dead, rc.d_dead.ptr, (size_t)(h->n_ev + 2));
+  const auto prefix = [&](int) {
+    if (!order_tiles) return;
+    hipLaunchKernelGGL(R::rankcorr_tile_kernel, dim3(order_tiles, (unsigned)cols), dim3(R::kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(R::rankcorr_offset_kernel, dim3((unsigned)cols, R::kSets), dim3(64), 0, h->stream, a);
+    hipLaunchKernelGGL(R::rankcorr_prefix_kernel, dim3(order_tiles, (unsigned)cols), dim3(R::kBlock), 0, h->stream, a);
+  };
+  const auto covariances = [&](int p) {  // into the point's slot of the stage
+    a.out = rows.slot<double>(0, p);
+    a.dead = rows.slot<int>(1, p);
+    if (n_tiles) R::launch_cov((unsigned)n_tiles, h->stream, a);
+    hipLaunchKernelGGL(R::rankcorr_merge_kernel, dim3(R::kSets), dim3(64), 0, h->stream, a);
+  };
+  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_rankcorr_times, 2, 7, prefix, covariances, [&](int p) { return rows.after(p); });
+}
+
+void gwi_point_rankcorr_times(double* logw_ms, double* prefix_ms, double* cov_ms, int32_t* launches) { g_point_rankcorr_times.report(logw_ms, prefix_ms, cov_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

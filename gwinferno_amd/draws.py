@@ -35,7 +35,12 @@ the loop and :func:`point_pits_reference` one point.
 
 ``gwi_point_pits_exact`` (gwinferno_amd/csrc/gwi_rank.h) gives the same transform without a grid, as the weighted rank of every PE sample
 among the injections: :func:`rank_codes` states the theta-independent ranks and :func:`point_pits_exact_reference` one point;
-:func:`pareto_smooth` and :func:`pareto_smoothed_summary` smooth the leave-one-out weights on the point axis."""
+:func:`pareto_smooth` and :func:`pareto_smoothed_summary` smooth the leave-one-out weights on the point axis.
+
+``gwi_point_rank_correlations`` (gwinferno_amd/csrc/gwi_rankcorr.h) ranks the members of a set among themselves -- the pooled PE samples,
+the injections -- under the point's weights and returns the second moments of the centred mid-ranks, of which Spearman's correlation
+is a ratio: :func:`rankcorr_codes` states the theta-independent codes, :func:`rankcorr_set` one set and
+:func:`point_rank_correlations_reference` one point."""
 import bisect
 import itertools
 import math
@@ -638,6 +643,136 @@ def point_pits_exact_reference(logw_pe, logw_inj, pe_mask, inj_mask, order_inj, 
             for i, ranks in enumerate((rank_lt[c, ev], rank_le[c, ev])):
                 pit[ev, c, i] = math.fsum((w * p[ranks]).tolist()) / total / p[n_inj]
     return pit, dead
+
+
+MAX_RANKCORR_COLUMNS = 8  # columns of gwi_set_rankcorr_columns (gwi_rankcorr.h: kMaxCols)
+RANKCORR_TILE = 1024      # members per tile of the device's sums (gwi_draw.h: kDrawTile)
+
+
+def rankcorr_codes(values):
+    """The theta-independent setup of ``gwi_point_rank_correlations`` for ONE rank set: ``values (n_cols, n)``, finite --
+    for the observed set the pooled ``(n_cols, n_ev n_pe)`` array -- -> ``(order, lt, le)``, each ``(n_cols, n)`` int32.  Per column
+    ``order`` is the stable argsort of the values, ``lt`` the number of members of the same set with a smaller value
+    (``np.searchsorted(..., "left")`` of the column in itself) and ``le`` the number with a value not larger (``"right"``): ``lt <=
+    position of the member along the order < le``.  Only the order of the values enters: a strictly increasing map of a column leaves
+    the three arrays as they are."""
+    x = np.asarray(values, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError(f"values is (n_cols, n); got {x.shape}")
+    if not 1 <= x.shape[0] <= MAX_RANKCORR_COLUMNS:
+        raise ValueError(f"{x.shape[0]} columns: between 1 and {MAX_RANKCORR_COLUMNS} can be ranked")
+    if x.shape[1] >= 2**31 - 1:
+        raise ValueError("more members than an int32 rank can count")
+    if not np.all(np.isfinite(x)):
+        raise ValueError("the values must be finite")
+    order = np.argsort(x, axis=-1, kind="stable")
+    lt, le = np.empty(x.shape, dtype=np.int32), np.empty(x.shape, dtype=np.int32)
+    for c in range(x.shape[0]):
+        ascending = x[c][order[c]]
+        lt[c] = np.searchsorted(ascending, x[c], side="left")
+        le[c] = np.searchsorted(ascending, x[c], side="right")
+    return np.ascontiguousarray(order, dtype=np.int32), lt, le
+
+
+def rankcorr_set(u, order, lt, le):
+    """``(out (1 + C + C (C + 1) / 2,), alive)`` of ONE rank set with the members' weights ``u (n,)``, finite and non-negative, and the
+    codes of :func:`rankcorr_codes`.  With ``P[c][r]`` the sum of ``u`` over the first ``r`` members along ``order[c]`` (exact, rounded
+    once) and ``T_c = P[c][n]``:
+
+    ``d_ci = ((P[c][lt_i] + P[c][le_i]) - T_c) / (2 T_c)``, the centred weighted mid-rank, and ``r_ci = 0.5 + d_ci``;
+    ``out = (U, m_0 ... m_{C-1}, R_00, R_01, ..., R_{C-1,C-1})`` with ``U = fsum u``, ``m_c = fsum_i (u_i r_ci) / U`` and ``R_cd = fsum_i
+    ((u_i d_ci) d_di) / U`` for ``c <= d``, the upper triangle row by row
+
+    -- every product rounded on its own, every sum exact and rounded once (``math.fsum``).  Ties share a rank; a column whose members
+    all tie has ``d = 0``, ``r = 0.5`` and ``R_cc = 0`` exactly; ``m_c`` is 0.5 in exact arithmetic.  Where ``U`` is 0 or not finite
+    ``alive`` is False and every slot but ``U`` NaN."""
+    u = np.asarray(u, dtype=np.float64).ravel()
+    order, lt, le = np.asarray(order), np.asarray(lt), np.asarray(le)
+    n_cols, n = order.shape
+    if u.size != n or lt.shape != order.shape or le.shape != order.shape:
+        raise ValueError("u is (n,), order, lt and le are (n_cols, n)")
+    out = np.full(1 + n_cols + n_cols * (n_cols + 1) // 2, np.nan)
+    total = math.fsum(u.tolist())
+    out[0] = total
+    if not (total > 0.0 and np.isfinite(total)):
+        return out, False
+    live = u > 0.0
+    ul = u[live]
+    d = np.empty((n_cols, ul.size))
+    for c in range(n_cols):
+        prefix = _rounded_prefix(u[order[c].astype(np.int64)])
+        t_c = prefix[n]
+        d[c] = ((prefix[lt[c][live]] + prefix[le[c][live]]) - t_c) / (2.0 * t_c)
+        out[1 + c] = math.fsum((ul * (0.5 + d[c])).tolist()) / total
+    t = 1 + n_cols
+    for c in range(n_cols):
+        ud = ul * d[c]
+        for e in range(c, n_cols):
+            out[t] = math.fsum((ud * d[e]).tolist()) / total
+            t += 1
+    return out, True
+
+
+def rankcorr_weights(logw_pe, logw_inj, pe_mask=None, inj_mask=None):
+    """The members' weights of the two rank sets at one point: ``(u_obs (n_ev n_pe,), u_det (n_inj,), dead (n_ev + 1,)
+    int32)``.  ``u_obs`` pools the events: ``w_i / S_e`` with ``w`` of :func:`draw_weights` and ``S_e`` its ``math.fsum``, one division
+    per sample, 0 for the samples of an event whose ``S_e`` is 0 or not finite; ``u_det`` is :func:`draw_weights` of the injection
+    set.  ``dead`` flags the segments without weight, the injection set last."""
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    n_ev, n_pe = logw_pe.shape
+    pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(n_ev, n_pe)
+    u_obs, dead = np.zeros((n_ev, n_pe)), np.zeros(n_ev + 1, dtype=np.int32)
+    for ev in range(n_ev):
+        w = draw_weights(logw_pe[ev], None if pe_mask is None else pe_mask[ev])
+        total = math.fsum(w.tolist())
+        if total > 0.0 and np.isfinite(total):
+            u_obs[ev] = w / total
+        else:
+            dead[ev] = 1
+    u_det = draw_weights(logw_inj, inj_mask)
+    t_det = math.fsum(u_det.tolist())
+    dead[n_ev] = 0 if t_det > 0.0 and np.isfinite(t_det) else 1
+    return u_obs.ravel(), u_det, dead
+
+
+def point_rank_correlations_reference(logw_pe, logw_inj, codes_obs, codes_det, pe_mask=None, inj_mask=None):
+    """One hyper-parameter point of ``gwi_point_rank_correlations``: ``logw_pe (n_ev, n_pe)``, ``logw_inj (n_inj,)``,
+    ``codes_obs`` and ``codes_det`` the triples of :func:`rankcorr_codes` of the pooled PE values and of the injection values, and the
+    masks of ``gwi_set_draw_mask`` (or None) -> ``(out (2, 1 + C + C (C + 1) / 2), dead (n_ev + 2,) int32)``: per set (observed,
+    detected) :func:`rankcorr_set` on the weights of :func:`rankcorr_weights`; ``dead`` flags the segments without weight, the
+    injection set last, and then the observed set, which is dead when no event is live.  Spearman's rho of columns ``c <= d`` is ``R_cd /
+    sqrt(R_cc R_dd)`` (:func:`rankcorr_matrix` unpacks the triangle)."""
+    u_obs, u_det, seg_dead = rankcorr_weights(logw_pe, logw_inj, pe_mask, inj_mask)
+    obs, obs_alive = rankcorr_set(u_obs, *codes_obs)
+    det, _ = rankcorr_set(u_det, *codes_det)
+    if obs.size != det.size:
+        raise ValueError("the two sets hold different numbers of columns")
+    return np.stack([obs, det]), np.concatenate([seg_dead, [0 if obs_alive else 1]]).astype(np.int32)
+
+
+def rankcorr_matrix(out, n_cols):
+    """``(U (...,), mean_rank (..., C), R (..., C, C))`` of rows ``out (..., 1 + C + C (C + 1) / 2)`` of ``gwi_point_rank_correlations``:
+    the symmetric matrix filled from the upper triangle."""
+    out = np.asarray(out, dtype=np.float64)
+    iu = np.triu_indices(n_cols)
+    cov = np.empty(out.shape[:-1] + (n_cols, n_cols))
+    cov[..., iu[0], iu[1]] = out[..., 1 + n_cols :]
+    cov[..., iu[1], iu[0]] = out[..., 1 + n_cols :]
+    return np.ascontiguousarray(out[..., 0]), np.ascontiguousarray(out[..., 1 : 1 + n_cols]), cov
+
+
+def rankcorr_error_bound(n_terms, n_order_tiles, n_sample_tiles, pooled):
+    """An ABSOLUTE bound on the rounding of one ``R_cd`` of ``gwi_point_rank_correlations`` and of the statement together (DESIGN 8l,
+    "Error"), from counts of roundings alone: ``n_terms`` bounds the live samples of one segment, ``n_order_tiles`` the tiles along
+    the set's order, ``n_sample_tiles`` its tiles in sample order; ``pooled`` for the observed set, whose weights carry their
+    event's total.  ``|d| <= 1/2`` makes the bound absolute.  What lies below it cannot be told from a rank variance of zero:
+    :func:`gwinferno_amd.postprocess.catalog_rank_correlation_check` divides by nothing smaller."""
+    eps = 2.0**-52
+    a = (2.0 + (n_terms + 8.5) + 1.0) if pooled else 2.0        # u: exp on either side; S (n + 8 units and fsum's half); the division
+    p = a + 0.5 * (18 + n_order_tiles + 1)                      # an entry of P, relative: the scan's depth, the offsets, the statement's rounding
+    e_d = 2.0 * p + 2.0                                         # d, absolute
+    depth = 3 + 6 + 3 + n_sample_tiles                          # lane, butterfly, waves, tiles
+    return 1.01 * eps * (0.25 * (a + 2.0) + e_d + 0.125 * (depth + 1) + 0.25 * (a + 0.5 * (depth + 1) + 1.0))
 
 
 MAX_MOMENT_COLUMNS = 8  # columns of gwi_point_moments (gwi_moment.h: kMaxCols)

@@ -1,5 +1,5 @@
 """The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
-injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments and conditional moments, marginal weights and their
+injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments, conditional moments and rank correlations, marginal weights and their
 quantiles and kernel density estimates.
 Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
 """
@@ -324,6 +324,45 @@ class PostprocessMixin:
                                     lambda k, s: ((k, self.n_ev + 1, n_pairs, 3, self._hist_shape[1]), (k, self.n_ev + 1)), thetas,
                                     extra=(n_pairs, pairs.ctypes.data_as(C.POINTER(C.c_int32))))
         return np.ascontiguousarray(raw[:, :, :, 0]), np.ascontiguousarray(raw[:, :, :, 1]), np.ascontiguousarray(raw[:, :, :, 2]), dead
+
+    def set_rankcorr_columns(self, pe_values, inj_values):
+        """The quantities :meth:`point_rank_correlations` ranks (``gwi_set_rankcorr_columns``): ``pe_values (n_cols, n_ev,
+        n_pe)`` and ``inj_values (n_cols, n_inj)``, finite, both needed; ``1 <= n_cols <= 8``.  Per set -- the PE samples pooled over
+        the events, the injections -- and column the members' sort order and every member's ranks within its own set
+        (:func:`gwinferno_amd.draws.rankcorr_codes`) are made here and copied to HBM once: they do not depend on theta.  A second call
+        replaces the columns.  Not available on an engine that holds a shard (``world > 1``)."""
+        from .draws import MAX_RANKCORR_COLUMNS, rankcorr_codes
+
+        self._whole_catalog("set_rankcorr_columns", "the rank sets need")
+        if pe_values is None or inj_values is None:
+            raise ValueError("the observed and the predicted correlation are compared: pe_values and inj_values are both needed")
+        pe, inj, n_cols = self._two_sets(pe_values, inj_values, "pe_values", "inj_values")
+        if not 1 <= n_cols <= MAX_RANKCORR_COLUMNS:
+            raise ValueError(f"{n_cols} columns: between 1 and {MAX_RANKCORR_COLUMNS} can be set")
+        codes = rankcorr_codes(pe.reshape(n_cols, -1)) + rankcorr_codes(inj)
+        i32 = C.POINTER(C.c_int32)
+        self._rankcorr_shape = None
+        self._check(self.lib.gwi_set_rankcorr_columns(self.handle, n_cols, *(a.ctypes.data_as(i32) for a in codes)))
+        self._rankcorr_shape = (n_cols,)
+
+    def point_rank_correlations(self, thetas):
+        """Per-point second moments of the weighted mid-ranks of the two rank sets, on the device (``gwi_point_rank_correlations``;
+        semantics: :func:`gwinferno_amd.draws.point_rank_correlations_reference`).  ``thetas`` is one point ``(n_theta,)``
+        or ``(k, n_theta)``.  Returns ``(total (k, 2), mean_rank (k, 2, C), cov (k, 2, C, C), dead (k, n_ev + 1) int32, dead_set (k, 2)
+        int32)``, the observed set (all PE samples pooled, each event's samples sharing the weight 1) first, the detected set (the
+        injections) second: the set's weight ``U``, the weighted means of the mid-ranks (0.5 up to rounding: a self-check), the
+        symmetric matrix ``R_cd = sum_i (u_i / U) d_ci d_di`` of the centred mid-ranks ``d`` (filled from the upper triangle the
+        device returns) -- Spearman's rho is ``R_cd / sqrt(R_cc R_dd)`` -- the segments' flags, the injection set last, and the
+        two sets' (the observed set is dead when no event is live).  NaN for a dead set; ``R_cc = 0`` exactly for a column whose
+        members all tie.  ``2 (1 + C + C (C + 1) / 2)`` doubles come back per point; the points may be split over calls without changing
+        a bit.  Not available on an engine that holds a shard (``world > 1``)."""
+        from .draws import rankcorr_matrix
+
+        raw, dead = self._per_point("point_rank_correlations", "the rank sets need", "_rankcorr_shape", "rank-correlation columns are set (set_rankcorr_columns)",
+                                    (np.float64, np.int32), lambda k, s: ((k, 2, 1 + s[0] + s[0] * (s[0] + 1) // 2), (k, self.n_ev + 2)), thetas)
+        total, mean_rank, cov = rankcorr_matrix(raw, self._rankcorr_shape[0])
+        n_ev = self.n_ev
+        return total, mean_rank, cov, np.ascontiguousarray(dead[:, : n_ev + 1]), np.ascontiguousarray(dead[:, [n_ev + 1, n_ev]])
 
     def marginal_weights_reset(self):
         """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""

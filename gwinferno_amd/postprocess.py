@@ -1117,6 +1117,117 @@ def catalog_correlation_check(eng, thetas, pe_values, inj_values=None, pairs=Non
     return out
 
 
+def _rankcorr_points(eng, thetas, x_pe, x_inj, masks, backend):
+    """``(total (K, 2), mean_rank (K, 2, C), cov (K, 2, C, C), dead (K, n_ev + 1), dead_set (K, 2))`` of the points on either backend
+    (DESIGN 8l)."""
+    from . import draws as D
+
+    if backend == "device":
+        if masks[0] is not None:
+            eng.set_draw_mask(*masks)
+        eng.set_rankcorr_columns(x_pe, x_inj)
+        return eng.point_rank_correlations(thetas)
+    k, n_cols, n_ev = thetas.shape[0], x_pe.shape[0], eng.n_ev
+    codes_obs, codes_det = D.rankcorr_codes(x_pe.reshape(n_cols, -1)), D.rankcorr_codes(x_inj)
+    raw, dead = np.empty((k, 2, 1 + n_cols + n_cols * (n_cols + 1) // 2)), np.empty((k, n_ev + 2), dtype=np.int32)
+    for i, th in enumerate(thetas):
+        lw_pe, lw_inj = eng.log_weights(th)
+        raw[i], dead[i] = D.point_rank_correlations_reference(lw_pe, lw_inj, codes_obs, codes_det, masks[0], masks[1])
+    total, mean_rank, cov = D.rankcorr_matrix(raw, n_cols)
+    return total, mean_rank, cov, np.ascontiguousarray(dead[:, : n_ev + 1]), np.ascontiguousarray(dead[:, [n_ev + 1, n_ev]])
+
+
+def catalog_rank_correlation_check(eng, thetas, pe_values, inj_values=None, pairs=None, levels=(0.05, 0.5, 0.95), point_weights=None, pedata=None, injdata=None,
+                                   param_names=None, m1min=None, m2min=None, mmax=None, backend="device"):
+    """Does the catalog's RANK correlation between two quantities agree with the one the fitted population predicts for detected
+    sources?    :func:`catalog_correlation_check` asks the same of Pearson's correlation, which changes with the coordinate
+    (``m1`` or ``log m1``, ``q`` or ``1 / q``) and is set by the tail of a heavy-tailed quantity.  Spearman's correlation is that of the
+    weighted mid-ranks: no monotone map of either quantity changes it, and it sees any monotone dependence.  Per hyper-posterior point
+    the observed catalog is the equal-weight mixture of its live events' population-informed posteriors -- all PE samples pooled, sample
+    ``i`` of event ``e`` weighing ``w_i / S_e`` -- and the prediction the injection set under the point's weights; a member's rank is the
+    weighted CDF of its own set at the member, so it changes with every point, and on the device (``eng.point_rank_correlations``) ``2
+    (1 + C + C (C + 1) / 2)`` doubles come back per point while the weights never leave HBM.
+
+    The arguments are :func:`catalog_correlation_check`'s, with ``inj_values`` (or ``injdata``) needed.  ``point_weights`` -- ``(K,)``, or
+    ``(K, n_ev + 1)`` as the leave-one-out and Pareto-smoothed weights come, of which the last column (the injection set's, which no
+    event's removal touches) is taken; finite, non-negative, not all 0; default equal -- weight the points in the bands and shares; they
+    are applied here and never go to the device.  The device backend replaces the engine's rank-correlation columns.
+    ``backend="host"`` runs the NumPy statement (:func:`gwinferno_amd.draws.point_rank_correlations_reference`) on
+    ``eng.log_weights``: the statement the kernels are tested against, not a fall-back.
+
+    Returns a dict: ``names``; ``pairs (n_pairs, 2)``; ``levels``; per point and pair ``rho_obs``, ``rho_det`` and ``delta = rho_obs -
+    rho_det``, each ``(K, n_pairs)``; ``bands_rho_obs``, ``bands_rho_det``, ``bands_delta (Q, n_pairs)``
+    (:func:`gwinferno_amd.draws.weighted_percentiles`); ``p_delta_positive (n_pairs,)``, the weighted share of the points with ``delta >
+    0`` among those where it is a number, and ``p_two_sided = 2 min(p, 1 - p)``.  A (point, pair) with a dead set is skipped (NaN) and
+    counted in ``n_skipped (n_pairs,)``.  Where a rank variance ``R_cc`` does not exceed ``variance_floor (2,)`` -- the derived bound on
+    its rounding, :func:`gwinferno_amd.draws.rankcorr_error_bound`; a column whose members all tie has exactly 0 -- nothing is divided,
+    the correlation is NaN and ``degenerate_obs`` / ``degenerate_det (K, n_pairs)`` flag it.  ``rank_mean_error``: the largest ``|m_c -
+    1/2|`` over the live (point, set, column), which exact arithmetic makes 0.  Also the raw ``total``, ``mean_rank``, ``rank_cov``,
+    ``dead`` and ``dead_set`` of ``eng.point_rank_correlations``, and ``n_points``."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or levels.size < 1 or not np.all((levels >= 0.0) & (levels <= 1.0)):
+        raise ValueError("levels must be numbers in [0, 1]")
+    _checked_names(pe_values, pedata, param_names)
+    names, x_pe, x_inj = _summary_columns(eng, pe_values, inj_values, pedata, injdata, param_names)
+    if x_inj is None:
+        raise ValueError("the predicted side ranks the injections: inj_values (or injdata) are needed")
+    n_cols, n_ev = len(names), eng.n_ev
+    if pairs is None:
+        pairs = [(c, d) for c in range(n_cols) for d in range(c + 1, n_cols)]
+    pairs = [tuple(names.index(p) if isinstance(p, str) else int(p) for p in pair) for pair in pairs]
+    if not pairs or any(len(p) != 2 or not all(0 <= c < n_cols for c in p) for p in pairs):
+        raise ValueError(f"pairs are pairs of names or of column indices below {n_cols}, at least one")
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if point_weights is None:
+        v = np.ones(k)
+    else:
+        v = np.asarray(point_weights, dtype=np.float64)
+        if v.shape == (k, n_ev + 1):
+            v = v[:, -1]
+        if v.shape != (k,) or not np.all(np.isfinite(v)) or np.any(v < 0.0) or not np.any(v > 0.0):
+            raise ValueError(f"point_weights are ({k},) or ({k}, {n_ev + 1}) finite non-negative numbers, not all 0")
+    masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    total, mean_rank, cov, dead, dead_set = _rankcorr_points(eng, thetas, x_pe, x_inj, masks, backend)
+    tile = D.RANKCORR_TILE
+    sample_tiles = (n_ev * -(-eng.n_pe // tile), -(-eng.n_inj // tile))
+    floor = np.array([D.rankcorr_error_bound(eng.n_pe, -(-(n_ev * eng.n_pe) // tile), sample_tiles[0], True),
+                      D.rankcorr_error_bound(eng.n_inj, sample_tiles[1], sample_tiles[1], False)])
+    c, d = pairs[:, 0], pairs[:, 1]
+    rho, flags = [], []
+    for s in range(2):
+        r_cd, r_cc, r_dd = cov[:, s, c, d], cov[:, s, c, c], cov[:, s, d, d]
+        alive = (dead_set[:, s] == 0)[:, None] & np.ones(r_cd.shape, dtype=bool)
+        with np.errstate(invalid="ignore"):
+            ok = alive & (r_cc > floor[s]) & (r_dd > floor[s])
+        one = np.full(r_cd.shape, np.nan)
+        one[ok] = r_cd[ok] / np.sqrt(r_cc[ok] * r_dd[ok])
+        rho.append(one)
+        flags.append((alive & ~ok).astype(np.int32))
+    rho_obs, rho_det = rho
+    delta = rho_obs - rho_det
+    skipped = ((dead_set[:, 0] != 0) | (dead_set[:, 1] != 0))[:, None] & np.ones(delta.shape, dtype=bool)
+    has = ~np.isnan(delta)
+    den = (v[:, None] * has).sum(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = (v[:, None] * (has & (np.where(has, delta, 0.0) > 0.0))).sum(axis=0) / den
+    live_means = mean_rank[dead_set == 0]
+    out = {"names": names, "pairs": pairs, "levels": levels, "rho_obs": rho_obs, "rho_det": rho_det, "delta": delta, "p_delta_positive": p,
+           "p_two_sided": 2.0 * np.minimum(p, 1.0 - p), "n_skipped": skipped.sum(axis=0).astype(np.int64), "degenerate_obs": flags[0], "degenerate_det": flags[1],
+           "variance_floor": floor, "rank_mean_error": float(np.max(np.abs(live_means - 0.5))) if live_means.size else float("nan"), "total": total,
+           "mean_rank": mean_rank, "rank_cov": cov, "dead": dead, "dead_set": dead_set, "n_points": k}
+    for key in ("rho_obs", "rho_det", "delta"):
+        out["bands_" + key] = D.weighted_percentiles(out[key], v, levels)
+    return out
+
+
 def event_variance_split(eng, thetas, pe_values, point_weights=None, leave_one_out=False, total_inj=None, nobs=None, marginalize_selection=False, pedata=None,
                          injdata=None, param_names=None, m1min=None, m2min=None, mmax=None, backend="device"):
     """How much of an event's population-informed variance is hyper-posterior uncertainty and how much its own measurement?  (DESIGN

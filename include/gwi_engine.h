@@ -585,7 +585,7 @@ void gwi_point_rank_times(double* logw_ms, double* prefix_ms, double* pit_ms, in
  * live sample gives that sample and a covariance of exactly 0.  k >= 1 is not bound by the batch limit: the points are staged on the
  * device 64 at a time and copied back per chunk.  Every sum has a fixed shape (sample order inside a tile of 1 024, then tile order)
  * and there are no atomics: the bits are a pure function of (theta_k, columns, masks), whatever the split of the points over calls, and
- * the call changes no state another entry reads.  Not done: sharded handles; more than 8 columns; rank correlation (conditional means: gwi_point_conditionals).
+ * the call changes no state another entry reads.  Not done: sharded handles; more than 8 columns (rank correlation: gwi_point_rank_correlations; conditional means: gwi_point_conditionals).
  * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, a host-only handle and a call before columns are set;
  * GWI_ERR_UNSUPPORTED on a handle that holds a shard.
  *
@@ -615,7 +615,7 @@ void gwi_point_moment_times(double* logw_ms, double* mean_ms, double* cov_ms, in
  * (dead still tells whether they had weight).  k >= 1 is not bound by the batch limit: the points are staged on the device 64 at a time
  * and copied back per chunk.  Every sum has a fixed shape (sample order inside a tile of 1 024 and a bin, then tile order) and there are
  * no atomics: the bits are a pure function of (theta_k, codes, columns, masks, pairs), whatever the split of the points over calls, and
- * the call changes no state another entry reads.  Not done: sharded handles; rank correlation; more than 8 pairs or 512 (pair, bin)
+ * the call changes no state another entry reads.  Not done: sharded handles; more than 8 pairs or 512 (pair, bin)
  * items; two conditioning quantities at once.
  * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, n_pairs outside 1 ... 8, an index outside the bin columns
  * or the value columns, n_pairs n_bins > 512, a call before bins are set or before columns are set, no sample set covered by both, and a
@@ -627,6 +627,45 @@ void gwi_point_moment_times(double* logw_ms, double* mean_ms, double* cov_ms, in
 gwi_status gwi_point_conditionals(gwi_handle h, const double* thetas, int32_t k, int32_t n_pairs, const int32_t* pairs /* [n_pairs][2] */,
                                   double* out /* [k][n_ev + 1][n_pairs][3][n_bins] */, int32_t* dead /* [k][n_ev + 1] */);
 void gwi_point_conditional_times(double* logw_ms, double* mean_ms, double* var_ms, int32_t* launches);
+
+/* Per-point rank (Spearman) correlations on the device: per hyper-parameter point and for each of two rank sets the weighted second
+ * moments of the members' weighted mid-ranks -- a correlation that no monotone map of either quantity changes and no heavy tail
+ * dominates (gwinferno_amd/csrc/gwi_rankcorr.h; the NumPy statement is gwinferno_amd/draws.py: rankcorr_codes,
+ * point_rank_correlations_reference; the contract is DESIGN 8l).
+ *
+ * The sets: obs, all PE samples pooled (N = n_ev n_pe members, member i = sample i % n_pe of event i / n_pe), u_i = w_i / S_e with w, M,
+ * S, the live rule and the masks of gwi_draw_indices and u_i = 0 for a sample of a dead event: the equal-weight mixture of the live
+ * events' population-informed posteriors; det, the injections, u_j = exp(lw_j - M).
+ *
+ * gwi_set_rankcorr_columns(): what does not depend on theta, made by the host once.  Per set and column c, 1 <= n_cols <= 8: order[c]
+ * is a permutation of the set's members along which the column's values do not decrease (a stable argsort); lt[c][i] and le[c][i] are
+ * the numbers of members of the SAME set with a value below / at or below member i's, in [0, n] with lt <= position of i along the
+ * order < le.  The arrays are checked (O(n)) and copied to HBM, and the entry's workspace is allocated here; no other setter's workspace
+ * is touched, and a second call replaces the columns.
+ *
+ * gwi_point_rank_correlations(): with P[c][r] the sum of u over the first r members along order[c] and T_c = P[c][n],
+ *   d_ci = ((P[c][lt_i] + P[c][le_i]) - T_c) / (2 T_c),   r_ci = 0.5 + d_ci
+ * is the centred and the plain weighted mid-rank of member i in column c: ties share a rank, a column whose members all tie has d = 0
+ * and r = 0.5 exactly.  For point k and set s (0 obs, 1 det), with I = 1 + C + C (C + 1) / 2 items:
+ *   U    = sum_i u_i                          out[k][s][0]
+ *   m_c  = sum_i u_i r_ci / U                 out[k][s][1 + c]         (0.5 in exact arithmetic: a self-check)
+ *   R_cd = sum_i u_i d_ci d_di / U,  c <= d   out[k][s][1 + C + t], t counting the upper triangle row by row
+ * Spearman's rho is R_cd / sqrt(R_cc R_dd) and is formed by the caller.  dead[k][0 ... n_ev] flags the segments whose S is 0 or not
+ * finite, the injection set last (as gwi_point_moments), dead[k][n_ev + 1] the observed set, which is dead when no event is live; a dead
+ * set gives NaN in every slot but U.  k >= 1 is not bound by the batch limit: the points are staged on the device 64 at a time and copied
+ * back per chunk.  Every sum has a fixed shape and there are no atomics: the bits are a pure function of (theta_k, codes, masks),
+ * whatever the split of the points over calls, and the call changes no state another entry reads.  Not done: sharded handles; per-event
+ * rank correlations (each event's own order); Kendall's tau; more than 8 columns.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, n_cols outside 1 ... 8, codes that fail a check, a call
+ * before columns are set and a host-only handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard, checked first.
+ *
+ * gwi_point_rankcorr_times(): DIAGNOSTIC ONLY, for tools/post_time.py: of the calling thread's last call, summed over its points, the
+ * wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge / tile-sum / offset / prefix
+ * launches together and of the covariance and merge launches, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_set_rankcorr_columns(gwi_handle h, int32_t n_cols, const int32_t* order_obs /* [n_cols][n_ev n_pe] */, const int32_t* lt_obs, const int32_t* le_obs,
+                                    const int32_t* order_det /* [n_cols][n_inj] */, const int32_t* lt_det, const int32_t* le_det);
+gwi_status gwi_point_rank_correlations(gwi_handle h, const double* thetas, int32_t k, double* out /* [k][2][1 + C + C(C+1)/2] */, int32_t* dead /* [k][n_ev + 2] */);
+void gwi_point_rankcorr_times(double* logw_ms, double* prefix_ms, double* cov_ms, int32_t* launches);
 
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is

@@ -7,7 +7,7 @@ timed on another build of the engine (the parent commit's), in child processes o
 half after, and this build's median is placed against the span of that build's own calls.  No figure is fixed in advance; what is not
 measured is named as unmeasured.  Writes a Markdown report.
 
-      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals} [--configs c2,c5] [--repeats 10]
+      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals,point_rankcorr} [--configs c2,c5] [--repeats 10]
                                 [--parent-lib PATH] [--out profiles/<entry>/RESULTS.md]
 
 What differs per entry is one record of ENTRIES: the set-up calls, one_round, the host route, the kernels to list and the row labels."""
@@ -448,6 +448,62 @@ def conditionals_tail(res):
             "larger number of distinct bin / value columns of the pairs, rounded up), the centred pass 4 KB of means more.", ""]
 
 
+# ---- point_rankcorr: the per-point rank correlations (gwi_rankcorr.h) --------------------------------------------------------
+def rankcorr_setup(c, extra, full):
+    cdfs_setup(c, extra, full)
+    c.eng.set_kde_columns(c.x_pe, c.x_inj)
+    c.eng.set_rank_columns(c.x_pe, c.x_inj)
+    if full:
+        t0 = time.perf_counter()
+        c.eng.set_rankcorr_columns(c.x_pe, c.x_inj)
+        extra["setup_s"] = time.perf_counter() - t0
+
+
+def rankcorr_round(c, thetas, full):
+    out = {}
+    hist_round(c, thetas, out)
+    t = timed(out, "rank", lambda: c.eng.point_pits_exact(thetas), c.eng.lib.gwi_point_rank_times, thetas)
+    out["rank"] = t[1] + t[2]
+    t = timed(out, "moment", lambda: c.eng.point_moments(thetas), c.eng.lib.gwi_point_moment_times, thetas)
+    out["moment"] = t[1] + t[2]
+    if full:
+        t = timed(out, "rankcorr", lambda: c.eng.point_rank_correlations(thetas), c.eng.lib.gwi_point_rankcorr_times, thetas)
+        out["rankcorr"], out["rankcorr prefix"], out["rankcorr cov"], out["rankcorr logw"] = t[1] + t[2], t[1], t[2], t[0]
+    return out
+
+
+def rankcorr_check(c, extra):
+    from gwinferno_amd import draws as D
+
+    n_cols = c.x_pe.shape[0]
+    codes = D.rankcorr_codes(c.x_pe.reshape(n_cols, -1)), D.rankcorr_codes(c.x_inj)
+    extra["host_ms"], (want, want_dead) = host_route(c, 2, lambda lw_pe, lw_inj: D.point_rank_correlations_reference(lw_pe, lw_inj, *codes))
+    total, mean_rank, cov, dead, dead_set = c.eng.point_rank_correlations(c.thetas[1])
+    _, _, want_cov = D.rankcorr_matrix(want, n_cols)
+    extra["deviation"] = float(np.nanmax(np.abs(cov[0] - want_cov)))
+    extra["mean_error"] = float(np.nanmax(np.abs(mean_rank[0] - 0.5)))
+    extra["flags"] = bool(np.array_equal(dead[0], want_dead[:-1])) and int(dead_set[0, 0]) == int(want_dead[-1])
+    extra["table_mb"] = 8 * (c.eng.n_ev * c.eng.n_pe + 1) / 1e6
+
+
+def rankcorr_notes(cfg, own, extra):
+    items = 1 + 3 + 6
+    return [f"- {cfg}: `set_rankcorr_columns` (the two sorts, the ranks, the checks and the upload, once per catalog) took {extra['setup_s']:.2f} s.  Host route (`Engine.log_weights` + "
+            f"`draws.point_rank_correlations_reference`, {extra['host_mb']:.1f} MB to the host per point against {8 * 2 * items + 4 * (extra['n_ev'] + 2)} bytes from the device): "
+            f"{extra['host_ms']:.1f} ms per point over 2 points, ONE run, no spread taken.  Largest absolute |device - host| entry of R of the last of them: {extra['deviation']:.2e}; largest "
+            f"|m_c - 1/2| on the device: {extra['mean_error']:.2e}; flags {'equal' if extra['flags'] else 'DIFFERENT'}.  The covariance launch gathers 2 C = 6 doubles per sample from "
+            f"prefix tables of {extra['table_mb']:.1f} MB per quantity (observed set): its time is the row `... of which the covariance and merge launches`; nothing was tuned for it."]
+
+
+def rankcorr_intro(repeats, how):
+    return (f"K = {K} points per call, C = 3 columns ({', '.join(MASS_CHI)}), {repeats} calls per row after two warm-up calls.  Times in ms; device times are HIP-event times of the "
+            f"launches after the log-weight pass (draw tile, draw merge and the entry's own), summed over the call and divided by K.  No ratio was promised in advance.  `parent`: {how}".rstrip())
+
+
+def rankcorr_tail(res):
+    return [f"Scratch is {max(r[4] for r in res)} bytes in every kernel listed: the {max(r[1] for r in res)} VGPRs of `rankcorr_cov_kernel<8>` hold its 45 running sums without a spill.", ""]
+
+
 QUANTITIES = f"C = 3 quantities ({', '.join(MASS_Z)})"
 WEIGHTED_LABEL = {"hist_merge_kernel<true>": "hist_merge_kernel<true> (weighted)", "marg_add_kernel<true>": "marg_add_kernel<true> (weighted)"}
 COMMON = dict(style="spread", columns=MASS_Z, relabel={}, resources_tail=lambda res: [], check=lambda c, extra: None)
@@ -513,6 +569,18 @@ ENTRIES = {e.name: e for e in (
                  ("cond logw", "`point_conditionals`, log-weight pass per point (host clock)"), ("cond wall", "`point_conditionals`, wall time per point of the call"),
                  ("moment", "`point_moments`, device time per point after the log-weight pass"), ("hist", "`weighted_histograms`, device time per point after the log-weight pass")],
            compare=("moment", "hist"), spans=[("moment", "`point_moments` (unchanged code)", " per point"), ("hist", "`weighted_histograms` (unchanged code)", " per point")],
+           unmeasured="NOT MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
+    record(style="calls", columns=MASS_CHI, resources_tail=rankcorr_tail, name="point_rankcorr", symbol="gwi_point_rank_correlations",
+           title="# Per-point rank correlations: measured times",
+           kernels="rankcorr_tile_kernel|rankcorr_offset_kernel|rankcorr_prefix_kernel|rankcorr_cov_kernel|rankcorr_merge_kernel|draw_tile_kernel|draw_merge_kernel",
+           setup=rankcorr_setup, one_round=rankcorr_round, notes=rankcorr_notes, check=rankcorr_check, intro=rankcorr_intro,
+           rows=[("rankcorr", "`point_rank_correlations`, device time per point after the log-weight pass"), ("rankcorr prefix", "... of which draw tile / merge, tile sums, offsets, prefix"),
+                 ("rankcorr cov", "... of which the covariance and merge launches"), ("rankcorr logw", "`point_rank_correlations`, log-weight pass per point (host clock)"),
+                 ("rankcorr wall", "`point_rank_correlations`, wall time per point of the call"), ("rank", "`point_pits_exact`, device time per point after the log-weight pass"),
+                 ("moment", "`point_moments`, device time per point after the log-weight pass"), ("hist", "`weighted_histograms`, device time per point after the log-weight pass")],
+           compare=("rank", "moment", "hist"),
+           spans=[("rank", "`point_pits_exact` (unchanged code)", " per point"), ("moment", "`point_moments` (unchanged code)", " per point"),
+                  ("hist", "`weighted_histograms` (unchanged code)", " per point")],
            unmeasured="NOT MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
 )}
 
