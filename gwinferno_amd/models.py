@@ -377,6 +377,16 @@ class BSplineRedshift(object):
         self.interpolator = it = LogXBSpline(self.n_splines, xrange=xrange, k=4, **kwargs)
         z, z_inj = _f(z), _f(z_inj)
         self._z = {PE: z, INJ: z_inj}
+        # Which samples carry the spline is decided as the reference decides it, on the doubles: xmin <= z <= xmax (:54-55) and
+        # log z inside [lo, hi] (interpolation.py:175).  The others (exponent 0) are parked a domain's length beyond hi: left at
+        # log z, a sample a few ulps above hi has a knot coordinate (log z - lo) / dx that rounds onto the last knot, and the
+        # scan would count it inside.
+        self._coord = {}
+        for side, zz in self._z.items():
+            Z = Sym.src(zz)
+            u = E.log(Z)
+            inside = (Z >= self.xmin) & (Z <= self.xmax) & ~((u < it.lo) | (u > it.hi))
+            self._coord[side] = E.where(inside, u, it.hi + (it.hi - it.lo))
         self.zmin = max(float(np.min(z)), float(np.min(z_inj)))
         self.zmax = min(float(np.max(z)), float(np.max(z_inj)))
         self.zgrid = np.linspace(self.zmin, self.zmax, 1000)
@@ -397,10 +407,12 @@ class BSplineRedshift(object):
     def normalization(self, cs):
         return LazyNorm(self, [], cs)
 
-    def __call__(self, coefs, pe_samples=True):
+    def __call__(self, coefs, pe_samples=True, exponent_coefs=None):
+        """``exponent_coefs``: the exponent's coefficient block as it is handed to the engine, in place of the host's scaling of
+        ``coefs`` (the two blocks of theta are then independent parameters: term-level tests differentiate each alone)."""
         side = PE if pe_samples else INJ
         it = self.interpolator
-        f = Factor(N.TERM_EXP_SPLINE, side, [Column("log", self._z[side])], coefs=self._exponent_coefs(coefs), consts=(it.lo, it.hi), n_basis=it.N,
+        f = Factor(N.TERM_EXP_SPLINE, side, [Column("id", self._coord[side])], coefs=self._exponent_coefs(coefs) if exponent_coefs is None else exponent_coefs, consts=(it.lo, it.hi), n_basis=it.N,
                    flags=N.SPLINE_OUTSIDE_ZERO_EXPONENT, static_log=self._static[side], owner=self, tag="zspline")
         f.norm = GridNorm(self._grid_tw, lb=self._grid_lb, us=self._grid_us, n_basis=it.N, lo=it.lo, hi=it.hi, spline_flags=N.SPLINE_OUTSIDE_ZERO_EXPONENT,
                           coefs=coefs if it.normalize else None)

@@ -8,6 +8,7 @@ rounded ONCE to float64.  Nothing of gwinferno_amd/ or oracle/ is imported, and 
 the engine and its C oracle share are NOT used: the bases come out of the recursion on the knot vector's own doubles.
 
     python tests/golden/make_spline_terms_hp.py      # rewrites the files (and checks the working precision)
+    python tests/golden/make_spline_terms_hp.py --tabulate   # first tabulates dVc/dz at the redshift samples from the reference
 
 One file per term (tests/test_terms_hp_cpu.py holds each below 256 KiB), in the layout of terms_hp.npz:
 ``{name}/params, columns, col/*, tags, theta, logp, dlogp`` -- tests/terms_hp_util.Term loads them unchanged.
@@ -33,6 +34,17 @@ Conventions
   * PowerlawRedshift on the z grid and dVc/dz table that tests/golden/terms.npz holds from the unmodified reference:
     log p = log interp(z) + (lamb - 1) log(1 + z) - log trapz(dVc/dz (1 + z)^(lamb - 1), zgrid) for z <= maximum, interp linear with the
     end values held outside the grid (jnp.interp); exact arithmetic on the committed doubles.
+  * The spline redshift models (PowerlawSplineRedshiftModel, models/spline_perturbation.py:304-372; BSplineRedshift, models/bsplines/
+    single.py:398-492): see ``_plz_term`` and ``_zspline_term``.  Cosmology is INPUT DATA: dVc/dz on the 1000-point z grid is the table
+    tests/golden/terms.npz holds from the unmodified reference, and the data ends of every term are that grid's ends (1e-9 and 1.9), so
+    that the models' own ``linspace(zmin, zmax, 1000)`` IS that grid; dVc/dz at the samples is tests/golden/z_samples_dVcdz.npz, tabulated
+    from the unmodified reference's cosmology (through ref_import.py) by ``python tests/golden/make_spline_terms_hp.py --tabulate``,
+    which needs the reference tree; without the flag the committed table is read.  d log p / d c_j carries -d log Z / d c_j, but
+    NO CATALOG EXERCISES THAT PART: log Z is the same for every sample, so it cancels between the events and the injections of a
+    hierarchical likelihood, neither the engine nor its oracle forms it, and the cross term d^2 / d lamb d c of the normaliser is not
+    refereed.  What is held of the normaliser is its VALUE, in every log-weight of the values catalog.
+  * BSplineDistribution (numpyro_distributions.py:266-293): see ``_lerp_term``, which also states what is recorded at a grid node that
+    carries -inf.
   * Excluded samples: logp = -inf, derivatives 0.  No finite value below -650 is stored (asserted, as in make_terms_hp.py).
   * Adding one constant to every coefficient of an exponentiated basis does not move the density inside the domain (the bases sum
     to one there): the points tagged ``shift+300`` / ``shift-300`` are ``normal1`` shifted, and ``_compute`` asserts that their
@@ -367,8 +379,392 @@ def _redshift_term():
             f"{name}/theta": np.array([[v] for _, v in Z_LAMBS], dtype=np.float64), f"{name}/logp": logp, f"{name}/dlogp": dlogp}
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the spline redshift models
+# ---------------------------------------------------------------------------------------------------------------------
+Z_SPLINES = [  # name, model, N, xrange (None: the data range), normalize
+    ("plzspline4", "PowerlawSplineRedshiftModel", 4, None, False),
+    ("plzspline7", "PowerlawSplineRedshiftModel", 7, None, False),
+    ("plzspline17", "PowerlawSplineRedshiftModel", 17, None, False),
+    ("zspline4", "BSplineRedshift", 4, (1e-4, 1.5), True),
+    ("zspline16", "BSplineRedshift", 16, (1e-4, 1.5), True),
+    ("zspline17", "BSplineRedshift", 17, (1e-4, 1.5), True),
+    ("zspline7_raw", "BSplineRedshift", 7, (1e-4, 1.5), False),
+]
+Z_META = {name: dict(model=model, n=N, xrange=xr, normalize=nz) for name, model, N, xr, nz in Z_SPLINES}
+COSMOLOGY = "z_samples_dVcdz.npz"  # dVc/dz of the unmodified reference at every redshift sample of the terms above
+
+
+def _z_grid():
+    with np.load(os.path.join(HERE, "terms.npz")) as t:
+        zg, dv = t["dist/z_grid"], t["dist/z_dVcdz"]
+    assert zg.dtype == np.float64 and dv.dtype == np.float64 and np.array_equal(np.linspace(zg[0], zg[-1], 1000), zg)
+    return zg, dv
+
+
+def z_samples(b, zmin, zmax, seed):
+    """Redshift samples of one term: the data ends zmin and zmax EXACTLY (the models take their grid from them), their inner
+    neighbours and nextafter(zmax, +inf); the two neighbours of each end of the spline domain where it lies inside the data range,
+    and points outside it on both sides; doubles whose float64 log lands on lo, on hi, on interior knots and one ulp either side
+    (and the neighbouring doubles of the z that lands on it); interval mid-points; seeded log-uniform points (float32 numbers); 2.0, beyond the grid."""
+    n_int = b.N - 3
+    inner = list(range(1, n_int)) if b.N <= 7 else sorted({1, 2, n_int // 2, n_int - 2, n_int - 1})
+    mids = list(range(n_int)) if n_int <= 6 else sorted({0, 1, n_int // 3, n_int // 2, n_int - 2, n_int - 1})
+    top = float(np.nextafter(zmax, np.inf))
+    # (zmin and zmax second and third: in a product with a fixture term on [0, 1] or [-1, 1], whose first sample lies below its domain,
+    # both stay live)
+    out = [float(np.nextafter(zmin, np.inf)), zmin, zmax, float(np.nextafter(zmax, -np.inf)), top]
+    if (b.xmin, b.xmax) != (zmin, zmax):
+        out += _neighbours(b.xmin) + _neighbours(b.xmax) + [1e-6, 3e-5, float(F32(0.5 * (b.xmax + zmax)))]
+    kn = b.knots[3:3 + n_int + 1]
+    for target in [b.lo, b.hi] + [kn[m] for m in inner]:
+        # (where the doubles are sparser than their logs no z lands one ulp beside the target: the neighbours in z stand in)
+        out += _log_landing(target) + [v for x in _log_landing(target) if float(np.log(x)) == target for v in _neighbours(x)]
+    out += [float(np.exp(0.5 * (kn[m] + kn[m + 1]))) for m in mids]
+    r = _quantised(np.random.RandomState(seed).uniform(0.0, 1.0, max(12, 54 - len({v for v in out if zmin <= v <= top}))))
+    out += [float(F32(v)) for v in np.exp(b.lo + (b.hi - b.lo) * r)]
+    out += [2.0]
+    seen, zs = set(), []
+    for v in out:
+        if zmin <= v and (v <= top or v == 2.0) and v not in seen:
+            seen.add(v)
+            zs.append(v)
+    return np.array(zs, dtype=np.float64)
+
+
+def _z_basis(name):
+    m = Z_META[name]
+    zg, _ = _z_grid()
+    zmin, zmax = float(zg[0]), float(zg[-1])
+    b = Basis("LogXBSpline", m["n"], m["xrange"] or (zmin, zmax))
+    return b, z_samples(b, zmin, zmax, 2000 + sum(ord(ch) for ch in name))
+
+
+def all_z_samples():
+    return np.unique(np.concatenate([_z_basis(name)[1] for name in Z_META]))
+
+
+def tabulate_cosmology():
+    """Rewrite COSMOLOGY from the unmodified reference's cosmology (imported through ref_import.py); needs the reference tree."""
+    import sys
+
+    sys.path.insert(0, HERE)
+    from ref_import import load_reference
+
+    ref = load_reference()
+    z = all_z_samples()
+    dv = np.asarray(ref.cosmology.PLANCK_2015_LVK_Cosmology.dVcdz(ref.jnp.asarray(z)), dtype=np.float64)
+    zg, dvg = _z_grid()
+    assert np.array_equal(np.asarray(ref.cosmology.PLANCK_2015_LVK_Cosmology.dVcdz(ref.jnp.asarray(zg)), dtype=np.float64), dvg)
+    np.savez_compressed(os.path.join(HERE, COSMOLOGY), z=z, dVcdz=dv)
+
+
+def _dvcdz_at(zs):
+    with np.load(os.path.join(HERE, COSMOLOGY)) as t:
+        z, dv = t["z"], t["dVcdz"]
+    i = np.searchsorted(z, zs)
+    assert np.all(i < len(z)) and np.array_equal(z[np.minimum(i, len(z) - 1)], zs), f"{COSMOLOGY} does not hold every sample: tabulate it again"
+    return dv[i]
+
+
+def plz_points(N, seed):
+    rs = np.random.RandomState(seed)
+    z = _quantised(rs.standard_normal((3, N)))
+    saw = np.array([10.0 if k % 2 == 0 else -10.0 for k in range(N)])
+    hole = z[0].copy()
+    hole[N // 2] = -300.0
+    zero = np.zeros(N)
+    return [("zeros/lamb-2", -2.0, zero), ("zeros/lamb0", 0.0, zero), ("zeros/lamb1", 1.0, zero), ("zeros/lamb2.7", 2.7, zero), ("zeros/lamb6", 6.0, zero),
+            ("normal1/lamb1", 1.0, z[0]), ("normal10/lamb2.7", 2.7, 10.0 * z[1]), ("normal40/lamb-2", -2.0, 40.0 * z[2]), ("sawtooth10/lamb6", 6.0, saw),
+            ("hole-300/lamb0", 0.0, hole), ("shift+300/lamb1", 1.0, z[0] + 300.0), ("shift-300/lamb1", 1.0, z[0] - 300.0)]
+
+
+def zspline_points(N, seed, normalize):
+    rs = np.random.RandomState(seed)
+    z = _quantised(rs.standard_normal((3, N)))
+    e = np.eye(N)
+    saw = np.array([10.0 if k % 2 == 0 else -10.0 for k in range(N)])
+    hole = z[0].copy()
+    hole[N // 2] = -300.0
+    # (all zeros under normalize=True is 0 / 0 in the reference: the flat point there is all ones)
+    # (and 5 e_0 would be divided by I_0 ~ 1e-4, the integral of the first basis over a grid linear in z: an exponent of thousands)
+    first = N // 2 if normalize else 0
+    return [("ones", np.ones(N)) if normalize else ("zeros", np.zeros(N)), (f"5e{first}", 5.0 * e[first]), (f"5e{N - 1}", 5.0 * e[N - 1]), ("normal1", z[0]), ("normal10", 10.0 * z[1]),
+            ("normal40", 40.0 * z[2]), ("sawtooth10", saw), ("hole-300", hole)]
+
+
+def _grid_tables(b, zg, dv, divide_by_1pz):
+    """Nodes, trapezoid weights, the static weight of every node (dVc/dz, over 1 + z for BSplineRedshift), log(1 + z) and the bases at
+    the nodes inside the spline domain (None outside: exponent 0 there)."""
+    g = [F(v) for v in zg]
+    tw = _trapezoid_weights(g)
+    stat = [F(d) / (1 + gi) if divide_by_1pz else F(d) for d, gi in zip(dv, g)]
+    l1 = [mp.log(1 + gi) for gi in g]
+    gu = b.coordinate(zg)
+    Bg = [b.bases(float(u)) if b.grid_inside(float(u)) else None for u in gu]
+    return g, tw, stat, l1, Bg
+
+
+def _exp_grid_sum(c, tw, stat, Bg, extra=None):
+    """Z = sum_g tw_g stat_g extra_g exp(sum_k c_k B_k(g)), and sum_g (the same) B_j(g) for every j."""
+    N = len(c)
+    Z, dZ, terms = mp.mpf(0), [mp.mpf(0)] * N, []
+    for i, (w, s, Bi) in enumerate(zip(tw, stat, Bg)):
+        y = w * s * (extra[i] if extra is not None else 1)
+        if Bi is not None:
+            y *= mp.exp(sum(c[k] * v for k, v in Bi.items()))
+            for k, v in Bi.items():
+                dZ[k] += y * v
+        terms.append(y)
+        Z += y
+    return Z, dZ, terms
+
+
+def _plz_term(name):
+    """PowerlawSplineRedshiftModel (models/spline_perturbation.py:304-372): p = dVc/dz (1 + z)^(lamb - 1) exp(sum_k c_k B_k(log z)) / Z
+    for z <= zmax, the bases 0 outside [lo, hi] (interpolation.py:175), Z the trapezoid sum of the same on the model's z grid.
+    Parameters (lamb, c_0 .. c_{N-1}); columns (z, dVc/dz(z))."""
+    N = Z_META[name]["n"]
+    b, zs = _z_basis(name)
+    zg, dvg = _z_grid()
+    zmax = float(zg[-1])
+    dvs = _dvcdz_at(zs)
+    g, tw, stat, l1, Bg = _grid_tables(b, zg, dvg, False)
+    assert all(Bi is not None for Bi in Bg)  # the basis covers the whole grid: the shift points are invariant
+    us = b.coordinate(zs)
+    points = plz_points(N, 2001 + sum(ord(ch) for ch in name))
+    H, n = len(points), len(zs)
+    logp = np.full((H, n), -np.inf)
+    dlogp = np.zeros((H, 1 + N, n))
+    exact = {}
+    gap = max(0.0, b.knots[3] - b.lo, b.hi - b.knots[N]) / (b.knots[4] - b.knots[3])
+    tol = mp.mpf(10) ** -60 + 2 * 300 * F(gap) ** 3
+    for h, (tag, lamb, c_d) in enumerate(points):
+        lm, c = F(lamb), [F(v) for v in c_d]
+        pw = [mp.exp((lm - 1) * li) for li in l1]
+        Z, dZ, terms = _exp_grid_sum(c, tw, stat, Bg, pw)
+        assert Z > 0, (name, tag)
+        dlam = sum((y * li for y, li in zip(terms, l1)), mp.mpf(0)) / Z
+        dlogZ = [d / Z for d in dZ]
+        logZ = mp.log(Z)
+        if tag.startswith("zeros"):  # the power law alone: the tabulated distribution's normaliser, as _redshift_term writes it
+            y = [F(d) * mp.exp((lm - 1) * li) for d, li in zip(dvg, l1)]
+            Zp = _trapezoid(g, y)
+            assert abs(logZ - mp.log(Zp)) < mp.mpf(10) ** -60 and abs(dlam - _trapezoid(g, [yi * li for yi, li in zip(y, l1)]) / Zp) < mp.mpf(10) ** -60, (name, tag)
+        row = []
+        for s, (z, u) in enumerate(zip(zs, us)):
+            if not z <= zmax:
+                row.append(None)
+                continue
+            Bs = b.bases(float(u)) if b.grid_inside(float(u)) else {}
+            l1z = mp.log(1 + F(z))
+            lp = mp.log(F(dvs[s])) + (lm - 1) * l1z + sum(c[k] * v for k, v in Bs.items()) - logZ
+            d = [l1z - dlam] + [Bs.get(j, mp.mpf(0)) - dlogZ[j] for j in range(N)]
+            row.append(lp)
+            assert lp > LOG_FLOOR, (name, tag, s, float(lp))
+            if tag.startswith("shift"):  # sum_j d log p / d c_j = sum_j B_j(u) - sum_j dlogZ_j = 1 - 1
+                assert abs(sum(d[1:])) < tol, (name, tag, s)
+            logp[h, s] = float(lp)
+            dlogp[h, :, s] = [float(v) for v in d]
+        exact[tag] = row
+    for tag in ("shift+300/lamb1", "shift-300/lamb1"):
+        for a, r in zip(exact[tag], exact["normal1/lamb1"]):
+            assert (a is None) == (r is None) and (a is None or abs(a - r) < tol), (name, tag)
+    return {f"{name}/params": np.array(["lamb"] + [f"c{k}" for k in range(N)]), f"{name}/columns": np.array(["z", "dVcdz"]), f"{name}/col/z": zs, f"{name}/col/dVcdz": dvs,
+            f"{name}/tags": np.array([t for t, _, _ in points]), f"{name}/theta": np.array([np.concatenate([[l], c]) for _, l, c in points], dtype=np.float64),
+            f"{name}/logp": logp, f"{name}/dlogp": dlogp}
+
+
+def _zspline_term(name):
+    """BSplineRedshift (models/bsplines/single.py:398-492): p = exp(f(z)) dVc/dz / (1 + z) / Z(c); f = sum_k e_k B_k(log z) where
+    xmin <= z <= xmax (:54-55) and log z is in [lo, hi] (interpolation.py:175), 0 elsewhere; Z(c) the trapezoid sum of
+    dVc/dz / (1 + z) exp(sum_k c_k B_k(log z)) on the model's z grid, exponent 0 at the nodes outside [lo, hi].  No sample is excluded.
+    normalize=True (the reference's default): e = c / (c . I), I_k = trapz(B_k(grid), grid) on the basis's own 1000-point grid
+    (interpolation.py:290, :343) -- a host matter; the parameters here are the two blocks (e_0 .. e_{N-1}, c_0 .. c_{N-1}), e the
+    double nearest to c / (c . I), and each block is differentiated alone: d / d e_k = B_k(log z), d / d c_j = -d log Z / d c_j.
+    ``{name}/I`` holds I_k.  normalize=False: one block, e = c."""
+    N, normalize = Z_META[name]["n"], Z_META[name]["normalize"]
+    b, zs = _z_basis(name)
+    zg, dvg = _z_grid()
+    dvs = _dvcdz_at(zs)
+    g, tw, stat, l1, Bg = _grid_tables(b, zg, dvg, True)
+    assert any(Bi is None for Bi in Bg[:5]) and any(Bi is None for Bi in Bg[-5:])  # live nodes outside the spline domain, both sides
+    us = b.coordinate(zs)
+    Bs = [b.bases(float(u)) if b.inside(float(z), float(u)) else {} for z, u in zip(zs, us)]
+    points = zspline_points(N, 2001 + sum(ord(ch) for ch in name), normalize)
+    I = [mp.mpf(0)] * N
+    if normalize:
+        bg = [F(v) for v in b.grid]
+        for w, u in zip(_trapezoid_weights(bg), b.coordinate(b.grid)):
+            if b.grid_inside(float(u)):
+                for k, v in b.bases(float(u)).items():
+                    I[k] += w * v
+    H, n, P = len(points), len(zs), (2 * N if normalize else N)
+    logp = np.full((H, n), -np.inf)
+    dlogp = np.zeros((H, P, n))
+    theta = np.zeros((H, P))
+    for h, (tag, c_d) in enumerate(points):
+        c = [F(v) for v in c_d]
+        if normalize:
+            cI = sum(ck * Ik for ck, Ik in zip(c, I))
+            assert abs(cI) >= CONDITION * sum(abs(ck * Ik) for ck, Ik in zip(c, I)), (name, tag)
+            e_d = np.array([float(ck / cI) for ck in c])
+            theta[h] = np.concatenate([e_d, c_d])
+        else:
+            e_d = np.asarray(c_d, dtype=np.float64)
+            theta[h] = c_d
+        e = [F(v) for v in e_d]
+        Z, dZ, _ = _exp_grid_sum(c, tw, stat, Bg)
+        assert Z > 0, (name, tag)
+        logZ, dlogZ = mp.log(Z), [d / Z for d in dZ]
+        for s, z in enumerate(zs):
+            lp = sum(e[k] * v for k, v in Bs[s].items()) + mp.log(F(dvs[s])) - mp.log(1 + F(z)) - logZ
+            assert LOG_FLOOR < lp < -LOG_FLOOR, (name, tag, s, float(lp))
+            logp[h, s] = float(lp)
+            dB = [Bs[s].get(j, mp.mpf(0)) for j in range(N)]
+            d = dB + [-v for v in dlogZ] if normalize else [bj - v for bj, v in zip(dB, dlogZ)]
+            dlogp[h, :, s] = [float(v) for v in d]
+    out = {f"{name}/params": np.array([f"e{k}" for k in range(N)] + [f"c{k}" for k in range(N)] if normalize else [f"c{k}" for k in range(N)]),
+           f"{name}/columns": np.array(["z", "dVcdz"]), f"{name}/col/z": zs, f"{name}/col/dVcdz": dvs, f"{name}/tags": np.array([t for t, _ in points]), f"{name}/theta": theta,
+           f"{name}/logp": logp, f"{name}/dlogp": dlogp}
+    if normalize:
+        out[f"{name}/I"] = np.array([float(v) for v in I])
+    return out
+
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# BSplineDistribution: a log-density tabulated on a grid and interpolated linearly
+# ---------------------------------------------------------------------------------------------------------------------
+LERPS = [  # name, basis, N, xrange, (first node, last node, number of nodes): the grid reaches beyond the basis domain on one side
+    ("lerp_logy7", "LogYBSpline", 7, (0.0, 1.0), (0.0, 1.25, 101)),          # above: node 80 is 1.0 = hi, nodes 81.. carry -inf
+    ("lerp_logxlogy20", "LogXLogYBSpline", 20, (3.0, 100.0), (2.0, 100.0, 197)),  # below: nodes 0, 1 carry -inf, node 2 is 3.0
+    ("lerp_bspline7", "BSpline", 7, (-1.0, 1.0), (-1.5, 1.0, 126)),           # below: the bases are 0 there, the log-density 0
+]
+LERP_META = {name: dict(basis=kind, n=N, xrange=xr, grid=gr) for name, kind, N, xr, gr in LERPS}
+
+
+def lerp_samples(b, grid, seed):
+    """On a node (f = 0) and one ulp either side; on grid[0] and grid[-1]; outside the grid on both sides (end values are held);
+    in the last cell one ulp below the end; on the nodes at both ends of the basis domain, on the first node outside it, and inside
+    the cells that touch it; cell mid-points and quarter points; seeded points over the whole grid (multiples of 2^-20)."""
+    n = len(grid)
+    us = b.coordinate(grid)
+    inside = np.array([b.grid_inside(float(u)) for u in us])
+    first, last = int(np.flatnonzero(inside)[0]), int(np.flatnonzero(inside)[-1])
+    span = grid[-1] - grid[0]
+    out = _neighbours(grid[n // 3]) + [float(grid[0]), float(np.nextafter(grid[0], np.inf)), float(grid[-1]), float(np.nextafter(grid[-1], -np.inf))]
+    out += [float(grid[0] - 0.125 * span), float(np.nextafter(grid[0], -np.inf)), float(np.nextafter(grid[-1], np.inf)), float(grid[-1] + 0.5 * span)]
+    for j in (first, last):
+        out += _neighbours(grid[j])
+    for j in (first - 1, first, last - 1, last):  # the cells that touch a node outside the domain, and their inner neighbours
+        if 0 <= j < n - 1:
+            out += [float(0.75 * grid[j] + 0.25 * grid[j + 1]), float(0.5 * (grid[j] + grid[j + 1]))]
+    for j in (first - 1, last + 1):
+        if 0 <= j < n:
+            out.append(float(grid[j]))
+    out += [float(0.5 * (grid[j] + grid[j + 1])) for j in sorted({0, 1, n // 5, n // 2, (2 * n) // 3, n - 3, n - 2})]
+    r = _quantised(np.random.RandomState(seed).uniform(0.0, 1.0, 64))
+    for v in _quantised(grid[0] + span * r):
+        if len(set(out)) >= 54:
+            break
+        out.append(float(v))
+    seen, xs = set(), []
+    for v in out:
+        if v not in seen:
+            seen.add(v)
+            xs.append(v)
+    return np.array(xs, dtype=np.float64)
+
+
+def _lerp_term(name):
+    """BSplineDistribution.log_prob (numpyro_distributions.py:266-293): lpdf_g = sum_k c_k B_k(grid_g) at the nodes inside the basis
+    domain; outside it the design matrix of a log-Y basis holds -inf (interpolation.py:407, :449) and that of a linear one 0 (:175).
+    log_prob(x) = interp(x, grid, lpdf) - log trapz(exp(lpdf), grid), linear between the nodes, the end values held outside the grid,
+    the cell of x being grid[j] <= x < grid[j+1] (compared as doubles); no sample is masked.
+
+    A NODE WITH -inf: c_k (-inf) summed over k is NaN for coefficients of mixed sign or with a zero among them, -inf for positive
+    ones, and ``nan_to_num(nan=-inf)`` makes both -inf (all-negative coefficients give +inf, which nan_to_num turns into 1.8e308: not a
+    density; ``_compute`` asserts that no hyper-point is one).  A sample strictly inside a cell that touches such a node, or on the
+    node, has log_prob = -inf (NaN = inf - inf under jax.numpy's interp, -inf under numpy's: zero weight either way).  A sample
+    EXACTLY ON THE LAST FINITE NODE whose right-hand partner is -inf has weight 0 on that partner: numpy.interp returns the node's own
+    finite value, which is also the limit from the left, and that is what is recorded here -- and what the unmodified reference yields
+    when run through ref_import.py, whose jax.numpy stand-in is numpy (``confirm_lerp_convention``, run with --tabulate).  jax.numpy's
+    own interp evaluates fp[j] + 0 * (fp[j+1] - fp[j]) = NaN there, which a hierarchical likelihood counts as zero weight."""
+    m = LERP_META[name]
+    N = m["n"]
+    b = Basis(m["basis"], N, m["xrange"])
+    grid = np.linspace(*m["grid"])
+    assert len(grid) <= 200
+    seed = 3000 + sum(ord(ch) for ch in name)
+    xs = lerp_samples(b, grid, seed)
+    points = [pt for pt in exp_points(N, seed + 1) if not pt[0].startswith("shift")]  # (a shift is invariant only where the basis covers the grid)
+    g = [F(v) for v in grid]
+    tw = _trapezoid_weights(g)
+    Bg = [b.bases(float(u)) if b.grid_inside(float(u)) else None for u in b.coordinate(grid)]
+    assert any(Bi is None for Bi in Bg)
+    cell = np.clip(np.searchsorted(grid, xs, side="right") - 1, 0, len(grid) - 2)
+    H, n = len(points), len(xs)
+    logp = np.full((H, n), -np.inf)
+    dlogp = np.zeros((H, N, n))
+    for h, (tag, c_d) in enumerate(points):
+        assert not np.all(c_d < 0), (name, tag)
+        c = [F(v) for v in c_d]
+        lp = [sum(c[k] * v for k, v in Bi.items()) if Bi is not None else (None if b.log_y else mp.mpf(0)) for Bi in Bg]
+        Z, dZ = mp.mpf(0), [mp.mpf(0)] * N
+        for w, l, Bi in zip(tw, lp, Bg):
+            if l is not None:
+                y = w * mp.exp(l)
+                Z += y
+                for k, v in (Bi or {}).items():
+                    dZ[k] += y * v
+        assert Z > 0, (name, tag)
+        logZ, dlogZ = mp.log(Z), [d / Z for d in dZ]
+        for s, (x, j) in enumerate(zip(xs, cell)):
+            j = int(j)
+            f = min(max((F(x) - g[j]) / (g[j + 1] - g[j]), mp.mpf(0)), mp.mpf(1))  # the end values are held outside the grid
+            parts = [(wt, j + e) for e, wt in ((0, 1 - f), (1, f)) if wt != 0]
+            if any(lp[i] is None for _, i in parts):
+                continue
+            val = sum(wt * lp[i] for wt, i in parts) - logZ
+            assert val > LOG_FLOOR, (name, tag, s, float(val))
+            logp[h, s] = _rounded(val)
+            d = [-v for v in dlogZ]
+            for wt, i in parts:
+                for k, v in (Bg[i] or {}).items():
+                    d[k] += wt * v
+            dlogp[h, :, s] = [float(v) for v in d]
+    return {f"{name}/params": np.array([f"c{k}" for k in range(N)]), f"{name}/columns": np.array(["x"]), f"{name}/col/x": xs, f"{name}/grid": grid,
+            f"{name}/tags": np.array([t for t, _ in points]), f"{name}/theta": np.array([c for _, c in points], dtype=np.float64), f"{name}/logp": logp, f"{name}/dlogp": dlogp}
+
+
+def confirm_lerp_convention():
+    """Run the unmodified reference's BSplineDistribution (through ref_import.py) on every LERP term at ``normal1`` and assert that
+    it is dead exactly where the fixture is and finite on the last finite node next to a -inf one; needs the reference tree."""
+    import sys
+
+    sys.path.insert(0, HERE)
+    from ref_import import load_reference
+
+    ref = load_reference()
+    for name, m in LERP_META.items():
+        with mp.workdps(DPS):
+            a = _lerp_term(name)
+        grid, xs = a[f"{name}/grid"], a[f"{name}/col/x"]
+        h = [str(t) for t in a[f"{name}/tags"]].index("normal1")
+        kw = dict(xrange=m["xrange"]) if m["basis"] != "BSpline" else dict(xrange=m["xrange"], normalize=False)
+        basis = getattr(ref.interpolation, m["basis"])(m["n"], **kw)
+        with np.errstate(all="ignore"):
+            dist = ref.numpyro_distributions.BSplineDistribution(grid[0], grid[-1], ref.jnp.asarray(a[f"{name}/theta"][h]), ref.jnp.asarray(grid), ref.jnp.asarray(basis.bases(ref.jnp.asarray(grid))))
+            got = np.asarray(dist.log_prob(ref.jnp.asarray(xs)), dtype=np.float64)
+        want = a[f"{name}/logp"][h]
+        dead = np.isneginf(want)
+        assert np.array_equal(~np.isfinite(got) | (got < -1e300), dead), (name, np.flatnonzero((~np.isfinite(got) | (got < -1e300)) != dead))
+        assert np.max(np.abs(got[~dead] - want[~dead])) < 1e-9, name
+
+
 def names():
-    return [s[0] for s in SPLINES] + ["powerlaw_redshift"]
+    return [s[0] for s in SPLINES] + ["powerlaw_redshift"] + [s[0] for s in Z_SPLINES] + [s[0] for s in LERPS]
 
 
 def _compute(dps, only=None):
@@ -379,6 +775,12 @@ def _compute(dps, only=None):
                 out[PREFIX + spec[0] + ".npz"] = _spline_term(*spec)
         if only is None or "powerlaw_redshift" in only:
             out[PREFIX + "powerlaw_redshift.npz"] = _redshift_term()
+        for name, model, _, _, _ in Z_SPLINES:
+            if only is None or name in only:
+                out[PREFIX + name + ".npz"] = _plz_term(name) if model == "PowerlawSplineRedshiftModel" else _zspline_term(name)
+        for spec in LERPS:
+            if only is None or spec[0] in only:
+                out[PREFIX + spec[0] + ".npz"] = _lerp_term(spec[0])
     return out
 
 
@@ -394,6 +796,11 @@ def generate(verify=True, only=None):
 
 
 if __name__ == "__main__":
+    import sys
+
+    if "--tabulate" in sys.argv[1:]:
+        tabulate_cosmology()
+        confirm_lerp_convention()
     for fn, arrays in generate(verify=True).items():
         path = os.path.join(HERE, fn)
         np.savez_compressed(path, **arrays)

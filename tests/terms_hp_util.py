@@ -12,6 +12,9 @@ Catalogs (the engine returns only the summed gradient):
           total_inj = 1:  log_l = sum_i l(x_i) - B l(x_0),  grad_j = sum_i g_j(x_i) - B g_j(x_0).
   B       events of 3 samples, 5 injections, total_inj = 5; samples that are excluded at some hyper-points ride along with core
           ones.  Reference: the weight-averaged form, assembled from the fixture in np.longdouble.
+  pinned  the spline redshift models take zmin, zmax and their z grid from the data: for their terms (and products with one) both sides
+          of every catalog carry the two end samples and no injection lies beyond zmax (``pins``); A has injections {z_lo, x_0, z_hi}
+          and total_inj = 3.  ``check_tables`` holds the models' grid and dVc/dz tables to the fixture's when a catalog is built.
 """
 import glob
 import os
@@ -43,7 +46,22 @@ SPLINE_TERMS = {
     "bspline7_f32": ("BSpline", 7, (0.0, 1.0), True),
     "logx4": ("LogXBSpline", 4, (0.01, 1.0), False), "logx7": ("LogXBSpline", 7, (0.001, 2.3), False), "logx17": ("LogXBSpline", 17, (0.01, 1.0), False),
 }
-SPLINE_FIXTURE_TERMS = list(SPLINE_TERMS) + ["powerlaw_redshift"]
+# The spline redshift models of the same fixture: name -> (model, number of coefficients, xrange (None: the data range), normalize).
+# Their z grid comes from the DATA (the common range of the two sides), so their catalogs are built to pin it: see ``pins``.
+Z_SPLINE_TERMS = {
+    "plzspline4": ("PowerlawSplineRedshiftModel", 4, None, False), "plzspline7": ("PowerlawSplineRedshiftModel", 7, None, False),
+    "plzspline17": ("PowerlawSplineRedshiftModel", 17, None, False),
+    "zspline4": ("BSplineRedshift", 4, (1e-4, 1.5), True), "zspline16": ("BSplineRedshift", 16, (1e-4, 1.5), True), "zspline17": ("BSplineRedshift", 17, (1e-4, 1.5), True),
+    "zspline7_raw": ("BSplineRedshift", 7, (1e-4, 1.5), False),
+}
+# BSplineDistribution.log_prob (GWI_TERM_EXP_SPLINE_LERP) of the same fixture: name -> (basis, number of coefficients, xrange, (first
+# node, last node, number of nodes) of the grid, which reaches beyond the basis domain on one side).
+LERP_TERMS = {
+    "lerp_logy7": ("LogYBSpline", 7, (0.0, 1.0), (0.0, 1.25, 101)), "lerp_logxlogy20": ("LogXLogYBSpline", 20, (3.0, 100.0), (2.0, 100.0, 197)),
+    "lerp_bspline7": ("BSpline", 7, (-1.0, 1.0), (-1.5, 1.0, 126)),
+}
+TABLE_RTOL = 1e-13  # the models' dVc/dz tables against the fixture's: two orders under VALUE_ATOL (the cosmology is input data)
+SPLINE_FIXTURE_TERMS = list(SPLINE_TERMS) + ["powerlaw_redshift"] + list(Z_SPLINE_TERMS) + list(LERP_TERMS)
 # A flat density again: all coefficients zero under the exponential, all coefficients one for a linear spline (the bases sum to one
 # inside the domain).  Every log-density is then the same number -log Z (0 on a domain of length 1), the fixture's log_l is 0 or the
 # rounding of sums that cancel, and the bar is relative to those sums as above.  On a domain of length 1 the sums themselves are 0
@@ -51,6 +69,10 @@ SPLINE_FIXTURE_TERMS = list(SPLINE_TERMS) + ["powerlaw_redshift"]
 # up to 50 log-weights, each within VALUE_ATOL = 1e-11 (the older cancelled tags have sums of 16 to 42 and are not touched by it).
 for _name, (_basis, _, _, _) in SPLINE_TERMS.items():
     LOGL_CANCELLED[_name] = {"zeros"} if "LogY" in _basis else {"ones"}
+# The tabulated log-density at all-zero coefficients is exactly flat wherever it is finite (lpdf = 0 at every live node): the same
+# cancellation, barred relative to the cancelled sums (n_obs |log Z|; log Z = log 1.00625, log 97.25 and log 2.5 for the three grids).
+for _name in LERP_TERMS:
+    LOGL_CANCELLED[_name] = {"zeros"}
 # ``dip`` (all ones but one coefficient at -2) with 17 coefficients, ON CATALOG A ONLY: the samples that are live at EVERY hyper-point,
 # which is all that catalog A is made of, lie outside the four intervals the negative coefficient touches -- among them the spline is
 # flat again.  Catalog B also carries samples inside the dip and is held to the plain relative bar.
@@ -123,14 +145,82 @@ class Product(Term):
         self.dlogp = np.where(dead[:, None, :], 0.0, self.dlogp)
 
 
+class Shared(Term):
+    """ONE fixture term read twice with ONE coefficient vector (the IID pair models: two terms scatter into the same gradient slots):
+    sample i is (x_i, x_perm[i]), its log-density and every derivative the sum of the two, dead where either part is."""
+
+    def __init__(self, term, perm):
+        perm = np.asarray(perm)
+        assert len(term.cols) == 1 and sorted(perm.tolist()) == list(range(term.n))
+        self.base, self.perm = term, perm
+        self.name = f"shared({term.name})"
+        self.params, self.tags, self.theta = term.params, term.tags, term.theta
+        self.columns = ["x1", "x2"]
+        self.cols = [term.cols[0], np.ascontiguousarray(term.cols[0][perm])]
+        self.logp = term.logp + term.logp[:, perm]
+        dead = np.isneginf(self.logp)
+        self.dlogp = np.where(dead[:, None, :], 0.0, term.dlogp + term.dlogp[:, :, perm])
+
+
+class LerpModel:
+    """The grid and design matrix of a BSplineDistribution term, made ONCE per catalog (the distribution keys its device tables on the
+    identity of the two arrays), and the drop-in call on them."""
+
+    def __init__(self, name):
+        from gwinferno_amd import interpolation as I
+
+        basis, n, xrange, grid = LERP_TERMS[name]
+        self.grid = np.linspace(*grid)
+        self.dmat = getattr(I, basis)(n, xrange=xrange).bases(self.grid)
+
+    def __call__(self, x, cs):
+        from gwinferno_amd import numpyro_distributions as D
+
+        return D.BSplineDistribution(self.grid[0], self.grid[-1], cs, self.grid, self.dmat).log_prob(x)
+
+
+def base_name(term):
+    return term.base.name if isinstance(term, Shared) else term.name
+
+
+def check_tables(name, model, pe, inj):
+    """The z grid of a spline redshift model must be the fixture's EXACTLY and its dVc/dz tables the fixture's to TABLE_RTOL, before
+    any density is compared: a miss here names the table, not the spline."""
+    zg, dv, _ = _z_table()
+    assert model.zmin == zg[0] and model.zmax == zg[-1], f"{name}: the catalog does not pin the redshift range: ({model.zmin!r}, {model.zmax!r})"
+    grid, table = (model.zs, model.dVdz_) if Z_SPLINE_TERMS[name][0] == "PowerlawSplineRedshiftModel" else (model.zgrid, model.dVcdzgrid)
+    assert np.array_equal(grid, zg), f"{name}: the model's z grid is not the fixture's"
+    err = np.max(np.abs(table / dv - 1.0))
+    assert err <= TABLE_RTOL, f"{name}: dVc/dz on the z grid differs from the fixture's table by {err:.3e} relative"
+    if Z_SPLINE_TERMS[name][0] == "PowerlawSplineRedshiftModel":  # this model tabulates dVc/dz at the samples itself
+        for side, got, ref in (("injection", model.dVdzs[0], inj[1]), ("posterior", model.dVdzs[1], pe[1])):
+            err = np.max(np.abs(np.asarray(got) / ref - 1.0))
+            assert err <= TABLE_RTOL, f"{name}: dVc/dz at the {side} samples differs from the fixture's column by {err:.3e} relative"
+
+
 def model_of(name, pe, inj):
     """The model OBJECT of a term whose drop-in call is a method of one (the spline models are constructed on both data arrays and
-    called with ``pe_samples=``); None for the terms that are plain functions."""
-    if name not in SPLINE_TERMS:
-        return None
+    called with ``pe_samples=``); None for the terms that are plain functions.  ``name``: a term's name, or a ``Shared`` term."""
     from gwinferno_amd import interpolation as I
     from gwinferno_amd import models as M
 
+    if isinstance(name, Shared):
+        basis, n, xrange, _ = SPLINE_TERMS[name.base.name]
+        assert basis == "LogYBSpline" and xrange in ((0.0, 1.0), (-1.0, 1.0))
+        cls = M.BSplineIIDSpinMagnitudes if xrange == (0.0, 1.0) else M.BSplineIIDSpinTilts
+        return cls(n, pe[0], pe[1], inj[0], inj[1])
+    if name in LERP_TERMS:
+        return LerpModel(name)
+    if name in Z_SPLINE_TERMS:
+        kind, n, xrange, normalize = Z_SPLINE_TERMS[name]
+        if kind == "PowerlawSplineRedshiftModel":
+            model = M.PowerlawSplineRedshiftModel(n, pe[0], inj[0])
+        else:
+            model = M.BSplineRedshift(n, pe[0], inj[0], pe[1], inj[1], xrange=xrange, normalize=normalize)
+        check_tables(name, model, pe, inj)
+        return model
+    if name not in SPLINE_TERMS:
+        return None
     basis, n, xrange, _ = SPLINE_TERMS[name]
     return M.Base1DBSplineModel(n, pe[0], inj[0], xrange=xrange, basis=getattr(I, basis), normalize=True)
 
@@ -140,6 +230,18 @@ def density(name, cols, p, model=None, pe_samples=True):
     ``model``: what ``model_of`` made on the catalog's two sides, ``pe_samples`` which of them ``cols`` is."""
     from gwinferno_amd import models as M
 
+    if name in LERP_TERMS:
+        return model(cols[0], np.asarray(p, dtype=np.float64))
+    if name in Z_SPLINE_TERMS:
+        kind, n, _, normalize = Z_SPLINE_TERMS[name]
+        p = np.asarray(p, dtype=np.float64)
+        if kind == "PowerlawSplineRedshiftModel":
+            return model(cols[0], p[0], p[1:])
+        if not normalize:
+            return model(p, pe_samples=pe_samples)
+        # theta as the engine lays it out: the exponent's block e and the normaliser's block c, each a parameter of its own here (the
+        # host's e = c / (c . I) is held to the fixture in tests/test_terms_hp_cpu.py)
+        return model(p[n:], pe_samples=pe_samples, exponent_coefs=p[:n])
     if model is not None:
         return model(np.asarray(p, dtype=np.float64), pe_samples=pe_samples)
     if name == "powerlaw_redshift":
@@ -182,7 +284,7 @@ class Catalog:
                 self.inj.append(MMIN / self.inj[1])
         parts = term.parts if isinstance(term, Product) else (term,)
         at = np.cumsum([0] + [len(t.cols) for t in parts])
-        self.models = [model_of(t.name, self.pe[a:b], self.inj[a:b]) for t, a, b in zip(parts, at[:-1], at[1:])]
+        self.models = [model_of(t if isinstance(t, Shared) else t.name, self.pe[a:b], self.inj[a:b]) for t, a, b in zip(parts, at[:-1], at[1:])]
         p0 = term.theta[0]
         self.ev = make(self._density(self.pe, p0), self._density(self.inj, p0))
         # theta slot of every named parameter: bind the model once more, lazily, with marker values (distinct and positive: the
@@ -223,19 +325,56 @@ def core_samples(term):
     return np.flatnonzero(live.all(axis=0)), np.flatnonzero(live.any(axis=0) & ~live.all(axis=0))
 
 
+def pins(term):
+    """None, or (index of z == zmin, index of z == zmax, whether z <= zmax per sample) where ``term`` is or contains a spline redshift
+    model: zmin and zmax of these models are the common range of the two sides' data, so BOTH sides of every catalog carry the two
+    end samples, and a sample beyond zmax stays off the injection side."""
+    parts = term.parts if isinstance(term, Product) else (term,)
+    at = 0
+    for t in parts:
+        if t.name in Z_SPLINE_TERMS:
+            zg, _, _ = _z_table()
+            z = term.cols[at]
+            return int(np.flatnonzero(z == zg[0])[0]), int(np.flatnonzero(z == zg[-1])[0]), z <= zg[-1]
+        at += len(t.cols)
+    return None
+
+
 def values_catalog(term, make):
     idx = np.arange(term.n)
-    return Catalog(term, make, idx.reshape(-1, 1), idx)
+    pin = pins(term)
+    return Catalog(term, make, idx.reshape(-1, 1), idx if pin is None else idx[pin[2]])
 
 
 def catalog_a(term, make):
     core, _ = core_samples(term)
     assert len(core) >= 8, (term.name, len(core))
-    return Catalog(term, make, core.reshape(-1, 1), core[:1])
+    pin = pins(term)
+    if pin is None:
+        return Catalog(term, make, core.reshape(-1, 1), core[:1])
+    lo, hi, inside = pin
+    assert lo in core and hi in core, (term.name, "an end sample is not live at every hyper-point")
+    x0 = [c for c in core if c not in (lo, hi) and inside[c]][0]
+    return Catalog(term, make, core.reshape(-1, 1), [lo, x0, hi])  # total_inj = 3
 
 
 def catalog_b(term, make):
     core, some = core_samples(term)
+    pin = pins(term)
+    if pin is not None:
+        # the two ends lead the events; samples dead at every hyper-point (beyond zmax) ride along with the partly dead ones
+        lo, hi, inside = pin
+        never = np.flatnonzero(~np.isfinite(term.logp).any(axis=0))
+        rest = [c for c in core if c not in (lo, hi)]
+        seq, s = [lo, hi], list(some) + list(never)
+        for k, c in enumerate(rest):
+            seq.append(c)
+            if k % 2 == 1 and s:
+                seq.append(s.pop(0))
+        n_ev = len(seq) // 3
+        assert n_ev >= 4 and lo in core and hi in core, (term.name, n_ev)
+        ok = [c for c in rest if inside[c]]
+        return Catalog(term, make, np.array(seq[: 3 * n_ev]).reshape(n_ev, 3), [lo, ok[1], ok[3], ok[5], hi])
     seq, s = [], list(some)
     for k, c in enumerate(core):
         seq.append(c)
@@ -296,6 +435,8 @@ def is_cancelled(term, h, cat=None):
     LOGL_CANCELLED_A); a product's is where every part's is (a flat density times a flat one)."""
     if isinstance(term, Product):
         return all(is_cancelled(t, int(hs[h]), cat) for t, hs in zip(term.parts, term.part_points))
+    if isinstance(term, Shared):  # a flat density times itself
+        return is_cancelled(term.base, h, cat)
     only_a = cat is not None and cat.pe_idx.shape[1] == 1 and len(cat.inj_idx) == 1
     return term.tags[h] in LOGL_CANCELLED.get(term.name, ()) or (only_a and term.tags[h] in LOGL_CANCELLED_A.get(term.name, ()))
 
@@ -303,7 +444,7 @@ def is_cancelled(term, h, cat=None):
 def marginalised_points(term):
     """Every hyper-point but the flat ones: with equal weights on all ``total_inj`` injections the reference's Monte-Carlo variance
     (analysis.py:128) is exactly 0, its n_eff infinite and the derivative of its own expression 0 / 0."""
-    flat = LOGL_CANCELLED.get(term.name, ())
+    flat = LOGL_CANCELLED.get(base_name(term), ())
     return [h for h, tag in enumerate(term.tags) if tag not in flat]
 
 
@@ -354,7 +495,7 @@ def check_gradients(cat, path, worst, failures, points=None, results=None, margi
         grad = np.asarray(grad)[cat.slot]
         ref_l, ref_g, scale_l = (reference_marginalised if marginalised else reference)(cat, h)
         cancelled = is_cancelled(t, h, cat)
-        e_l = 0.0 if log_l == ref_l else abs(log_l - ref_l) / (max(scale_l, abs(ref_l), 1.0 if t.name in SPLINE_TERMS else 0.0) if cancelled else (abs(ref_l) or 1e-300))
+        e_l = 0.0 if log_l == ref_l else abs(log_l - ref_l) / (max(scale_l, abs(ref_l), 1.0 if base_name(t) in SPLINE_TERMS else 0.0) if cancelled else (abs(ref_l) or 1e-300))
         worst.note((t.name, path, "log_l (relative)"), e_l, t.tags[h])
         if not e_l < LOGL_RTOL:
             failures.append(f"{t.name} [{path}] {t.tags[h]}: log_l {log_l!r} vs {ref_l!r}: relative {e_l:.3e} >= {LOGL_RTOL:g}{' (of the cancelled sums)' if cancelled else ''}")

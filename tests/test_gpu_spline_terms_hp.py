@@ -12,6 +12,11 @@ engine picks, the generic kernel, a chain compiled at run time for a product of 
 K = 16 on float32 columns), the matrix-core GEMM on full and ragged groups (K = 16, 17) and its rows variant, float32 coordinate
 columns, replay mode, and the squared-weight pass of the marginalised selection.
 
+The two spline redshift models (PowerlawSplineRedshiftModel: "plzspline*", BSplineRedshift: "zspline*") ride the same tests on
+catalogs that pin the models' z grid to the fixture's (tests/terms_hp_util.pins; the dVc/dz tables are checked when a catalog is
+built), the "lerp_*" terms are BSplineDistribution.log_prob (GWI_TERM_EXP_SPLINE_LERP) on grids that reach beyond the basis domain, and
+``Shared`` holds the IID pair models, two terms scattering into one block of gradient slots.
+
 The matrix-core kernel runs on the product redshift x LogY (17) x LogY (16), not on a one-term model.  For a model of ONE spline term
 there is no ahead-of-time instantiation (gwi_engine.hip, kMfmaVariants: all carry the redshift term), and the one hipRTC makes under
 GWI_BATCH_MFMA=1 spills 24 bytes per lane to scratch, which the engine refuses by rule (try_jit_mfma: "the instantiation spills
@@ -103,7 +108,16 @@ def test_single_evaluations_through_the_chain_the_engine_picks(fixture, name, mo
     _run(U.Term(fixture, name), "chain", _compiled_chain)
 
 
-@pytest.mark.parametrize("name", ["logy17", "bspline7"])
+@pytest.mark.parametrize("name", ["logy7", "logy17"])
+def test_one_coefficient_vector_read_by_two_terms(fixture, name, monkeypatch, tmp_path):
+    """BSplineIIDSpinTilts (7 coefficients on (-1, 1)) and BSplineIIDSpinMagnitudes (17 on (0, 1)): both terms add into the same slots."""
+    monkeypatch.setenv("GWI_JIT_CACHE", str(tmp_path))
+    t = U.Term(fixture, name)
+    term = U.Shared(t, np.roll(np.arange(t.n), 7))
+    _run(term, "chain", _compiled_chain, engine_ok=lambda e: len(e.bound.terms) == 2 and e.bound.n_theta == len(term.params) or pytest.fail("not one shared block"))
+
+
+@pytest.mark.parametrize("name", ["logy17", "bspline7", "plzspline7", "zspline16", "lerp_logy7"])
 def test_generic_kernel(fixture, name, monkeypatch):
     monkeypatch.setenv("GWI_FORCE_GENERIC", "1")
     _run(U.Term(fixture, name), "generic", lambda k: k.startswith("generic"))
@@ -115,6 +129,14 @@ def test_product_of_two_spline_terms_compiled_at_run_time(fixture, monkeypatch, 
     monkeypatch.setenv("GWI_JIT_CACHE", str(tmp_path))
     monkeypatch.setenv("GWI_FORCE_JIT", "1")
     term = U.Product(U.Term(fixture, "logxlogy17"), U.Term(fixture, "logy7"))
+    _run(term, "jit", lambda k: k.startswith("jit:"))
+
+
+def test_redshift_spline_times_spin_spline_compiled_at_run_time(fixture, monkeypatch, tmp_path):
+    """PowerlawSplineRedshiftModel (17) x LogY (7): the normaliser over (lamb, c) next to a grid normaliser of the plain kind."""
+    monkeypatch.setenv("GWI_JIT_CACHE", str(tmp_path))
+    monkeypatch.setenv("GWI_FORCE_JIT", "1")
+    term = U.Product(U.Term(fixture, "plzspline17"), U.Term(fixture, "logy7"))
     _run(term, "jit", lambda k: k.startswith("jit:"))
 
 
@@ -157,6 +179,34 @@ def test_batch_of_4_on_the_4_tap_kernel(fixture, name):
     term = U.Term(fixture, name)
     worst, failures = U.Worst(), []
     _batch(term, (LINEAR_MIX if name in ("bspline7", "logx17") else EXP_MIX)[:4], 4, "taps", EngineEvaluator, worst, failures)
+    _finish(worst, failures)
+
+
+def test_batch_of_4_mixes_the_exact_exponent_the_hole_and_the_scale_40_point(fixture):
+    """lamb = 1 (lamb - 1 = 0 exactly), hole-300 and normal40 in ONE launch of the 4-tap kernel."""
+    worst, failures = U.Worst(), []
+    _batch(U.Term(fixture, "plzspline17"), ["normal1/lamb1", "hole-300/lamb0", "normal40/lamb-2", "zeros/lamb1"], 4, "taps", EngineEvaluator, worst, failures)
+    _batch(U.Term(fixture, "zspline17"), ["ones", "hole-300", "normal40", "sawtooth10"], 4, "taps", EngineEvaluator, worst, failures)
+    _finish(worst, failures)
+
+
+@pytest.mark.parametrize("K", [16, 17])
+def test_batches_of_the_redshift_spline_product_without_the_rows_variant(fixture, K, monkeypatch, tmp_path):
+    """PowerlawSplineRedshiftModel (17) x LogY (17) x LogY (16) on whichever batched kernel the engine reports when asked for the
+    matrix cores: that kernel, or the 4-tap one with the reason named.  THE ROWS VARIANT IS NOT COVERED for this product: it exists
+    for ahead-of-time instantiations only (tests/test_gpu_spline_terms_hp.py's matrix-core product has one), this kind sequence has
+    none, and a matrix-core kernel compiled at run time has no rows form -- under GWI_BATCH_ROWS=1 the engine reports the 4-tap
+    kernel, which ``test_batch_of_4...`` and the K = 16 float32 test already run."""
+    monkeypatch.setenv("GWI_JIT_CACHE", str(tmp_path))
+    monkeypatch.setenv("GWI_MAX_BATCH", "24")
+    monkeypatch.setenv("GWI_BATCH_MFMA", "1")
+    term = U.Product(U.Term(fixture, "plzspline17"), U.Term(fixture, "logy17"), U.Term(fixture, "logy16"))
+    probe = U.catalog_a(term, EngineEvaluator)
+    path, note = probe.ev.eng.batch_path(K), probe.ev.eng.batch_calibration()["matrix_core_kernel"]
+    probe.close()
+    assert path == "mfma" or (path == "taps" and note != ""), (path, note)
+    worst, failures = U.Worst(), []
+    _batch(term, range(len(term.theta)), K, path, EngineEvaluator, worst, failures, repeatable=True)
     _finish(worst, failures)
 
 
@@ -226,14 +276,14 @@ def test_float32_columns(fixture, name, monkeypatch, tmp_path):
     _finish(worst, failures)
 
 
-@pytest.mark.parametrize("name", ["logy20", "bspline17"])
+@pytest.mark.parametrize("name", ["logy20", "bspline17", "plzspline17", "zspline17"])
 def test_replay_mode(fixture, name, monkeypatch, tmp_path):
     monkeypatch.setenv("GWI_JIT_CACHE", str(tmp_path))
     monkeypatch.setenv("GWI_DETERMINISTIC", "1")
     _run(U.Term(fixture, name), "deterministic", _compiled_chain, repeat=True)
 
 
-@pytest.mark.parametrize("name, which", [("logy17", "fixture"), ("plpeak", "parametric_fixture")])
+@pytest.mark.parametrize("name, which", [("logy17", "fixture"), ("plpeak", "parametric_fixture"), ("plzspline7", "fixture")])
 def test_marginalised_selection(request, name, which, monkeypatch, tmp_path):
     """The squared-weight pass (marginalize_selection=True) against ``reference_marginalised``, assembled from the fixture: catalog B,
     whose five injections give the correction real weight."""
