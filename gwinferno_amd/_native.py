@@ -291,6 +291,7 @@ EXPORTED_SYMBOLS = [
     "gwi_last_kernel_ms",
     "gwi_set_timing",
     "gwi_launch_geometry",
+    "gwi_tail_path",
     "gwi_dispatch_info",
     "gwi_pin_thread_to_engine",
     "gwi_pin_thread_to_device",
@@ -536,6 +537,9 @@ def load_library():
     if hasattr(lib, "gwi_launch_geometry"):
         lib.gwi_launch_geometry.restype = C.c_int32
         lib.gwi_launch_geometry.argtypes = [vp, C.POINTER(C.c_int32)]
+    if hasattr(lib, "gwi_tail_path"):
+        lib.gwi_tail_path.restype = C.c_int32
+        lib.gwi_tail_path.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.gwi_set_timing.restype = C.c_int32
     lib.gwi_set_timing.argtypes = [vp, C.c_int32]
     lib.gwi_pin_thread_to_engine.restype = C.c_int32

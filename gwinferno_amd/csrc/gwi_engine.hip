@@ -646,6 +646,8 @@ struct gwi_engine {
   float last_ms[3] = {0, 0, 0};
   bool timed_final = false;
   bool last_host_rows = false;   // how the most recent run_pipeline publishes (what its waiter must poll)
+  bool last_publish_events = true;  // ... and whether its tail published the per-event sites (gwi_tail_path)
+  int last_final_groups = 0;        // ... and the workgroups of its final launch (0: none yet)
   bool pending = false;          // gwi_eval_begin issued, gwi_eval_end not yet called
   bool pending_sq = false;
   bool pending_batch = false;          // ... the pending evaluation is a batch (gwi_eval_batch_begin)
@@ -1165,6 +1167,8 @@ gwi_status run_pipeline_once(gwi_handle h, const double* theta, double* record_d
     ta.publish_events = h->batch_events ? 1 : 0;
   }
   h->last_host_rows = ta.host_rows != nullptr;
+  h->last_publish_events = ta.publish_events != 0;
+  h->last_final_groups = ta.final_groups;
   h->kargs.norm_seq = h->seq + 1;  // the normaliser workgroups of this launch stamp their results with it
   GWI_PHASE(0);
   gwi_status st = launch_scan(h, false, K, batch);
@@ -2900,6 +2904,15 @@ gwi_status gwi_launch_geometry(gwi_handle h, int32_t out[6]) {
   out[3] = g.n_inj_tiles;
   out[4] = g.n_scan_blocks;
   out[5] = g.n_inj_groups;
+  return GWI_OK;
+}
+
+gwi_status gwi_tail_path(gwi_handle h, int32_t out[4]) {
+  if (!h || !out || h->host_only) return GWI_ERR_INVALID;
+  out[0] = (h->seq == 0 ? h->host_final : h->last_host_rows) ? 1 : 0;
+  out[1] = h->last_final_groups ? h->last_final_groups : h->final_groups;
+  out[2] = h->combine_threads;
+  out[3] = h->last_publish_events ? 1 : 0;
   return GWI_OK;
 }
 

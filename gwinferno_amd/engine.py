@@ -964,6 +964,14 @@ class NativePopulationLikelihood(PostprocessMixin):
         self._check(self.lib.gwi_launch_geometry(self.handle, out))
         return dict(zip(("chunk_pe", "chunk_inj", "tiles_per_event", "n_inj_tiles", "n_scan_blocks", "n_inj_groups"), [int(v) for v in out]))
 
+    def tail_path(self):
+        """``gwi_tail_path``: how the most recent evaluation on this engine summed over groups -- ``host_final`` (the host summed the
+        combine launch's rows) or not (the final launch did, in ``final_groups`` workgroups), the combine launch's workgroup size
+        and whether the per-event sites were published.  Read-only."""
+        out = (C.c_int32 * 4)()
+        self._check(self.lib.gwi_tail_path(self.handle, out))
+        return {"host_final": bool(out[0]), "final_groups": int(out[1]), "combine_threads": int(out[2]), "publish_events": bool(out[3])}
+
     def read_column(self, side, col):
         """Column ``col`` of the engine's resident catalog (``gwi_read_column``): ``(n_ev, n_pe)`` for ``side == "pe"``, else
         ``(n_inj,)`` -- what the setup path (host or device) left in HBM."""

@@ -958,6 +958,12 @@ gwi_status gwi_shm_exchange_batch(gwi_handle h, const double* records, int32_t k
  * tiles, scan workgroups per hyper-parameter point, injection groups of the combine launch} (samples / counts). */
 gwi_status gwi_launch_geometry(gwi_handle h, int32_t out[6]);
 
+/* Diagnostic: the tail of the MOST RECENT evaluation launched on this handle -- out = {1 where the combine launch published
+ * per-group rows that the host summed (host-final mode), 0 where the final launch summed them on the device; workgroups of the
+ * final launch (GWI_FINAL_GROUPS; not launched in host-final mode); workgroup size of the combine launch; 1 where that
+ * evaluation published the per-event sites}.  Before any evaluation: what a single evaluation would take.  Changes nothing. */
+gwi_status gwi_tail_path(gwi_handle h, int32_t out[4]);
+
 /* Timing of the most recent gwi_eval*: milliseconds between the start/stop HIP events attached to each
  * launch on the engine's stream ([0]=scan kernel, [1]=per-event combine, [2]=final reduce; 0 when the
  * host does the final sum). */
