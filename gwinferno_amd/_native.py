@@ -296,6 +296,7 @@ EXPORTED_SYMBOLS = [
     "gwi_pin_thread_to_engine",
     "gwi_pin_thread_to_device",
     "gwi_hbm_bandwidth",
+    "gwi_math_probe",
     "gwi_last_error",
     "gwi_destroy",
     "gwi_abi_version",
@@ -548,6 +549,9 @@ def load_library():
     lib.gwi_pin_thread_to_device.argtypes = [C.c_int32]
     lib.gwi_hbm_bandwidth.restype = C.c_int32
     lib.gwi_hbm_bandwidth.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(lib, "gwi_math_probe"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        lib.gwi_math_probe.restype = C.c_int32
+        lib.gwi_math_probe.argtypes = [C.c_int32, C.c_int32, C.c_int64, _DP, _DP, _DP, C.POINTER(C.c_int32)]
     lib.gwi_dispatch_info.restype = C.c_char_p
     lib.gwi_dispatch_info.argtypes = [vp]
     lib.gwi_last_error.restype = C.c_char_p

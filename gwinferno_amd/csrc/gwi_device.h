@@ -178,6 +178,8 @@ __device__ __forceinline__ double wave_max(double v) {
 // vector instructions for the six steps of wave_max); here the value becomes an ordered 32-bit key (the float's bits, the
 // lower 31 flipped for negative values: signed-integer order = float order, -inf the smallest) and every step is ONE
 // v_max_i32 with a DPP operand: 11 vector instructions, the key's way back on the scalar unit.  NaN never gets here.
+// Measured domain (tests/test_gpu_math_probe.py): within one float32 rounding, 2^-24 |m|, of the true maximum m for -inf, 0 and
+// 2^-126 <= |m| <= 3.4e38; outside the float32 range it saturates -- 1e300 and 3.5e38 come back as +inf, 1e-300 as 0.
 __device__ __forceinline__ double wave_max_coarse(double v) {
   const int bits = __float_as_int((float)v);
   int k = bits ^ ((bits >> 31) & 0x7fffffff);
@@ -244,8 +246,10 @@ __device__ __forceinline__ double wave_sum8(const double* v) {
 // densities times e^{l - m}, i.e. down to the bottom of the range for samples ~700 e-folds under the tile's best one
 // (a narrow peak: the 2000-point fuzz sweep found sigma = 0.33).  Such a sample's weight is < 1e-290 of the best one's.
 constexpr double kRcpFloor = 1e-290;
-// 1/x to ~1 ulp for normal x: hardware seed + two Newton steps (no IEEE special-case handling:
-// callers only need it where the weight is non-zero)
+// 1/x: hardware seed + two Newton steps (no IEEE special-case handling: callers only need it where the weight is non-zero).
+// Held to 2 ulp on 2^-1022 <= |x| <= 2^1022, x and 1/x both normal (tests/test_gpu_math_probe.py; measured 0.5 ulp at the worst).
+// Measured outside, not held: a subnormal quotient (|x| up to the largest double) and the reciprocal of a subnormal that does not
+// overflow (1e-308) came back correctly rounded; 0, +-inf and a subnormal whose reciprocal overflows (1e-310, 2^-1074) give NaN.
 __device__ __forceinline__ double fast_rcp(double x) {
   double r = __builtin_amdgcn_rcp(x);
   double e = fma(-x, r, 1.0);
@@ -279,7 +283,7 @@ __device__ __forceinline__ double fma_sc(double a, double b, double c_uniform) {
 }
 // The two halves of the exponential, as few vector instructions as the parity budget allows:
 //   * q = an eighth-degree MINIMAX polynomial for (e^r - 1)/r on |r| <= 0.3466: the relative error of e^r = 1 + r q(r) is
-//     <= 1.6e-14 over the whole interval (tools/exp_poly.py), eight FMAs;
+//     <= 1.6e-14 over the whole interval (tools/exp_poly.py; held by tests/test_gpu_math_probe.py), eight FMAs;
 //   * r = x - n ln2 in ONE fused multiply-add with ln2 rounded to double (off by 2.3e-17): r is then off by 2.3e-17 |n|, i.e. the
 //     result by 2e-14 relative at |x| = 700 and 1e-13 at the |l| of a few thousand that spline models under the reference's priors
 //     reach -- against a bar of 1e-10 on per-sample log-weights and 1e-9 on log_l.  The shift of fast_exp_shift stays exact: it
@@ -320,8 +324,11 @@ __device__ __forceinline__ double fast_exp(double x) {
 // two, so sums of such weights scale exactly with the shift and every quantity derived from them is, to the bit,
 // independent of which shift was used (as long as nothing leaves the normal range -- the scan checks that).  That is what
 // lets spline models weigh a tile against a reference exponent remembered from the previous evaluation (scan_kernel)
-// without the results depending on the evaluation history.  The argument range is the full range of log-weights:
-// |x| <= 7e5 keeps n ln2_hi exact (ln2_hi has 21 trailing zero bits, |n| < 2^20).
+// without the results depending on the evaluation history.  The argument range is the full range of log-weights, clamped to
+// |x| <= 7e5.  The reduction is exp_reduce's ONE-PIECE r = fma(n, -ln2, x) with ln 2 rounded to double (there is no high / low
+// split): r is off by 2.32e-17 |n|, so the relative error of the result is the polynomial's 1.6e-14 + 2.32e-17 |n| + roundings --
+// 2.3e-14 at |x| = 700, 3.3e-12 at 1e5 and 2.34e-11 at the clamp (|n| = 1 009 887), inside the 1e-10 bar on per-sample log-weights
+// over the whole clamped range.  Held by tests/test_gpu_math_probe.py.
 constexpr double kLog2e = 1.4426950408889634;
 constexpr double kLn2 = 0.6931471805599453;
 constexpr int kNoRef = -2147483647 - 1;  // tile_nref: no reference yet / tile without a live sample
@@ -331,10 +338,18 @@ __device__ __forceinline__ double fast_exp_shift(double x, int shift) {
   const double r = exp_reduce(x, nf);
   return ldexp(fma(exp_q(r), r, 1.0), (int)nf - shift);
 }
+// e^x - 1 = 2^n (1 + rq) - 1 = fma(2^n, rq, 2^n - 1), with 2^1024 kept out of it: for x in [709.44, 709.78) n is 1024 while r < 0, and
+// fma(2^1024 = inf, rq < 0, inf) was inf - inf = NaN where e^x - 1 is finite.  The power of two stops at 2^1023 and the last binade
+// is applied to the result (ldexp by n - min(n, 1023), i.e. by 0 for every n <= 1023: the bits of fma(2^n, rq, 2^n - 1) there, three
+// more vector instructions); above 1024 ln 2 that doubling overflows to +inf.
+// Relative error of e^x - 1 (held by tests/test_gpu_math_probe.py): n = 0 (|x| <= 0.3466), where the result is x q(x): up to 2.2e-13
+// (the minimax fit bounds x (q - q*), not q - q*: 8.7e-14 = |C0 - 1| at x -> 0, the most near |x| = 0.07); otherwise the bound of
+// fast_exp times e^x / |e^x - 1| (<= 3.5); x <= -40 gives exactly -1.
 __device__ __forceinline__ double fast_expm1(double x) {
   const ExpParts p = exp_parts(x);
-  const double s = ldexp(1.0, p.n);
-  return fma(s, p.rq, s - 1.0);
+  const int m = min(p.n, 1023);
+  const double s = ldexp(1.0, m);
+  return ldexp(fma(s, p.rq, s - 1.0), p.n - m);
 }
 
 // ---- uniform cubic B-spline: 4 taps from the fractional knot coordinate --------------------
@@ -345,53 +360,64 @@ __device__ __forceinline__ double fast_expm1(double x) {
 struct Taps {
   double b0, b1, b2, b3;
 };
-// b0 = v^3/6, b3 = t^3/6, b1 = 2/3 - t^2 + t^3/2, b2 = b1(1 - t)  (v = 1 - t): 6 multiplies, 4 FMAs, 1 add
+// b0 = v^3/6, b3 = t^3/6 (v = 1 - t) and the inner taps about their SMALL end, where they are 1/6:
+//   b1 = 1/6 + (v/2)(1 + t v),  b2 = 1/6 + (t/2)(1 + t v)      (= 2/3 - t^2 + t^3/2 and its mirror image),
+// one shared P = 1 + t v and an FMA each.  Every addend is positive and the one that carries roundings vanishes where the tap
+// falls to 1/6, so each tap is within 4 x 2^-53 max(b, 1/6) of its value (held by tests/test_gpu_math_probe.py; the form
+// 2/3 - s^2 + s^3/2 used before was 1.5 times that off near 1/6, the roundings of its terms of size 1/2 and 2/3 not shrinking
+// with the result).  8 multiplies, 3 FMAs, 1 add.
 __device__ __forceinline__ Taps cubic_taps(double t) {
   const double v = 1.0 - t;
   const double t2 = t * t, v2 = v * v;
+  const double P = fma(t, v, 1.0);
   Taps r;
   r.b0 = v2 * (v * (1.0 / 6.0));
-  r.b1 = fma(t2, fma(t, 0.5, -1.0), 2.0 / 3.0);
-  r.b2 = fma(v2, fma(v, 0.5, -1.0), 2.0 / 3.0);
+  r.b1 = fma(0.5 * v, P, 1.0 / 6.0);
+  r.b2 = fma(0.5 * t, P, 1.0 / 6.0);
   r.b3 = t2 * (t * (1.0 / 6.0));
   return r;
 }
 // the same scaled by a weight w, for the gradient numerators.  The fraction is laundered through an empty asm so that the
 // compiler cannot share sub-expressions with the cubic_taps() of the evaluation: shared, they stay live across the sample's
 // exponential -- 8-10 VGPRs per spline term, config 5: 108 -> 159, a resident wave per SIMD -- for 7 of ~50 vector
-// instructions per term.  w/6 and 2w/3 are handed in -- they are the SAME for every spline term of a sample, but each term's
-// block sits behind its own exec-mask branch, across which the compiler does not share them -- and the inner taps are formed
-// from the outer ones, b1 = 2/3 - t^2 + t^3/2 = 2/3 - t^2 + 3 b3:  w b1 = fma(3, w b3, fma(-w, t^2, 2w/3)): 11 vector
-// instructions per term.  (Cancellation is benign: the three addends are O(w), the result >= w/6.)
+// instructions per term.  w/6 and w/2 are handed in -- they are the SAME for every spline term of a sample, but each term's
+// block sits behind its own exec-mask branch, across which the compiler does not share them:
+//   w b1 = fma((w/2) v, P, w/6),  w b2 = fma((w/2) t, P, w/6),  P = 1 + t v:  12 vector instructions per term, each tap within
+// 4 x 2^-53 max(|w b|, |w|/6) (tests/test_gpu_math_probe.py).
 struct Weight {
-  double w, w6, w23;
+  double w6, wh;
 };
 __device__ __forceinline__ Weight make_weight(double w) {
   Weight r;
-  r.w = w;
   r.w6 = w * (1.0 / 6.0);
-  r.w23 = w * (2.0 / 3.0);
+  r.wh = w * 0.5;
   return r;
 }
 __device__ __forceinline__ Taps cubic_taps_weighted(double t, const Weight& ww) {
   asm("" : "+v"(t));
   const double v = 1.0 - t;
   const double t2 = t * t, v2 = v * v;
+  const double P = fma(t, v, 1.0);
   Taps r;
   r.b3 = (ww.w6 * t) * t2;
   r.b0 = (ww.w6 * v) * v2;
-  r.b1 = fma(3.0, r.b3, fma(-ww.w, t2, ww.w23));
-  r.b2 = fma(3.0, r.b0, fma(-ww.w, v2, ww.w23));
+  r.b1 = fma(ww.wh * v, P, ww.w6);
+  r.b2 = fma(ww.wh * t, P, ww.w6);
   return r;
 }
-// The spline VALUE in the local power basis: on knot interval k the uniform cubic B-spline sum is one cubic in t,
-//   sum_i c_{k+i} b_i(t) = A + B t + C t^2 + D t^3,   A = (c0 + 4 c1 + c2)/6, B = (c2 - c0)/2, C = (c0 - 2 c1 + c2)/2, D = (c3 - c0)/6 + (c1 - c2)/2,
-// tabulated per workgroup when theta is staged: four arrays A[], B[], C[], D[] indexed like the coefficients (position
+// The spline VALUE from a per-interval table: on knot interval k the uniform cubic B-spline sum is one cubic in t, kept in its
+// BERNSTEIN form (v = 1 - t),
+//   sum_i c_{k+i} b_i(t) = E v^3 + F v^2 t + G v t^2 + H t^3,   E = (c0 + 4 c1 + c2)/6, F = 2 c1 + c2, G = c1 + 2 c2, H = (c1 + 4 c2 + c3)/6,
+// tabulated per workgroup when theta is staged: four arrays E[], F[], G[], H[] indexed like the coefficients (position
 // th0 + k), kPolyStride doubles apart -- each array is read exactly as the coefficient array was (neighbouring lanes on the
 // same or neighbouring 8-byte words: broadcast, no bank conflicts; interleaved 32-byte rows per interval measured 7 % SLOWER
 // than the taps, profiles/round3/EXPERIMENTS.md section 8), and the constant stride lets one ds_read2st64_b64 fetch two of them.
-// A sample's value is then 3 FMAs instead of the four taps + dot product (15 vector instructions); the taps are only formed
-// once per sample, weighted, for the gradient rows.
+// A sample's value is v^2 (E v + F t) + t^2 (H t + G v): nine vector instructions instead of the four taps + dot product (15); the
+// taps are only formed once per sample, weighted, for the gradient rows.  Every entry is a combination of the coefficients with
+// positive weights and every product above is one of them times a non-negative factor, so the value is within 8 x 2^-53
+// sum_i |c_i| b_i(t) of the sum (held by tests/test_gpu_math_probe.py).  The powers of t about the interval's left end, A + B t +
+// C t^2 + D t^3 in three FMAs, were used before: their error is proportional to max |c_i| -- 2e10 times that bound for
+// c = (1e6, 1e-6, 1e-6, 1e-6) near t = 1 -- because a large c0 has to cancel out of A, B, C and D.
 // The stride is deliberately NOT a multiple of 64 doubles: with 256 the compiler fuses the four reads of a sample into two
 // ds_read2st64_b64, which the LDS serves as two 4 x 16-lane accesses each (8 LDS cycles per instruction, 16 per term);
 // 257 keeps them four ds_read_b64 at immediate offsets (2 x 32 lanes, ~2.3 cycles each: 9 per term, conflict-free for any
@@ -400,9 +426,9 @@ __device__ __forceinline__ Taps cubic_taps_weighted(double t, const Weight& ww) 
 constexpr int kPolyStride = GWI_MAX_THETA + 1;
 __device__ __forceinline__ void spline_poly(double c0, double c1, double c2, double c3, double* out) {
   out[0] = (c0 + 4.0 * c1 + c2) * (1.0 / 6.0);
-  out[kPolyStride] = (c2 - c0) * 0.5;
-  out[2 * kPolyStride] = (c0 - 2.0 * c1 + c2) * 0.5;
-  out[3 * kPolyStride] = (c3 - c0) * (1.0 / 6.0) + (c1 - c2) * 0.5;
+  out[kPolyStride] = 2.0 * c1 + c2;
+  out[2 * kPolyStride] = c1 + 2.0 * c2;
+  out[3 * kPolyStride] = (c1 + 4.0 * c2 + c3) * (1.0 / 6.0);
 }
 // The columns of EXP_SPLINE / LINEAR_SPLINE terms hold the KNOT COORDINATE u = (x - lo) / dx of the sample, not x: the engine
 // converts them once when the catalog becomes resident (gwi_engine.hip: spline_knot_kernel), so the scan never spends the
@@ -463,16 +489,18 @@ struct Ctx {
   const double* theta;          // scalar hyper-parameters: uniform index -> scalar loads, never LDS
   const double (*derived)[kMaxDerived];  // host-precomputed theta-only scalars per term
   const double* coefs;          // LDS copy of theta for the lane-varying spline coefficient reads
-  const double* poly;           // LDS: the cubic of every knot interval in the local power basis, four arrays kPolyStride apart (spline_poly)
+  const double* poly;           // LDS: the cubic of every knot interval in its Bernstein form, four arrays kPolyStride apart (spline_poly)
   double* gacc;                 // LDS gradient numerators [n_theta][rep] + this lane's replica: coefficient p lives at gacc[p << rep_shift]
   int rep_shift;
   const double* const (*tcols)[2];  // per-term column pointers of the sample set this workgroup scans
-  mutable Weight wt;                // the weight of the sample being accumulated with w/6 and 2w/3 (set by the scan loop: shared by its spline terms)
+  mutable Weight wt;                // the weight of the sample being accumulated with w/6 and w/2 (set by the scan loop: shared by its spline terms)
 };
 
 __device__ __forceinline__ double spline_value(const Ctx& c, int first, double t) {
   const double* q = c.poly + first;
-  return fma(fma(fma(q[3 * kPolyStride], t, q[2 * kPolyStride]), t, q[kPolyStride]), t, q[0]);
+  const double v = 1.0 - t;
+  const double lo = fma(q[0], v, q[kPolyStride] * t), hi = fma(q[3 * kPolyStride], t, q[2 * kPolyStride] * v);
+  return fma(lo * v, v, (hi * t) * t);
 }
 
 // ---- spline-coefficient gradient numerators ------------------------------------------------------

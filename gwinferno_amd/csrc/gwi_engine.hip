@@ -19,6 +19,7 @@
 #include "gwi_jit.h"
 #include "gwi_sampler_queue.h"
 #include "gwi_plan.h"
+#include "gwi_probe.h"
 
 #include <hip/hip_ext.h>
 
@@ -2887,6 +2888,31 @@ gwi_status gwi_hbm_bandwidth(int32_t device, int64_t n_doubles, int32_t iters, d
   if (!ok || hipGetLastError() != hipSuccess) return GWI_ERR_HIP;
   *read_gbs = 16.0 * (double)n2 / ((double)best_r * 1e-3) / 1e9;
   *triad_gbs = 48.0 * (double)n2 / ((double)best_t * 1e-3) / 1e9;
+  return GWI_OK;
+}
+
+gwi_status gwi_math_probe(int32_t device, int32_t op, int64_t n, const double* a, const double* b, double* out, int32_t* iout) {
+  namespace P = gwi::probe;
+  if (!a || !b || !out || !iout || n < 0 || op < GWI_PROBE_EXP || op > GWI_PROBE_BINADES_OF) return GWI_ERR_INVALID;
+  if (n > ((int64_t)1 << 24)) return GWI_ERR_INVALID;  // a testing aid: 16 Mi lanes at the most
+  DeviceScope scope;
+  const gwi_status st = scope.select(device);
+  if (st != GWI_OK) return st;
+  if (n == 0) return GWI_OK;
+  LaunchScratch sc("gwi_math_probe");
+  if (!sc.open()) return GWI_ERR_HIP;
+  const size_t na = (size_t)n * (size_t)P::a_stride(op), nb = (size_t)n * (size_t)P::b_stride(op);
+  double *d_a = sc.alloc<double>(na), *d_b = sc.alloc<double>(nb), *d_out = sc.alloc<double>((size_t)n * P::kOutDoubles);
+  int* d_iout = sc.alloc<int>((size_t)n);
+  if (!d_a || !d_b || !d_out || !d_iout) return GWI_ERR_HIP;
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_a, a, sizeof(double) * na, hipMemcpyHostToDevice, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(d_b, b, sizeof(double) * nb, hipMemcpyHostToDevice, sc.stream));
+  const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(P::math_probe_kernel, dim3(blocks), dim3(kBlock), 0, sc.stream, (int)op, (long long)n, (const double*)d_a, (const double*)d_b, d_out, d_iout);
+  GWI_SCRATCH_HIP(hipGetLastError());
+  GWI_SCRATCH_HIP(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n * P::kOutDoubles, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipMemcpyAsync(iout, d_iout, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, sc.stream));
+  GWI_SCRATCH_HIP(hipStreamSynchronize(sc.stream));
   return GWI_OK;
 }
 

@@ -1013,6 +1013,37 @@ gwi_status gwi_pin_thread_to_device(int32_t device);
  * counterpart (a measurement aid). */
 gwi_status gwi_hbm_bandwidth(int32_t device, int64_t n_doubles, int32_t iters, double* read_gbs, double* triad_gbs);
 
+/* The device maths primitives of the scan kernels, called on their own: one launch applies primitive `op` to n lanes of
+ * caller-supplied arguments (gwinferno_amd/csrc/gwi_probe.h holds the table: what a[] and b[] carry and what comes back per op).
+ * No reference counterpart (a testing aid: tests/test_gpu_math_probe.py holds every primitive to a 50-digit reference).
+ *   a     per lane: 1 double (8 for GWI_PROBE_WAVE_SUM8: the eight values of the lane)
+ *   b     per lane: 1 double -- the shift of fast_exp_shift, the weight of cubic_taps_weighted, the spline coefficient of
+ *         GWI_PROBE_SPLINE_VALUE (lanes 4g .. 4g + 3 evaluate the cubic of b[4g .. 4g + 3], each at its own t = a[i]) --, or 3 for
+ *         GWI_PROBE_LOCATE_TERM / _X / GWI_PROBE_LOCATE: lo, inv_dx, n_basis as doubles; read only by these ops, never NULL
+ *   out   4 doubles per lane: the four taps; otherwise the result in slot 0 and zeros.  The wave reductions store what each of
+ *         the 64 lanes of a wave received (lanes past n enter with the reduction's identity)
+ *   iout  1 int per lane: k of the locate family, binades_of; otherwise 0
+ * GWI_ERR_INVALID for a NULL pointer, n < 0 or an unknown op, with nothing written; n == 0 is a successful no-op. */
+enum {
+  GWI_PROBE_EXP = 1,
+  GWI_PROBE_EXP_SHIFT = 2,
+  GWI_PROBE_EXPM1 = 3,
+  GWI_PROBE_RCP = 4,
+  GWI_PROBE_CUBIC_TAPS = 5,
+  GWI_PROBE_CUBIC_TAPS_WEIGHTED = 6,
+  GWI_PROBE_SPLINE_VALUE = 7, /* spline_poly into LDS, then spline_value */
+  GWI_PROBE_LOCATE_KNOT = 8,
+  GWI_PROBE_LOCATE_TERM = 9,
+  GWI_PROBE_LOCATE_X = 10,
+  GWI_PROBE_LOCATE = 11,
+  GWI_PROBE_WAVE_SUM = 12,
+  GWI_PROBE_WAVE_MAX = 13,
+  GWI_PROBE_WAVE_MAX_COARSE = 14,
+  GWI_PROBE_WAVE_SUM8 = 15,
+  GWI_PROBE_BINADES_OF = 16
+};
+gwi_status gwi_math_probe(int32_t device, int32_t op, int64_t n, const double* a, const double* b, double* out, int32_t* iout);
+
 /* How plain evaluations are dispatched: "aql: active" (AQL packets into a user-mode queue of the engine's own,
  * gwinferno_amd/csrc/gwi_aql.h: 0.4 us of host time per launch instead of 3.5) or the reason the HIP stream is used. */
 const char* gwi_dispatch_info(gwi_handle h);

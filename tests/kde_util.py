@@ -73,7 +73,7 @@ def bound_1d(W, x, grid_c, h, bounds=None):
     term is off by at most
       * the summation of n non-negative terms in any order, the product p e, the normalisation and its square root:
         (n_live + 8) 2^-52 relative to the whole sum (with reflection the sum has 3 n_live terms);
-      * fast_exp's stated 1.6e-14 + 2.3e-17 |a| / ln 2 on the device and one ulp of NumPy's exp on the host;
+      * fast_exp's 1.6e-14 + 2.3e-17 |a| / ln 2 on the device (held by tests/test_gpu_math_probe.py) and one ulp of NumPy's exp on the host;
       * the rounding of the argument: d = g - x, d^2 and the product with -1/2h^2 round once each on either side (3 * 2^-52), and
         h^2 differs by moment_eps: exp(a (1 + delta)) = exp(a) (1 + a delta), so |a| (3 * 2^-52 + moment_eps) relative;
       * norm = 1 / (mass sqrt(2 pi h^2)) differs by moment_eps / 2 (within the flat term below).
