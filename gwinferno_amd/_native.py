@@ -251,6 +251,9 @@ EXPORTED_SYMBOLS = [
     "gwi_set_rankcorr_columns",
     "gwi_point_rank_correlations",
     "gwi_point_rankcorr_times",
+    "gwi_set_tail_sizes",
+    "gwi_point_tails",
+    "gwi_point_tail_times",
     "gwi_marginal_weights_reset",
     "gwi_marginal_weights_add",
     "gwi_marginal_weights_add_weighted",
@@ -466,6 +469,14 @@ def load_library():
         lib.gwi_point_rank_correlations.argtypes = [vp, _DP, C.c_int32, _DP, _I32P]
         lib.gwi_point_rankcorr_times.restype = None
         lib.gwi_point_rankcorr_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_point_tails"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_set_tail_sizes.restype = C.c_int32
+        lib.gwi_set_tail_sizes.argtypes = [vp, C.c_int32, C.c_int32]
+        lib.gwi_point_tails.restype = C.c_int32
+        lib.gwi_point_tails.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _I32P]
+        lib.gwi_point_tail_times.restype = None
+        lib.gwi_point_tail_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

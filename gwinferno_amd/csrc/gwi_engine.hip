@@ -554,6 +554,17 @@ struct RankcorrBuffers {
   DeviceBuffer<double> d_tiles, d_prefix, d_partial, d_stage;
   int cols = 0;
 };
+// ... and of the per-point tails (gwi_tail.h): the tail sizes of gwi_set_tail_sizes, and the entry's own workspace -- the segments'
+// prefixes [n_ev + 1] and the tiles' largest keys below [n_tiles] (d_keys), the tiles' histograms, then candidates [n_tiles][2048], the
+// segments' ranks [n_ev + 1][2] and the tiles' counts [n_tiles][4] (d_ints), the tiles' body sums [n_tiles] and the staged rows
+// [64][n_ev m_pe + m_inj] and [64][n_ev + 1][4] of either kind (grown on demand, kept).  A pointer for ConditionalBuffers' reason,
+// released with it.
+struct TailBuffers {
+  DeviceBuffer<unsigned long long> d_keys;
+  DeviceBuffer<int> d_hist, d_ints, d_counts;
+  DeviceBuffer<double> d_body, d_tail, d_stats;
+  int m_pe = 0, m_inj = 0;
+};
 }  // namespace
 
 struct gwi_engine {
@@ -691,6 +702,7 @@ struct gwi_engine {
   MomentBuffers moment;       // gwi_point_moments (freed with `post`)
   ConditionalBuffers* cond = nullptr;  // gwi_point_conditionals (release_moment_and_conditional_buffers, with `post`)
   RankcorrBuffers* rankcorr = nullptr;  // gwi_set_rankcorr_columns / gwi_point_rank_correlations (released with `cond`)
+  TailBuffers* tail = nullptr;          // gwi_set_tail_sizes / gwi_point_tails (released with `cond`)
 };
 
 namespace {
@@ -4408,6 +4420,8 @@ __attribute__((noinline)) void release_moment_and_conditional_buffers(gwi_handle
   h->cond = nullptr;
   delete h->rankcorr;
   h->rankcorr = nullptr;
+  delete h->tail;
+  h->tail = nullptr;
 }
 }  // namespace
 extern "C" {
@@ -4627,6 +4641,91 @@ gwi_status gwi_point_rank_correlations(gwi_handle h, const double* thetas, int32
 }
 
 void gwi_point_rankcorr_times(double* logw_ms, double* prefix_ms, double* cov_ms, int32_t* launches) { g_point_rankcorr_times.report(logw_ms, prefix_ms, cov_ms, launches); }
+
+// ---- per-point tails: the m largest live log-weights of every segment, the cut-off below them and the rest's sum (gwi_tail.h) ----------
+// (the header is included here for gwi_cond.h's reason)
+}  // extern "C"
+#include "gwi_tail.h"
+extern "C" {
+static thread_local StageTimes g_point_tail_times;
+
+gwi_status gwi_set_tail_sizes(gwi_handle h, int32_t m_pe, int32_t m_inj) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace T = gwi::tail;
+  const char* who = "gwi_set_tail_sizes";
+  gwi_status st = post_preflight(h, who, "keep a tail on", "the injection tail needs", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_point_moments: a shard says that it is one)
+  std::string why;
+  const auto bad = [&](const char* name, int m, long long n, const char* n_name) -> std::string {
+    if (m < 1 || m > T::kMaxTail) return std::string(name) + " = " + std::to_string(m) + " is not in 1 ... " + std::to_string(T::kMaxTail);
+    if (m >= n) return std::string(name) + " = " + std::to_string(m) + " is not below " + n_name + " = " + std::to_string(n);
+    return "";
+  };
+  why = bad("m_pe", m_pe, h->n_pe, "n_pe");
+  if (why.empty()) why = bad("m_inj", m_inj, h->n_inj, "n_inj");
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, std::string(who) + ": " + why);
+  if (!h->tail) h->tail = new (std::nothrow) TailBuffers();
+  if (!h->tail) return fail(h, GWI_ERR_INVALID, std::string(who) + ": out of host memory");
+  h->tail->m_pe = m_pe;
+  h->tail->m_inj = m_inj;
+  return GWI_OK;
+}
+
+gwi_status gwi_point_tails(gwi_handle h, const double* thetas, int32_t k, double* tail, double* stats, int32_t* counts) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_tails";
+  g_point_tail_times = StageTimes();
+  gwi_status st = post_preflight(h, who, "select on", "the injection tail needs", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_point_moments)
+  const bool set = h->tail && h->tail->m_pe > 0;
+  const std::string why = bad_point_args(h, set ? "" : "no tail sizes are set (gwi_set_tail_sizes)", thetas, k, {{"tail", tail}, {"stats", stats}, {"counts", counts}});
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, std::string(who) + ": " + why);
+  namespace T = gwi::tail;
+  TailBuffers& tb = *h->tail;
+  T::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);
+  if (st != GWI_OK) return st;
+  const size_t n_segs = (size_t)(h->n_ev + 1), tiles = (size_t)n_tiles, row = (size_t)h->n_ev * (size_t)tb.m_pe + (size_t)tb.m_inj;
+  GWI_HIP(tb.d_keys.reserve(n_segs + tiles));
+  GWI_HIP(tb.d_hist.reserve(tiles * T::kHistStride + 1));
+  GWI_HIP(tb.d_ints.reserve(2 * n_segs + tiles * T::kTileInts));
+  GWI_HIP(tb.d_body.reserve(tiles + 1));
+  GWI_HIP(tb.d_tail.reserve((size_t)kStagePoints * row));
+  GWI_HIP(tb.d_stats.reserve((size_t)kStagePoints * n_segs * T::kStats));
+  GWI_HIP(tb.d_counts.reserve((size_t)kStagePoints * n_segs * T::kCounts));
+  a.prefix = tb.d_keys;
+  a.tile_below = tb.d_keys.ptr + n_segs;
+  a.hist = tb.d_hist;
+  a.rank = tb.d_ints;
+  a.tile_counts = tb.d_ints.ptr + 2 * n_segs;
+  a.tile_body = tb.d_body;
+  a.m_pe = tb.m_pe;
+  a.m_inj = tb.m_inj;
+  StagedRows rows(h, k);  // n_ev m_pe + m_inj + 4 (n_ev + 1) doubles and 4 (n_ev + 1) ints per point
+  rows.add(tail, tb.d_tail.ptr, row);
+  rows.add(stats, tb.d_stats.ptr, n_segs * T::kStats);
+  rows.add(counts, tb.d_counts.ptr, n_segs * T::kCounts);
+  const auto selection = [&](int) {  // the same launches whatever the data are
+    for (a.pass = 0; a.pass < T::kPasses; ++a.pass) {
+      if (n_tiles) hipLaunchKernelGGL(T::tail_hist_kernel, dim3((unsigned)n_tiles), dim3(T::kBlock), 0, h->stream, a);
+      hipLaunchKernelGGL(T::tail_pick_kernel, dim3((unsigned)n_segs), dim3(T::kBlock), 0, h->stream, a);
+    }
+  };
+  const auto collection = [&](int p) {  // into the point's slot of the stage
+    a.tail = rows.slot<double>(0, p);
+    a.stats = rows.slot<double>(1, p);
+    a.counts = rows.slot<int>(2, p);
+    if (n_tiles) hipLaunchKernelGGL(T::tail_collect_kernel, dim3((unsigned)n_tiles), dim3(T::kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(T::tail_merge_kernel, dim3((unsigned)n_segs), dim3(T::kBlock), 0, h->stream, a);
+  };
+  return per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_tail_times, 2, 2 + 2 * T::kPasses + 2, selection, collection, [&](int p) { return rows.after(p); });
+}
+
+void gwi_point_tail_times(double* logw_ms, double* select_ms, double* collect_ms, int32_t* launches) { g_point_tail_times.report(logw_ms, select_ms, collect_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

@@ -40,7 +40,11 @@ among the injections: :func:`rank_codes` states the theta-independent ranks and 
 ``gwi_point_rank_correlations`` (gwinferno_amd/csrc/gwi_rankcorr.h) ranks the members of a set among themselves -- the pooled PE samples,
 the injections -- under the point's weights and returns the second moments of the centred mid-ranks, of which Spearman's correlation
 is a ratio: :func:`rankcorr_codes` states the theta-independent codes, :func:`rankcorr_set` one set and
-:func:`point_rank_correlations_reference` one point."""
+:func:`point_rank_correlations_reference` one point.
+
+``gwi_point_tails`` (gwinferno_amd/csrc/gwi_tail.h) selects, per point and segment, the largest live log-weights and what is needed of
+the rest: :func:`tails_segment` and :func:`point_tails_reference` state them, :func:`tail_cutoff_and_rest` what the host derives, and
+:func:`pareto_tail_fit` fits the tail under :func:`pareto_smooth`'s conventions."""
 import bisect
 import itertools
 import math
@@ -923,21 +927,31 @@ def pareto_smooth(log_ratios):
         order = np.argsort(col, kind="stable")
         tail_at = order[k_pts - m_tail :]  # ascending
         cutoff = col[order[k_pts - m_tail - 1]]
-        tail = col[tail_at]
-        if not tail[-1] > tail[0]:
+        kh, new = _smooth_shifted_tail(col[tail_at], cutoff)
+        if new is None:
             continue
-        x = np.exp(tail) - math.exp(cutoff)
-        if not x[int(m_tail / 4.0 + 0.5) - 1] > 0.0:  # (the lowest quarter of the tail ties with the cutoff: the fit has no scale)
-            continue
-        k_fit, sigma = _gpd_fit(x)
-        kh = (m_tail * k_fit + 5.0) / (m_tail + 10.0)
         khat[s] = kh
-        p = (np.arange(1, m_tail + 1, dtype=np.float64) - 0.5) / m_tail
-        with np.errstate(divide="ignore", invalid="ignore"):
-            q = sigma * np.expm1(-kh * np.log1p(-p)) / kh if kh != 0.0 else -sigma * np.log1p(-p)
-            new = np.log(math.exp(cutoff) + q)
-        lr[tail_at, s] = np.minimum(new, 0.0)
+        lr[tail_at, s] = new
     return lr, khat
+
+
+def _smooth_shifted_tail(tail, cutoff):
+    """The fit and the replacement of :func:`pareto_smooth` for one ascending tail ``(M,)`` and its cut-off, both already shifted so
+    that the largest value the tail may take is 0: ``(khat, new (M,))``, or ``(inf, None)`` where nothing is smoothed (``M < 5``, a
+    constant tail, or a lowest quarter that ties with the cut-off)."""
+    m_tail = tail.size
+    if m_tail < 5 or not tail[-1] > tail[0]:
+        return np.inf, None
+    x = np.exp(tail) - math.exp(cutoff)
+    if not x[int(m_tail / 4.0 + 0.5) - 1] > 0.0:  # (the lowest quarter of the tail ties with the cutoff: the fit has no scale)
+        return np.inf, None
+    k_fit, sigma = _gpd_fit(x)
+    kh = (m_tail * k_fit + 5.0) / (m_tail + 10.0)
+    p = (np.arange(1, m_tail + 1, dtype=np.float64) - 0.5) / m_tail
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = sigma * np.expm1(-kh * np.log1p(-p)) / kh if kh != 0.0 else -sigma * np.log1p(-p)
+        new = np.log(math.exp(cutoff) + q)
+    return kh, np.minimum(new, 0.0)
 
 
 def _gpd_fit(x):
@@ -986,3 +1000,83 @@ def pareto_smoothed_summary(log_l_event):
         neff[e] = s1 * s1 / math.fsum((ve * ve).tolist())
     out.update(point_weights=v, elpd_loo=elpd, neff_points=neff, pareto_k=khat)
     return out
+
+
+MAX_TAIL = 4096  # the longest tail of gwi_point_tails (gwi_tail.h: kMaxTail)
+
+
+def psis_tail_size(n):
+    """The tail size of Pareto smoothed importance sampling for ``n`` samples: ``min(floor(n / 5), ceil(3 sqrt(n)))``, as
+    :func:`pareto_smooth` takes it."""
+    n = int(n)
+    return min(n // 5, int(math.ceil(3.0 * math.sqrt(n))))
+
+
+def tails_segment(logw, mask, m):
+    """``(tail (m,), stats (4,), counts (4,) int32)`` of ONE segment of ``gwi_point_tails``.  The live values are the finite
+    ``logw`` the mask leaves.  ``tail``: the ``m`` largest of them in ascending order (``np.sort``), ``-inf`` in front where fewer are
+    live.  With ``v* = tail[0]``: ``counts = (n_live, #(l > v*), #(l == v*), dead)`` and ``stats = (max, S, body, below_max)``: the
+    largest live value, ``S = fsum w`` of the shifted weights of :func:`draw_weights`, ``body = fsum`` of those of the values below
+    ``v*`` and the largest live value below ``v*`` (``-inf``: none).  A segment whose ``S`` is 0 or not finite is dead: an all ``-inf``
+    tail, zero counts, NaN ``body``."""
+    lw = np.asarray(logw, dtype=np.float64).ravel()
+    live = np.isfinite(lw)
+    if mask is not None:
+        live &= np.asarray(mask).ravel().astype(bool)
+    m = int(m)
+    w = draw_weights(lw, mask)
+    total = math.fsum(w.tolist())
+    vals = lw[live]
+    top = float(vals.max()) if vals.size else -np.inf
+    tail = np.full(m, -np.inf)
+    if not (total > 0.0 and np.isfinite(total)):
+        return tail, np.array([top, total, np.nan, -np.inf]), np.array([0, 0, 0, 1], dtype=np.int32)
+    take = min(m, vals.size)
+    tail[m - take:] = np.sort(vals)[vals.size - take:]
+    v_star = tail[0]
+    below = live & (lw < v_star)
+    stats = np.array([top, total, math.fsum(w[below].tolist()), float(lw[below].max()) if below.any() else -np.inf])
+    return tail, stats, np.array([vals.size, np.count_nonzero(vals > v_star), np.count_nonzero(vals == v_star), 0], dtype=np.int32)
+
+
+def point_tails_reference(logw_pe, logw_inj, pe_mask, inj_mask, m_pe, m_inj):
+    """One hyper-parameter point of ``gwi_point_tails``: ``logw_pe (n_ev, n_pe)``, ``logw_inj (n_inj,)`` -- what
+    ``Engine.log_weights`` returns --, the masks of ``gwi_set_draw_mask`` (or None) and the two tail sizes -> ``(tail_pe (n_ev, m_pe),
+    tail_inj (m_inj,), stats (n_ev + 1, 4), counts (n_ev + 1, 4) int32)``, the injection set last: per segment :func:`tails_segment`."""
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    n_ev, n_pe = logw_pe.shape
+    m_pe, m_inj = int(m_pe), int(m_inj)
+    if not (1 <= m_pe <= MAX_TAIL and 1 <= m_inj <= MAX_TAIL) or m_pe >= n_pe or m_inj >= np.asarray(logw_inj).size:
+        raise ValueError(f"a tail size is in 1 ... {MAX_TAIL} and below its segment's length")
+    pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(n_ev, n_pe)
+    tail_pe, stats, counts = np.empty((n_ev, m_pe)), np.empty((n_ev + 1, 4)), np.empty((n_ev + 1, 4), dtype=np.int32)
+    for ev in range(n_ev):
+        tail_pe[ev], stats[ev], counts[ev] = tails_segment(logw_pe[ev], None if pe_mask is None else pe_mask[ev], m_pe)
+    tail_inj, stats[n_ev], counts[n_ev] = tails_segment(logw_inj, inj_mask, m_inj)
+    return tail_pe, tail_inj, stats, counts
+
+
+def tail_cutoff_and_rest(tail, stats, counts):
+    """What the host derives from ``gwi_point_tails``' rows, for any leading shape: ``tail (..., m)``, ``stats (..., 4)``, ``counts (...,
+    4)`` -> ``(cutoff (...), rest (...))``.  ``cutoff`` is the ``(m + 1)``-th largest live value: ``v* = tail[..., 0]`` where ``n_gt +
+    n_eq > m`` (ties of ``v*`` remain outside the tail), else ``below_max``.  ``rest`` is the sum of ``exp(l - max)`` over everything
+    outside the tail, ``body + (n_gt + n_eq - m) exp(v* - max)``: nothing is subtracted.  NaN ``rest`` for a dead segment."""
+    tail, stats, counts = np.asarray(tail, dtype=np.float64), np.asarray(stats, dtype=np.float64), np.asarray(counts)
+    m, v_star = tail.shape[-1], tail[..., 0]
+    extra = np.maximum(counts[..., 1].astype(np.int64) + counts[..., 2] - m, 0)
+    with np.errstate(invalid="ignore"):
+        ties = np.where(extra > 0, extra * np.exp(v_star - stats[..., 0]), 0.0)
+    return np.where(extra > 0, v_star, stats[..., 3]), stats[..., 2] + ties
+
+
+def pareto_tail_fit(tail, cutoff, top):
+    """The Pareto fit of ONE ascending tail ``(m,)`` of log-weights with its cut-off (the largest value outside the tail) and the value
+    ``top`` to shift by (the segment's maximum): ``(khat, smoothed (m,))`` under exactly :func:`pareto_smooth`'s conventions -- the
+    generalised Pareto distribution fitted to ``exp(tail - top) - exp(cutoff - top)``, the regularised ``khat``, the quantile
+    replacement truncated at 0 -- with ``smoothed`` RELATIVE TO ``top``, as ``pareto_smooth``'s output is relative to the column's
+    maximum: for a column's own tail, cut-off and maximum the bits are that function's.  ``khat`` is inf and ``smoothed = tail - top``
+    when ``m < 5``, the tail is constant or its lowest quarter ties with the cut-off."""
+    tail = np.asarray(tail, dtype=np.float64).ravel()
+    shifted = tail - float(top)
+    kh, new = _smooth_shifted_tail(shifted, float(cutoff) - float(top))
+    return float(kh), shifted if new is None else new

@@ -1,5 +1,5 @@
 """The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
-injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments, conditional moments and rank correlations, marginal weights and their
+injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments, conditional moments, rank correlations and tails, marginal weights and their
 quantiles and kernel density estimates.
 Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
 """
@@ -363,6 +363,38 @@ class PostprocessMixin:
         total, mean_rank, cov = rankcorr_matrix(raw, self._rankcorr_shape[0])
         n_ev = self.n_ev
         return total, mean_rank, cov, np.ascontiguousarray(dead[:, : n_ev + 1]), np.ascontiguousarray(dead[:, [n_ev + 1, n_ev]])
+
+    def set_tail_sizes(self, m_pe=None, m_inj=None):
+        """The tail sizes of :meth:`point_tails` (``gwi_set_tail_sizes``): ``m_pe`` for every event's segment and ``m_inj`` for
+        the injection set, ``1 <= m <= 4096``, ``m_pe < n_pe`` and ``m_inj < n_inj``.  ``None`` means the rule of Pareto smoothed
+        importance sampling on the segment's length, ``min(floor(n / 5), ceil(3 sqrt(n)))``, capped at 4096
+        (:func:`gwinferno_amd.draws.psis_tail_size`).  Nothing is uploaded; a second call replaces the sizes.  Not available on an engine
+        that holds a shard (``world > 1``)."""
+        from .draws import MAX_TAIL, psis_tail_size
+
+        self._whole_catalog("set_tail_sizes", "the injection tail needs")
+        m_pe = min(psis_tail_size(self.n_pe), MAX_TAIL) if m_pe is None else int(m_pe)
+        m_inj = min(psis_tail_size(self.n_inj), MAX_TAIL) if m_inj is None else int(m_inj)
+        self._tail_shape = None
+        self._check(self.lib.gwi_set_tail_sizes(self.handle, m_pe, m_inj))
+        self._tail_shape = (m_pe, m_inj)
+
+    def point_tails(self, thetas):
+        """Per-point tails of the inner importance sums, on the device (``gwi_point_tails``; semantics:
+        :func:`gwinferno_amd.draws.point_tails_reference`).  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.  Returns
+        ``(tail_pe (k, n_ev, m_pe), tail_inj (k, m_inj), stats (k, n_ev + 1, 4), counts (k, n_ev + 1, 4) int32)``, the injection set last:
+        per segment the ``m`` largest live log-weights in ascending order with the bits :meth:`log_weights` returns (``-inf`` in front
+        where fewer are live), ``stats = (max, S, body, below_max)`` and ``counts = (n_live, n_gt, n_eq, dead)`` about ``v* = tail[0]``:
+        the live samples, those above and at ``v*``, the largest live value below it and ``body``, the sum of ``exp(l - max)`` over the
+        values below it.  The masks of :meth:`set_draw_mask` apply.  :func:`gwinferno_amd.draws.tail_cutoff_and_rest` gives the cut-off
+        of the Pareto fit and the sum outside the tail, :func:`gwinferno_amd.draws.pareto_tail_fit` the fit.  A dead segment has an all
+        ``-inf`` tail, zero counts and NaN ``body``.  ``n_ev m_pe + m_inj + 4 (n_ev + 1)`` doubles come back per point; the points may be
+        split over calls without changing a bit.  Not available on an engine that holds a shard (``world > 1``)."""
+        row, stats, counts = self._per_point("point_tails", "the injection tail needs", "_tail_shape", "tail sizes are set (set_tail_sizes)", (np.float64, np.float64, np.int32),
+                                             lambda k, s: ((k, self.n_ev * s[0] + s[1]), (k, self.n_ev + 1, 4), (k, self.n_ev + 1, 4)), thetas)
+        m_pe, m_inj = self._tail_shape
+        cut = self.n_ev * m_pe
+        return np.ascontiguousarray(row[:, :cut]).reshape(-1, self.n_ev, m_pe), np.ascontiguousarray(row[:, cut:]), stats, counts
 
     def marginal_weights_reset(self):
         """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""

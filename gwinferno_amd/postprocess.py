@@ -1472,3 +1472,120 @@ def event_conditional_moments(eng, thetas, x, y, edges, *, pe_values, inj_values
         if "pareto_k" in loo:
             out["pareto_k"] = loo["pareto_k"]
     return out
+
+
+def _tail_points(eng, thetas, m_pe, m_inj, masks, backend):
+    """``(tail_pe (K, n_ev, m_pe), tail_inj (K, m_inj), stats (K, n_ev + 1, 4), counts (K, n_ev + 1, 4))`` of the points on either backend
+    (DESIGN 8m)."""
+    from . import draws as D
+
+    if backend == "device":
+        if masks[0] is not None:
+            eng.set_draw_mask(*masks)
+        eng.set_tail_sizes(m_pe, m_inj)
+        return eng.point_tails(thetas)
+    k, n_ev = thetas.shape[0], eng.n_ev
+    tail_pe, tail_inj = np.empty((k, n_ev, m_pe)), np.empty((k, m_inj))
+    stats, counts = np.empty((k, n_ev + 1, 4)), np.empty((k, n_ev + 1, 4), dtype=np.int32)
+    for i, th in enumerate(thetas):
+        lw_pe, lw_inj = eng.log_weights(th)
+        tail_pe[i], tail_inj[i], stats[i], counts[i] = D.point_tails_reference(lw_pe, lw_inj, masks[0], masks[1], m_pe, m_inj)
+    return tail_pe, tail_inj, stats, counts
+
+
+def importance_sum_diagnostics(eng, thetas, m_pe=None, m_inj=None, point_weights=None, backend="device", pedata=None, injdata=None, m1min=None, m2min=None, mmax=None):
+    """Can the inner importance sums be trusted?    Every number the engine returns is a self-normalised sum of ``w = p(x |
+    theta) / prior`` over an event's PE samples or over the found injections.  ``log_nEffs`` and the variance site are made of the same
+    weights and stay finite when a handful of samples carry the sum; the Pareto shape ``khat`` of the largest weights (Vehtari et al.,
+    *Pareto smoothed importance sampling*) says when that is so: below 0.5 good, up to 0.7 usable, above it unreliable.  Per
+    hyper-posterior point and segment -- the events, then the injection set -- ``eng.point_tails`` returns the ``m`` largest live
+    log-weights and the sum of the rest, about 0.1 MB per point where the weights themselves are megabytes and never leave HBM; the fit
+    (:func:`gwinferno_amd.draws.pareto_tail_fit`) is made here.
+
+    ``m_pe`` / ``m_inj``: the tail sizes, ``None`` for ``min(floor(n / 5), ceil(3 sqrt(n)))`` capped at 4096.  ``point_weights`` -- ``(K,)``
+    or ``(K, n_ev + 1)``, finite, non-negative, not all 0 in a column; default equal -- weight the points in the shares; they are applied
+    here and never go to the device.  ``pedata``, ``injdata``, ``m1min``, ``m2min``, ``mmax``: the mass cuts of
+    :func:`posterior_predictive_draws` as masks; without them the mask the engine holds stays (device backend).  The device backend
+    replaces the engine's tail sizes.  ``backend="host"`` runs the NumPy statement
+    (:func:`gwinferno_amd.draws.point_tails_reference`) on ``eng.log_weights``: the statement the kernels are tested against, not a
+    fall-back.
+
+    A (point, segment) is SKIPPED -- counted, never fitted -- when the segment is dead there or has ``n_live <= m``: nothing lies outside
+    the tail.  Returns a dict.  Per point and segment, ``(K, n_ev + 1)``: ``pareto_k`` (NaN where skipped; inf where the fit has nothing
+    to work on: ``m < 5``, a constant tail, a lowest quarter that ties with the cut-off); ``n_live``; ``skipped``; ``log_sum_raw = max +
+    log S``; ``log_sum_psis = max + log(rest + sum exp(smoothed tail))`` with the tail's weights replaced by the fitted quantiles and
+    ``rest`` the sum outside the tail (:func:`gwinferno_amd.draws.tail_cutoff_and_rest`); ``log_sum_diff``, their difference; ``neff``, a
+    LOWER bound of the engine's ``n_eff = S^2 / sum w^2`` from what came back: the tail's and the ties' squares exactly, the samples below
+    the cut-off counted as ``w_below body >= sum w^2`` of them (exact for ``n_live <= m``; with a heavy tail, where it matters, the tail's
+    squares dominate); on the host backend also ``neff_exact``.  NaN for a dead segment.  Per segment over the points, ``(n_ev + 1,)``:
+    ``share_above_0.5`` and ``share_above_0.7``, the weighted share of the fitted points with ``khat`` above the level (NaN: none
+    fitted); ``worst_point`` (-1: none fitted) and ``worst_k``; ``n_skipped``.  Also ``m_pe``, ``m_inj``, ``n_points`` and the raw
+    ``tail_pe``, ``tail_inj``, ``stats``, ``counts``."""
+    import math
+
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k, n_ev = thetas.shape[0], eng.n_ev
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    m_pe = min(D.psis_tail_size(eng.n_pe), D.MAX_TAIL) if m_pe is None else int(m_pe)
+    m_inj = min(D.psis_tail_size(eng.n_inj), D.MAX_TAIL) if m_inj is None else int(m_inj)
+    if point_weights is None:
+        v = np.ones((k, n_ev + 1))
+    else:
+        v = np.asarray(point_weights, dtype=np.float64)
+        if v.shape == (k,):
+            v = np.repeat(v[:, None], n_ev + 1, axis=1)
+        if v.shape != (k, n_ev + 1) or not np.all(np.isfinite(v)) or np.any(v < 0.0) or not np.all(np.any(v > 0.0, axis=0)):
+            raise ValueError(f"point_weights are ({k},) or ({k}, {n_ev + 1}) finite non-negative numbers, not all 0 in a column")
+    masks = _mass_cut_masks(pedata, injdata, m1min, m2min, mmax)
+    tail_pe, tail_inj, stats, counts = _tail_points(eng, thetas, m_pe, m_inj, masks, backend)
+    shape = (k, n_ev + 1)
+    khat, psis, neff = np.full(shape, np.nan), np.full(shape, np.nan), np.full(shape, np.nan)
+    dead = counts[..., 3] != 0
+    n_live = counts[..., 0].astype(np.int64)
+    sizes = np.array([m_pe] * n_ev + [m_inj])
+    skipped = dead | (n_live <= sizes[None, :])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        raw = np.where(dead, np.nan, stats[..., 0] + np.log(stats[..., 1]))
+    for p in range(k):
+        for s in range(n_ev + 1):
+            if dead[p, s]:
+                continue
+            tail = tail_pe[p, s] if s < n_ev else tail_inj[p]
+            top, total, body, below_max = stats[p, s]
+            cutoff, rest = D.tail_cutoff_and_rest(tail, stats[p, s], counts[p, s])
+            w_tail = np.exp(tail - top)
+            extra = max(int(counts[p, s, 1]) + int(counts[p, s, 2]) - tail.size, 0)
+            squares = math.fsum((w_tail * w_tail).tolist()) + extra * w_tail[0] * w_tail[0] + (math.exp(below_max - top) * body if body > 0.0 else 0.0)
+            neff[p, s] = total * total / squares
+            if skipped[p, s]:
+                continue
+            khat[p, s], smoothed = D.pareto_tail_fit(tail, float(cutoff), top)
+            psis[p, s] = top + math.log(float(rest) + math.fsum(np.exp(smoothed).tolist()))
+    fitted = ~skipped
+    share, worst_point, worst_k = {}, np.full(n_ev + 1, -1, dtype=np.int64), np.full(n_ev + 1, np.nan)
+    den = (v * fitted).sum(axis=0)
+    for level in (0.5, 0.7):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share[level] = (v * (fitted & (np.where(fitted, khat, 0.0) > level))).sum(axis=0) / den
+    for s in range(n_ev + 1):
+        if fitted[:, s].any():
+            worst_point[s] = int(np.argmax(np.where(fitted[:, s], khat[:, s], -np.inf)))
+            worst_k[s] = khat[worst_point[s], s]
+    out = {"pareto_k": khat, "n_live": n_live, "skipped": skipped, "neff": neff, "log_sum_raw": raw, "log_sum_psis": psis, "log_sum_diff": psis - raw,
+           "share_above_0.5": share[0.5], "share_above_0.7": share[0.7], "worst_point": worst_point, "worst_k": worst_k, "n_skipped": skipped.sum(axis=0).astype(np.int64),
+           "m_pe": m_pe, "m_inj": m_inj, "n_points": k, "tail_pe": tail_pe, "tail_inj": tail_inj, "stats": stats, "counts": counts}
+    if backend == "host":
+        exact = np.full(shape, np.nan)
+        for p, th in enumerate(thetas):
+            lw_pe, lw_inj = eng.log_weights(th)
+            for s in range(n_ev + 1):
+                w = D.draw_weights(lw_pe[s], None if masks[0] is None else np.asarray(masks[0]).reshape(n_ev, -1)[s]) if s < n_ev else D.draw_weights(lw_inj, masks[1])
+                if not dead[p, s]:
+                    exact[p, s] = math.fsum(w.tolist()) ** 2 / math.fsum((w * w).tolist())
+        out["neff_exact"] = exact
+    return out

@@ -667,6 +667,42 @@ gwi_status gwi_set_rankcorr_columns(gwi_handle h, int32_t n_cols, const int32_t*
 gwi_status gwi_point_rank_correlations(gwi_handle h, const double* thetas, int32_t k, double* out /* [k][2][1 + C + C(C+1)/2] */, int32_t* dead /* [k][n_ev + 2] */);
 void gwi_point_rankcorr_times(double* logw_ms, double* prefix_ms, double* cov_ms, int32_t* launches);
 
+/* Per-point tails of the inner importance sums on the device: per hyper-parameter point and segment the m largest live log-weights,
+ * what defines the cut-off below them and the sum of everything outside the tail -- all a Pareto fit of the largest weights (Vehtari
+ * et al., Pareto smoothed importance sampling) needs, without the weights leaving HBM (gwinferno_amd/csrc/gwi_tail.h; the NumPy
+ * statement is gwinferno_amd/draws.py: point_tails_reference; the fit is the host's, draws.pareto_tail_fit; the contract is DESIGN 8m).
+ *
+ * Segments (an event's n_pe samples; the injection set, last), the masks, M and S are gwi_draw_indices' and gwi_weighted_histograms'.
+ * A sample is live when it is unmasked and l_j = lw_j + log_const is finite; l_j has the bits gwi_log_weights returns for the sample.
+ *
+ * gwi_set_tail_sizes(): the tail sizes of the events' segments and of the injection set, 1 <= m <= 4096, m_pe < n_pe, m_inj < n_inj.
+ * Nothing is uploaded; a second call replaces the sizes.
+ *
+ * gwi_point_tails(): per point k and segment s with tail size m (the events' tails first, [n_ev][m_pe], then the injection set's):
+ *   tail[m]    the m largest live l_j in ascending order, as the bits of the inputs; values compare as numbers, -0.0 and +0.0 tie and
+ *              which of them appears is unspecified; with fewer than m live samples the live values sit at the top end, -inf in front
+ *   v* = tail[0], the m-th largest
+ *   counts[k][s] = (n_live, n_gt, n_eq, dead): the live samples, those > v*, those == v*, and 1 for a segment whose S is 0 or not finite
+ *   stats[k][s]  = (M, S, body, below_max): below_max the largest live l_j < v* (-inf: none), body = sum over l_j < v* of exp(l_j - M)
+ * The cut-off of the fit, the (m + 1)-th largest, is v* when n_gt + n_eq > m and below_max otherwise, and the sum of exp(l_j - M) over
+ * everything outside the tail is body + (n_gt + n_eq - m) exp(v* - M): no subtraction.  A dead segment has an all -inf tail, zero counts,
+ * below_max = -inf and NaN body.  The selection is an exact radix selection on order-preserving 64-bit keys followed by a sort of the
+ * tail: tail, counts and below_max are the same bits on every call, handle and split of the points over calls; body is a sum of a fixed
+ * shape (four consecutive samples per lane, butterfly, wave order, tile order) and so are its bits.  No floating-point atomics.  k >= 1
+ * is not bound by the batch limit: the points are staged on the device 64 at a time and copied back per chunk; n_ev m_pe + m_inj +
+ * 4 (n_ev + 1) doubles and 4 (n_ev + 1) ints come back per point.  The call changes no state another entry reads.  Not done: the fit on
+ * the device; sharded handles; tails longer than 4096; smoothed weights fed back into the likelihood.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, a tail size out of range or not below the segment's
+ * length, a call before the sizes are set and a host-only handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard, checked first.
+ *
+ * gwi_point_tail_times(): DIAGNOSTIC ONLY, for tools/post_time.py: of the calling thread's last call, summed over its points, the
+ * wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge launches with the twelve
+ * selection launches and of the two collection launches, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_set_tail_sizes(gwi_handle h, int32_t m_pe, int32_t m_inj);
+gwi_status gwi_point_tails(gwi_handle h, const double* thetas, int32_t k, double* tail /* [k][n_ev * m_pe + m_inj] */,
+                           double* stats /* [k][n_ev + 1][4]: max, S, body, below_max */, int32_t* counts /* [k][n_ev + 1][4]: n_live, n_gt, n_eq, dead */);
+void gwi_point_tail_times(double* logw_ms, double* select_ms, double* collect_ms, int32_t* launches); /* diagnostic only */
+
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is
  * gwinferno_amd/draws.py: marginal_weights_reference, weighted_quantiles_reference).

@@ -7,7 +7,7 @@ timed on another build of the engine (the parent commit's), in child processes o
 half after, and this build's median is placed against the span of that build's own calls.  No figure is fixed in advance; what is not
 measured is named as unmeasured.  Writes a Markdown report.
 
-      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals,point_rankcorr} [--configs c2,c5] [--repeats 10]
+      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals,point_rankcorr,point_tails} [--configs c2,c5] [--repeats 10]
                                 [--parent-lib PATH] [--out profiles/<entry>/RESULTS.md]
 
 What differs per entry is one record of ENTRIES: the set-up calls, one_round, the host route, the kernels to list and the row labels."""
@@ -504,6 +504,58 @@ def rankcorr_tail(res):
     return [f"Scratch is {max(r[4] for r in res)} bytes in every kernel listed: the {max(r[1] for r in res)} VGPRs of `rankcorr_cov_kernel<8>` hold its 45 running sums without a spill.", ""]
 
 
+# ---- point_tails: the per-point tails of the inner importance sums (gwi_tail.h) ----------------------------------------------
+def tails_setup(c, extra, full):
+    cdfs_setup(c, extra, full)
+    c.eng.set_kde_columns(c.x_pe, c.x_inj)
+    if full:
+        c.eng.set_tail_sizes()  # the rule on n_pe / n_inj
+        extra["m"] = c.eng._tail_shape
+
+
+def tails_round(c, thetas, full):
+    out = {}
+    hist_round(c, thetas, out)
+    t = timed(out, "moment", lambda: c.eng.point_moments(thetas), c.eng.lib.gwi_point_moment_times, thetas)
+    out["moment"] = t[1] + t[2]
+    if full:
+        t = timed(out, "tails", lambda: c.eng.point_tails(thetas), c.eng.lib.gwi_point_tail_times, thetas)
+        out["tails"], out["tails select"], out["tails collect"], out["tails logw"] = t[1] + t[2], t[1], t[2], t[0]
+    return out
+
+
+def tails_check(c, extra):
+    from gwinferno_amd import draws as D
+
+    m_pe, m_inj = extra["m"]
+    extra["host_ms"], want = host_route(c, 2, lambda lw_pe, lw_inj: D.point_tails_reference(lw_pe, lw_inj, None, None, m_pe, m_inj))
+    got = c.eng.point_tails(c.thetas[1])
+    extra["equal"] = bool(np.array_equal(got[0][0], want[0]) and np.array_equal(got[1][0], want[1]) and np.array_equal(got[3][0], want[3])
+                          and np.array_equal(got[2][0][:, [0, 3]], want[2][:, [0, 3]]))
+    ok = want[2][:, 2] > 0.0
+    extra["deviation"] = float(np.max(np.abs(got[2][0][ok, 2] - want[2][ok, 2]) / want[2][ok, 2])) if ok.any() else float("nan")
+    extra["bytes"] = 8 * (c.eng.n_ev * m_pe + m_inj + 4 * (c.eng.n_ev + 1)) + 4 * 4 * (c.eng.n_ev + 1)
+
+
+def tails_notes(cfg, own, extra):
+    return [f"- {cfg}: m_pe = {extra['m'][0]}, m_inj = {extra['m'][1]} (the rule).  {extra['bytes']} bytes ({extra['bytes'] / 1e6:.3f} MB) come back per point against {extra['host_mb']:.1f} MB of "
+            f"log-weights on the host route (`Engine.log_weights` + `draws.point_tails_reference`): {extra['host_ms']:.1f} ms per point over 2 points, ONE run, no spread taken.  tail, counts, "
+            f"max and below_max of the last of them {'EQUAL the statement in every bit' if extra['equal'] else 'DIFFER from the statement'}; largest relative |device - host| body: "
+            f"{extra['deviation']:.2e}."]
+
+
+def tails_intro(repeats, how):
+    return (f"K = {K} points per call, the default tail sizes, {repeats} calls per row after two warm-up calls.  Times in ms; device times are HIP-event times of the launches after the "
+            f"log-weight pass, summed over the call and divided by K: `selection` is draw tile, draw merge and the six passes of histogram and pick, `collection` the collect and merge "
+            f"launches.  No ratio was promised in advance.  The digit widths (11, 11, 11, 11, 10, 10 bits: six passes) were not chosen by measurement; no alternative was timed.  "
+            f"`parent`: {how}".rstrip())
+
+
+def tails_tail(res):
+    return [f"Scratch is {max(r[4] for r in res)} bytes in every kernel listed.  `tail_hist_kernel` and `tail_pick_kernel` hold one pass's 2 048 counters (8 KB) in LDS, `tail_merge_kernel` the "
+            "4 096 keys it sorts (32 KB).", ""]
+
+
 QUANTITIES = f"C = 3 quantities ({', '.join(MASS_Z)})"
 WEIGHTED_LABEL = {"hist_merge_kernel<true>": "hist_merge_kernel<true> (weighted)", "marg_add_kernel<true>": "marg_add_kernel<true> (weighted)"}
 COMMON = dict(style="spread", columns=MASS_Z, relabel={}, resources_tail=lambda res: [], check=lambda c, extra: None)
@@ -581,6 +633,15 @@ ENTRIES = {e.name: e for e in (
            compare=("rank", "moment", "hist"),
            spans=[("rank", "`point_pits_exact` (unchanged code)", " per point"), ("moment", "`point_moments` (unchanged code)", " per point"),
                   ("hist", "`weighted_histograms` (unchanged code)", " per point")],
+           unmeasured="NOT MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
+    record(style="calls", columns=MASS_CHI, resources_tail=tails_tail, name="point_tails", symbol="gwi_point_tails", title="# Per-point tails of the inner importance sums: measured times",
+           kernels="tail_hist_kernel|tail_pick_kernel|tail_collect_kernel|tail_merge_kernel|draw_tile_kernel|draw_merge_kernel",
+           setup=tails_setup, one_round=tails_round, notes=tails_notes, check=tails_check, intro=tails_intro,
+           rows=[("tails", "`point_tails`, device time per point after the log-weight pass"), ("tails select", "... of which draw tile / merge and the selection's twelve launches"),
+                 ("tails collect", "... of which the collect and merge launches"), ("tails logw", "`point_tails`, log-weight pass per point (host clock)"),
+                 ("tails wall", "`point_tails`, wall time per point of the call"), ("moment", "`point_moments`, device time per point after the log-weight pass"),
+                 ("hist", "`weighted_histograms`, device time per point after the log-weight pass")],
+           compare=("moment", "hist"), spans=[("moment", "`point_moments` (unchanged code)", " per point"), ("hist", "`weighted_histograms` (unchanged code)", " per point")],
            unmeasured="NOT MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
 )}
 
