@@ -254,6 +254,9 @@ EXPORTED_SYMBOLS = [
     "gwi_set_tail_sizes",
     "gwi_point_tails",
     "gwi_point_tail_times",
+    "gwi_set_bootstrap",
+    "gwi_point_bootstrap",
+    "gwi_point_bootstrap_times",
     "gwi_marginal_weights_reset",
     "gwi_marginal_weights_add",
     "gwi_marginal_weights_add_weighted",
@@ -477,6 +480,14 @@ def load_library():
         lib.gwi_point_tails.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _I32P]
         lib.gwi_point_tail_times.restype = None
         lib.gwi_point_tail_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_point_bootstrap"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_set_bootstrap.restype = C.c_int32
+        lib.gwi_set_bootstrap.argtypes = [vp, C.c_uint64, C.c_int32, C.c_int32]
+        lib.gwi_point_bootstrap.restype = C.c_int32
+        lib.gwi_point_bootstrap.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _I32P, C.POINTER(C.c_int64)]
+        lib.gwi_point_bootstrap_times.restype = None
+        lib.gwi_point_bootstrap_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

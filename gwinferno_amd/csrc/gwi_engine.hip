@@ -565,6 +565,16 @@ struct TailBuffers {
   DeviceBuffer<double> d_body, d_tail, d_stats;
   int m_pe = 0, m_inj = 0;
 };
+// ... and of the bootstrap replicates (gwi_boot.h): the setting of gwi_set_bootstrap, and the entry's own workspace -- the tiles' partial
+// sums and counts [n_tiles][B], the staged rows [64][n_ev + 1][B], [64][n_ev + 1][2] and [64][n_ev + 1] and the call's counts
+// [n_ev + 1][B] (grown on demand, kept).  A pointer for ConditionalBuffers' reason, released with it.
+struct BootBuffers {
+  DeviceBuffer<double> d_tile_sum, d_sums, d_stats;
+  DeviceBuffer<int> d_tile_count, d_dead;
+  DeviceBuffer<long long> d_counts;
+  unsigned long long seed = 0;
+  int n_rep = 0, first_rep = 0;
+};
 }  // namespace
 
 struct gwi_engine {
@@ -703,6 +713,7 @@ struct gwi_engine {
   ConditionalBuffers* cond = nullptr;  // gwi_point_conditionals (release_moment_and_conditional_buffers, with `post`)
   RankcorrBuffers* rankcorr = nullptr;  // gwi_set_rankcorr_columns / gwi_point_rank_correlations (released with `cond`)
   TailBuffers* tail = nullptr;          // gwi_set_tail_sizes / gwi_point_tails (released with `cond`)
+  BootBuffers* boot = nullptr;          // gwi_set_bootstrap / gwi_point_bootstrap (released with `cond`)
 };
 
 namespace {
@@ -4422,6 +4433,8 @@ __attribute__((noinline)) void release_moment_and_conditional_buffers(gwi_handle
   h->rankcorr = nullptr;
   delete h->tail;
   h->tail = nullptr;
+  delete h->boot;
+  h->boot = nullptr;
 }
 }  // namespace
 extern "C" {
@@ -4726,6 +4739,85 @@ gwi_status gwi_point_tails(gwi_handle h, const double* thetas, int32_t k, double
 }
 
 void gwi_point_tail_times(double* logw_ms, double* select_ms, double* collect_ms, int32_t* launches) { g_point_tail_times.report(logw_ms, select_ms, collect_ms, launches); }
+
+// ---- bootstrap replicates of the inner importance sums: the same Poisson resampling of every segment at every point (gwi_boot.h) ------
+// (the header is included here for gwi_cond.h's reason)
+}  // extern "C"
+#include "gwi_boot.h"
+extern "C" {
+static thread_local StageTimes g_point_bootstrap_times;
+
+gwi_status gwi_set_bootstrap(gwi_handle h, uint64_t seed, int32_t n_replicates, int32_t first_replicate) {
+  if (!h) return GWI_ERR_INVALID;
+  namespace B = gwi::boot;
+  const char* who = "gwi_set_bootstrap";
+  gwi_status st = post_preflight(h, who, "resample on", "the injection replicates need", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_point_moments: a shard says that it is one)
+  if (n_replicates < 1 || n_replicates > B::kMaxReplicates)
+    return fail(h, GWI_ERR_INVALID, std::string(who) + ": n_replicates = " + std::to_string(n_replicates) + " is not in 1 ... " + std::to_string(B::kMaxReplicates));
+  if (first_replicate < 0 || (long long)first_replicate + n_replicates > B::kMaxReplicate)
+    return fail(h, GWI_ERR_INVALID, std::string(who) + ": first_replicate = " + std::to_string(first_replicate) + " is negative or first_replicate + n_replicates exceeds " +
+                                        std::to_string(B::kMaxReplicate));
+  if (!h->boot) h->boot = new (std::nothrow) BootBuffers();
+  if (!h->boot) return fail(h, GWI_ERR_INVALID, std::string(who) + ": out of host memory");
+  h->boot->seed = seed;
+  h->boot->n_rep = n_replicates;
+  h->boot->first_rep = first_replicate;
+  return GWI_OK;
+}
+
+gwi_status gwi_point_bootstrap(gwi_handle h, const double* thetas, int32_t k, double* sums, double* stats, int32_t* dead, int64_t* counts) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_bootstrap";
+  g_point_bootstrap_times = StageTimes();
+  gwi_status st = post_preflight(h, who, "resample on", "the injection replicates need", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_point_moments)
+  const bool set = h->boot && h->boot->n_rep > 0;
+  const std::string why = bad_point_args(h, set ? "" : "no replicates are set (gwi_set_bootstrap)", thetas, k, {{"sums", sums}, {"stats", stats}, {"dead", dead}, {"counts", counts}});
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, std::string(who) + ": " + why);
+  namespace B = gwi::boot;
+  BootBuffers& bb = *h->boot;
+  B::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);
+  if (st != GWI_OK) return st;
+  const size_t n_segs = (size_t)(h->n_ev + 1), tiles = (size_t)n_tiles, n_rep = (size_t)bb.n_rep;
+  GWI_HIP(bb.d_tile_sum.reserve(tiles * n_rep + 1));
+  GWI_HIP(bb.d_tile_count.reserve(tiles * n_rep + 1));
+  GWI_HIP(bb.d_sums.reserve((size_t)kStagePoints * n_segs * n_rep));
+  GWI_HIP(bb.d_stats.reserve((size_t)kStagePoints * n_segs * B::kStats));
+  GWI_HIP(bb.d_dead.reserve((size_t)kStagePoints * n_segs));
+  GWI_HIP(bb.d_counts.reserve(n_segs * n_rep));
+  a.tile_sum = bb.d_tile_sum;
+  a.tile_count = bb.d_tile_count;
+  a.counts = bb.d_counts;
+  a.seed = bb.seed;
+  a.n_rep = bb.n_rep;
+  a.first_rep = bb.first_rep;
+  StagedRows rows(h, k);  // (n_ev + 1)(B + 2) doubles and n_ev + 1 ints per point
+  rows.add(sums, bb.d_sums.ptr, n_segs * n_rep);
+  rows.add(stats, bb.d_stats.ptr, n_segs * B::kStats);
+  rows.add(dead, bb.d_dead.ptr, n_segs);
+  const auto tile = [&](int p) {
+    a.want_counts = p == 0;  // the counts do not depend on the point
+    if (n_tiles) hipLaunchKernelGGL(B::boot_tile_kernel, dim3((unsigned)n_tiles), dim3(B::kBlock), 0, h->stream, a);
+  };
+  const auto merge = [&](int p) {  // into the point's slot of the stage
+    a.sums = rows.slot<double>(0, p);
+    a.stats = rows.slot<double>(1, p);
+    a.dead = rows.slot<int>(2, p);
+    hipLaunchKernelGGL(B::boot_merge_kernel, dim3((unsigned)n_segs), dim3(B::kBlock), 0, h->stream, a);
+  };
+  st = per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_bootstrap_times, 2, 4, tile, merge, [&](int p) { return rows.after(p); });
+  if (st != GWI_OK) return st;
+  GWI_HIP(hipMemcpy(counts, bb.d_counts.ptr, n_segs * n_rep * sizeof(long long), hipMemcpyDeviceToHost));
+  return GWI_OK;
+}
+
+void gwi_point_bootstrap_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) { g_point_bootstrap_times.report(logw_ms, tile_ms, merge_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

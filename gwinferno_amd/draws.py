@@ -44,7 +44,11 @@ is a ratio: :func:`rankcorr_codes` states the theta-independent codes, :func:`ra
 
 ``gwi_point_tails`` (gwinferno_amd/csrc/gwi_tail.h) selects, per point and segment, the largest live log-weights and what is needed of
 the rest: :func:`tails_segment` and :func:`point_tails_reference` state them, :func:`tail_cutoff_and_rest` what the host derives, and
-:func:`pareto_tail_fit` fits the tail under :func:`pareto_smooth`'s conventions."""
+:func:`pareto_tail_fit` fits the tail under :func:`pareto_smooth`'s conventions.
+
+``gwi_point_bootstrap`` (gwinferno_amd/csrc/gwi_boot.h) sums the same ``w_j`` under Poisson(1) counts that depend on (seed, sample,
+replicate) and never on the point: :func:`bootstrap_counts` states the counts, :func:`point_bootstrap_reference` one point, and
+:func:`bootstrap_likelihood` the replicates of the likelihood the host forms from the sums."""
 import bisect
 import itertools
 import math
@@ -1080,3 +1084,135 @@ def pareto_tail_fit(tail, cutoff, top):
     shifted = tail - float(top)
     kh, new = _smooth_shifted_tail(shifted, float(cutoff) - float(top))
     return float(kh), shifted if new is None else new
+
+
+# ---- bootstrap replicates of the inner importance sums (gwi_boot.h) ----------------------------------------------------------
+BOOTSTRAP_TAG = 0x424F4F54  # counter word 3 of the bootstrap stream (gwi_boot.h: kTag, "BOOT")
+MAX_BOOTSTRAP_REPLICATES = 1024    # replicates of one gwi_point_bootstrap call (gwi_boot.h: kMaxReplicates)
+MAX_BOOTSTRAP_REPLICATE = 1 << 20  # first_replicate + n_replicates of gwi_set_bootstrap (gwi_boot.h: kMaxReplicate)
+# floor(2^32 F(j)), F the Poisson(1) CDF, j = 0 ... 12 (gwi_boot.h: kPoisson1): the table ends with the largest word, which no later
+# entry could exceed.  The count of a 32-bit word is the number of entries that are <= it
+POISSON1_THRESHOLDS = (1580030168, 3160060337, 3950075421, 4213413783, 4279248373, 4292415291, 4294609777,
+                       4294923276, 4294962463, 4294966817, 4294967252, 4294967292, 4294967295)
+
+
+def _replicate_indices(replicates):
+    """``replicates`` -- a number B (the replicates 0 ... B - 1) or the replicate numbers themselves -- as an int64 array."""
+    if np.ndim(replicates) == 0:
+        reps = np.arange(int(replicates), dtype=np.int64)
+    else:
+        reps = np.asarray(replicates, dtype=np.int64).ravel()
+    if reps.size < 1 or reps.min() < 0 or reps.max() >= MAX_BOOTSTRAP_REPLICATE:
+        raise ValueError(f"replicates are at least one number in 0 ... {MAX_BOOTSTRAP_REPLICATE - 1}")
+    return reps
+
+
+def bootstrap_counts(seed, first_index, n, replicates):
+    """The Poisson(1) counts ``(n, B)`` int64 of the samples with the global indices ``first_index ... first_index + n`` in the
+    replicates ``replicates`` (a number B: 0 ... B - 1; or the replicate numbers): replicate ``b`` takes word ``b % 4`` of the
+    Philox4x32-10 block with the key ``(seed low, seed high)`` and the counter ``(index low, index high, b // 4, BOOTSTRAP_TAG)``, and the
+    count is the number of entries of ``POISSON1_THRESHOLDS`` that are ``<=`` the word.  A pure function of (seed, index, replicate): any
+    split of the indices or of the replicates gives the same numbers.  PE sample ``j`` of event ``e`` has the index ``e n_pe + j``,
+    injection ``j`` the index ``n_ev n_pe + j``."""
+    from .spin_priors import philox4x32_10
+
+    m64 = 2**64 - 1
+    seed, first_index, n = int(seed) & m64, int(first_index) & m64, int(n)
+    reps = _replicate_indices(replicates)
+    out = np.empty((n, reps.size), dtype=np.int64)
+    if n == 0:
+        return out
+    idx = np.arange(n, dtype=np.uint64) + np.uint64(first_index)
+    lo, hi = idx & np.uint64(0xFFFFFFFF), idx >> np.uint64(32)
+    table = np.array(POISSON1_THRESHOLDS, dtype=np.uint64)
+    groups, place = np.unique(reps // 4, return_inverse=True)
+    step = max(1, (1 << 20) // n)  # about 2^20 blocks at a time
+    for g0 in range(0, groups.size, step):
+        g = groups[g0 : g0 + step].astype(np.uint64)
+        words = philox4x32_10(np.repeat(lo[:, None], g.size, axis=1), np.repeat(hi[:, None], g.size, axis=1), np.repeat(g[None, :], n, axis=0),
+                              np.full((n, g.size), BOOTSTRAP_TAG, dtype=np.uint64), seed & 0xFFFFFFFF, seed >> 32)
+        cols = np.nonzero((place >= g0) & (place < g0 + g.size))[0]
+        for word in range(4):
+            sel = cols[reps[cols] % 4 == word]
+            if sel.size:
+                out[:, sel] = np.searchsorted(table, words[word][:, place[sel] - g0], side="right")
+    return out
+
+
+def bootstrap_segment(logw, mask, counts):
+    """``(sums (B,), (M, S), dead, C (B,) int64)`` of ONE segment of ``gwi_point_bootstrap`` under the counts ``counts (n, B)`` of its
+    samples: ``A_b = sum_i c_ib w_i`` with the ``w_i`` of :func:`draw_weights` (a plain ``np.sum`` per replicate), ``M`` the largest live
+    log-weight, ``S = fsum w``, and ``C_b = sum_i c_ib`` over the unmasked samples, whether or not their weight is finite.  A segment
+    whose ``S`` is 0 or not finite is dead: NaN sums."""
+    lw = np.asarray(logw, dtype=np.float64).ravel()
+    counts = np.asarray(counts, dtype=np.int64).reshape(lw.size, -1)
+    keep = np.ones(lw.size, dtype=bool) if mask is None else np.asarray(mask).ravel().astype(bool)
+    live = keep & np.isfinite(lw)
+    w = draw_weights(lw, mask)
+    total = math.fsum(w.tolist())
+    top = float(lw[live].max()) if live.any() else -np.inf
+    c_b = counts[keep].sum(axis=0)
+    if not (total > 0.0 and np.isfinite(total)):
+        return np.full(counts.shape[1], np.nan), (top, total), 1, c_b
+    sums = np.sum(np.ascontiguousarray(counts[live].T) * w[live], axis=1)  # (a plain np.sum per replicate: each row on its own)
+    return sums, (top, total), 0, c_b
+
+
+def point_bootstrap_reference(log_w_pe, log_w_inj, masks, seed, replicates):
+    """One hyper-parameter point of ``gwi_point_bootstrap``: ``log_w_pe (n_ev, n_pe)``, ``log_w_inj (n_inj,)`` -- what
+    ``Engine.log_weights`` returns --, ``masks = (pe_mask, inj_mask)`` of ``gwi_set_draw_mask`` (or None, also for either), the seed and
+    the replicates (a number B, or the replicate numbers) -> ``(sums (n_ev + 1, B), stats (n_ev + 1, 2), dead (n_ev + 1,) int32, counts
+    (n_ev + 1, B) int64)``, the injection set last: per segment :func:`bootstrap_segment` under :func:`bootstrap_counts`.  It states the
+    entry; it does not mirror the device's summation shape."""
+    log_w_pe = np.asarray(log_w_pe, dtype=np.float64)
+    log_w_inj = np.asarray(log_w_inj, dtype=np.float64).ravel()
+    n_ev, n_pe = log_w_pe.shape
+    pe_mask, inj_mask = (None, None) if masks is None else masks
+    pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(n_ev, n_pe)
+    reps = _replicate_indices(replicates)
+    sums, stats = np.empty((n_ev + 1, reps.size)), np.empty((n_ev + 1, 2))
+    dead, counts = np.empty(n_ev + 1, dtype=np.int32), np.empty((n_ev + 1, reps.size), dtype=np.int64)
+    for seg in range(n_ev + 1):
+        lw, mk = (log_w_pe[seg], None if pe_mask is None else pe_mask[seg]) if seg < n_ev else (log_w_inj, inj_mask)
+        sums[seg], stats[seg], dead[seg], counts[seg] = bootstrap_segment(lw, mk, bootstrap_counts(seed, seg * n_pe, lw.size, reps))
+    return sums, stats, dead, counts
+
+
+def bootstrap_likelihood(sums, stats, dead, counts, n_live, total_inj, n_obs, seed):
+    """The replicates of the likelihood from the raw sums of ``gwi_point_bootstrap`` / :func:`point_bootstrap_reference`, shared by the
+    device route and the host route: ``sums (K, n_ev + 1, B)``, ``stats (K, n_ev + 1, 2)``, ``dead (K, n_ev + 1)``, ``counts
+    (n_ev + 1, B)``, ``n_live (n_ev + 1,)`` the segments' unmasked sample counts ``n_e``, ``total_inj`` the injections made, ``n_obs``
+    the events of the likelihood.  With ``logBF_e = M_e + log(S_e / n_e)`` and ``log mu = M_inj + log(S_inj / total_inj)``:
+
+    * ``logBF_eb = logBF_e + log(A_eb / S_e) - log(C_eb / n_e)``,
+    * ``log mu_b = log mu + log(A_inj,b / S_inj) - log((C_inj,b + C_miss,b) / total_inj)`` with ``C_miss,b ~ Poisson(total_inj -
+      n_inj_unmasked)`` drawn here from ``np.random.Generator(np.random.Philox(seed))``, once per replicate and the same at every point:
+      the injections that were not found are resampled as well,
+    * ``log L_b = sum_e logBF_eb - n_obs log mu_b``.
+
+    No cuts and no marginalised-selection term are applied.  A replicate of a dead segment, or one with ``C_eb = 0`` (possible only for
+    tiny segments), is NaN and is counted, never divided.  Returns a dict: ``log_bf (K, n_ev)``, ``log_mu (K,)``, ``log_l (K,)``,
+    ``log_bf_rep (K, n_ev, B)``, ``log_mu_rep (K, B)``, ``log_l_rep (K, B)``, ``c_miss (B,)``, ``n_dead`` (the (point, segment) pairs
+    without weight) and ``n_empty`` (the (segment, replicate) pairs with ``C = 0``)."""
+    sums, stats = np.asarray(sums, dtype=np.float64), np.asarray(stats, dtype=np.float64)
+    counts, n_live = np.asarray(counts, dtype=np.int64), np.asarray(n_live, dtype=np.float64).ravel()
+    is_dead = np.asarray(dead) != 0
+    n_rep = sums.shape[2]
+    missed = float(total_inj) - n_live[-1]
+    if missed < 0.0:
+        raise ValueError(f"total_inj = {total_inj} is below the {int(n_live[-1])} unmasked found injections")
+    c_miss = np.random.Generator(np.random.Philox(int(seed) & (2**64 - 1))).poisson(missed, size=n_rep).astype(np.float64)
+    denom = counts.astype(np.float64)
+    denom[-1] += c_miss
+    norm = n_live.copy()
+    norm[-1] = float(total_inj)
+    empty = denom <= 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        base = np.where(is_dead, np.nan, stats[..., 0] + np.log(stats[..., 1] / norm[None, :]))
+        shift = np.log(sums / stats[..., 1][..., None]) - np.log(denom / norm[:, None])[None]
+    rep = np.where(is_dead[..., None] | empty[None], np.nan, base[..., None] + shift)
+    log_bf, log_mu = base[:, :-1], base[:, -1]
+    log_bf_rep, log_mu_rep = rep[:, :-1], rep[:, -1]
+    return {"log_bf": log_bf, "log_mu": log_mu, "log_l": log_bf.sum(axis=1) - float(n_obs) * log_mu, "log_bf_rep": log_bf_rep, "log_mu_rep": log_mu_rep,
+            "log_l_rep": log_bf_rep.sum(axis=1) - float(n_obs) * log_mu_rep, "c_miss": c_miss, "n_dead": int(np.count_nonzero(is_dead)),
+            "n_empty": int(np.count_nonzero(empty))}

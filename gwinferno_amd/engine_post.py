@@ -1,5 +1,5 @@
 """The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
-injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments, conditional moments, rank correlations and tails, marginal weights and their
+injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments, conditional moments, rank correlations, tails and bootstrap replicates, marginal weights and their
 quantiles and kernel density estimates.
 Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
 """
@@ -211,7 +211,7 @@ class PostprocessMixin:
         return (hist_pe if with_pe else None), (hist_inj if with_inj else None), dead
 
     def _per_point(self, what, need, shape_attr, missing, dtypes, shapes, thetas, extra=()):
-        """One per-point entry: the library's ``gwi_<what>`` fills one array per dtype, float64 or int32, of the shapes ``shapes(k, shape)``,
+        """One per-point entry: the library's ``gwi_<what>`` fills one array per dtype, float64, int32 or int64, of the shapes ``shapes(k, shape)``,
         where ``shape`` is what the setter left in ``shape_attr``; the arrays are returned.  ``need`` and ``missing`` word the refusals;
         ``extra`` holds the entry's own arguments between ``k`` and the outputs."""
         self._whole_catalog(what, need)
@@ -221,7 +221,7 @@ class PostprocessMixin:
         if shape is None:
             self._nothing_set(what, missing, entry, N.as_dp(thetas), k, *extra, *(None for _ in dtypes))
         out = [np.empty(s, dtype=dt) for s, dt in zip(shapes(k, shape), dtypes)]
-        self._check(entry(self.handle, N.as_dp(thetas), k, *extra, *(N.as_dp(o) if o.dtype == np.float64 else o.ctypes.data_as(C.POINTER(C.c_int32)) for o in out)))
+        self._check(entry(self.handle, N.as_dp(thetas), k, *extra, *(N.as_dp(o) if o.dtype == np.float64 else o.ctypes.data_as(C.POINTER(C.c_int64 if o.dtype == np.int64 else C.c_int32)) for o in out)))
         return out
 
     def point_cdfs(self, thetas):
@@ -395,6 +395,38 @@ class PostprocessMixin:
         m_pe, m_inj = self._tail_shape
         cut = self.n_ev * m_pe
         return np.ascontiguousarray(row[:, :cut]).reshape(-1, self.n_ev, m_pe), np.ascontiguousarray(row[:, cut:]), stats, counts
+
+    def set_bootstrap(self, seed, n_replicates, first_replicate=0):
+        """The replicates of :meth:`point_bootstrap` (``gwi_set_bootstrap``): the seed of the Poisson counts
+        (:func:`gwinferno_amd.draws.bootstrap_counts`), ``1 <= n_replicates <= 1024`` replicates per call and the first of them,
+        ``first_replicate >= 0`` with ``first_replicate + n_replicates <= 2^20``.  Nothing is uploaded; a second call replaces the setting.
+        Not available on an engine that holds a shard (``world > 1``)."""
+        from .draws import MAX_BOOTSTRAP_REPLICATE, MAX_BOOTSTRAP_REPLICATES
+
+        self._whole_catalog("set_bootstrap", "the injection replicates need")
+        seed, n_replicates, first_replicate = int(seed), int(n_replicates), int(first_replicate)
+        if not 1 <= n_replicates <= MAX_BOOTSTRAP_REPLICATES:
+            raise ValueError(f"n_replicates = {n_replicates} is not in 1 ... {MAX_BOOTSTRAP_REPLICATES}")
+        if first_replicate < 0 or first_replicate + n_replicates > MAX_BOOTSTRAP_REPLICATE:
+            raise ValueError(f"first_replicate = {first_replicate} is negative or first_replicate + n_replicates exceeds {MAX_BOOTSTRAP_REPLICATE}")
+        self._boot_shape = None
+        self._check(self.lib.gwi_set_bootstrap(self.handle, seed & (2**64 - 1), n_replicates, first_replicate))
+        self._boot_shape = (n_replicates, first_replicate)
+
+    def point_bootstrap(self, thetas):
+        """Bootstrap replicates of the inner importance sums per point, on the device (``gwi_point_bootstrap``; semantics:
+        :func:`gwinferno_amd.draws.point_bootstrap_reference`).  ``thetas`` is one point ``(n_theta,)`` or ``(k, n_theta)``.
+        Returns ``(sums (k, n_ev + 1, B), stats (k, n_ev + 1, 2), dead (k, n_ev + 1) int32, counts (n_ev + 1, B) int64)``, the injection set
+        last: per segment and replicate ``A_b = sum_i c_ib w_i`` with ``w_i = exp(lw_i - M)`` and the Poisson(1) counts ``c_ib`` of
+        :func:`gwinferno_amd.draws.bootstrap_counts` -- the same at every point --, ``stats = (M, S)`` with the bits :meth:`point_tails`
+        returns, ``dead`` = 1 for a segment without weight (NaN sums), and ``C_b = sum_i c_ib`` over the segment's unmasked samples, once
+        per call.  The masks of :meth:`set_draw_mask` apply.  :func:`gwinferno_amd.draws.bootstrap_likelihood` forms the replicates of the
+        likelihood.  ``(n_ev + 1)(B + 2)`` doubles come back per point; the points and the replicates may be split over calls without
+        changing a bit.  Not available on an engine that holds a shard (``world > 1``)."""
+        sums, stats, dead, counts = self._per_point("point_bootstrap", "the injection replicates need", "_boot_shape", "replicates are set (set_bootstrap)",
+                                                    (np.float64, np.float64, np.int32, np.int64),
+                                                    lambda k, s: ((k, self.n_ev + 1, s[0]), (k, self.n_ev + 1, 2), (k, self.n_ev + 1), (self.n_ev + 1, s[0])), thetas)
+        return sums, stats, dead, counts
 
     def marginal_weights_reset(self):
         """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""

@@ -1589,3 +1589,115 @@ def importance_sum_diagnostics(eng, thetas, m_pe=None, m_inj=None, point_weights
                     exact[p, s] = math.fsum(w.tolist()) ** 2 / math.fsum((w * w).tolist())
         out["neff_exact"] = exact
     return out
+
+
+BOOTSTRAP_CHUNK = 64  # points per gwi_point_bootstrap call of likelihood_bootstrap (the sums do not depend on it)
+
+
+def _bootstrap_points(eng, thetas, seed, n_replicates, masks, backend, chunk):
+    """``(sums (K, n_ev + 1, B), stats (K, n_ev + 1, 2), dead (K, n_ev + 1), counts (n_ev + 1, B))`` of the points on either backend
+    (DESIGN 8n); more replicates than one call takes are split over ``first_replicate``."""
+    from . import draws as D
+
+    k, n_ev = thetas.shape[0], eng.n_ev
+    sums, counts = np.empty((k, n_ev + 1, n_replicates)), np.empty((n_ev + 1, n_replicates), dtype=np.int64)
+    stats, dead = np.empty((k, n_ev + 1, 2)), np.empty((k, n_ev + 1), dtype=np.int32)
+    if backend == "device":
+        eng.set_draw_mask(*masks)
+        for b0 in range(0, n_replicates, D.MAX_BOOTSTRAP_REPLICATES):
+            b1 = min(n_replicates, b0 + D.MAX_BOOTSTRAP_REPLICATES)
+            eng.set_bootstrap(seed, b1 - b0, b0)
+            for k0 in range(0, k, chunk):
+                sums[k0 : k0 + chunk, :, b0:b1], stats[k0 : k0 + chunk], dead[k0 : k0 + chunk], counts[:, b0:b1] = eng.point_bootstrap(thetas[k0 : k0 + chunk])
+        return sums, stats, dead, counts
+    # the statement, one segment's counts at a time: they serve every point
+    lw = [eng.log_weights(th) for th in thetas]
+    for seg in range(n_ev + 1):
+        n = eng.n_pe if seg < n_ev else eng.n_inj
+        c = D.bootstrap_counts(seed, seg * eng.n_pe, n, n_replicates)
+        mask = None if masks[0 if seg < n_ev else 1] is None else (np.asarray(masks[0]).reshape(n_ev, -1)[seg] if seg < n_ev else masks[1])
+        for p in range(k):
+            sums[p, seg], stats[p, seg], dead[p, seg], counts[seg] = D.bootstrap_segment(lw[p][0][seg] if seg < n_ev else lw[p][1], mask, c)
+    return sums, stats, dead, counts
+
+
+def likelihood_bootstrap(eng, thetas, total_inj, n_replicates=128, seed=0, nobs=None, backend="device", chunk=BOOTSTRAP_CHUNK, masks=None):
+    """How much of ``log L(theta_a) - log L(theta_b)`` is sampling noise of the catalog?    Every number the engine returns
+    is a Monte-Carlo sum over a finite set of PE samples and found injections.  ``log_nEffs``, the delta-method
+    ``variance_log_likelihood`` and the Pareto ``khat`` (:func:`importance_sum_diagnostics`) speak of one point; the errors at two points
+    of a chain are made of the same samples and largely cancel in the difference, and the delta method says nothing about the bias of
+    the logarithm of a noisy mean.  This is the non-parametric answer: a Poisson bootstrap with common random numbers.  Every event's
+    PE samples and the injection set are resampled ``n_replicates`` times -- sample ``i`` is taken ``c_ib ~ Poisson(1)`` times in
+    replicate ``b``, the same at every point (:func:`gwinferno_amd.draws.bootstrap_counts`) --, ``eng.point_bootstrap`` returns the
+    resampled sums, ``(n_ev + 1) B`` doubles per point while the weights never leave HBM, and
+    :func:`gwinferno_amd.draws.bootstrap_likelihood` forms ``log L_b = sum_e logBF_eb - N_obs log mu_b`` here.  The injections that were
+    not found are resampled as well (a Poisson number of them per replicate, from ``total_inj``).  NO cuts (``min_neff``, variance) and
+    NO marginalised-selection term are applied: the replicates are those of the plain ``sum logBF - N_obs log mu``.
+
+    ``thetas (K, n_theta)``; ``total_inj`` the injections made; ``nobs`` the events of the likelihood (default: the engine's);
+    ``n_replicates`` any number up to 2^20, split over calls of at most 1 024; ``chunk`` the points per call (the sums do not depend on
+    either split).  ``masks = (pe_mask, inj_mask)`` as :meth:`Engine.set_draw_mask` takes them (None: every sample; a masked found
+    injection counts as one that was not found).  The device backend replaces the engine's draw mask and bootstrap setting.  ``backend="host"``
+    runs the NumPy statement on ``eng.log_weights``: the statement the kernels are tested against, not a fall-back.
+
+    Returns a dict: ``log_l (K,)``, the uncut value from the entry's own ``M`` and ``S``; ``log_l_rep (K, B)``; ``std_log_l (K,)``;
+    ``bias_log_l (K,)`` = the mean over the replicates minus ``log_l``; ``std_log_bf (K, n_ev)``; ``std_log_mu (K,)``; ``delta_std (K,
+    K)``, the standard deviation over the replicates of ``log_l_rep[a] - log_l_rep[b]`` -- the noise of the difference; ``corr (K, K)``,
+    the correlation of the replicates of two points; ``variance_log_likelihood (K,)`` from ``eng.evaluate_batch`` for the side-by-side
+    with ``std_log_l ** 2``; ``n_dead``, the (point, segment) pairs without weight, whose replicates are NaN -- counted, never divided;
+    ``n_nan_replicates (K,)``, the replicates of a point that are NaN (a dead segment: all; a replicate that drew nothing from a
+    segment, ``C_eb = 0``, possible only for tiny segments), left out of the moments of that point and of its pairs; ``counts (n_ev + 1,
+    B)``; ``c_miss (B,)``; ``log_bf (K, n_ev)``, ``log_mu (K,)``; ``n_replicates``, ``seed``.  Standard deviations divide by the
+    replicates used minus one."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k, n_ev = thetas.shape[0], eng.n_ev
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    n_replicates, chunk = int(n_replicates), int(chunk)
+    if not 1 <= n_replicates <= D.MAX_BOOTSTRAP_REPLICATE:
+        raise ValueError(f"n_replicates = {n_replicates} is not in 1 ... {D.MAX_BOOTSTRAP_REPLICATE}")
+    if chunk < 1:
+        raise ValueError("chunk is at least 1")
+    n_obs = float(getattr(eng, "n_ev_global", n_ev) if nobs is None else nobs)
+    pe_mask, inj_mask = (None, None) if masks is None else masks
+    held = (pe_mask, inj_mask)
+    sums, stats, dead, counts = _bootstrap_points(eng, thetas, seed, n_replicates, held, backend, chunk)
+    n_live = np.array([eng.n_pe if held[0] is None else int(np.count_nonzero(np.asarray(held[0]).reshape(n_ev, -1)[e])) for e in range(n_ev)]
+                      + [eng.n_inj if held[1] is None else int(np.count_nonzero(held[1]))])
+    out = D.bootstrap_likelihood(sums, stats, dead, counts, n_live, total_inj, n_obs, seed)
+    rep = out["log_l_rep"]
+
+    def spread(x):  # over the last axis, NaN replicates left out
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ok = np.isfinite(x)
+            n = ok.sum(axis=-1)
+            mean = np.where(ok, x, 0.0).sum(axis=-1) / n
+            var = np.where(ok, (x - mean[..., None]) ** 2, 0.0).sum(axis=-1) / (n - 1)
+            return mean, np.sqrt(np.where(n > 1, var, np.nan))
+
+    mean_l, std_l = spread(rep)
+    delta, corr = np.empty((k, k)), np.empty((k, k))
+    for a in range(k):
+        _, delta[a] = spread(rep[a][None, :] - rep)
+        for b in range(k):
+            ok = np.isfinite(rep[a]) & np.isfinite(rep[b])
+            if ok.sum() > 1:
+                xa, xb = rep[a][ok] - rep[a][ok].mean(), rep[b][ok] - rep[b][ok].mean()
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    corr[a, b] = 1.0 if a == b and np.any(xa != 0.0) else float(np.dot(xa, xb) / np.sqrt(np.dot(xa, xa) * np.dot(xb, xb)))
+            else:
+                corr[a, b] = np.nan
+    var_site = np.empty(k)
+    step = int(eng.max_batch)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k0 in range(0, k, step):
+            res = eng.evaluate_batch(thetas[k0 : k0 + step], total_inj, nobs=nobs, marginalize_selection=False, min_neff_cut=False, max_variance_cut=False, want_grad=False)
+            var_site[k0 : k0 + len(res)] = [r.summary.variance_log_likelihood for r in res]
+    out.update(std_log_l=std_l, bias_log_l=mean_l - out["log_l"], std_log_bf=spread(out["log_bf_rep"])[1], std_log_mu=spread(out["log_mu_rep"])[1], delta_std=delta, corr=corr,
+               variance_log_likelihood=var_site, n_nan_replicates=(~np.isfinite(rep)).sum(axis=1).astype(np.int64), counts=counts, sums=sums, stats=stats, dead=dead,
+               n_replicates=n_replicates, seed=int(seed))
+    return out

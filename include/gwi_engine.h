@@ -703,6 +703,46 @@ gwi_status gwi_point_tails(gwi_handle h, const double* thetas, int32_t k, double
                            double* stats /* [k][n_ev + 1][4]: max, S, body, below_max */, int32_t* counts /* [k][n_ev + 1][4]: n_live, n_gt, n_eq, dead */);
 void gwi_point_tail_times(double* logw_ms, double* select_ms, double* collect_ms, int32_t* launches); /* diagnostic only */
 
+/* Bootstrap replicates of the inner importance sums on the device: per hyper-parameter point and segment the sums of B Poisson-bootstrap
+ * replicates of the segment's samples, with the SAME resampling at every point (common random numbers), so that the sampling noise of
+ * a difference log L(theta_a) - log L(theta_b) and the bias of the logarithm follow on the host while the weights never leave HBM
+ * (gwinferno_amd/csrc/gwi_boot.h; the NumPy statement is gwinferno_amd/draws.py: bootstrap_counts, point_bootstrap_reference; the
+ * replicates of the likelihood are the host's, draws.bootstrap_likelihood; the contract is DESIGN 8n).
+ *
+ * Segments (an event's n_pe samples; the injection set, last), the masks, M and S are gwi_draw_indices' and gwi_weighted_histograms'.
+ * w_i = exp(lw_i - M), 0 for a sample that is masked or whose log-weight is not finite.  Sample i of a segment has the global index
+ * e n_pe + j (PE sample j of event e) or n_ev n_pe + j (injection j).  In replicate b it is taken c_ib times, c_ib ~ Poisson(1): word
+ * b % 4 of the Philox4x32-10 block with the key (seed low, seed high) and the counter (index low, index high, b / 4, 0x424F4F54), and
+ * c_ib = the number of entries of the table floor(2^32 F(j)), j = 0 ... 12 (F the Poisson(1) CDF), that are <= the word.  Integer
+ * comparisons only: a count is the same bits on host and device and depends on (seed, index, b) alone, never on the point.
+ *
+ * gwi_set_bootstrap(): the seed, the number of replicates of a call, 1 <= n_replicates <= 1024, and the first one,
+ * first_replicate >= 0, first_replicate + n_replicates <= 2^20.  Nothing is uploaded; a second call replaces the setting.
+ *
+ * gwi_point_bootstrap(): per point k, segment s and replicate b = first_replicate + r
+ *   sums[k][s][r]   A_b = sum_i c_ib w_i over the segment
+ *   stats[k][s]     (M, S), the bits gwi_point_tails returns
+ *   dead[k][s]      1 for a segment whose S is 0 or not finite: its sums are NaN
+ *   counts[s][r]    C_b = sum_i c_ib over the segment's unmasked samples, whether or not their weight is finite: exact, the same at
+ *                   every point, returned once per call
+ * A_b is a sum of ONE shape -- sample order within a slice of 128 consecutive samples of a tile, the tile's 8 slices in order, the
+ * segment's tiles in order -- that involves neither n_replicates nor first_replicate: the bits of A_b are the same on every call,
+ * handle and split of the points or of the replicates over calls.  No atomics.  k >= 1 is not bound by the batch limit: the points are
+ * staged on the device 64 at a time and copied back per chunk; (n_ev + 1)(B + 2) doubles and n_ev + 1 ints come back per point.  The
+ * call changes no state another entry reads.  Not done: sharded handles; replicates of the gradient; the Bayesian (exponential-weight)
+ * bootstrap; replicates of the marginalised-selection term and of the cuts; more than 1024 replicates per call; feeding anything back
+ * into the likelihood.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer, k < 1, a setting out of range, a call before the setting and a
+ * host-only handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard, checked first.
+ *
+ * gwi_point_bootstrap_times(): DIAGNOSTIC ONLY, for tools/post_time.py: of the calling thread's last call, summed over its points, the
+ * wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge launches with the tile
+ * launch and of the merge launch, and the number of kernel launches after the log-weight passes. */
+gwi_status gwi_set_bootstrap(gwi_handle h, uint64_t seed, int32_t n_replicates, int32_t first_replicate);
+gwi_status gwi_point_bootstrap(gwi_handle h, const double* thetas, int32_t k, double* sums /* [k][n_ev + 1][B] */, double* stats /* [k][n_ev + 1][2]: M, S */,
+                               int32_t* dead /* [k][n_ev + 1] */, int64_t* counts /* [n_ev + 1][B] */);
+void gwi_point_bootstrap_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches); /* diagnostic only */
+
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is
  * gwinferno_amd/draws.py: marginal_weights_reference, weighted_quantiles_reference).

@@ -7,7 +7,7 @@ timed on another build of the engine (the parent commit's), in child processes o
 half after, and this build's median is placed against the span of that build's own calls.  No figure is fixed in advance; what is not
 measured is named as unmeasured.  Writes a Markdown report.
 
-      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals,point_rankcorr,point_tails} [--configs c2,c5] [--repeats 10]
+      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals,point_rankcorr,point_tails,point_bootstrap} [--configs c2,c5] [--repeats 10]
                                 [--parent-lib PATH] [--out profiles/<entry>/RESULTS.md]
 
 What differs per entry is one record of ENTRIES: the set-up calls, one_round, the host route, the kernels to list and the row labels."""
@@ -556,6 +556,59 @@ def tails_tail(res):
             "4 096 keys it sorts (32 KB).", ""]
 
 
+# ---- point_bootstrap: bootstrap replicates of the inner importance sums (gwi_boot.h) ------------------------------------------
+BOOT_REPLICATES, BOOT_SEED = 128, 1
+
+
+def boot_setup(c, extra, full):
+    tails_setup(c, extra, False)
+    c.eng.set_tail_sizes()
+    if full:
+        c.eng.set_bootstrap(BOOT_SEED, BOOT_REPLICATES)
+
+
+def boot_round(c, thetas, full):
+    out = {}
+    hist_round(c, thetas, out)
+    t = timed(out, "tails", lambda: c.eng.point_tails(thetas), c.eng.lib.gwi_point_tail_times, thetas)
+    out["tails"] = t[1] + t[2]
+    if full:
+        t = timed(out, "boot", lambda: c.eng.point_bootstrap(thetas), c.eng.lib.gwi_point_bootstrap_times, thetas)
+        out["boot"], out["boot tile"], out["boot merge"], out["boot logw"] = t[1] + t[2], t[1], t[2], t[0]
+    return out
+
+
+def boot_check(c, extra):
+    from gwinferno_amd import draws as D
+
+    extra["host_ms"], want = host_route(c, 2, lambda lw_pe, lw_inj: D.point_bootstrap_reference(lw_pe, lw_inj, None, BOOT_SEED, BOOT_REPLICATES))
+    got = c.eng.point_bootstrap(c.thetas[1])
+    extra["equal"] = bool(np.array_equal(got[3], want[3]) and np.array_equal(got[2][0], want[2]) and np.array_equal(got[1][0][:, 0], want[1][:, 0]))
+    ok = want[0] > 0.0
+    extra["deviation"] = float(np.max(np.abs(got[0][0][ok] - want[0][ok]) / want[0][ok])) if ok.any() else float("nan")
+    extra["bytes"] = (c.eng.n_ev + 1) * (8 * (BOOT_REPLICATES + 2) + 4)
+    extra["count_bytes"] = 8 * (c.eng.n_ev + 1) * BOOT_REPLICATES
+
+
+def boot_notes(cfg, own, extra):
+    return [f"- {cfg}: B = {BOOT_REPLICATES} replicates.  {extra['bytes']} bytes ({extra['bytes'] / 1e6:.3f} MB) come back per point, and {extra['count_bytes']} bytes of counts once per call, "
+            f"against {extra['host_mb']:.1f} MB of log-weights per point on the host route (`Engine.log_weights` + `draws.point_bootstrap_reference`): {extra['host_ms']:.1f} ms per point over "
+            f"2 points, ONE run, no spread taken.  counts, dead and M of the last of them {'EQUAL the statement in every bit' if extra['equal'] else 'DIFFER from the statement'}; largest "
+            f"relative |device - host| of a sum: {extra['deviation']:.2e}."]
+
+
+def boot_intro(repeats, how):
+    return (f"K = {K} points per call, B = {BOOT_REPLICATES} replicates, {repeats} calls per row after two warm-up calls.  ONE run, nothing tuned, no ratio promised.  Times in ms; device "
+            f"times are HIP-event times of the launches after the log-weight pass, summed over the call and divided by K: `tile` is draw tile, draw merge and the bootstrap tile launch, "
+            f"`merge` the bootstrap merge launch.  The block shape (8 slices of 128 samples x 32 replicate groups) was not chosen by measurement; no alternative was timed.  "
+            f"`parent`: {how}".rstrip())
+
+
+def boot_tail(res):
+    return [f"Scratch is {max(r[4] for r in res)} bytes in every kernel listed.  `boot_tile_kernel` holds the tile's 1 024 weights (8 KB), a byte per sample, and the 8 x 128 slice sums and "
+            "counts of a pass (8 KB + 4 KB) in LDS.", ""]
+
+
 QUANTITIES = f"C = 3 quantities ({', '.join(MASS_Z)})"
 WEIGHTED_LABEL = {"hist_merge_kernel<true>": "hist_merge_kernel<true> (weighted)", "marg_add_kernel<true>": "marg_add_kernel<true> (weighted)"}
 COMMON = dict(style="spread", columns=MASS_Z, relabel={}, resources_tail=lambda res: [], check=lambda c, extra: None)
@@ -643,6 +696,16 @@ ENTRIES = {e.name: e for e in (
                  ("hist", "`weighted_histograms`, device time per point after the log-weight pass")],
            compare=("moment", "hist"), spans=[("moment", "`point_moments` (unchanged code)", " per point"), ("hist", "`weighted_histograms` (unchanged code)", " per point")],
            unmeasured="NOT MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
+    record(style="calls", columns=MASS_CHI, resources_tail=boot_tail, name="point_bootstrap", symbol="gwi_point_bootstrap", title="# Bootstrap replicates of the importance sums: measured times",
+           kernels="boot_tile_kernel|boot_merge_kernel|draw_tile_kernel|draw_merge_kernel",
+           setup=boot_setup, one_round=boot_round, notes=boot_notes, check=boot_check, intro=boot_intro,
+           rows=[("boot", "`point_bootstrap`, device time per point after the log-weight pass"), ("boot tile", "... of which draw tile / merge and the bootstrap tile launch"),
+                 ("boot merge", "... of which the merge launch"), ("boot logw", "`point_bootstrap`, log-weight pass per point (host clock)"),
+                 ("boot wall", "`point_bootstrap`, wall time per point of the call"), ("tails", "`point_tails`, device time per point after the log-weight pass"),
+                 ("hist", "`weighted_histograms`, device time per point after the log-weight pass")],
+           compare=("tails", "hist"), spans=[("tails", "`point_tails` (unchanged code; a difference is process noise)", " per point"),
+                                             ("hist", "`weighted_histograms` (unchanged code; a difference is process noise)", " per point")],
+           unmeasured="NOTHING WAS MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
 )}
 
 
