@@ -488,6 +488,12 @@ def load_library():
         lib.gwi_point_bootstrap.argtypes = [vp, _DP, C.c_int32, _DP, _DP, _I32P, C.POINTER(C.c_int64)]
         lib.gwi_point_bootstrap_times.restype = None
         lib.gwi_point_bootstrap_times.argtypes = [_DP, _DP, _DP, _I32P]
+    if hasattr(lib, "gwi_point_histograms2d"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing; not in EXPORTED_SYMBOLS (a digit in the name)
+        _I32P = C.POINTER(C.c_int32)
+        lib.gwi_point_histograms2d.restype = C.c_int32
+        lib.gwi_point_histograms2d.argtypes = [vp, _DP, C.c_int32, C.c_int32, _I32P, _DP, _DP, _DP, _DP, _DP, _I32P, _I32P, _DP]
+        lib.gwi_point_hist2d_times.restype = None
+        lib.gwi_point_hist2d_times.argtypes = [_DP, _DP, _DP, _I32P]
     if hasattr(lib, "gwi_effective_spins"):  # absent from older builds loaded through GWI_ENGINE_LIB for A/B timing
         _I32P = C.POINTER(C.c_int32)
         lib.gwi_effective_spins.restype = C.c_int32

@@ -575,6 +575,14 @@ struct BootBuffers {
   unsigned long long seed = 0;
   int n_rep = 0, first_rep = 0;
 };
+// ... and of the per-point joint histograms (gwi_hist2d.h), which read the codes of gwi_set_histogram_bins where they lie: ONE pair's
+// partials [n_tiles][B B] and shares [n_ev + 1][B B], the point's segment flags [n_ev + 1], the running sums [n_ev + 1][n_pairs][B B]
+// with the dead counts and weight sums [n_ev + 1] of one call, and the staged rows [64][n_pairs][B B] of either kind and [64][2]
+// (reserved on the entry's first call, grown on demand, kept).  A pointer for ConditionalBuffers' reason, released with it.
+struct Hist2dBuffers {
+  DeviceBuffer<double> d_partial, d_share, d_sums, d_vsum, d_obs, d_pred;
+  DeviceBuffer<int> d_seg_dead, d_dead, d_live;
+};
 }  // namespace
 
 struct gwi_engine {
@@ -714,6 +722,7 @@ struct gwi_engine {
   RankcorrBuffers* rankcorr = nullptr;  // gwi_set_rankcorr_columns / gwi_point_rank_correlations (released with `cond`)
   TailBuffers* tail = nullptr;          // gwi_set_tail_sizes / gwi_point_tails (released with `cond`)
   BootBuffers* boot = nullptr;          // gwi_set_bootstrap / gwi_point_bootstrap (released with `cond`)
+  Hist2dBuffers* hist2d = nullptr;      // gwi_point_histograms2d (released with `cond`)
 };
 
 namespace {
@@ -4435,6 +4444,8 @@ __attribute__((noinline)) void release_moment_and_conditional_buffers(gwi_handle
   h->tail = nullptr;
   delete h->boot;
   h->boot = nullptr;
+  delete h->hist2d;
+  h->hist2d = nullptr;
 }
 }  // namespace
 extern "C" {
@@ -4818,6 +4829,130 @@ gwi_status gwi_point_bootstrap(gwi_handle h, const double* thetas, int32_t k, do
 }
 
 void gwi_point_bootstrap_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) { g_point_bootstrap_times.report(logw_ms, tile_ms, merge_ms, launches); }
+
+// ---- per-point joint histograms of two bin columns: every segment's table, the catalog's mixture, the predicted table (gwi_hist2d.h) --
+// (the header is included here for gwi_cond.h's reason)
+}  // extern "C"
+#include "gwi_hist2d.h"
+extern "C" {
+static thread_local StageTimes g_point_hist2d_times;
+
+gwi_status gwi_point_histograms2d(gwi_handle h, const double* thetas, int32_t k, int32_t n_pairs, const int32_t* pairs, const double* v, double* hist_pe, double* hist_inj,
+                                  double* obs, double* pred, int32_t* live, int32_t* n_dead, double* vsum) {
+  if (!h) return GWI_ERR_INVALID;
+  const char* who = "gwi_point_histograms2d";
+  g_point_hist2d_times = StageTimes();
+  namespace J = gwi::hist2d;
+  const PostprocessBuffers::Histogram& hist = h->post.hist;
+  gwi_status st = post_preflight(h, who, "sum on", "the injection table needs", [&] { return std::string(h->variant ? "" : "the engine has no scan kernel"); });
+  if (st != GWI_OK) return st;
+  // (after the shard refusal, as gwi_point_moments: a shard cannot be given bins, and says that it is one)
+  const bool with_pe = hist.d_bins_pe.ptr != nullptr, with_inj = hist.d_bins_inj.ptr != nullptr;
+  std::string why = bad_point_args(h, hist.cols ? "" : "no bins are set (gwi_set_histogram_bins)", thetas, k, {{"pairs", pairs}, {"obs", obs}, {"pred", pred}, {"live", live}});
+  if (why.empty() && (n_pairs < 1 || n_pairs > J::kMaxPairs)) why = "n_pairs = " + std::to_string(n_pairs) + " is not in 1 ... " + std::to_string(J::kMaxPairs);
+  for (int r = 0; why.empty() && r < n_pairs; ++r)
+    for (int side = 0; why.empty() && side < 2; ++side)
+      if (pairs[2 * r + side] < 0 || pairs[2 * r + side] >= hist.cols)
+        why = "pair " + std::to_string(r) + ": bin column " + std::to_string(pairs[2 * r + side]) + " is not in 0 ... " + std::to_string(hist.cols - 1) + " (gwi_set_histogram_bins)";
+  if (why.empty() && hist.bins > J::kMaxBins)
+    why = "the bins were set with n_bins = " + std::to_string(hist.bins) + ": a joint table takes at most " + std::to_string(J::kMaxBins) + " bins per axis";
+  if (why.empty() && v) why = bad_point_weights(v, k, h->n_ev + 1);
+  if (!why.empty()) return fail(h, GWI_ERR_INVALID, std::string(who) + ": " + why);
+  J::Args a;
+  std::memset(&a, 0, sizeof(a));
+  long long n_tiles = 0;
+  st = draw_workspace(h, who, "tiles", &a.d, &n_tiles);  // (as gwi_set_histogram_bins found it)
+  if (st != GWI_OK) return st;
+  const size_t n_segs = (size_t)(h->n_ev + 1), n_cells = (size_t)hist.bins * (size_t)hist.bins, per_point = (size_t)n_pairs * n_cells;
+  const size_t per_seg = per_point, n_pe_out = (size_t)h->n_ev * per_seg;
+  if (!h->hist2d) h->hist2d = new (std::nothrow) Hist2dBuffers();
+  if (!h->hist2d) return fail(h, GWI_ERR_INVALID, std::string(who) + ": out of host memory");
+  Hist2dBuffers& jb = *h->hist2d;
+  GWI_HIP(jb.d_partial.reserve((size_t)n_tiles * n_cells));
+  GWI_HIP(jb.d_share.reserve(n_segs * n_cells));
+  GWI_HIP(jb.d_seg_dead.reserve(n_segs));
+  GWI_HIP(jb.d_obs.reserve((size_t)kStagePoints * per_point));
+  GWI_HIP(jb.d_pred.reserve((size_t)kStagePoints * per_point));
+  GWI_HIP(jb.d_live.reserve((size_t)kStagePoints * 2));
+  // the caller's running sums: the points of this call are added onto them, so a request may be split over calls
+  const bool sum_pe = with_pe && hist_pe && n_pe_out, sum_inj = with_inj && hist_inj;
+  if (sum_pe || sum_inj) {
+    GWI_HIP(jb.d_sums.reserve(n_segs * per_seg));
+    if (sum_pe) GWI_HIP(hipMemcpy(jb.d_sums, hist_pe, sizeof(double) * n_pe_out, hipMemcpyHostToDevice));
+    else if (n_pe_out) GWI_HIP(hipMemsetAsync(jb.d_sums, 0, sizeof(double) * n_pe_out, h->stream));
+    if (sum_inj) GWI_HIP(hipMemcpy(jb.d_sums + n_pe_out, hist_inj, sizeof(double) * per_seg, hipMemcpyHostToDevice));
+    else GWI_HIP(hipMemsetAsync(jb.d_sums + n_pe_out, 0, sizeof(double) * per_seg, h->stream));
+    a.hist = jb.d_sums;
+  }
+  if (n_dead) {
+    GWI_HIP(jb.d_dead.reserve(n_segs));
+    GWI_HIP(hipMemcpy(jb.d_dead, n_dead, sizeof(int) * n_segs, hipMemcpyHostToDevice));
+    a.n_dead = jb.d_dead;
+  }
+  const double* d_v = nullptr;
+  if (v) {
+    st = upload_point_weights(h, v, k, &d_v);
+    if (st != GWI_OK) return st;
+    if (vsum) {
+      GWI_HIP(jb.d_vsum.reserve(n_segs));
+      GWI_HIP(hipMemcpy(jb.d_vsum, vsum, sizeof(double) * n_segs, hipMemcpyHostToDevice));
+      a.vsum = jb.d_vsum;
+    }
+  }
+  StagedRows rows(h, k);  // 2 n_pairs B B doubles and two ints per point
+  rows.add(obs, jb.d_obs.ptr, per_point);
+  rows.add(pred, jb.d_pred.ptr, per_point);
+  rows.add(live, jb.d_live.ptr, 2);
+  // a set without bins is left out of the tile and merge launches; its side of the point's rows comes back NaN
+  const QueryCover cover(with_pe, with_inj, h->n_ev, a.d);
+  a.bins_pe = hist.d_bins_pe;
+  a.bins_inj = hist.d_bins_inj;
+  a.partial = jb.d_partial;
+  a.share = jb.d_share;
+  a.seg_dead = jb.d_seg_dead;
+  a.n_bins = hist.bins;
+  a.n_pairs = n_pairs;
+  a.first_tile = cover.first_tile;
+  a.first_seg = cover.first_seg;
+  a.with_pe = with_pe ? 1 : 0;
+  a.with_inj = with_inj ? 1 : 0;
+  const unsigned cell_blocks = (unsigned)((n_cells + J::kBlock - 1) / J::kBlock);
+  const auto pair_tiles = [&](int r) {
+    a.pair = r;
+    a.cx = pairs[2 * r];
+    a.cy = pairs[2 * r + 1];
+    if (cover.tiles) hipLaunchKernelGGL(J::hist2d_tile_kernel, dim3((unsigned)cover.tiles), dim3(J::kBlock), sizeof(double) * n_cells, h->stream, a);
+  };
+  const auto pair_rest = [&]() {
+    if (cover.segs) hipLaunchKernelGGL(J::hist2d_merge_kernel, dim3((unsigned)cover.segs, cell_blocks), dim3(J::kBlock), 0, h->stream, a);
+    hipLaunchKernelGGL(J::hist2d_mix_kernel, dim3(cell_blocks), dim3(J::kBlock), 0, h->stream, a);
+  };
+  // the timed split is that of the first pair: tile | merge + mix; the launches of the pairs that follow (one pair's partials are
+  // the whole workspace, so they run after the first pair's merge) are counted in the second stage
+  const auto tile = [&](int p) {  // into the point's slot of the stage
+    a.obs = rows.slot<double>(0, p);
+    a.pred = rows.slot<double>(1, p);
+    a.live = rows.slot<int>(2, p);
+    a.v = d_v ? d_v + (size_t)p * n_segs : nullptr;
+    pair_tiles(0);
+  };
+  const auto rest = [&](int) {
+    pair_rest();
+    for (int r = 1; r < n_pairs; ++r) {
+      pair_tiles(r);
+      pair_rest();
+    }
+  };
+  st = per_point_pass(h, who, thetas, k, &a.d, n_tiles, &g_point_hist2d_times, 2, 2 + 3 * n_pairs, tile, rest, [&](int p) { return rows.after(p); });
+  if (st != GWI_OK) return st;
+  if (sum_pe) GWI_HIP(hipMemcpy(hist_pe, jb.d_sums, sizeof(double) * n_pe_out, hipMemcpyDeviceToHost));
+  if (sum_inj) GWI_HIP(hipMemcpy(hist_inj, jb.d_sums + n_pe_out, sizeof(double) * per_seg, hipMemcpyDeviceToHost));
+  if (n_dead) GWI_HIP(hipMemcpy(n_dead, jb.d_dead, sizeof(int) * n_segs, hipMemcpyDeviceToHost));
+  if (a.vsum) GWI_HIP(hipMemcpy(vsum, jb.d_vsum, sizeof(double) * n_segs, hipMemcpyDeviceToHost));
+  return GWI_OK;
+}
+
+void gwi_point_hist2d_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches) { g_point_hist2d_times.report(logw_ms, tile_ms, merge_ms, launches); }
 
 // ---- marginal weights and their quantiles (gwi_quant.h) ---------------------------------------------------------------------
 enum { kQuantLogw, kQuantAdd, kQuantQuery };

@@ -904,6 +904,110 @@ def point_conditionals_reference(logw_pe, logw_inj, codes_pe, codes_inj, x_pe, x
     return out, dead
 
 
+MAX_HIST2D_BINS = 64   # bins per axis of gwi_point_histograms2d (gwi_hist2d.h: kMaxBins)
+MAX_HIST2D_PAIRS = 8   # pairs of one call (gwi_hist2d.h: kMaxPairs)
+
+
+def joint_table_segment(w, code_x, code_y, n_bins):
+    """ONE segment's joint table ``(B, B)`` for the weights ``w`` of :func:`draw_weights`: cell ``[bx, by]`` = (sum of ``w_i`` over the
+    samples coded ``bx`` and ``by``) / (sum of ``w_i`` over the segment).  A sample coded :data:`OUTSIDE_BIN` (or no bin) in either
+    column is in no cell but counts in the total.  ``None`` when the total is 0 or not finite."""
+    total = w.sum()
+    if not (total > 0.0 and np.isfinite(total)):
+        return None
+    cx, cy = np.asarray(code_x).ravel().astype(np.int64), np.asarray(code_y).ravel().astype(np.int64)
+    inside = (cx < n_bins) & (cy < n_bins)
+    table = np.zeros(n_bins * n_bins)
+    np.add.at(table, cx[inside] * n_bins + cy[inside], w[inside])
+    return (table / total).reshape(n_bins, n_bins)
+
+
+def point_histograms2d_reference(logw_pe, logw_inj, pe_mask, inj_mask, pe_bins, inj_bins, n_bins, pairs, v=None):
+    """One hyper-parameter point of ``gwi_point_histograms2d``: the arguments of :func:`weighted_histograms_reference` and
+    ``pairs (R, 2)`` of bin columns ``(cx, cy)`` -> a dict.  ``hist_pe (n_ev, R, B, B)`` and ``hist_inj (R, B, B)``: what the point adds to
+    the running sums, ``v`` times :func:`joint_table_segment` per segment and pair (``None`` for a set whose bins are ``None``; zeros for
+    a dead segment).  ``obs (R, B, B)``: (the sum of the live events' tables, in event order) / their number; ``pred (R, B, B)``: the
+    injection set's table; NaN without a live event / for a dead injection set / for a set without bins.  ``live (2,) int32`` = (live
+    events, 1 if the injection set is live else 0); ``n_dead (n_ev + 1,) int32``: 1 for every segment without weight of a set that has
+    bins; ``vsum (n_ev + 1,)``: ``v`` for every live segment of such a set (``None`` without ``v``).  ``v (n_ev + 1,)`` is the point's row
+    of linear weights in ``[0, 1]``: a segment whose ``v`` is 0 adds nothing and is not counted in ``n_dead``; ``obs``, ``pred`` and
+    ``live`` do not depend on ``v``."""
+    logw_pe = np.asarray(logw_pe, dtype=np.float64)
+    n_ev, n_bins = logw_pe.shape[0], int(n_bins)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if not 1 <= pairs.shape[0] <= MAX_HIST2D_PAIRS:
+        raise ValueError(f"{pairs.shape[0]} pairs: between 1 and {MAX_HIST2D_PAIRS}")
+    if not 1 <= n_bins <= MAX_HIST2D_BINS:
+        raise ValueError(f"n_bins = {n_bins}: between 1 and {MAX_HIST2D_BINS}")
+    if pe_bins is None and inj_bins is None:
+        raise ValueError("pe_bins and inj_bins are both None")
+    n_cols = np.asarray(pe_bins if pe_bins is not None else inj_bins).shape[0]
+    if np.any(pairs < 0) or np.any(pairs >= n_cols):
+        raise ValueError(f"a pair is two bin columns below {n_cols}")
+    if v is not None:
+        v = point_weights_array(np.asarray(v, dtype=np.float64).reshape(1, -1), 1, n_ev + 1)[0]
+    n_pairs = pairs.shape[0]
+    n_dead, vsum, live = np.zeros(n_ev + 1, dtype=np.int32), np.zeros(n_ev + 1), np.zeros(2, dtype=np.int32)
+    obs, pred = np.full((n_pairs, n_bins, n_bins), np.nan), np.full((n_pairs, n_bins, n_bins), np.nan)
+    hist_pe = hist_inj = None
+
+    def segment(seg, logw, mask, codes):
+        """``(tables (R, B, B) or None when dead, what the segment adds to the running sums)``"""
+        w = draw_weights(logw, mask)
+        tables = [joint_table_segment(w, codes[cx], codes[cy], n_bins) for cx, cy in pairs]
+        alive = tables[0] is not None
+        pv = 1.0 if v is None else v[seg]
+        add = np.zeros((n_pairs, n_bins, n_bins))
+        if pv != 0.0:
+            if not alive:
+                n_dead[seg] = 1
+            else:
+                vsum[seg] = pv
+                add = np.stack(tables) if v is None else pv * np.stack(tables)
+        return (np.stack(tables) if alive else None), add
+
+    if pe_bins is not None:
+        pe_bins = np.asarray(pe_bins)
+        pe_mask = None if pe_mask is None else np.asarray(pe_mask).reshape(logw_pe.shape)
+        hist_pe = np.zeros((n_ev, n_pairs, n_bins, n_bins))
+        total = np.zeros((n_pairs, n_bins, n_bins))
+        for ev in range(n_ev):
+            tables, hist_pe[ev] = segment(ev, logw_pe[ev], None if pe_mask is None else pe_mask[ev], pe_bins[:, ev])
+            if tables is not None:
+                total += tables
+                live[0] += 1
+        if live[0]:
+            obs = total / float(live[0])
+    if inj_bins is not None:
+        tables, hist_inj = segment(n_ev, logw_inj, inj_mask, np.asarray(inj_bins))
+        if tables is not None:
+            pred, live[1] = tables, 1
+    return {"hist_pe": hist_pe, "hist_inj": hist_inj, "obs": obs, "pred": pred, "live": live, "n_dead": n_dead, "vsum": vsum if v is not None else None}
+
+
+def joint_table_summaries(p):
+    """Summaries of joint tables ``p (..., B, B)`` of non-negative shares whose in-range total ``t = sum p`` may fall short of 1 (the
+    rest lies outside the edges): a dict with the marginals ``px (..., B) = sum_y p / t`` and ``py (..., B) = sum_x p / t``, the plug-in
+    mutual information ``mi (...)`` = ``sum over the cells with p > 0 of (p / t) log((p / t) / (px py))`` in nats, ``total (...)`` = ``t``
+    and ``outside (...)`` = ``1 - t``.  A table with ``t = 0`` (or a NaN in it) gives NaN marginals and ``mi``.
+
+    The plug-in estimate is biased UPWARD by roughly ``(cells - 1) / (2 n_eff)`` with ``cells`` the occupied cells and ``n_eff`` the
+    effective number of samples behind the table; no correction is applied."""
+    p = np.asarray(p, dtype=np.float64)
+    if p.ndim < 2 or p.shape[-1] != p.shape[-2]:
+        raise ValueError(f"p has shape {p.shape}; expected (..., B, B)")
+    t = p.sum(axis=(-2, -1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        good = t > 0.0
+        scale = np.where(good, t, np.nan)
+        q = p / scale[..., None, None]
+        px, py = q.sum(axis=-1), q.sum(axis=-2)
+        has = q > 0.0
+        ratio = np.where(has, q / (px[..., :, None] * py[..., None, :]), 1.0)
+        mi = np.where(good, (np.where(has, q, 0.0) * np.log(ratio)).sum(axis=(-2, -1)), np.nan)
+    return {"px": px, "py": py, "mi": mi, "total": t, "outside": 1.0 - t}
+
+
 def pareto_smooth(log_ratios):
     """Pareto-smoothed importance sampling on the point axis (Vehtari, Simpson, Gelman, Yao & Gabry, *Pareto smoothed importance
     sampling*; the fit is Zhang & Stephens 2009): ``log_ratios (K, n_seg)`` -> ``(log_weights (K, n_seg), khat (n_seg,))``.  Per column:

@@ -1,5 +1,5 @@
 """The post-processing wrappers of :class:`gwinferno_amd.engine.NativePopulationLikelihood`: per-sample log-weights, index draws,
-injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments, conditional moments, rank correlations, tails and bootstrap replicates, marginal weights and their
+injection resampling, weighted histograms, per-point CDFs, PIT brackets, exact PITs, moments, conditional moments, rank correlations, tails, bootstrap replicates and joint histograms, marginal weights and their
 quantiles and kernel density estimates.
 Host-side argument checks and array bookkeeping only -- every per-sample operation runs in gwinferno_amd/csrc (HIP, gfx950).
 """
@@ -427,6 +427,60 @@ class PostprocessMixin:
                                                     (np.float64, np.float64, np.int32, np.int64),
                                                     lambda k, s: ((k, self.n_ev + 1, s[0]), (k, self.n_ev + 1, 2), (k, self.n_ev + 1), (self.n_ev + 1, s[0])), thetas)
         return sums, stats, dead, counts
+
+    def point_histograms2d(self, thetas, pairs, point_weights=None, accumulate=True, out=None):
+        """Per-point joint histograms of pairs of bin columns, on the device (``gwi_point_histograms2d``; semantics:
+        :func:`gwinferno_amd.draws.point_histograms2d_reference`).  ``pairs`` is ``(R, 2)`` of ``(cx, cy)``, both bin columns of
+        :meth:`set_histogram_bins`, read where they lie; ``1 <= R <= 8`` and the bins were set with ``n_bins = B <= 64``.  ``thetas`` is one
+        point ``(n_theta,)`` or ``(k, n_theta)``.  Returns a dict: ``obs (k, R, B, B)``, per point the mean over the live events of the
+        event's table of weight shares (cell ``[bx, by]`` = the share of the samples coded ``bx`` in ``cx`` and ``by`` in ``cy``); ``pred
+        (k, R, B, B)``, the injection set's table; ``live (k, 2) int32`` = (live events, injection set live); and the running SUMS over the
+        points ``hist_pe (n_ev, R, B, B)``, ``hist_inj (R, B, B)`` with ``n_dead (n_ev + 1,) int32``, the points at which the segment had
+        no weight, and ``vsum (n_ev + 1,)``, as :meth:`weighted_histograms` keeps them (``None`` for a set without bins; NaN ``obs`` /
+        ``pred`` for it).  ``out`` is such a dict from an earlier call with the same pairs: the new points are added onto its sums in
+        place, with the bits one call over all points would give.  ``accumulate=False`` keeps no sums (``None`` in their places) and leaves
+        ``obs`` / ``pred`` / ``live`` as they are.  ``point_weights`` -- ``(k, n_ev + 1)``, the injection set last, or ``(k,)`` -- gives
+        every (point, segment) a linear weight ``v`` in ``[0, 1]`` in the SUMS only (``vsum`` is ``None`` without): ``v = 1`` gives the
+        bits of the call without weights, ``v = 0`` adds nothing and is not counted in ``n_dead``; ``obs`` and ``pred`` do not depend on
+        it.  ``2 R B B`` doubles come back per point; the points may be split over calls without changing a bit.  Not available on an
+        engine that holds a shard (``world > 1``)."""
+        from .draws import MAX_HIST2D_PAIRS
+
+        self._whole_catalog("point_histograms2d", "the injection table needs")
+        thetas = self._points(thetas)
+        k = thetas.shape[0]
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        n_pairs = pairs.shape[0]
+        if not 1 <= n_pairs <= MAX_HIST2D_PAIRS:
+            raise ValueError(f"{n_pairs} pairs: between 1 and {MAX_HIST2D_PAIRS} can be asked for in one call")
+        v = None if point_weights is None else self._point_weights(point_weights, k)
+        i32 = C.POINTER(C.c_int32)
+        shape = getattr(self, "_hist_shape", None)
+        if shape is None:
+            self._nothing_set("point_histograms2d", "bins are set (set_histogram_bins)", self.lib.gwi_point_histograms2d, N.as_dp(thetas), k, n_pairs, pairs.ctypes.data_as(i32),
+                              None, None, None, None, None, None, None, None)
+        _, n_bins, with_pe, with_inj = shape
+        table = (n_pairs, n_bins, n_bins)
+        want = {"hist_pe": ((self.n_ev, *table), np.float64) if with_pe else None, "hist_inj": (table, np.float64) if with_inj else None,
+                "n_dead": ((self.n_ev + 1,), np.int32), "vsum": ((self.n_ev + 1,), np.float64) if v is not None else None}
+        if not accumulate:
+            if out is not None:
+                raise ValueError("accumulate=False keeps no sums: out must be None")
+            sums = dict.fromkeys(want)
+        elif out is None:
+            sums = {name: None if w is None else np.zeros(w[0], dtype=w[1]) for name, w in want.items()}
+        else:
+            sums = {}
+            for name, w in want.items():
+                o = out.get(name)
+                if w is not None and (not isinstance(o, np.ndarray) or o.shape != w[0] or o.dtype != w[1] or not o.flags.c_contiguous or not o.flags.writeable):
+                    raise ValueError(f"out: {name} must be a writeable C-contiguous {np.dtype(w[1]).name} array of shape {w[0]}")
+                sums[name] = o if w is not None else None
+        obs, pred, live = np.empty((k, *table)), np.empty((k, *table)), np.empty((k, 2), dtype=np.int32)
+        self._check(self.lib.gwi_point_histograms2d(self.handle, N.as_dp(thetas), k, n_pairs, pairs.ctypes.data_as(i32), N.as_dp(v), N.as_dp(sums["hist_pe"]),
+                                                    N.as_dp(sums["hist_inj"]), N.as_dp(obs), N.as_dp(pred), live.ctypes.data_as(i32),
+                                                    None if sums["n_dead"] is None else sums["n_dead"].ctypes.data_as(i32), N.as_dp(sums["vsum"])))
+        return {"obs": obs, "pred": pred, "live": live, **sums}
 
     def marginal_weights_reset(self):
         """Zeroes the marginal weights, the dead counts and the number of points (``gwi_marginal_weights_reset``)."""

@@ -1701,3 +1701,220 @@ def likelihood_bootstrap(eng, thetas, total_inj, n_replicates=128, seed=0, nobs=
                variance_log_likelihood=var_site, n_nan_replicates=(~np.isfinite(rep)).sum(axis=1).astype(np.int64), counts=counts, sums=sums, stats=stats, dead=dead,
                n_replicates=n_replicates, seed=int(seed))
     return out
+
+
+def _joint_setup(eng, pe_values, inj_values, edges, pairs, param_names):
+    """``(names, pair names, pairs (R, 2), grid, n_bins, pe_bins (C, n_ev, n_pe), inj_bins (C, n_inj) or None)`` of a joint-table call:
+    the quantities digitised once with ``np.histogram``'s rule (:func:`gwinferno_amd.draws.digitize`)."""
+    from . import draws as D
+
+    names = list(param_names) if param_names is not None else list(pe_values)
+    if not 1 <= len(names) <= 8:
+        raise ValueError("between 1 and 8 quantities can be binned in one pass")
+    grid = {p: np.asarray(edges[p], dtype=np.float64).ravel() for p in names}
+    n_bins = grid[names[0]].size - 1
+    if any(g.size - 1 != n_bins for g in grid.values()):
+        raise ValueError("every quantity needs the same number of bins")
+    if not 1 <= n_bins <= D.MAX_HIST2D_BINS:
+        raise ValueError(f"n_bins must be in 1 ... {D.MAX_HIST2D_BINS}")
+    if pairs is None:
+        pairs = [(names[i], names[j]) for i in range(len(names)) for j in range(i + 1, len(names))]
+    pair_names = [tuple(p) for p in pairs]
+    if not 1 <= len(pair_names) <= D.MAX_HIST2D_PAIRS:
+        raise ValueError(f"{len(pair_names)} pairs: between 1 and {D.MAX_HIST2D_PAIRS} can be asked for in one call")
+    for p in pair_names:
+        if len(p) != 2 or p[0] not in names or p[1] not in names:
+            raise ValueError(f"unknown pair {p!r}: a pair is two of {names}")
+    index = np.array([[names.index(x), names.index(y)] for x, y in pair_names], dtype=np.int32)
+    _, v_pe, v_inj = _summary_columns(eng, pe_values, inj_values, None, None, names)
+    pe_bins = np.stack([D.digitize(v_pe[c], grid[p]) for c, p in enumerate(names)])
+    inj_bins = None if v_inj is None else np.stack([D.digitize(v_inj[c], grid[p]) for c, p in enumerate(names)])
+    return names, pair_names, index, grid, n_bins, pe_bins, inj_bins
+
+
+def event_joint_posteriors(eng, thetas, pe_values, edges, pairs=None, inj_values=None, param_names=None, point_weights=None, leave_one_out=False, total_inj=None, nobs=None,
+                           marginalize_selection=False, backend="device", chunk=HISTOGRAM_CHUNK):
+    """The two-dimensional panels of the corner plot of every event's population-informed posterior, marginalised over K hyper-posterior
+    draws, at histogram cost: per event, pair of quantities ``(x, y)`` and cell the mean over the draws of ``(sum of w_i in
+    the cell) / (sum of w_i)`` with ``w_i = p(x_i | theta_k) / prior_i`` -- the joint counterpart of :func:`reweighted_event_posteriors`
+    -- and the same table for the injection set, the predicted detected distribution.  On the device (``eng.point_histograms2d``) the
+    weights never leave HBM.
+
+    ``thetas`` is ``(K, n_theta)``.  ``pe_values`` maps a name to ``(n_ev, n_pe)``, ``inj_values`` the same names to ``(n_inj,)`` (``None``:
+    no predicted table); ``edges`` maps each name to increasing bin edges, all with the same number of bins ``B <= 64``
+    (``np.histogram``'s rule).  ``param_names`` selects and orders the names (at most 8); ``pairs`` is a list of ``(x name, y name)``, at
+    most 8, default every pair ``i < j`` of the names.  The point weights are :func:`reweighted_event_posteriors`': equal by default,
+    ``point_weights (K, n_ev + 1)`` or ``(K,)`` in ``[0, 1]``, ``leave_one_out=True`` for :func:`leave_one_out_weights` and
+    ``leave_one_out="psis"`` for :func:`pareto_smoothed_loo_weights` (``total_inj`` is then needed); they go to the device with the
+    points.  The device backend replaces the engine's histogram bins; the draw mask the engine holds stays.  ``backend="host"`` runs
+    the NumPy statement (:func:`gwinferno_amd.draws.point_histograms2d_reference`) on ``eng.log_weights``, without a mask: the statement
+    the kernels are tested against, not a fall-back.
+
+    Returns a dict: ``pairs`` (the name pairs), ``edges``; ``events (n_ev, R, B, B)``, the mean share per cell, indexed ``[x bin, y
+    bin]``, and ``events_density``, the same divided by the cell areas -- ``pcolormesh(edges[x], edges[y], events_density[e, r].T)``;
+    ``predicted (R, B, B)`` and ``predicted_density`` (with ``inj_values``); ``outside``, ``{"events": (n_ev, R), "predicted": (R,)}``,
+    the weight share outside the edges in either coordinate; ``n_points``, the same layout per segment, the points at which it had
+    weight (NaN tables where that is 0); with weights ``point_weight_sum (n_ev + 1,)``, and with leave-one-out weights ``elpd_loo``,
+    ``neff_points`` and for ``"psis"`` ``pareto_k``."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k, n_ev = thetas.shape[0], eng.n_ev
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    chunk = int(chunk)
+    if not 1 <= chunk <= HISTOGRAM_CHUNK:
+        raise ValueError(f"chunk must be in 1 ... {HISTOGRAM_CHUNK}")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    if not (isinstance(leave_one_out, bool) or leave_one_out == "psis"):
+        raise ValueError(f"leave_one_out must be False, True or 'psis', not {leave_one_out!r}")
+    names, pair_names, index, grid, n_bins, pe_bins, inj_bins = _joint_setup(eng, pe_values, inj_values, edges, pairs, param_names)
+    if leave_one_out == "psis":
+        if point_weights is not None:
+            raise ValueError("leave_one_out='psis' makes the point weights itself: point_weights must be None")
+        if total_inj is None:
+            raise ValueError("leave_one_out='psis' needs total_inj")
+        loo = pareto_smoothed_loo_weights(eng, thetas, total_inj, nobs=nobs, marginalize_selection=marginalize_selection)
+        v = loo["point_weights"]
+    else:
+        v, loo = _resolve_point_weights(eng, thetas, point_weights, leave_one_out, total_inj, nobs, marginalize_selection)
+    n_pairs = len(pair_names)
+    if backend == "device":
+        eng.set_histogram_bins(pe_bins, inj_bins, n_bins=n_bins)
+        out = None
+        for i in range(0, k, chunk):
+            out = eng.point_histograms2d(thetas[i : i + chunk], index, out=out, **({} if v is None else {"point_weights": v[i : i + chunk]}))
+        hist_pe, hist_inj, dead, vsum = out["hist_pe"], out["hist_inj"], out["n_dead"], out["vsum"]
+    else:
+        hist_pe, hist_inj = np.zeros((n_ev, n_pairs, n_bins, n_bins)), (None if inj_bins is None else np.zeros((n_pairs, n_bins, n_bins)))
+        dead, vsum = np.zeros(n_ev + 1, dtype=np.int32), (None if v is None else np.zeros(n_ev + 1))
+        for p, th in enumerate(thetas):
+            lw_pe, lw_inj = eng.log_weights(th)
+            one = D.point_histograms2d_reference(lw_pe, lw_inj, None, None, pe_bins, inj_bins, n_bins, index, v=None if v is None else v[p])
+            hist_pe += one["hist_pe"]
+            if hist_inj is not None:
+                hist_inj += one["hist_inj"]
+            dead += one["n_dead"]
+            if v is not None:
+                vsum += one["vsum"]
+    live = (k - dead).astype(np.float64) if vsum is None else vsum
+    area = np.stack([np.outer(np.diff(grid[x]), np.diff(grid[y])) for x, y in pair_names])
+    result = {"pairs": pair_names, "edges": {p: grid[p] for p in names}}
+    _point_weight_entries(result, loo, vsum)
+    if loo is not None and "pareto_k" in loo:
+        result["pareto_k"] = loo["pareto_k"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        events = hist_pe / live[:n_ev, None, None, None]
+        result.update(events=events, events_density=events / area, outside={"events": 1.0 - events.sum(axis=(-2, -1))},
+                      n_points={"events": (k - dead[:n_ev]).astype(np.int64)})
+        if hist_inj is not None:
+            predicted = hist_inj / live[n_ev]
+            result.update(predicted=predicted, predicted_density=predicted / area)
+            result["outside"]["predicted"] = 1.0 - predicted.sum(axis=(-2, -1))
+            result["n_points"]["predicted"] = int(k - dead[n_ev])
+    return result
+
+
+def joint_check_summaries(obs, pred, live, point_weights=None, levels=(5, 50, 95)):
+    """The host half of :func:`catalog_joint_check` on per-point tables ``obs``, ``pred (K, R, B, B)`` and ``live (K, 2)`` as
+    ``Engine.point_histograms2d`` returns them.  A point without a live event or with a dead injection set is SKIPPED -- counted, never
+    divided: its rows are NaN in every per-point output and it is left out of the bands and shares."""
+    from . import draws as D
+
+    obs, pred, live = np.asarray(obs, dtype=np.float64), np.asarray(pred, dtype=np.float64), np.asarray(live)
+    k = obs.shape[0]
+    if obs.ndim != 4 or pred.shape != obs.shape or live.shape != (k, 2) or k < 1:
+        raise ValueError("obs and pred are (K, R, B, B) and live is (K, 2)")
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or levels.size < 1 or not np.all((levels >= 0.0) & (levels <= 100.0)):
+        raise ValueError("levels must be percentiles in [0, 100]")
+    if point_weights is None:
+        v = np.ones(k)
+    else:
+        v = np.asarray(point_weights, dtype=np.float64)
+        if v.shape != (k,) or not np.all(np.isfinite(v)) or np.any(v < 0.0) or not np.any(v > 0.0):
+            raise ValueError(f"point_weights are ({k},) finite non-negative numbers, not all 0")
+    no_event, no_inj = live[:, 0] == 0, live[:, 1] == 0
+    used = ~(no_event | no_inj)
+    hole = np.full(obs.shape[1:], np.nan)
+    obs_u, pred_u = np.where(used[:, None, None, None], obs, hole), np.where(used[:, None, None, None], pred, hole)
+    delta = obs_u - pred_u
+    s_obs, s_pred = D.joint_table_summaries(obs_u), D.joint_table_summaries(pred_u)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tv = 0.5 * np.abs(obs_u / s_obs["total"][..., None, None] - pred_u / s_pred["total"][..., None, None]).sum(axis=(-2, -1))
+        tv = np.where(used[:, None] & (s_obs["total"] > 0.0) & (s_pred["total"] > 0.0), tv, np.nan)
+        has = ~np.isnan(delta)
+        den = (v[:, None, None, None] * has).sum(axis=0)
+        p_pos = (v[:, None, None, None] * (has & (np.where(has, delta, 0.0) > 0.0))).sum(axis=0) / den
+    delta_mi = s_obs["mi"] - s_pred["mi"]
+    q = levels / 100.0
+    return {"levels": levels, "obs": obs_u, "pred": pred_u, "delta": delta, "bands_delta": D.weighted_percentiles(delta, v, q), "p_delta_positive": p_pos,
+            "p_two_sided": 2.0 * np.minimum(p_pos, 1.0 - p_pos), "tv": tv, "bands_tv": D.weighted_percentiles(tv, v, q), "mi_obs": s_obs["mi"], "mi_pred": s_pred["mi"],
+            "delta_mi": delta_mi, "bands_mi_obs": D.weighted_percentiles(s_obs["mi"], v, q), "bands_mi_pred": D.weighted_percentiles(s_pred["mi"], v, q),
+            "bands_delta_mi": D.weighted_percentiles(delta_mi, v, q), "outside_obs": s_obs["outside"], "outside_pred": s_pred["outside"], "live": live,
+            "n_skipped": int(np.count_nonzero(~used)), "n_skipped_no_event": int(np.count_nonzero(no_event)), "n_skipped_dead_injections": int(np.count_nonzero(no_inj)),
+            "n_points": k}
+
+
+def catalog_joint_check(eng, thetas, pe_values, edges, inj_values, pairs=None, param_names=None, point_weights=None, levels=(5, 50, 95), backend="device", total_inj=None):
+    """Does the observed catalog fill the plane of two quantities the way the fitted population predicts for detected sources?  (DESIGN
+    8o.)  Pearson's rho (:func:`catalog_correlation_check`), the conditional moments (:func:`catalog_conditional_check`) and Spearman's
+    rho (:func:`catalog_rank_correlation_check`) compress the joint distribution to a number or two per pair; a dependence that is
+    neither linear nor monotone -- a sub-population in one corner of the ``q``-``chi_eff`` plane -- shows only in the table itself.  Per
+    hyper-posterior point k the device (``eng.point_histograms2d``) returns the observed table ``obs``, the equal-weight mixture of the
+    live events' population-informed tables, and ``pred``, the injection set's table.
+
+    ``thetas`` is ``(K, n_theta)``; ``pe_values``, ``inj_values`` (needed), ``edges``, ``param_names`` and ``pairs`` are
+    :func:`event_joint_posteriors`'.  ``point_weights (K,)`` -- finite, non-negative, not all 0; default equal -- weight the points in the
+    bands and shares; they are applied here and never go to the device.  ``levels`` are percentiles in ``[0, 100]``.  The device backend
+    replaces the engine's histogram bins; the draw mask stays.  ``backend="host"`` runs the NumPy statement
+    (:func:`gwinferno_amd.draws.point_histograms2d_reference`) on ``eng.log_weights``, without a mask: the statement the kernels are
+    tested against, not a fall-back.
+
+    Returns :func:`joint_check_summaries` of the tables with ``pairs`` and ``edges``: per point ``obs``, ``pred`` and ``delta = obs - pred
+    (K, R, B, B)``; per cell ``bands_delta (Q, R, B, B)``, ``p_delta_positive`` and ``p_two_sided = 2 min(p, 1 - p) (R, B, B)``; per point
+    and pair the total-variation distance of the tables renormalised to their in-range totals, ``tv = sum |obs / t_o - pred / t_p| / 2``,
+    and the mutual informations ``mi_obs``, ``mi_pred``, ``delta_mi`` (:func:`gwinferno_amd.draws.joint_table_summaries`), each ``(K, R)``
+    with ``bands_<key> (Q, R)``; ``outside_obs`` / ``outside_pred (K, R)``; the counts ``n_skipped``, ``n_skipped_no_event``,
+    ``n_skipped_dead_injections`` of points without a live event or with a dead injection set, which are skipped (NaN rows), never
+    divided; ``live (K, 2)`` and ``n_points``.
+
+    The plug-in mutual information is biased UPWARD by roughly ``(cells - 1) / (2 n_eff)``, and the two sides have different ``n_eff``:
+    the observed table rests on the events' PE samples, the predicted one on the found injections.  No correction is applied;
+    ``log_nEffs (K, n_ev + 1)``, the engine's own log effective sample sizes per point -- the events, then the injection set, without
+    the draw mask -- are returned beside it so that the size of the bias on either side can be judged (``total_inj`` is passed to
+    ``eng.evaluate_batch``; the effective sizes do not depend on it)."""
+    from . import draws as D
+
+    thetas = np.asarray(thetas, dtype=np.float64).reshape(-1, eng.n_theta)
+    k = thetas.shape[0]
+    if k < 1:
+        raise ValueError("thetas holds no point")
+    if backend not in ("device", "host"):
+        raise ValueError(f"backend must be 'device' or 'host', not {backend!r}")
+    if inj_values is None:
+        raise ValueError("the predicted table is the injection set's: inj_values is needed")
+    names, pair_names, index, grid, n_bins, pe_bins, inj_bins = _joint_setup(eng, pe_values, inj_values, edges, pairs, param_names)
+    if backend == "device":
+        eng.set_histogram_bins(pe_bins, inj_bins, n_bins=n_bins)
+        got = eng.point_histograms2d(thetas, index, accumulate=False)
+        obs, pred, live = got["obs"], got["pred"], got["live"]
+    else:
+        shape = (k, len(pair_names), n_bins, n_bins)
+        obs, pred, live = np.empty(shape), np.empty(shape), np.empty((k, 2), dtype=np.int32)
+        for p, th in enumerate(thetas):
+            lw_pe, lw_inj = eng.log_weights(th)
+            one = D.point_histograms2d_reference(lw_pe, lw_inj, None, None, pe_bins, inj_bins, n_bins, index)
+            obs[p], pred[p], live[p] = one["obs"], one["pred"], one["live"]
+    out = joint_check_summaries(obs, pred, live, point_weights=point_weights, levels=levels)
+    out.update(pairs=pair_names, edges={p: grid[p] for p in names})
+    log_neffs = np.empty((k, eng.n_ev + 1))
+    step = int(eng.max_batch)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k0 in range(0, k, step):
+            res = eng.evaluate_batch(thetas[k0 : k0 + step], float(eng.n_inj if total_inj is None else total_inj), min_neff_cut=False, max_variance_cut=False, want_grad=False)
+            for i, r in enumerate(res):
+                log_neffs[k0 + i, : eng.n_ev], log_neffs[k0 + i, eng.n_ev] = r.log_neffs, r.summary.log_nEff_inj
+    out["log_nEffs"] = log_neffs
+    return out

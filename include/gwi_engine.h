@@ -743,6 +743,47 @@ gwi_status gwi_point_bootstrap(gwi_handle h, const double* thetas, int32_t k, do
                                int32_t* dead /* [k][n_ev + 1] */, int64_t* counts /* [n_ev + 1][B] */);
 void gwi_point_bootstrap_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches); /* diagnostic only */
 
+/* Per-point joint (two-dimensional) histograms on the device: per hyper-parameter point, segment and pair (cx, cy) of the bin columns of
+ * gwi_set_histogram_bins the B x B table of weight shares -- what Pearson's rho (gwi_point_moments), the conditional moments
+ * (gwi_point_conditionals) and Spearman's rho (gwi_point_rank_correlations) each compress to a number or two per pair, and the only
+ * object that shows a dependence that is neither linear nor monotone (gwinferno_amd/csrc/gwi_hist2d.h; the NumPy statement is
+ * gwinferno_amd/draws.py: point_histograms2d_reference; the contract is DESIGN 8o).
+ *
+ * gwi_point_histograms2d(): pairs[r] = (cx, cy), both bin columns of gwi_set_histogram_bins, read where they lie: nothing is uploaded
+ * and there is no setter of this entry's own.  1 <= n_pairs <= 8; the bins must have been set with n_bins = B <= 64 (this entry alone
+ * refuses more; the other entries keep their 256).  Segments, lw_i, the masks of gwi_set_draw_mask, M, w_i = exp(lw_i - M) and the
+ * segment total S are gwi_draw_indices'.  For point k, segment s (the injection segment last), pair r and cell (bx, by)
+ *   q_s[r][bx][by] = (sum of w_i over the samples coded bx in column cx and by in column cy) / S
+ * (a sample coded 0xFFFF in either column counts in S and in no cell).  Per point come back
+ *   obs[k][r][bx][by]    (sum of q_e over the live events e, in event order) / n_live_events   NaN without a live event or PE bins
+ *   pred[k][r][bx][by]   q of the injection segment                                           NaN when it is dead or has no bins
+ *   live[k]              (n_live_events, 1 if the injection segment is live else 0)
+ * and, onto the caller's running sums (in/out, as gwi_weighted_histograms'; each may be NULL: not kept),
+ *   hist_pe[e][r] += v q_e   hist_inj[r] += v q_inj   n_dead[s] += 1 for a dead segment   vsum[s] += v for a live one (with v only)
+ * with v[k][s] in [0, 1] the point's linear weight of the segment, or v = NULL for 1 everywhere.  The quotient is formed as without
+ * weights and then multiplied in a product of its own: v = 1 gives the bits of v = NULL; v = 0 touches nothing of the segment's sums,
+ * n_dead included.  obs, pred and live do not depend on v.  A segment whose S is 0 or not finite is dead: it adds nothing and is left
+ * out of obs.  Every sum has a fixed shape (sample order inside a tile of 1 024 and a cell, then tile order, then event order for obs,
+ * then point order for the running sums) and there are no atomics: the bits are a pure function of (theta_k, codes, masks, pairs, v),
+ * whatever the split of the points over calls or the other pairs of the call; a pair (c, c) has gwi_weighted_histograms' bits for
+ * column c on its diagonal and exact zeros off it.  k >= 1 is not bound by the batch limit: the points are staged on the device 64 at a
+ * time; 2 n_pairs B B doubles and two ints come back per point.  The call changes no state another entry reads.  Not done: sharded
+ * handles; more than 64 bins per axis or 8 pairs; different bin counts per axis; three-way tables; per-event tables per point.
+ * GWI_ERR_INVALID (with a gwi_last_error message) for a null pointer among thetas, pairs, obs, pred and live, k < 1, n_pairs outside
+ * 1 ... 8, a column index outside the bin columns, bins set with more than 64 bins, a v outside [0, 1] or NaN, a call before bins are
+ * set, and a host-only handle; GWI_ERR_UNSUPPORTED on a handle that holds a shard.
+ *
+ * gwi_point_hist2d_times(): DIAGNOSTIC ONLY, for tools/post_time.py: of the calling thread's last call, summed over its points, the
+ * wall time of the (blocking) log-weight passes, the device times (HIP events) of the draw tile / draw merge launches with the first
+ * pair's tile launch and of everything after it (the first pair's merge and mix launches, then the other pairs' three launches), and
+ * the number of kernel launches after the log-weight passes (2 + 3 n_pairs per point). */
+gwi_status gwi_point_histograms2d(gwi_handle h, const double* thetas, int32_t k, int32_t n_pairs, const int32_t* pairs /* [n_pairs][2] */,
+                                  const double* v /* [k][n_ev + 1] or NULL */, double* hist_pe /* in/out [n_ev][n_pairs][B][B] or NULL */,
+                                  double* hist_inj /* in/out [n_pairs][B][B] or NULL */, double* obs /* [k][n_pairs][B][B] */, double* pred /* like obs */,
+                                  int32_t* live /* [k][2]: live events, injection set live */, int32_t* n_dead /* in/out [n_ev + 1] or NULL */,
+                                  double* vsum /* in/out [n_ev + 1] or NULL */);
+void gwi_point_hist2d_times(double* logw_ms, double* tile_ms, double* merge_ms, int32_t* launches); /* diagnostic only */
+
 /* Credible intervals of the population-informed event posteriors on the device: the marginal posterior weight of every sample, and
  * weighted quantiles and moments of any quantity under it (gwinferno_amd/csrc/gwi_quant.h; the NumPy statement is
  * gwinferno_amd/draws.py: marginal_weights_reference, weighted_quantiles_reference).

@@ -7,7 +7,7 @@ timed on another build of the engine (the parent commit's), in child processes o
 half after, and this build's median is placed against the span of that build's own calls.  No figure is fixed in advance; what is not
 measured is named as unmeasured.  Writes a Markdown report.
 
-      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals,point_rankcorr,point_tails,point_bootstrap} [--configs c2,c5] [--repeats 10]
+      python tools/post_time.py --entry {leave_one_out,point_cdfs,point_pits,point_ranks,point_moments,point_conditionals,point_rankcorr,point_tails,point_bootstrap,hist2d} [--configs c2,c5] [--repeats 10]
                                 [--parent-lib PATH] [--out profiles/<entry>/RESULTS.md]
 
 What differs per entry is one record of ENTRIES: the set-up calls, one_round, the host route, the kernels to list and the row labels."""
@@ -609,6 +609,93 @@ def boot_tail(res):
             "counts of a pass (8 KB + 4 KB) in LDS.", ""]
 
 
+# ---- hist2d: the per-point joint histograms (gwi_hist2d.h) --------------------------------------------------------------------
+H2D_BINS = (32, 64)
+MASS_PAIR = ("mass_1", "mass_ratio")
+
+
+def hist2d_setup(c, extra, full):
+    from gwinferno_amd import draws as D
+
+    c.codes = {}
+    for b in H2D_BINS:
+        edges = [np.quantile(np.concatenate([p.ravel(), i]), np.linspace(0.01, 0.99, b + 1)) for p, i in zip(c.x_pe, c.x_inj)]
+        c.codes[b] = tuple(np.stack([D.digitize(v, e) for v, e in zip(x, edges)]) for x in (c.x_pe, c.x_inj))
+    c.eng.set_kde_columns(c.x_pe, c.x_inj)
+    c.eng.marginal_weights_reset()
+    c.eng.marginal_weights_add(c.thetas[:4])  # (something for weighted_kde2d to smooth)
+    c.grids = [np.linspace(*np.quantile(np.concatenate([p.ravel(), i]), [0.01, 0.99]), 128) for p, i in zip(c.x_pe, c.x_inj)]
+    n_tiles = c.eng.n_ev * -(-c.eng.n_pe // 1024) + -(-c.eng.n_inj // 1024)
+    extra["workspace"] = {b: 8 * b * b * (n_tiles + c.eng.n_ev + 1 + 2 * K) for b in H2D_BINS}
+
+
+def hist2d_round(c, thetas, full):
+    out = {}
+    c.rounds = getattr(c, "rounds", 0) + 1
+    for b in H2D_BINS if c.rounds % 2 else H2D_BINS[::-1]:  # (the two bin counts take turns at being first after the bins are set)
+        c.eng.set_histogram_bins(*c.codes[b], n_bins=b)
+        if full:
+            c.eng.point_histograms2d(thetas[:2], [(0, 1)], accumulate=False)  # (untimed: the first call after new bins)
+            key = f"h2d{b}"
+            t = timed(out, key, lambda: c.eng.point_histograms2d(thetas, [(0, 1)], accumulate=False), c.eng.lib.gwi_point_hist2d_times, thetas)
+            out[key], out[key + " tile"], out[key + " merge"] = t[1] + t[2], t[1], t[2]
+    c.eng.set_histogram_bins(*c.codes[H2D_BINS[-1]], n_bins=H2D_BINS[-1])
+    hist_round(c, thetas, out)  # (B = 64, the same two columns)
+    t = timed(out, "cond", lambda: c.eng.point_conditionals(thetas, [(0, 1)]), c.eng.lib.gwi_point_conditional_times, thetas)
+    out["cond"] = t[1] + t[2]
+    c.eng.weighted_kde2d([(0, 1)], c.grids[0], c.grids[1])
+    t = stage_times(c.eng.lib.gwi_kde_times)
+    out["kde2d"] = t[0] + t[1]
+    return out
+
+
+def hist2d_check(c, extra):
+    b = H2D_BINS[-1]
+    c.eng.set_histogram_bins(*c.codes[b], n_bins=b)
+    edges = [np.quantile(np.concatenate([p.ravel(), i]), np.linspace(0.01, 0.99, b + 1)) for p, i in zip(c.x_pe, c.x_inj)]
+
+    def table(lw, x):
+        live = np.isfinite(lw)
+        if not live.any():
+            return None
+        w = np.where(live, np.exp(np.where(live, lw, 0.0) - lw[live].max()), 0.0)
+        return np.histogram2d(x[0], x[1], bins=edges, weights=w)[0] / w.sum()
+
+    def reference(lw_pe, lw_inj):  # the host route: Engine.log_weights + np.histogram2d of every event and of the injection set, the mixture
+        events = [t for t in (table(lw_pe[e], c.x_pe[:, e]) for e in range(lw_pe.shape[0])) if t is not None]
+        return sum(events) / len(events), table(lw_inj, c.x_inj)
+
+    extra["host_ms"], want = host_route(c, 2, reference)
+    got = c.eng.point_histograms2d(c.thetas[1], [(0, 1)], accumulate=False)
+    worst, same = 0.0, True
+    for mine, theirs in ((got["obs"][0, 0], want[0]), (got["pred"][0, 0], want[1])):
+        ok = theirs > 0.0
+        worst = max(worst, float(np.max(np.abs(mine[ok] - theirs[ok]) / theirs[ok])))
+        same = same and bool(np.array_equal(mine > 0.0, ok))
+    extra["deviation"], extra["flags"] = worst, same
+
+
+def hist2d_notes(cfg, own, extra):
+    return [f"- {cfg}: host route (`Engine.log_weights` + `np.histogram2d` of every event and of the injection set, the mixture formed on the host: the same work, {extra['host_mb']:.1f} MB to the host per point against "
+            f"{2 * 8 * H2D_BINS[-1] ** 2 + 8} bytes from the device at B = {H2D_BINS[-1]}): {extra['host_ms']:.1f} ms per point over 2 points, ONE run, no spread taken.  Largest relative "
+            f"|device - host| cell of the observed and the predicted table of the last of them: {extra['deviation']:.2e}; occupied cells {'equal' if extra['flags'] else 'DIFFERENT'}.",
+            f"- {cfg}: workspace (one pair's partials and shares, the staged rows of 64 points): " + ", ".join(f"{extra['workspace'][b] / 1e6:.1f} MB at B = {b}" for b in H2D_BINS)
+            + "; returned per point: " + ", ".join(f"{2 * 8 * b * b + 8} bytes at B = {b}" for b in H2D_BINS) + "."]
+
+
+def hist2d_intro(repeats, how):
+    return (f"K = {K} points per call, C = 2 bin columns ({', '.join(MASS_PAIR)}), one pair, B = {H2D_BINS[0]} and {H2D_BINS[1]}, accumulate=False, {repeats} calls per row after two "
+            f"warm-up calls; the two bin counts take turns at being first in a round, and each timed call follows one untimed call of two points after the bins were set.  ONE run on ONE box: no spread between runs or boxes was taken.  Nothing was tuned: the owner rule (cell j mod 256), four codes per LDS read and the 256-cell merge "
+            f"blocks are the first shapes written; no alternative was timed.  No ratio was promised in advance.  Times in ms; device times are HIP-event times of the launches after the "
+            f"log-weight pass, summed over the call and divided by K: `tile` is draw tile, draw merge and the joint tile launch, `merge + mix` the two launches after it.  `weighted_kde2d` "
+            f"is one 128 x 128 map of one pair under the marginal weights of 4 points, per query.  `parent`: {how}".rstrip())
+
+
+def hist2d_tail(res):
+    return [f"Scratch is {max(r[4] for r in res)} bytes in every kernel listed.  `hist2d_tile_kernel` holds 8 KB of weights and 2 KB of joint codes in static LDS and the B x B cells in dynamic "
+            "LDS (8 KB at B = 32, 32 KB at B = 64), which the column above does not show.", ""]
+
+
 QUANTITIES = f"C = 3 quantities ({', '.join(MASS_Z)})"
 WEIGHTED_LABEL = {"hist_merge_kernel<true>": "hist_merge_kernel<true> (weighted)", "marg_add_kernel<true>": "marg_add_kernel<true> (weighted)"}
 COMMON = dict(style="spread", columns=MASS_Z, relabel={}, resources_tail=lambda res: [], check=lambda c, extra: None)
@@ -705,6 +792,16 @@ ENTRIES = {e.name: e for e in (
                  ("hist", "`weighted_histograms`, device time per point after the log-weight pass")],
            compare=("tails", "hist"), spans=[("tails", "`point_tails` (unchanged code; a difference is process noise)", " per point"),
                                              ("hist", "`weighted_histograms` (unchanged code; a difference is process noise)", " per point")],
+           unmeasured="NOTHING WAS MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
+    record(style="calls", columns=MASS_PAIR, resources_tail=hist2d_tail, name="hist2d", symbol="gwi_point_histograms2d", title="# Per-point joint histograms: measured times",
+           kernels="hist2d_tile_kernel|hist2d_merge_kernel|hist2d_mix_kernel|hist_tile_kernel|draw_tile_kernel|draw_merge_kernel",
+           setup=hist2d_setup, one_round=hist2d_round, notes=hist2d_notes, check=hist2d_check, intro=hist2d_intro,
+           rows=[(f"h2d{b}{part}", f"`point_histograms2d`, B = {b}{label}") for b in H2D_BINS
+                 for part, label in (("", ", device time per point after the log-weight pass"), (" tile", ": ... of which draw tile / merge and the joint tile launch"),
+                                     (" merge", ": ... of which merge + mix"), (" wall", ", wall time per point of the call"))]
+           + [("hist", "`weighted_histograms`, the same two columns, B = 64, device time per point after the log-weight pass"),
+              ("cond", "`point_conditionals`, one pair, B = 64, device time per point after the log-weight pass"), ("kde2d", "`weighted_kde2d`, one 128 x 128 pair, device time per query")],
+           compare=("hist", "cond"), spans=[("hist", "`weighted_histograms` (unchanged code)", " per point"), ("cond", "`point_conditionals` (unchanged code)", " per point")],
            unmeasured="NOTHING WAS MEASURED: no GPU was available where this file was written.  No time, no ratio and no comparison with the host route or the parent commit is claimed."),
 )}
 
