@@ -663,7 +663,7 @@ struct Term<GWI_TERM_PLPEAK> {
 };
 
 // q^beta (1+beta)/(1 - r^(1+beta)), r = mmin/m1  (distributions.py:111-116 with low = mmin/m1)
-// derived: d0 = 1/(1+beta)
+// derived: d0 = 1/(1+beta), d1 = 2^53 d0 (1 / (1 - r^(1+beta)) at r = 1 - 2^-53)
 template <>
 struct Term<GWI_TERM_POWERLAW_RATIO> {
   static constexpr bool kSpline = false;
@@ -688,15 +688,18 @@ struct Term<GWI_TERM_POWERLAW_RATIO> {
     const double lr = t.p0 - lm;  // log(mmin/m1) <= 0 for every non-excluded sample
     const double beta = c.theta[t.th0];
     const double b1 = 1.0 + beta;
+    // lr == 0: log m1 EQUALS log mmin in float64.  m1 == mmin itself (an empty q interval: the reference's weight is NaN -> 0) never
+    // gets here alive -- the caller's mask excludes it on the quotient mmin / m1 (models.py) -- so this is an m1 within an ulp or two
+    // ABOVE mmin whose logarithm rounded onto log mmin.  The reference forms r = fl(mmin / m1) = 1 - 2^-53 there and keeps the sample
+    // with a finite weight; so does this term, with that r: log r = -2^-53, 1 / (1 - r^b1) = 2^53 / b1 (d[1], from the prelude).
+    // The value is conditioned to ~1e16 in m1 and claims no digits; what is kept is that the sample is alive and every state finite.
     if (b1 == 0.0) {  // alpha == -1 branch of the reference: 1/log(high/low)
       s.db = lq - 0.5 * lr;
-      lin *= -fast_rcp(lr);
+      lin *= (lr != 0.0) ? -fast_rcp(lr) : 0x1p53;
       return -lq;
     }
     const double em1 = fast_expm1(b1 * lr);   // r^(1+beta) - 1
-    // m1 == mmin exactly (lr = 0): the q interval is empty, the reference's weight is NaN -> 0; keep the
-    // gradient state finite so that the dead sample adds 0, not NaN
-    const double inv_den = (em1 != 0.0) ? -fast_rcp(em1) : 0.0;  // 1/(1 - r^(1+beta))
+    const double inv_den = (em1 != 0.0) ? -fast_rcp(em1) : d[1];  // 1/(1 - r^(1+beta))
     // d/dbeta = log q + 1/b1 + r^b1 log r / (1 - r^b1): the last two cancel as b1 -> 0 (what is left of 1/b1 ~ 1e15 after the
     // subtraction carries expm1's ~6e-15 relative error: 1e-8 of the result at |b1| = 1e-6, all of it at 1e-15).  Next to the
     // removable singularity the same number is log q - lr/2 - (lr/2) L(b1 lr/2) with the Langevin function L(t) = coth t - 1/t

@@ -347,25 +347,29 @@ double langevin(double t) {
   }
   return 1.0 / std::tanh(t) - 1.0 / t;
 }
+//
+// The WIDTH log(hi / lo) = 2 h is taken as log1p((hi - lo) / lo), not as log hi - log lo: the difference of two separately rounded
+// logarithms carries an absolute error of an ulp of log hi, which for sampled bounds (GWI_TERM_POWERLAW_BOUNDS) that lie
+// close together is a large relative error of h -- 1.3e-10 in log(2 h) at hi / lo - 1 = 1e-6.  hi - lo is exact for hi < 2 lo.
 void powerlaw_lognorm(double alpha, double lo, double hi, double* logA, double* dlogA) {
-  const double a1 = 1.0 + alpha, llo = std::log(lo), lhi = std::log(hi);
+  const double a1 = 1.0 + alpha, llo = std::log(lo), lhi = std::log(hi), lw = std::log1p((hi - lo) / lo);
   if (a1 == 0.0) {
-    *logA = -std::log(lhi - llo);
+    *logA = -std::log(lw);
     *dlogA = -0.5 * (lhi + llo);
     return;
   }
-  const double c = 0.5 * (lhi + llo), h = 0.5 * (lhi - llo), t = a1 * h;
+  const double c = 0.5 * (lhi + llo), h = 0.5 * lw, t = a1 * h;
   if (std::fabs(t) < 1.0) {
     *logA = -a1 * c - std::log(2.0 * h) - std::log(std::sinh(t) / t);
     *dlogA = -c - h * langevin(t);
     return;
   }
   if (a1 > 0) {
-    const double rho = std::exp(a1 * (llo - lhi));  // (lo/hi)^a1
+    const double rho = std::exp(-a1 * lw);  // (lo/hi)^a1
     *logA = std::log(a1) - (a1 * lhi + std::log1p(-rho));
     *dlogA = 1.0 / a1 - (lhi - rho * llo) / (1.0 - rho);
   } else {
-    const double rho = std::exp(a1 * (lhi - llo));  // (hi/lo)^a1
+    const double rho = std::exp(a1 * lw);  // (hi/lo)^a1
     *logA = std::log(-a1) - (a1 * llo + std::log1p(-rho));
     *dlogA = 1.0 / a1 - (llo - rho * lhi) / (1.0 - rho);
   }
@@ -866,6 +870,7 @@ void prelude(gwi_engine* h, const double* theta, double* theta_out, double (*der
       case GWI_TERM_POWERLAW_RATIO: {
         const double b1 = 1.0 + theta[tm.theta[0]];
         d[0] = b1 != 0.0 ? 1.0 / b1 : 0.0;
+        d[1] = 0x1p53 * d[0];  // 1 / (1 - r^b1) at r = 1 - 2^-53: a sample whose log m1 rounded onto log mmin (gwi_device.h)
         break;
       }
       case GWI_TERM_BETA: {

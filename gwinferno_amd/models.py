@@ -74,7 +74,10 @@ def powerlaw_pdf(xx, alpha, low, high, floor=0.0):
     if float(high) != 1.0:
         raise NotImplementedError("per-sample lower bound is implemented for high == 1 (the reference's only use)")
     low = _f(low)
-    mask = lambda: ~((Sym.src(xx) < Sym.src(low)) | (Sym.src(xx) > high))  # noqa: E731
+    # low >= 1: the interval [low, 1] is empty (low == 1: the reference's normaliser is (1+alpha)/0, a NaN / inf weight that counts as
+    # zero; low > 1 is excluded by the first two tests already).  Decided HERE, on the quotient the reference forms: the term works
+    # from logarithms, where a low one ulp below 1 cannot always be told from 1 (gwi_device.h, Term<GWI_TERM_POWERLAW_RATIO>)
+    mask = lambda: ~((Sym.src(xx) < Sym.src(low)) | (Sym.src(xx) > high) | (Sym.src(low) >= 1))  # noqa: E731
     # log r = 0 - (-log low)
     return Density([Factor(N.TERM_POWERLAW_RATIO, side, [Column("log", xx), Column("neglog", low)], [alpha], consts=(0.0,), mask=mask)], side)
 
@@ -83,7 +86,8 @@ def _powerlaw_ratio(q, m1, beta, mmin):
     """powerlaw_pdf(q, beta, mmin/m1, 1) sharing the log m1 column (parametric.py:28, :40; separable.py:364)."""
     q, m1 = _f(q), _f(m1)
     side = side_of(q)
-    mask = lambda: ~((Sym.src(q) < mmin / Sym.src(m1)) | (Sym.src(q) > 1))  # noqa: E731 -- built when an engine is bound
+    # (mmin / m1 >= 1 -- m1 == mmin, an empty q interval -- is excluded here, on the reference's own quotient: see powerlaw_pdf)
+    mask = lambda: ~((Sym.src(q) < mmin / Sym.src(m1)) | (Sym.src(q) > 1) | (mmin / Sym.src(m1) >= 1))  # noqa: E731 -- built when an engine is bound
     return Density([Factor(N.TERM_POWERLAW_RATIO, side, [Column("log", q), Column("log", m1)], [beta], consts=(np.log(mmin),), mask=mask)], side)
 
 

@@ -67,6 +67,8 @@ enum {
   GWI_TERM_PLPEAK = 2,
   /* q^beta on [mmin/m1, 1]: powerlaw_pdf(q, beta, mmin/m1, 1)   parametric.py:28,40; separable.py:364
    * cols[0]=log q, cols[1]=log m1; theta[0]=beta; p[0]=log(mmin).
+   * m1 == mmin (an empty q interval, a NaN weight in the reference) is the CALLER's to exclude through kappa, on the quotient
+   * mmin / m1; a live sample whose log m1 equals log(mmin) is an m1 an ulp above mmin and is evaluated at r = 1 - 2^-53.
    * With GWI_RATIO_LOGM_FROM_SPLINE in flags, cols[1] is the coordinate column of a spline term in log m1 of the same model
    * (BSplinePrimaryPowerlawRatio, separable.py:295-365: the LogXLogYBSpline of m1) and p[1], p[2], p[3] = that spline's lo,
    * (n_basis - 3) / (hi - lo), (hi - lo) / (n_basis - 3): the engine keeps that column as the knot coordinate u and this term

@@ -98,19 +98,23 @@ static double langevin(double t) {
   return 1.0 / tanh(t) - 1.0 / t;
 }
 
-static void pl_lognorm_log(double a1, double llo, double lhi, double* la, double* dla) {
+/* lw = log(hi / lo), the width, is an argument of its own: formed as lhi - llo from two separately rounded logarithms it carries an
+ * ulp of lhi, which is a large RELATIVE error where the bounds lie close together (sampled bounds: 1.3e-10 in log(2h) at
+ * hi / lo - 1 = 1e-6). */
+static void pl_lognorm_log(double a1, double llo, double lhi, double lw, double* la, double* dla) {
   if (a1 == 0.0) {
-    *la = -log(lhi - llo);
+    *la = -log(lw);
     *dla = -0.5 * (lhi + llo);
     return;
   }
-  const double c = 0.5 * (lhi + llo), h = 0.5 * (lhi - llo), t = a1 * h, at = fabs(t);
+  const double c = 0.5 * (lhi + llo), h = 0.5 * lw, t = a1 * h, at = fabs(t);
   const double lsh = at < 1.0 ? log(sinh(t) / t) : at + log1p(-exp(-2.0 * at)) - log(2.0 * at); /* log(sinh t / t) */
   *la = -a1 * c - log(2.0 * h) - lsh;
   *dla = -c - h * langevin(t);
 }
 
-static void pl_lognorm(double alpha, double lo, double hi, double* la, double* dla) { pl_lognorm_log(1.0 + alpha, log(lo), log(hi), la, dla); }
+/* width from the bounds themselves: hi - lo is exact for hi < 2 lo, and log1p keeps its relative accuracy */
+static void pl_lognorm(double alpha, double lo, double hi, double* la, double* dla) { pl_lognorm_log(1.0 + alpha, log(lo), log(hi), log1p((hi - lo) / lo), la, dla); }
 
 static void tn_lognorm(double mu, double sg, double lo, double hi, double* lc, double* dmu, double* dsg) {
   const double r2 = sqrt(2.0), a = (lo - mu) / sg, b = (hi - mu) / sg;
@@ -192,9 +196,14 @@ static double sample_logw(const gwi_spec* sp, const double* const* cols, int64_t
         /* cols[1] = log m1.  Under GWI_RATIO_LOGM_FROM_SPLINE it is the coordinate column of the model's m1 spline, which on
          * the HOST side -- what this checker is handed -- holds that spline's coordinate x = log m1 itself (only the device
          * copy is converted to knot coordinates, gwi_engine.hip: spline_knot_kernel): the same read either way. */
-        const double lr = tm->p[0] - cols[tm->cols[1]][idx], beta = th[tm->theta[0]], b1 = 1.0 + beta;
-        double la, dla; /* powerlaw_pdf(q, beta, mmin / m1, 1): bounds log r and 0; m1 == mmin (lr = 0): la = +inf (b1 == 0) or NaN (sinh t / t = 0/0), excluded below by !(ell < INFINITY) */
-        pl_lognorm_log(b1, lr, 0.0, &la, &dla);
+        double lr = tm->p[0] - cols[tm->cols[1]][idx];
+        const double beta = th[tm->theta[0]], b1 = 1.0 + beta;
+        /* m1 == mmin (an empty q interval) is excluded by the caller's mask, on the quotient mmin / m1 (kappa = -inf: not reached).
+         * lr == 0 HERE is an m1 just above mmin whose float64 logarithm equals log mmin: the reference forms r = fl(mmin / m1) =
+         * 1 - 2^-53 and keeps the sample, and so does this, with that r (the value claims no digits there). */
+        if (!(lr < 0.0)) lr = -0x1p-53;
+        double la, dla; /* powerlaw_pdf(q, beta, mmin / m1, 1): bounds log r and 0 */
+        pl_lognorm_log(b1, lr, 0.0, -lr, &la, &dla);
         ell += beta * x0 + la;
         push(d, tm->theta[0], x0 + dla);
         break;

@@ -25,10 +25,14 @@ def _spline(x, coefs, lo, hi, zero_outside):
 
 
 def _pl_lognorm(alpha, lo, hi):
+    """log((1 + alpha) / (hi^(1+alpha) - lo^(1+alpha))) = -a1 log lo - log(expm1(a1 w) / a1) with the width w = log(hi / lo) taken as
+    log1p((hi - lo) / lo): the closed form cancels for a1 -> 0 and for hi -> lo (sampled bounds), this one does neither."""
     a1 = 1.0 + alpha
+    w = np.log1p((hi - lo) / lo)
     if a1 == 0:
-        return -np.log(np.log(hi / lo))
-    return np.log(a1 / (hi**a1 - lo**a1))
+        return -np.log(w)
+    t = a1 * w
+    return -a1 * np.log(lo) - (np.log(np.expm1(t) / a1) if t < 30.0 else t + np.log1p(-np.exp(-t)) - np.log(a1))
 
 
 def _tn_lognorm(mu, sg, lo, hi):
@@ -98,6 +102,7 @@ def log_weights(bm, theta, include_consts=True):
                     ell = ell - np.log1p(np.exp(th[0] / c[0] + th[0] / (c[0] - th[0])))
                 elif k == N.TERM_POWERLAW_RATIO:
                     lr = p[0] - c[1]
+                    lr = np.where(lr == 0, -(2.0**-53), lr)  # log m1 rounded onto log mmin (m1 == mmin itself is masked): r = 1 - 2^-53
                     b1 = 1 + th[0]
                     if b1 == 0:
                         ell = ell - c[0] - np.log(-lr)

@@ -1,7 +1,9 @@
-"""Shared by tests/test_terms_hp_cpu.py (C oracle), tests/test_gpu_terms_hp.py and tests/test_gpu_spline_terms_hp.py (engine): the
-high-precision term fixtures (tests/golden/terms_hp.npz, written by tests/golden/make_terms_hp.py; tests/golden/spline_terms_hp_*.npz,
-written by tests/golden/make_spline_terms_hp.py), the drop-in model call of every term in them, the catalogs that make a summed
-gradient transparent, and the assertions -- the same ones, with the same bars, for both.
+"""Shared by tests/test_terms_hp_cpu.py, tests/test_mass_forms_hp_cpu.py (C oracle), tests/test_gpu_terms_hp.py,
+tests/test_gpu_spline_terms_hp.py and tests/test_gpu_mass_forms_hp.py (engine): the high-precision term fixtures
+(tests/golden/terms_hp.npz, written by tests/golden/make_terms_hp.py; tests/golden/spline_terms_hp_*.npz, written by
+tests/golden/make_spline_terms_hp.py; tests/golden/mass_forms_hp.npz, written by tests/golden/make_mass_forms_hp.py), the drop-in
+model call of every term in them, the catalogs that make a summed gradient transparent, and the assertions -- the same ones, with the
+same bars, for both.
 
 An EVALUATOR is anything with ``log_weights(theta) -> (n_ev, n_pe) array`` and ``evaluate(theta, total_inj) -> (log_l, grad)``
 on a catalog it was built for; ``make(d_pe, d_inj)`` builds one from a pair of lazy densities and must expose ``.bound``.
@@ -78,6 +80,45 @@ for _name in LERP_TERMS:
 # flat again.  Catalog B also carries samples inside the dip and is held to the plain relative bar.
 LOGL_CANCELLED_A = {"bspline17": {"dip"}, "logx17": {"dip"}}
 
+# The pairing factor (m2 / m1)^beta at beta = 0 is 1 for every pair: every live sample has the same log-density, 0.
+LOGL_CANCELLED["pairing_iid"] = {"beta0"}
+LOGL_CANCELLED["pairing_indep"] = {"beta0"}
+
+# ``plbounds`` on the narrow intervals, ON CATALOG A ONLY: catalog A of that nest of intervals is made of the samples inside its
+# narrowest one, [30, 30.00003], across which x^alpha changes by |alpha| 1e-6 -- every live sample has the same log-density to six
+# digits.  log_l is then ~1e-5 (4.5e-6 at alpha = -1 - 1e-6) assembled from sums of ~30: a bar of 1e-9 relative to it asks for 4e-15
+# absolute, 1.5e-16 of the sums, which ten float64 additions do not hold (the C oracle's error there is 1.1e-14).  Catalog B of the same
+# points carries samples from all of [30, 33] and is held to the plain relative bar, as are the values and every gradient component.
+LOGL_CANCELLED_A["plbounds"] = {f"narrow{w}/alpha{a}" for w in ("1e-1", "1e-3", "1e-6") for a in ("-2.5", "-1+1e-6", "-1-1e-6", "-1")}
+
+# tests/golden/mass_forms_hp.npz: the terms, and for the mass-ratio power laws the call's mmin; tests/test_mass_forms_hp_cpu.py holds
+# this table and the numbers below to the generator's.
+MASS_FORM_TERMS = ["plbounds", "pairing_iid", "pairing_indep", "ratio_on_logxlogy20_mmin3", "ratio_on_logxlogy20_mmin5"]
+RATIO_MMIN = {"ratio_on_logxlogy20_mmin3": 3.0, "ratio_on_logxlogy20_mmin5": 5.0}
+# ``ratio_on_logxlogy20_*``: log p is ill-conditioned in log m1 next to m1 = mmin (d log p / d log m1 ~ 1 / log(mmin / m1)), and log m1
+# is a ROUNDED input of the term: the value bar at sample i is VALUE_ATOL + |dlogp_dlogm1[i]| eps_lm, with eps_lm the error of the
+# log m1 the term works with -- derived from the arithmetic in the source, never from what a device returned.  u = 2^-53.
+#   own column (GWI_FOLD_LOGM=0): the term reads log m1 as the setup kernel's logarithm wrote it: one ulp of log m1.  m1 <= 100, so
+#     log m1 < 8 and an ulp is at most 2^-50:                                            EPS_LM_OWN = 2^-50 = 8.9e-16.
+#   folded (GWI_RATIO_LOGM_FROM_SPLINE): the term rebuilds log m1 = fma(u, dx, lo) from the m1 spline's knot coordinate
+#     u = (log m1 - lo) inv_dx (gwi_ingest.h: spline_knot_kernel, contraction off; engine.py: inv_dx = n_int / (hi - lo),
+#     dx = (hi - lo) / n_int).  With D = log m1 - lo <= log(100 / 3) < 4, on top of the column's own ulp:
+#       the subtraction                        D u
+#       hi - lo and the division in inv_dx      2 D u
+#       the product (log m1 - lo) inv_dx        D u
+#       the clamp into [0, nextafter(n_int, 0)] D 2u   (a live sample lies in the closed domain: only x = hi moves, by one ulp of u)
+#       hi - lo and the division in dx          2 D u
+#       the one rounding of fma(u, dx, lo)      half an ulp of log m1 < 8: 2^-51
+#     (lo itself is the same double in the subtraction and in the FMA and cancels.)  8 D u + 2^-51 <= 4 x 2^-50 + 2^-51:
+#                                                                                      EPS_LM_FOLD = 5.5 x 2^-50 = 4.9e-15.
+# The gradient bar gains the same product with the second derivative d^2 log p / d beta d log m1 (and, in an event of several
+# samples, with the move of the weights; ``_conditioning``).  A sample whose conditioning term exceeds COND_CAP tells nothing about
+# the arithmetic: only its liveness is compared, it stays out of the gradient catalogs, and the generator asserts that there are at
+# most two per mmin (the nextafter neighbour above 3.0, where 1 / log(m1 / mmin) = 6.8e15).
+EPS_LM_OWN = 2.0**-50
+EPS_LM_FOLD = EPS_LM_OWN + 4.0 * 2.0**-50 + 2.0**-51
+COND_CAP = 1e-9
+
 MMIN, MMAX = 5.0, 100.0
 
 
@@ -96,6 +137,11 @@ def load_spline():
         with np.load(path) as z:
             out.update({k: z[k] for k in z.files})
     return out
+
+
+def load_mass_forms():
+    with np.load(os.path.join(GOLDEN_DIR, "mass_forms_hp.npz")) as z:
+        return {k: z[k] for k in z.files}
 
 
 _Z_TABLE = []
@@ -162,6 +208,67 @@ class Shared(Term):
         self.dlogp = np.where(dead[:, None, :], 0.0, term.dlogp + term.dlogp[:, :, perm])
 
 
+class RatioTerm(Term):
+    """``ratio_on_logxlogy20_*`` of mass_forms_hp.npz: the call's mmin and the two conditioning arrays with the term."""
+
+    def __init__(self, z, name):
+        super().__init__(z, name)
+        self.mmin = float(z[f"{name}/mmin"])
+        self.cond = z[f"{name}/dlogp_dlogm1"]                       # (H, n)
+        self.cond2 = z[f"{name}/d2logp_dbeta_dlogm1"][:, None, :]   # (H, 1, n)
+
+
+class Subset(Term):
+    """The samples ``idx`` of a fixture term, in that order, under a name of its own (a second reading of one term in a ``Product``)."""
+
+    def __init__(self, term, idx, name):
+        idx = np.asarray(idx)
+        self.name, self.params, self.columns, self.tags, self.theta = name, term.params, term.columns, term.tags, term.theta
+        self.cols = [np.ascontiguousarray(c[idx]) for c in term.cols]
+        self.logp, self.dlogp = term.logp[:, idx], term.dlogp[:, :, idx]
+        self.base_term = term
+
+
+class Joint(Term):
+    """Fixture terms that SHARE A COLUMN as one model (``Product`` is for disjoint columns): a column of a later part that equals one
+    already seen is that column.  ``Joint(logxlogy20, ratio_on_logxlogy20_*)`` share m1 (BSplinePrimaryPowerlawRatio);
+    ``Joint(Shared(logxlogy17), pairing_*)`` share both (the component-mass models).  Parameters are the parts' in turn; sample i is
+    every part's sample i, hyper-point h every part's point h mod its number of points; dead where any part is."""
+
+    def __init__(self, *parts):
+        n = parts[0].n
+        assert all(t.n == n for t in parts)
+        hs = [np.arange(max(len(t.theta) for t in parts)) % len(t.theta) for t in parts]
+        self.name = "&".join(t.name for t in parts)
+        self.parts, self.part_points = parts, hs
+        self.params = [f"{t.name}.{p}" for t in parts for p in t.params]
+        self.cols, self.col_of = [], []
+        for t in parts:
+            at = []
+            for c in t.cols:
+                hit = [k for k, have in enumerate(self.cols) if np.array_equal(have, c)]
+                if not hit:
+                    self.cols.append(c)
+                at.append(hit[0] if hit else len(self.cols) - 1)
+            self.col_of.append(at)
+        assert len(self.cols) < sum(len(t.cols) for t in parts), "no column is shared: this is a Product"
+        self.tags = ["|".join(t.tags[h[k]] for t, h in zip(parts, hs)) for k in range(len(hs[0]))]
+        self.theta = np.concatenate([t.theta[h] for t, h in zip(parts, hs)], axis=1)
+        self.logp = sum(t.logp[h] for t, h in zip(parts, hs))
+        dead = np.isneginf(self.logp)
+        self.dlogp = np.where(dead[:, None, :], 0.0, np.concatenate([t.dlogp[h] for t, h in zip(parts, hs)], axis=1))
+        # conditioning with respect to a rounded input (the ratio term's log m1): |d log p / d log m1| and the same for every
+        # derivative; zero for the parts that have none
+        if any(hasattr(t, "cond") for t in parts):
+            self.cond = np.where(dead, 0.0, sum(t.cond[h] for t, h in zip(parts, hs) if hasattr(t, "cond")))
+            self.cond2 = np.where(dead[:, None, :], 0.0, np.concatenate([t.cond2[h] if hasattr(t, "cond2") else np.zeros_like(t.dlogp[h]) for t, h in zip(parts, hs)], axis=1))
+            self.waived = np.flatnonzero((np.abs(self.cond) * EPS_LM_FOLD > COND_CAP).any(axis=0))
+
+    @property
+    def kind(self):
+        return self.parts[-1].name
+
+
 class LerpModel:
     """The grid and design matrix of a BSplineDistribution term, made ONCE per catalog (the distribution keys its device tables on the
     identity of the two arrays), and the drop-in call on them."""
@@ -204,6 +311,17 @@ def model_of(name, pe, inj):
     from gwinferno_amd import interpolation as I
     from gwinferno_amd import models as M
 
+    if isinstance(name, Joint) or name in ("pairing_iid", "pairing_indep"):
+        kind = name.kind if isinstance(name, Joint) else name
+        if kind in ("pairing_iid", "pairing_indep"):  # columns (m1, m2); the splines are logxlogy17's
+            basis, n, (mmin, mmax), _ = SPLINE_TERMS["logxlogy17"]
+            assert basis == "LogXLogYBSpline" and (not isinstance(name, Joint) or base_name(name.parts[0]) == "logxlogy17")
+            if kind == "pairing_iid":
+                return M.BSplineIIDComponentMasses(n, pe[0], pe[1], inj[0], inj[1], mmin=mmin, mmax=mmax)
+            return M.BSplineIndependentComponentMasses(n, n, pe[0], pe[1], inj[0], inj[1], mmin1=mmin, mmax1=mmax, mmin2=mmin, mmax2=mmax)
+        basis, n, (mmin, mmax), _ = SPLINE_TERMS["logxlogy20"]  # columns (m1, q)
+        assert kind in RATIO_MMIN and name.parts[0].name == "logxlogy20" and basis == "LogXLogYBSpline"
+        return M.BSplinePrimaryPowerlawRatio(n, pe[0], inj[0], mmin=mmin, mmax=mmax)
     if isinstance(name, Shared):
         basis, n, xrange, _ = SPLINE_TERMS[name.base.name]
         assert basis == "LogYBSpline" and xrange in ((0.0, 1.0), (-1.0, 1.0))
@@ -230,6 +348,19 @@ def density(name, cols, p, model=None, pe_samples=True):
     ``model``: what ``model_of`` made on the catalog's two sides, ``pe_samples`` which of them ``cols`` is."""
     from gwinferno_amd import models as M
 
+    if isinstance(name, Joint):
+        coefs = np.asarray(p[:-1], dtype=np.float64)  # ONE array: the binder gives one block of slots to a vector it meets twice
+        if name.kind == "pairing_iid":
+            return model(coefs, p[-1], pe_samples=pe_samples)
+        if name.kind == "pairing_indep":
+            return model(coefs, coefs, p[-1], pe_samples=pe_samples)
+        return model(cols[0], cols[1], p[-1], RATIO_MMIN[name.kind], coefs, pe_samples=pe_samples)
+    if name in ("pairing_iid", "pairing_indep"):  # the pairing factor alone, as the component-mass models form it
+        return model._pairing(p[0], pe_samples)
+    if name == "plbounds" or name.startswith("plbounds:"):
+        from gwinferno_amd import numpyro_distributions as D
+
+        return D.Powerlaw(p[0], minimum=p[1], maximum=p[2]).log_prob(cols[0])
     if name in LERP_TERMS:
         return model(cols[0], np.asarray(p, dtype=np.float64))
     if name in Z_SPLINE_TERMS:
@@ -284,7 +415,7 @@ class Catalog:
                 self.inj.append(MMIN / self.inj[1])
         parts = term.parts if isinstance(term, Product) else (term,)
         at = np.cumsum([0] + [len(t.cols) for t in parts])
-        self.models = [model_of(t if isinstance(t, Shared) else t.name, self.pe[a:b], self.inj[a:b]) for t, a, b in zip(parts, at[:-1], at[1:])]
+        self.models = [model_of(t if isinstance(t, (Shared, Joint)) else t.name, self.pe[a:b], self.inj[a:b]) for t, a, b in zip(parts, at[:-1], at[1:])]
         p0 = term.theta[0]
         self.ev = make(self._density(self.pe, p0), self._density(self.inj, p0))
         # theta slot of every named parameter: bind the model once more, lazily, with marker values (distinct and positive: the
@@ -306,7 +437,7 @@ class Catalog:
                 out = d if out is None else Density.__mul__(out, d)
                 c0, p0 = c0 + len(part.cols), p0 + len(part.params)
             return out
-        return density(t.name, cols, p, self.models[0], pe)
+        return density(t if isinstance(t, Joint) else t.name, cols, p, self.models[0], pe)
 
     def theta(self, h):
         th = np.zeros(len(self.slot))
@@ -319,10 +450,21 @@ class Catalog:
             close()
 
 
-def core_samples(term):
-    """Samples in the support at every hyper-point, and those in it at some but not all."""
-    live = np.isfinite(term.logp)
-    return np.flatnonzero(live.all(axis=0)), np.flatnonzero(live.any(axis=0) & ~live.all(axis=0))
+def core_samples(term, points=None):
+    """Samples in the support at every hyper-point (of ``points``), and those in it at some but not all.  The samples a term waives
+    (``Joint.waived``: conditioned beyond COND_CAP) are in neither."""
+    live = np.isfinite(term.logp if points is None else term.logp[list(points)])
+    keep = np.ones(live.shape[1], dtype=bool)
+    keep[getattr(term, "waived", [])] = False
+    return np.flatnonzero(live.all(axis=0) & keep), np.flatnonzero(live.any(axis=0) & ~live.all(axis=0) & keep)
+
+
+def group_points(term, z, group):
+    """Hyper-points of ``plbounds`` (or of a product that carries it as its longest part) in nest ``group`` of intervals: the catalogs
+    of summed gradients are built per nest, from the samples inside its narrowest interval."""
+    g = z["plbounds/group"]
+    assert len(g) == len(term.theta)
+    return [int(h) for h in np.flatnonzero(g == group)]
 
 
 def pins(term):
@@ -340,14 +482,32 @@ def pins(term):
     return None
 
 
+def plbounds_arranged(z, n, second=False):
+    """The first ``n`` samples of an arrangement of ``plbounds`` that leads with the samples inside [20, 30], the narrowest interval of
+    nest 0 (a ``Product`` keeps only as many samples as its shortest part has: catalog A needs its core among them).  ``second``:
+    another arrangement with the same property, under another name."""
+    t = Term(z, "plbounds")
+    core, _ = core_samples(t, group_points(t, z, 0))
+    rest = [i for i in range(t.n) if i not in set(core)]
+    order = (list(np.roll(core, 3)) + list(np.roll(rest, 11))) if second else (list(core) + rest)
+    return Subset(t, order[:n], "plbounds:2" if second else "plbounds:1")
+
+
+def plbounds_product(z, spline_z):
+    """powerlaw_redshift x plbounds x plbounds on a second arrangement of the samples (the ahead-of-time chain "plz+plb2")."""
+    zt = Term(spline_z, "powerlaw_redshift")
+    return Product(zt, plbounds_arranged(z, zt.n), plbounds_arranged(z, zt.n, second=True))
+
+
 def values_catalog(term, make):
     idx = np.arange(term.n)
     pin = pins(term)
     return Catalog(term, make, idx.reshape(-1, 1), idx if pin is None else idx[pin[2]])
 
 
-def catalog_a(term, make):
-    core, _ = core_samples(term)
+def catalog_a(term, make, points=None):
+    """``points``: the hyper-points the catalog will be run at (plbounds: one nest of intervals); every point otherwise."""
+    core, _ = core_samples(term, points)
     assert len(core) >= 8, (term.name, len(core))
     pin = pins(term)
     if pin is None:
@@ -358,8 +518,8 @@ def catalog_a(term, make):
     return Catalog(term, make, core.reshape(-1, 1), [lo, x0, hi])  # total_inj = 3
 
 
-def catalog_b(term, make):
-    core, some = core_samples(term)
+def catalog_b(term, make, points=None):
+    core, some = core_samples(term, points)
     pin = pins(term)
     if pin is not None:
         # the two ends lead the events; samples dead at every hyper-point (beyond zmax) ride along with the partly dead ones
@@ -376,6 +536,8 @@ def catalog_b(term, make):
         ok = [c for c in rest if inside[c]]
         return Catalog(term, make, np.array(seq[: 3 * n_ev]).reshape(n_ev, 3), [lo, ok[1], ok[3], ok[5], hi])
     seq, s = [], list(some)
+    if isinstance(term, Joint) and not s:  # a support that no hyper-parameter moves: the samples outside it ride along instead
+        s = [int(i) for i in np.flatnonzero(~np.isfinite(term.logp).any(axis=0))]
     for k, c in enumerate(core):
         seq.append(c)
         if k % 2 == 1 and s:
@@ -433,8 +595,10 @@ def reference_marginalised(cat, h):
 def is_cancelled(term, h, cat=None):
     """Whether hyper-point ``h`` is one of LOGL_CANCELLED (or, on a catalog of one sample per event and one injection -- catalog A -- of
     LOGL_CANCELLED_A); a product's is where every part's is (a flat density times a flat one)."""
-    if isinstance(term, Product):
+    if isinstance(term, (Product, Joint)):
         return all(is_cancelled(t, int(hs[h]), cat) for t, hs in zip(term.parts, term.part_points))
+    if isinstance(term, Subset):
+        return is_cancelled(term.base_term, h, cat)
     if isinstance(term, Shared):  # a flat density times itself
         return is_cancelled(term.base, h, cat)
     only_a = cat is not None and cat.pe_idx.shape[1] == 1 and len(cat.inj_idx) == 1
@@ -462,20 +626,65 @@ class Worst:
         return [f"{' / '.join(k)}: {e:.3e} at {w}" for k, (e, w) in sorted(self.rows.items())]
 
 
-def check_values(cat, path, worst, failures):
+def check_values(cat, path, worst, failures, eps_lm=None):
+    """``eps_lm`` (terms with a ``cond`` array): the bar at sample i is VALUE_ATOL + |cond_i| eps_lm; a sample whose conditioning term
+    exceeds COND_CAP is compared for liveness only.  The error is noted in units of the bar times VALUE_ATOL."""
     t = cat.term
     for h in range(len(t.theta)):
         got = cat.ev.log_weights(cat.theta(h))[:, 0]
         ref = t.logp[h]
         dead = np.isneginf(ref)
-        if not np.array_equal(np.isneginf(got), dead):
-            failures.append(f"{t.name} [{path}] {t.tags[h]}: support differs at samples {np.flatnonzero(np.isneginf(got) != dead)[:6].tolist()}")
+        # (the liveness of a WAIVED sample is ``check_waived_liveness``'s, a test of its own: a miss there must not hide the rest)
+        told = np.ones(len(ref), dtype=bool) if eps_lm is None else ~(np.abs(t.cond[h]) * eps_lm > COND_CAP)
+        if not np.array_equal(np.isneginf(got)[told], dead[told]):
+            failures.append(f"{t.name} [{path}] {t.tags[h]}: support differs at samples {np.flatnonzero((np.isneginf(got) != dead) & told)[:6].tolist()}")
             continue
-        err = np.abs(got[~dead] - ref[~dead])
+        keep = ~dead
+        scale = np.ones(len(ref))
+        if eps_lm is not None:
+            extra = np.abs(t.cond[h]) * eps_lm
+            keep &= told
+        if not keep.any():  # (a product whose parts have no common live sample at this point: the support was all there is to compare)
+            continue
+        if eps_lm is not None:
+            scale = 1.0 + extra / VALUE_ATOL
+            raw = np.abs(got[keep] - ref[keep])
+            worst.note((t.name, path, "value, unscaled"), raw.max(), f"{t.tags[h]} sample {np.flatnonzero(keep)[int(np.argmax(raw))]}")
+        err = np.abs(got[keep] - ref[keep]) / scale[keep]
         k = int(np.argmax(err))
-        worst.note((t.name, path, "value"), err[k], f"{t.tags[h]} theta={t.theta[h].tolist()} sample {np.flatnonzero(~dead)[k]}")
+        worst.note((t.name, path, "value"), err[k], f"{t.tags[h]} theta={t.theta[h].tolist()} sample {np.flatnonzero(keep)[k]}")
         if not err[k] < VALUE_ATOL:
-            failures.append(f"{t.name} [{path}] {t.tags[h]}: |log w - ref| = {err[k]:.3e} >= {VALUE_ATOL:g} (sample {np.flatnonzero(~dead)[k]})")
+            failures.append(f"{t.name} [{path}] {t.tags[h]}: |log w - ref| = {err[k]:.3e} x its bar / {VALUE_ATOL:g} >= {VALUE_ATOL:g} (sample {np.flatnonzero(keep)[k]})")
+
+
+def check_waived_liveness(cat, failures):
+    """A sample conditioned beyond COND_CAP tells nothing about the arithmetic, but it is finite or -inf as the fixture has it."""
+    t = cat.term
+    for h in range(len(t.theta)):
+        got = cat.ev.log_weights(cat.theta(h))[:, 0]
+        for i in t.waived:
+            if np.isneginf(got[i]) != np.isneginf(t.logp[h][i]):
+                failures.append(f"{t.name} {t.tags[h]}: sample {i} ({[c[i] for c in t.cols]}) is {'dead' if np.isneginf(got[i]) else 'alive'}, the fixture has {t.logp[h][i]!r}")
+
+
+def _conditioning(cat, h, eps_lm):
+    """First-order bound on what an error of ``eps_lm`` in the rounded input of every sample does to log_l and to every gradient
+    component on ``cat``: per event (and, n_obs times, for the injections), with normalised weights w_i, conditioning c_i = |d log p_i /
+    d log m1| and c2_ij the same for derivative j:  log_l moves by at most eps sum_i w_i c_i, the weight-averaged derivative j by at
+    most eps sum_i w_i (|g_ij - mean_j| c_i + c2_ij)."""
+    t = cat.term
+
+    def side(idx):
+        lp, g = t.logp[h][idx], t.dlogp[h][:, idx]
+        c, c2 = np.abs(t.cond[h][idx]), np.abs(t.cond2[h][:, idx])
+        w = np.exp(lp - np.max(lp, axis=-1, keepdims=True))
+        w = w / np.sum(w, axis=-1, keepdims=True)
+        mean = np.sum(w * g, axis=-1, keepdims=True)
+        return eps_lm * np.sum(w * c, axis=-1), eps_lm * np.sum(w * (np.abs(g - mean) * c + c2), axis=-1)
+
+    (l_pe, g_pe), (l_inj, g_inj) = side(cat.pe_idx), side(cat.inj_idx)
+    n_ev = cat.pe_idx.shape[0]
+    return float(np.sum(l_pe) + n_ev * l_inj), np.sum(g_pe, axis=-1) + n_ev * g_inj
 
 
 def grad_errors(t, got_grad, ref_grad):
@@ -483,8 +692,10 @@ def grad_errors(t, got_grad, ref_grad):
     return np.abs(got_grad - ref_grad) / np.maximum(1.0, np.abs(ref_grad))
 
 
-def check_gradients(cat, path, worst, failures, points=None, results=None, marginalised=False):
-    """``marginalised``: against ``reference_marginalised``, the evaluator called with ``marginalize_selection=True``."""
+def check_gradients(cat, path, worst, failures, points=None, results=None, marginalised=False, eps_lm=None):
+    """``marginalised``: against ``reference_marginalised``, the evaluator called with ``marginalize_selection=True``.  ``eps_lm`` (terms
+    with a ``cond`` array): the bars gain what ``_conditioning`` allows a rounded input; the errors are then noted in units of the
+    widened bar, i.e. divided by (size + allowance / RTOL)."""
     t = cat.term
     total = float(len(cat.inj_idx))
     for h in (range(len(t.theta)) if points is None else points):
@@ -495,11 +706,12 @@ def check_gradients(cat, path, worst, failures, points=None, results=None, margi
         grad = np.asarray(grad)[cat.slot]
         ref_l, ref_g, scale_l = (reference_marginalised if marginalised else reference)(cat, h)
         cancelled = is_cancelled(t, h, cat)
-        e_l = 0.0 if log_l == ref_l else abs(log_l - ref_l) / (max(scale_l, abs(ref_l), 1.0 if base_name(t) in SPLINE_TERMS else 0.0) if cancelled else (abs(ref_l) or 1e-300))
+        extra_l, extra_g = _conditioning(cat, h, eps_lm) if eps_lm is not None else (0.0, 0.0)
+        e_l = 0.0 if log_l == ref_l else abs(log_l - ref_l) / ((max(scale_l, abs(ref_l), 1.0 if base_name(t) in SPLINE_TERMS else 0.0) if cancelled else (abs(ref_l) or 1e-300)) + extra_l / LOGL_RTOL)
         worst.note((t.name, path, "log_l (relative)"), e_l, t.tags[h])
         if not e_l < LOGL_RTOL:
             failures.append(f"{t.name} [{path}] {t.tags[h]}: log_l {log_l!r} vs {ref_l!r}: relative {e_l:.3e} >= {LOGL_RTOL:g}{' (of the cancelled sums)' if cancelled else ''}")
-        e = grad_errors(t, grad, ref_g)
+        e = np.abs(grad - ref_g) / (np.maximum(1.0, np.abs(ref_g)) + extra_g / GRAD_RTOL)
         for j, name in enumerate(t.params):
             worst.note((t.name, path, f"d/d{name}"), e[j], f"{t.tags[h]} theta={t.theta[h].tolist()} ref={ref_g[j]:.6g}")
             if not e[j] <= GRAD_RTOL:
